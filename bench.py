@@ -2,7 +2,13 @@
 """Headline benchmark: examples/sec of one forward+backward pass (loss -> gradient
 of every parameter, optimizer step excluded) on synthetic Criteo-shaped batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload deepfm|xdeepfm|dcn]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload deepfm|xdeepfm|dcn] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the contract line (`value`, `ms_per_step`,
+`config`).  Everything else below - the sub-records, rooflines, PMC traffic, CPU baseline and parity
+check, optimizer and train-step records, the single-batch replay beside the rotating one - is measured
+with --full only.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs()).
 
 N = 1 runs in this process.  N > 1: one rank per GPU over RCCL, the embedding table
 row-sharded over the ranks (recman_amd/dist.py), per-GPU batch fixed (weak scaling).
@@ -12,14 +18,14 @@ unset, by this script itself: BEFORE any GPU call it starts `torch.distributed.r
 as a child process, relays rank 0's JSON line and exits with the child's code.
 Rank 0 prints ONE JSON line.
 
-The default run (N = 1, no --workload) measures BASELINE configs[1] (DeepFM) as the
+The default --full run (N = 1, no --workload) measures BASELINE configs[1] (DeepFM) as the
 contract line - `value`, `roofline`, `cpu_baseline` - and adds, in the same line,
 `workloads.xdeepfm` (configs[2], CIN on the f32 MFMA roofline) and `workloads.dcn`
 (configs[3], dense GEMM on MFMA + the fused cross kernels on HBM), each with its own
 `ms_per_step`, `value`, `roofline(s)` and `cpu_baseline`, plus `zipf` (the DeepFM step
 with Zipf(1.05) ids).  `--workload X` (or --only) measures that workload alone.
 
-`roofline.traffic`: HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE and
+`roofline.traffic` (--full): HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE and
 WRITE_SIZE each in its own `--pmc ... --kernel-trace` run, FETCH_SIZE doubled as
 MI355X_MICROARCH.md prescribes for gfx950) of THIS build, collected live by two child
 processes (`bench.py --pmc-child`, the roofline kernels only) started before this
@@ -83,6 +89,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the contract line: sub-records, rooflines, PMC traffic, "
+                         "CPU baseline + parity check, optimizer / train-step records (minutes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, logits, gradients) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--table-row-reuse", default="", choices=["", "stream", "cache"],
                     help="gather kernel's row loads: stream = non-temporal (default for uniform ids), "
                          "cache = plain (default with --zipf)")
@@ -132,7 +144,10 @@ def parse(argv=None):
                     help="row-sharded exchange layout: fixed capacity (equal splits, no host sync, one "
                          "hipGraph per step; falls back when a batch overflows) or dynamic split sizes; "
                          "auto = fixed for uniform indices, dynamic for --zipf")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ---------------------------------------------------------------------- self-launch (N > 1)
@@ -378,6 +393,55 @@ def attach_traffic(roofs, wname, live, fallback):
             r["frac_traffic"] = round(r["traffic"] / (r["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
 
 
+# ---------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_ELEMS = 1 << 21     # per array (8 MB of fp32): a larger output is dumped as a fixed sample of its rows
+DUMP_MAX_BYTES = 64 << 20    # all arrays together
+DUMP_SAMPLE_SEED = 0
+
+
+def output_arrays(engine, loss):
+    """name -> device tensor: what a caller of engine.fwd_bwd holds after the step - the loss it returned,
+    logit / pred, dLoss/dlogit, the embedding-row gradients in IndexedSlices form (d_rows [B, F, D] beside the
+    ids; d_bias where the model keeps one) and every dense parameter's gradient; the row-sharded engine adds
+    the gradient rows its table shard received.  Floating-point tensors only."""
+    out = {"loss": loss}
+    for k in ("logit", "pred", "dlogit", "d_rows", "d_bias"):
+        out[k] = getattr(engine, k, None)
+    for k, g in sorted(engine.grads.items()):
+        out[f"grad_{k}"] = g
+    rows = getattr(engine, "shard_grad_rows", None)
+    if isinstance(rows, (list, tuple)):
+        out.update({f"shard_grad_rows_{c}": r for c, r in enumerate(rows)})
+    else:
+        out["shard_grad_rows"] = rows
+    return {k: v for k, v in out.items() if torch.is_tensor(v) and v.is_floating_point()}
+
+
+def dump_outputs(engine, loss, d):
+    """Writes output_arrays() as d/<name>.npy (fp32, fp64 where the tensor is).  An array of more than
+    DUMP_MAX_ELEMS elements is cut to the rows (along dim 0) of a sample drawn with a fixed seed, the same for
+    every run of the same shape, so that two builds compare output for output."""
+    import numpy as np
+
+    if torch.cuda.is_initialized():
+        torch.cuda.synchronize()
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in output_arrays(engine, loss).items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            n = max(1, DUMP_MAX_ELEMS // max(1, t.numel() // t.shape[0]))
+            sel = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.shape[0], n, replace=False))
+            t = t[torch.as_tensor(sel, device=t.device)]
+        arr = t.cpu().numpy()
+        arr = arr.astype(np.float64 if arr.dtype == np.float64 else np.float32, copy=False)
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(d, "".join(c if c.isalnum() or c in "_.-" else "_" for c in name) + ".npy"), arr)
+    print(f"[bench] last timed step's outputs -> {d} ({total / 1e6:.1f} MB)", file=sys.stderr, flush=True)
+
+
 # ---------------------------------------------------------------------- one workload
 def make_engine(a, w, B, V, dev, rank, world, sharded, zipf=0.0):
     from recman_amd import engine as eng
@@ -405,9 +469,10 @@ def make_engine(a, w, B, V, dev, rank, world, sharded, zipf=0.0):
 
 
 def time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse, dev, steps, warmup, batches=None):
-    """W warmup + K timed steps of engine.fwd_bwd -> (ms per step, host enqueue ms, graph kind, fixed, rotation).
+    """W warmup + K timed steps of engine.fwd_bwd -> (ms per step, host enqueue ms, graph kind, fixed, rotation,
+    the loss tensor the last timed step returned).
     batches: further (idx, dense, y) triples - the timed steps then cycle through all of them (one captured
-    hipGraph per batch, replayed round robin), and the single-batch replay is timed beside it."""
+    hipGraph per batch, replayed round robin), and (--full) the single-batch replay is timed beside it."""
     # (the captured graphs / replay closures are dropped on return: they pin the capture's memory pool)
     allb = [(idx, dense, y)] + list(batches or [])
 
@@ -447,14 +512,14 @@ def time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse, dev, st
             torch.cuda.current_stream().wait_stream(side)
             import gc
 
-            graphs = []
+            graphs, graph_outs = [], []
             gc.collect()
             gc.disable()  # (a collection inside the capture could free device memory: unsafe there)
             try:
                 for k in range(len(allb)):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
-                        step(k)
+                        graph_outs.append(step(k))  # the graph's static output: each replay rewrites it
                     graphs.append(g)
             finally:
                 gc.enable()
@@ -477,8 +542,8 @@ def time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse, dev, st
     def run(i=0):
         if graphs is not None:
             graphs[i % nrot].replay()
-        else:
-            step(i % nrot)
+            return graph_outs[i % nrot]
+        return step(i % nrot)
 
     def barrier():
         if dist is not None:
@@ -505,7 +570,7 @@ def time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse, dev, st
         barrier()
         t0 = time.perf_counter()
         for i in range(steps):
-            run(i if rotating else 0)
+            out = run(i if rotating else 0)
         enq = time.perf_counter() - t0  # host time to enqueue the steps (launch-bound when ~= elapsed)
         barrier()
         el = time.perf_counter() - t0
@@ -513,23 +578,27 @@ def time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse, dev, st
             t = torch.tensor([el], device="cpu" if rehearse else dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t)
-        return el / steps * 1e3, enq / steps * 1e3
+        return el / steps * 1e3, enq / steps * 1e3, out
 
     rotation = None
-    if nrot > 1:
-        ms_one, _ = timed(False)
-        ms, enq_ms = timed(True)
+    if nrot > 1 and a.full:
+        ms_one, _, _ = timed(False)
+        ms, enq_ms, last = timed(True)
         rotation = {"batches": nrot, "ms_per_step_one_batch_replayed": round(ms_one, 4),
                     "ms_per_step_rotating": round(ms, 4),
                     "what": f"the timed steps cycle through {nrot} distinct synthetic batches (one captured hipGraph "
                             "each, replayed round robin): `value` is the ROTATING number; the single-batch replay "
                             "beside it shows what a resident batch would be worth"}
     else:
-        ms, enq_ms = timed(False)
+        ms, enq_ms, last = timed(nrot > 1)
+        if nrot > 1:
+            rotation = {"batches": nrot, "ms_per_step_rotating": round(ms, 4),
+                        "what": f"the timed steps cycle through {nrot} distinct synthetic batches (one captured "
+                                "hipGraph each, replayed round robin); --full times the single-batch replay beside it"}
     if any_overflow():
         raise SystemExit("[bench] a timed batch overflowed the fixed-capacity exchange: rerun with --exchange dynamic")
     kind = "segments between the collectives" if segments else graphs is not None
-    return ms, enq_ms, kind, fixed, rotation
+    return ms, enq_ms, kind, fixed, rotation, last
 
 
 def train_step_record(a, w, engine, dev, B, V, steps=60):
@@ -617,8 +686,9 @@ def step_hbm(w, B, ms):
 
 
 def measure(a, wname, dev, rank, world, dist, rehearse, sharded, live_traffic, fallback, steps, warmup,
-            cpu_budget, zipf=0.0, want_cpu=True, want_opt=True):
-    """One workload at the current world size -> its record (dict)."""
+            cpu_budget, zipf=0.0, want_cpu=True, want_opt=True, dump_dir=""):
+    """One workload at the current world size -> its record (dict).  Without --full: the timed steps alone.
+    dump_dir: where dump_outputs() writes what the last timed step computed (rank 0)."""
     w = dict(WORKLOADS[wname])
     B = a.batch or w["B"]
     V = a.vocab or w["V"]
@@ -626,17 +696,20 @@ def measure(a, wname, dev, rank, world, dist, rehearse, sharded, live_traffic, f
     # further batches to rotate through (the big-table configs[4] keeps one: its table alone is 51 GB)
     nrot = max(1, a.rotate) if (not sharded and w["D"] * w["V"] * w["F"] < 1 << 31) else 1
     batches = [synth_inputs(w, B, V, dev, 2019 + rank + 1000 * k, zipf) for k in range(1, nrot)]
-    ms, enq_ms, graph_kind, fixed, rotation = time_steps(a, engine, idx, dense, y, sharded, world, dist, rehearse,
-                                                         dev, steps, warmup, batches)
+    ms, enq_ms, graph_kind, fixed, rotation, last_loss = time_steps(a, engine, idx, dense, y, sharded, world, dist,
+                                                                    rehearse, dev, steps, warmup, batches)
     value = world * B / (ms * 1e-3)
+    if dump_dir and rank == 0:
+        # before anything below launches more kernels into the engine's buffers
+        dump_outputs(engine, last_loss, dump_dir)
 
     # ---- rooflines of the hand-written hot kernels, HIP events on the stream they run on ----
     # (sharded: only for the models whose dominant kernel is the gather; rank 0, local kernel only)
     roofs = []
-    if not sharded or (rank == 0 and w["model"] == "deepfm"):
+    if a.full and (not sharded or (rank == 0 and w["model"] == "deepfm")):
         roofs = engine.roofline_probe_all(idx, dense, y, iters=max(10, min(steps, 50)))
-        full = not sharded and B == w["B"] and V == w["V"] and zipf == 0
-        attach_traffic(roofs, wname, live_traffic if full else {}, fallback if full else {})
+        full_size = not sharded and B == w["B"] and V == w["V"] and zipf == 0
+        attach_traffic(roofs, wname, live_traffic if full_size else {}, fallback if full_size else {})
     for r in roofs:
         r.pop("fn", None)
 
@@ -675,14 +748,17 @@ def measure(a, wname, dev, rank, world, dist, rehearse, sharded, live_traffic, f
                                 else "dynamic split sizes (one host sync per batch)")
                              + f", {engine.micro_batches} micro-batch(es) per step") if sharded
                    else "single GPU"},
-        "roofline": roofs[0] if roofs else None,
     }
+    if a.full:
+        rec["roofline"] = roofs[0] if roofs else None
     if sharded:
         rec["exchange"] = exchange_record(engine, world, (dist.get_backend() if dist is not None else "none"), B, w)
     if len(roofs) > 1:
         rec["rooflines"] = roofs
-    if w["model"] == "deepfm" and not sharded:
+    if a.full and w["model"] == "deepfm" and not sharded:
         rec["step_hbm"] = step_hbm(w, B, ms)
+    want_opt = want_opt and a.full
+    want_cpu = want_cpu and a.full
     if rank == 0 and want_opt and not a.no_optimizer:
         # reported separately (the headline metric is fwd+bwd only): the row-wise step on the table
         # rows this batch touched + dense Adam on the dense parameters
@@ -753,7 +829,8 @@ def collect(a, rank, world, local, dist, rehearse, backend, live, pmc_note, fall
     dev = torch.device("cuda", local)
     wname = a.workload or "deepfm"
     sharded = world > 1 or a.force_sharded
-    plain = a.workload is None and not a.only and not a.batch and not a.vocab and a.zipf == 0
+    # the sub-records: a --full run with no workload named
+    plain = a.full and a.workload is None and not a.only and not a.batch and not a.vocab and a.zipf == 0
     extras = plain and world == 1 and not a.force_sharded
     bname = {"nccl": "nccl (RCCL over xGMI)", "gloo": "gloo (one-GPU rehearsal, host-staged)"}.get(
         backend, backend) if backend else "none (single process)"
@@ -766,7 +843,7 @@ def collect(a, rank, world, local, dist, rehearse, backend, live, pmc_note, fall
         return _sub(r, steps=steps, warmup=warm)
 
     rec = measure(a, wname, dev, rank, world, dist, rehearse, sharded, live, fallback, a.steps, a.warmup,
-                  a.cpu_budget or 20.0, zipf=a.zipf)
+                  a.cpu_budget or 20.0, zipf=a.zipf, dump_dir=a.dump_outputs)
     out = {
         "metric": METRIC, "value": rec.pop("value"), "unit": rec.pop("unit"), "n_gpus": world,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": rec.pop("ms_per_step"),
@@ -798,7 +875,7 @@ def collect(a, rank, world, local, dist, rehearse, backend, live, pmc_note, fall
                                          note="per-GPU batch 65536 (weak scaling)")
         if world > 1:
             wl["xdeepfm"] = sharded_sub("xdeepfm", 0, sub_steps, sub_warm)
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         out["pmc_passes"] = pmc_note
     return out
 
@@ -820,7 +897,7 @@ def rank_main(a, rank, world, local):
         # ---- HBM traffic of the roofline kernels: rocprofv3 --pmc child passes, BEFORE any GPU call here ----
         live, pmc_note = {}, "not requested"
         full_size = not a.batch and not a.vocab and a.zipf == 0
-        if rank == 0 and world == 1 and not sharded and not a.no_pmc and full_size:
+        if a.full and rank == 0 and world == 1 and not sharded and not a.no_pmc and full_size:
             t0 = time.perf_counter()
             live, pmc_note = pmc_passes(["deepfm", "xdeepfm", "dcn"] if extras else [wname])
             pmc_note = pmc_note or f"ok ({time.perf_counter() - t0:.0f} s)"

@@ -154,3 +154,60 @@ def test_default_run_is_the_contract_line_plus_sub_records():
     assert a.gpus == 1 and a.workload is None and not a.only and a.steps > 0 and a.warmup > 0
     assert bench.parse(["--workload", "dcn"]).workload == "dcn"
     assert set(bench.CONFIG_NO) == {"deepfm", "xdeepfm", "dcn", "xdeepfm_100m"}
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse(bad)
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(f"{bad} accepted")
+
+
+class _FakeEngine:
+    """The output attributes of recman_amd.engine.Engine on CPU tensors."""
+
+    def __init__(self, B, F, D, seed=0):
+        import torch
+
+        g = torch.Generator().manual_seed(seed)
+        self.logit = torch.randn(B, generator=g)
+        self.pred = torch.sigmoid(self.logit)
+        self.dlogit = torch.randn(B, generator=g)
+        self.d_rows = torch.randn(B, F, D, generator=g)
+        self.d_bias = None
+        self.grads = {"linear_w0": torch.randn(1, generator=g), "dnn_w": torch.randn(32, 1, generator=g),
+                      "dnn_layer_0_weights": torch.randn(F * D + 13, 32, generator=g, dtype=torch.float64)}
+        self.loss = torch.randn(1, generator=g)
+
+
+def test_dump_outputs_writes_every_output_and_samples_the_big_ones_the_same_way(tmp_path):
+    import numpy as np
+
+    B, F, D = 6000, 26, 16  # d_rows: 2.5 M elements, over DUMP_MAX_ELEMS
+    e = _FakeEngine(B, F, D)
+    for d in ("a", "b"):
+        bench.dump_outputs(e, e.loss, str(tmp_path / d))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(["loss.npy", "logit.npy", "pred.npy", "dlogit.npy", "d_rows.npy", "grad_linear_w0.npy",
+                            "grad_dnn_w.npy", "grad_dnn_layer_0_weights.npy"])
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    assert np.array_equal(np.load(tmp_path / "a" / "logit.npy"), e.logit.numpy())
+    assert np.load(tmp_path / "a" / "grad_dnn_layer_0_weights.npy").dtype == np.float64
+    rows = np.load(tmp_path / "a" / "d_rows.npy")
+    n = bench.DUMP_MAX_ELEMS // (F * D)
+    assert rows.shape == (n, F, D)
+    # a fixed sample of whole rows of the batch: each dumped row is one of d_rows, in ascending order
+    flat = e.d_rows.reshape(B, -1).numpy()
+    first = {r.tobytes(): i for i, r in enumerate(flat)}
+    at = [first[r.tobytes()] for r in rows.reshape(n, -1)]
+    assert at == sorted(at) and len(set(at)) == n
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

@@ -27,7 +27,7 @@ def traf(x):
 o = d["optimizer_step"]
 s = f"""# {tag} - rocprofv3 kernel summaries of the three single-GPU bench workloads (end of round 3)
 
-`bash tools/final_profiles.sh {run}` on one MI355X: the default `python3 bench.py --steps 30 --warmup 5` line is `profiles/{tag}_bench_default.json`; per workload `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload W --steps 20 --warmup 3 --no-cpu-baseline --no-graph --no-pmc --no-optimizer` (eager launches so that every kernel is attributed; call counts include the 0.25 s of untimed pre-warm steps; torch's one-off initialisation kernels filtered out; a profiled run holds a 3-5 % lower clock than the un-profiled bench line).
+`bash tools/final_profiles.sh {run}` on one MI355X: the `python3 bench.py --full --steps 30 --warmup 5` line is `profiles/{tag}_bench_default.json`; per workload `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --workload W --steps 20 --warmup 3 --no-cpu-baseline --no-graph --no-pmc --no-optimizer` (eager launches so that every kernel is attributed; call counts include the 0.25 s of untimed pre-warm steps; torch's one-off initialisation kernels filtered out; a profiled run holds a 3-5 % lower clock than the un-profiled bench line).
 
 ## deepfm
 
