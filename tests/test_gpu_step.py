@@ -18,7 +18,7 @@ CASES = [
     dict(B=33, F=7, Dn=16, hidden=(32, 24)),                 # Dn at its limit, ragged last tile
     dict(B=16 * 9 + 1, F=26, Dn=16, hidden=(8, 8)),          # the widest x the kernel takes
     dict(B=1, F=1, Dn=1, hidden=(32, 1)),
-    dict(B=1000, F=21, Dn=2, hidden=(24, 32), scale=0.1),    # several tiles per block round, 3-slot workers
+    dict(B=1000, F=21, Dn=2, hidden=(24, 32), scale=0.1),    # 63 tiles on 63 blocks, one each; 3-slot workers
 ]
 
 
