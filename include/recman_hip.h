@@ -575,6 +575,37 @@ int rm_gather_rows(const float *table, int64_t table_ld, const int64_t *rows, in
 int rm_permute_rows(const float *src, const int64_t *slot, int64_t n, int width, int inverse,
                     float *dst, rm_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Evaluation metrics of a prediction vector (csrc/metrics.hip): what fit() / evaluate() score with.
+ * Replaces recman/metrics/roc_auc.py:4-16 and recman/metrics/logloss.py:4-19 (sklearn's roc_auc_score /
+ * log_loss on the host) and the scoring of DeepModel.py:72-74,92-131.
+ *
+ *   scores / pred [n]  fp32 (any finite value for the AUC; probabilities for the log loss)
+ *   labels [n]         int64 0 / 1;   1 <= n <= 2^31 - 1
+ *   workspace          rm_metric_workspace(n) BYTES, 16-byte aligned; one workspace serves both calls
+ *   out                ONE device record, read by the host in one copy
+ * rm_roc_auc: the exact Mann-Whitney AUC, ties counted one half: 2U in uint64, one division in double.
+ * rm_log_loss: -mean(log(clip(p or 1 - p))) with the clip in fp32 at eps (and 1 - eps), log and sum in
+ *   fp64 - sklearn 1.7.2's binary log_loss on float32 input when eps = FLT_EPSILON.  0 < eps < 0.5.
+ * Both are deterministic (fixed-order reductions, no float atomics).  Invalid inputs do not fail the call:
+ * they set bits of out->flags, and the value is then meaningless.  With one class present (pos or neg 0)
+ * RM_METRIC_ONE_CLASS is set and the AUC is NaN. */
+#define RM_METRIC_BAD_LABEL 1  /* a label outside {0, 1}                  */
+#define RM_METRIC_BAD_SCORE 2  /* a NaN or infinite score                  */
+#define RM_METRIC_ONE_CLASS 4  /* every label equal                        */
+#define RM_METRIC_PROB_RANGE 8 /* rm_log_loss: a probability outside [0, 1] */
+typedef struct rm_metric_result {
+  double value;
+  int64_t pos;   /* P: labels equal to 1 */
+  int64_t neg;   /* N = n - P            */
+  int64_t flags; /* RM_METRIC_*          */
+} rm_metric_result;
+int64_t rm_metric_workspace(int64_t n);
+int rm_roc_auc(const float *scores, const int64_t *labels, int64_t n, void *workspace, rm_metric_result *out,
+               rm_stream_t stream);
+int rm_log_loss(const float *pred, const int64_t *labels, int64_t n, float eps, void *workspace,
+                rm_metric_result *out, rm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,8 @@ SIGNATURES = {
     "rm_dense_wgrad": [P, I64, c_int, P, I64, c_int, P, I64, c_int, I64, P, I64, c_int, P, P, I64, P],
     "rm_dense_wgrad6": [P, I64, c_int, P, I64, c_int, P, I64, c_int, P, I64, c_int, I64, P, I64, P, I64, c_int, P, P,
                         I64, P],
+    "rm_roc_auc": [P, P, I64, P, P, P],
+    "rm_log_loss": [P, P, I64, c_float, P, P, P],
 }
 
 
@@ -104,6 +106,7 @@ SIGNATURES_I64 = {
     "rm_dense_wgrad6_workspace": [c_int, c_int, I64],
     "rm_dense_wgrad_workspace": [c_int, c_int, I64],
     "rm_sparse_optimizer_workspace": [I64],
+    "rm_metric_workspace": [I64],
 }
 
 

@@ -1,0 +1,628 @@
+// Exact binary ROC AUC and log loss of a prediction vector, on the device: the metrics fit() and
+// evaluate() score with.  Replaces recman/metrics/roc_auc.py:4-16 and recman/metrics/logloss.py:4-19
+// (sklearn.metrics.roc_auc_score / log_loss on the host, DeepModel.py:72-74,92-131); see recman_hip.h.
+//
+// ROC AUC (Mann-Whitney): sort the scores, group equal scores, and with [a, b) the sorted positions of a
+// positive example's group
+//     2U = sum_{positives} (a + b + 1) - P (P + 1),   AUC = 2U / (2 P N)
+// (a + b + 1 is twice the 1-based mid-rank of the group).  Every term is an integer: 2U is counted in uint64
+// and divided once in double, so the result is exact up to that rounding and does not depend on the order of
+// anything.  Kernels, in launch order:
+//   auc_keys_kernel       validate, score -> order-preserving uint32 key, label -> byte; P; the four
+//                         digit histograms of all keys (one read)
+//   auc_plan_kernel       which of the four 8-bit digits vary (a constant digit's pass is skipped) and the
+//                         global digit bases of each pass
+//   per pass (LSD radix sort of (key, label), 4096 keys per tile):
+//     auc_hist_kernel       per-tile digit counts
+//     auc_scan_kernel       device-wide exclusive scan of the counts, digit-major
+//     auc_sort_pass_kernel  stable tile-local ranking (wave match + per-wave counters) staged through LDS,
+//                           then a scatter in runs of equal digits
+//   auc_groups_kernel     per tile: group starts / ends (neighbour keys across the tile edges), the known
+//                         part of sum (a + b + 1) and the positives whose group runs past either edge
+//   auc_final_kernel      resolves those edge groups with a prefix max / suffix min over the tiles and
+//                         writes the record
+// One sort path serves every score: the label rides as a byte beside the key.  A keys-only sort of
+// (bits << 1 | label) would save 2 B/element per pass (about 15 %) but holds only for scores >= +0.
+// Log loss: logloss_kernel (fp32 clip as sklearn 1.7.2, log and sum in fp64, per-block partials) and
+// logloss_final_kernel (fixed-order reduction).  No float atomics anywhere: bitwise reproducible.
+#include <math.h>
+
+#include "rm_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;             // 4 waves: every kernel here
+constexpr int kWaves = kThreads / 64;
+constexpr int kItems = 16;                // keys per thread of a sort / group tile
+constexpr int kTile = kThreads * kItems;  // 4096
+constexpr int kRadix = 256;               // 8-bit digits
+constexpr int kPasses = 4;
+constexpr int kKeyBlocks = 1024;          // grid cap of the grid-stride passes
+constexpr int kLossBlocks = 1024;
+constexpr unsigned kNoEnd = 0xFFFFFFFFu;  // "group end not in this tile" (ends are <= n <= 2^31 - 1)
+
+struct AucHeader {
+  unsigned long long pos;               // P
+  unsigned flags;                       // RM_METRIC_* of the inputs
+  unsigned pad;
+  unsigned ghist[kPasses][kRadix];      // digit p of every key
+  int m;                                // passes that run (digits that vary)
+  int shift[kPasses];                   // their bit offsets, low digit first
+  unsigned base[kPasses][kRadix];       // exclusive scan of the pass's global digit counts
+};
+
+struct Layout {
+  size_t header, hist, part, head, tail, last, first, keys0, keys1, lab0, lab1, total;
+  size_t loss_part, loss_pos, loss_flags, loss_total;
+};
+
+inline size_t take(size_t &o, size_t bytes) {
+  const size_t at = o;
+  o += (bytes + 255) & ~size_t(255);
+  return at;
+}
+
+Layout layout(int64_t n) {
+  const size_t tiles = (size_t)((n + kTile - 1) / kTile), un = (size_t)n;
+  Layout L;
+  size_t o = 0;
+  L.header = take(o, sizeof(AucHeader));
+  L.hist = take(o, 4 * kRadix * tiles);
+  L.part = take(o, 8 * tiles);
+  L.head = take(o, 4 * tiles);
+  L.tail = take(o, 4 * tiles);
+  L.last = take(o, 4 * tiles);
+  L.first = take(o, 4 * tiles);
+  L.keys0 = take(o, 4 * un);
+  L.keys1 = take(o, 4 * un);
+  L.lab0 = take(o, un);
+  L.lab1 = take(o, un);
+  L.total = o;
+  o = 0;  // log loss uses the front of the same workspace
+  L.loss_part = take(o, 8 * kLossBlocks);
+  L.loss_pos = take(o, 8 * kLossBlocks);
+  L.loss_flags = take(o, 4 * kLossBlocks);
+  L.loss_total = o;
+  return L;
+}
+
+// order-preserving key of a float; -0.0 is canonicalised to +0.0 (they compare equal and must tie)
+__device__ __forceinline__ unsigned score_key(float s) {
+  unsigned b = __float_as_uint(s);
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// block-wide sum in a fixed order (every lane of the block gets it); sm: kWaves entries
+template <typename T>
+__device__ T block_sum(T v, T *sm) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = sm[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) s += sm[w];
+  __syncthreads();
+  return s;
+}
+
+// block-wide inclusive scan (kRev: from the last thread down) of a commutative, associative op
+template <bool kRev, typename T, typename Op>
+__device__ T block_scan(T v, Op op, T *sm) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T u = kRev ? __shfl_down(v, o, 64) : __shfl_up(v, o, 64);
+    if (kRev ? lane + o < 64 : lane >= o) v = op(v, u);
+  }
+  if (lane == (kRev ? 0 : 63)) sm[w] = v;
+  __syncthreads();
+  if (kRev) {
+    for (int i = w + 1; i < kWaves; ++i) v = op(v, sm[i]);
+  } else {
+    for (int i = 0; i < w; ++i) v = op(v, sm[i]);
+  }
+  __syncthreads();
+  return v;
+}
+
+struct OpAdd {
+  template <typename T>
+  __device__ T operator()(T a, T b) const { return a + b; }
+};
+struct OpMax {
+  template <typename T>
+  __device__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+struct OpMin {
+  template <typename T>
+  __device__ T operator()(T a, T b) const { return a < b ? a : b; }
+};
+
+// ------------------------------------------------------------------------------------------ ROC AUC
+__global__ __launch_bounds__(kThreads) void auc_keys_kernel(const float *__restrict__ scores,
+                                                            const int64_t *__restrict__ labels, int64_t n,
+                                                            unsigned *__restrict__ keys,
+                                                            unsigned char *__restrict__ lab,
+                                                            AucHeader *__restrict__ hd) {
+  __shared__ unsigned h[kPasses * kRadix];
+  __shared__ unsigned long long smp[kWaves];
+  __shared__ unsigned smf[kWaves];
+  for (int i = threadIdx.x; i < kPasses * kRadix; i += kThreads) h[i] = 0u;
+  __syncthreads();
+  unsigned long long pos = 0;
+  unsigned flags = 0;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+    const float s = scores[i];
+    const int64_t y = labels[i];
+    if (!isfinite(s)) flags |= RM_METRIC_BAD_SCORE;
+    if (y != 0 && y != 1) flags |= RM_METRIC_BAD_LABEL;
+    const unsigned k = score_key(s);
+    keys[i] = k;
+    lab[i] = (unsigned char)(y == 1);
+    pos += (y == 1);
+#pragma unroll
+    for (int p = 0; p < kPasses; ++p) atomicAdd(&h[p * kRadix + ((k >> (8 * p)) & 255u)], 1u);
+  }
+  pos = wave_sum(pos);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) flags |= __shfl_xor(flags, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    smp[threadIdx.x >> 6] = pos;
+    smf[threadIdx.x >> 6] = flags;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long p = 0;
+    unsigned f = 0;
+    for (int w = 0; w < kWaves; ++w) {
+      p += smp[w];
+      f |= smf[w];
+    }
+    if (p) atomicAdd(&hd->pos, p);
+    if (f) atomicOr(&hd->flags, f);
+  }
+  for (int i = threadIdx.x; i < kPasses * kRadix; i += kThreads)
+    if (h[i]) atomicAdd(&hd->ghist[i / kRadix][i % kRadix], h[i]);
+}
+
+__global__ __launch_bounds__(kThreads) void auc_plan_kernel(AucHeader *__restrict__ hd, int64_t n) {
+  __shared__ unsigned sm[kWaves];
+  const int d = threadIdx.x;
+  int m = 0;
+  for (int p = 0; p < kPasses; ++p) {
+    const unsigned c = hd->ghist[p][d];
+    if (__syncthreads_or(c == (unsigned)n)) continue;  // one digit value for every key: nothing to sort
+    const unsigned incl = block_scan<false>(c, OpAdd(), sm);
+    hd->base[m][d] = incl - c;
+    if (d == 0) hd->shift[m] = 8 * p;
+    ++m;
+  }
+  if (d == 0) hd->m = m;
+}
+
+__global__ __launch_bounds__(kThreads) void auc_hist_kernel(const AucHeader *__restrict__ hd, int slot,
+                                                            const unsigned *__restrict__ keys0,
+                                                            const unsigned *__restrict__ keys1, int64_t n,
+                                                            int64_t tiles, unsigned *__restrict__ hist) {
+  if (slot >= hd->m) return;
+  const int shift = hd->shift[slot];
+  const unsigned *keys = (slot & 1) ? keys1 : keys0;
+  __shared__ unsigned h[kRadix];
+  h[threadIdx.x] = 0u;
+  __syncthreads();
+  const int64_t t0 = (int64_t)blockIdx.x * kTile;
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int64_t i = t0 + j * kThreads + threadIdx.x;
+    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  hist[(int64_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// one block per digit: its row of per-tile counts -> global positions (base of the digit + the counts of
+// the tiles before)
+__global__ __launch_bounds__(kThreads) void auc_scan_kernel(const AucHeader *__restrict__ hd, int slot,
+                                                            int64_t tiles, unsigned *__restrict__ hist) {
+  if (slot >= hd->m) return;
+  __shared__ unsigned sm[kWaves];
+  const int d = blockIdx.x;
+  unsigned *row = hist + (int64_t)d * tiles;
+  const int64_t seg = (tiles + kThreads - 1) / kThreads;
+  const int64_t lo = min((int64_t)threadIdx.x * seg, tiles), hi = min(lo + seg, tiles);
+  unsigned s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += row[i];
+  const unsigned incl = block_scan<false>(s, OpAdd(), sm);
+  unsigned run = hd->base[slot][d] + incl - s;
+  for (int64_t i = lo; i < hi; ++i) {
+    const unsigned c = row[i];
+    row[i] = run;
+    run += c;
+  }
+}
+
+// One LSD pass over a tile of 4096 (key, label) pairs.  Wave w holds tile positions [1024 w, 1024 w + 1024),
+// item j of lane l at 1024 w + 64 j + l: the tile order is (wave, item, lane), which the ranking keeps.  Past
+// the end of the array a slot holds key 0xFFFFFFFF: it ranks after every real key of digit 255 and is never
+// written.
+__global__ __launch_bounds__(kThreads) void auc_sort_pass_kernel(
+    const AucHeader *__restrict__ hd, int slot, unsigned *__restrict__ keys0, unsigned *__restrict__ keys1,
+    unsigned char *__restrict__ lab0, unsigned char *__restrict__ lab1, int64_t n, int64_t tiles,
+    const unsigned *__restrict__ hist) {
+  if (slot >= hd->m) return;
+  const int shift = hd->shift[slot];
+  const unsigned *src_k = (slot & 1) ? keys1 : keys0;
+  unsigned *dst_k = (slot & 1) ? keys0 : keys1;
+  const unsigned char *src_l = (slot & 1) ? lab1 : lab0;
+  unsigned char *dst_l = (slot & 1) ? lab0 : lab1;
+
+  __shared__ unsigned wcnt[kWaves][kRadix];  // per-wave digit counters, then per-wave digit offsets
+  __shared__ unsigned tstart[kRadix];        // first tile rank of each digit
+  __shared__ unsigned gofs[kRadix];          // global position of that rank
+  __shared__ unsigned skey[kTile];
+  __shared__ unsigned char slab[kTile];
+  __shared__ unsigned sm[kWaves];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&wcnt[0][0])[i] = 0u;
+  __syncthreads();
+  const int64_t t0 = (int64_t)blockIdx.x * kTile;
+  const int valid = (int)min((int64_t)kTile, n - t0);
+  const unsigned long long below_mask = (1ull << lane) - 1ull;
+
+  unsigned k[kItems], r[kItems], lbits = 0u;
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int li = w * (kTile / kWaves) + j * 64 + lane;
+    unsigned key = 0xFFFFFFFFu, y = 0u;
+    if (li < valid) {
+      key = src_k[t0 + li];
+      y = src_l[t0 + li];
+    }
+    k[j] = key;
+    lbits |= y << j;
+    const unsigned d = (key >> shift) & 255u;
+    unsigned long long peers = ~0ull;  // lanes with the same digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const unsigned long long bal = __ballot(bit);
+      peers &= bit ? bal : ~bal;
+    }
+    const unsigned before = (unsigned)__popcll(peers & below_mask);
+    const int leader = __ffsll((long long)peers) - 1;
+    unsigned old = 0u;
+    if (before == 0u) old = atomicAdd(&wcnt[w][d], (unsigned)__popcll(peers));
+    r[j] = (unsigned)__shfl((int)old, leader, 64) + before;
+  }
+  __syncthreads();
+  {
+    const int d = tid;
+    unsigned run = 0u;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) {
+      const unsigned c = wcnt[v][d];
+      wcnt[v][d] = run;
+      run += c;
+    }
+    const unsigned incl = block_scan<false>(run, OpAdd(), sm);
+    tstart[d] = incl - run;
+    gofs[d] = hist[(int64_t)d * tiles + blockIdx.x];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const unsigned d = (k[j] >> shift) & 255u;
+    const unsigned rank = tstart[d] + wcnt[w][d] + r[j];
+    skey[rank] = k[j];
+    slab[rank] = (unsigned char)((lbits >> j) & 1u);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int li = j * kThreads + tid;
+    if (li < valid) {
+      const unsigned key = skey[li];
+      const unsigned d = (key >> shift) & 255u;
+      const int64_t g = (int64_t)gofs[d] + (li - (int)tstart[d]);
+      dst_k[g] = key;
+      dst_l[g] = slab[li];
+    }
+  }
+}
+
+// Per tile of the sorted keys: thread t owns positions c0 + 16 t .. c0 + 16 t + 15.  For a positive at position
+// i in group [a, b) it adds a + b + 1 where a (b) lies inside the tile, and counts it in head (tail) where the
+// group starts before (ends after) the tile; last / first: the tile's last group start and first group end.
+__global__ __launch_bounds__(kThreads) void auc_groups_kernel(
+    const AucHeader *__restrict__ hd, const unsigned *__restrict__ keys0, const unsigned *__restrict__ keys1,
+    const unsigned char *__restrict__ lab0, const unsigned char *__restrict__ lab1, int64_t n,
+    unsigned long long *__restrict__ part, unsigned *__restrict__ head, unsigned *__restrict__ tail,
+    int *__restrict__ last, unsigned *__restrict__ first) {
+  const int m = hd->m;  // the sorted pairs are in buffer m & 1
+  const unsigned *keys = (m & 1) ? keys1 : keys0;
+  const unsigned char *lab = (m & 1) ? lab1 : lab0;
+  __shared__ unsigned sk[kTile + 2];  // sk[1 + li]; sk[0] / sk[valid + 1]: the neighbours across the edges
+  __shared__ unsigned char sl[kTile];
+  __shared__ int exs[kThreads];
+  __shared__ unsigned exe[kThreads];
+  __shared__ int smi[kWaves];
+  __shared__ unsigned smu[kWaves];
+  __shared__ unsigned long long sml[kWaves];
+
+  const int tid = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * kTile;
+  const int valid = (int)min((int64_t)kTile, n - c0);
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const int li = j * kThreads + tid;
+    if (li < valid) {
+      sk[1 + li] = keys[c0 + li];
+      sl[li] = lab[c0 + li];
+    }
+  }
+  if (tid == 0) sk[0] = c0 > 0 ? keys[c0 - 1] : 0u;
+  if (tid == 1) sk[valid + 1] = c0 + valid < n ? keys[c0 + valid] : 0u;
+  __syncthreads();
+
+  unsigned sbits = 0u, ebits = 0u, pbits = 0u;
+  int agg_s = -1;
+  unsigned agg_e = kNoEnd;
+#pragma unroll
+  for (int q = 0; q < kItems; ++q) {
+    const int li = tid * kItems + q;
+    if (li < valid) {
+      const int64_t i = c0 + li;
+      const bool st = i == 0 || sk[li + 1] != sk[li];
+      const bool en = i == n - 1 || sk[li + 1] != sk[li + 2];
+      sbits |= (unsigned)st << q;
+      ebits |= (unsigned)en << q;
+      pbits |= (unsigned)sl[li] << q;
+      if (st) agg_s = (int)i;
+      if (en && agg_e == kNoEnd) agg_e = (unsigned)(i + 1);
+    }
+  }
+  // last start among the threads before, first end among the threads after
+  const int incl_s = block_scan<false>(agg_s, OpMax(), smi);
+  const unsigned incl_e = block_scan<true>(agg_e, OpMin(), smu);
+  exs[tid] = incl_s;
+  exe[tid] = incl_e;
+  __syncthreads();
+  const int carry_s = tid > 0 ? exs[tid - 1] : -1;
+  const unsigned carry_e = tid + 1 < kThreads ? exe[tid + 1] : kNoEnd;
+
+  int a[kItems];
+  int run = carry_s;
+#pragma unroll
+  for (int q = 0; q < kItems; ++q) {
+    if ((sbits >> q) & 1u) run = (int)(c0 + tid * kItems + q);
+    a[q] = run;
+  }
+  unsigned long long acc = 0;
+  unsigned nh = 0u, nt = 0u;
+  unsigned b = carry_e;
+#pragma unroll
+  for (int q = kItems - 1; q >= 0; --q) {
+    if ((ebits >> q) & 1u) b = (unsigned)(c0 + tid * kItems + q + 1);
+    if ((pbits >> q) & 1u) {
+      acc += 1ull + (a[q] >= 0 ? (unsigned long long)a[q] : 0ull) + (b != kNoEnd ? (unsigned long long)b : 0ull);
+      nh += a[q] < 0;
+      nt += b == kNoEnd;
+    }
+  }
+  acc = block_sum(acc, sml);
+  nh = block_sum(nh, smu);
+  nt = block_sum(nt, smu);
+  if (tid == 0) {
+    part[blockIdx.x] = acc;
+    head[blockIdx.x] = nh;
+    tail[blockIdx.x] = nt;
+    last[blockIdx.x] = exs[kThreads - 1];
+    first[blockIdx.x] = exe[0];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void auc_final_kernel(
+    const AucHeader *__restrict__ hd, int64_t n, int64_t tiles, const unsigned long long *__restrict__ part,
+    const unsigned *__restrict__ head, const unsigned *__restrict__ tail, const int *__restrict__ last,
+    const unsigned *__restrict__ first, rm_metric_result *__restrict__ out) {
+  __shared__ int smi[kWaves];
+  __shared__ unsigned smu[kWaves];
+  __shared__ unsigned long long sml[kWaves];
+  __shared__ int exs[kThreads];
+  __shared__ unsigned exe[kThreads];
+  const int tid = threadIdx.x;
+  const int64_t seg = (tiles + kThreads - 1) / kThreads;
+  const int64_t lo = min((int64_t)tid * seg, tiles), hi = min(lo + seg, tiles);
+  int agg_s = -1;
+  unsigned agg_e = kNoEnd;
+  for (int64_t c = lo; c < hi; ++c) {
+    agg_s = max(agg_s, last[c]);
+    agg_e = min(agg_e, first[c]);
+  }
+  exs[tid] = block_scan<false>(agg_s, OpMax(), smi);
+  exe[tid] = block_scan<true>(agg_e, OpMin(), smu);
+  __syncthreads();
+  // a tile's head positives belong to the group of the last start before it, its tail positives to the
+  // group of the first end after it (position 0 starts and position n - 1 ends a group: both exist
+  // whenever they are needed)
+  unsigned long long acc = 0;
+  int run = tid > 0 ? exs[tid - 1] : -1;
+  for (int64_t c = lo; c < hi; ++c) {
+    acc += part[c];
+    if (head[c]) acc += (unsigned long long)head[c] * (unsigned long long)run;
+    run = max(run, last[c]);
+  }
+  unsigned runE = tid + 1 < kThreads ? exe[tid + 1] : kNoEnd;
+  for (int64_t c = hi - 1; c >= lo; --c) {
+    if (tail[c]) acc += (unsigned long long)tail[c] * (unsigned long long)runE;
+    runE = min(runE, first[c]);
+  }
+  acc = block_sum(acc, sml);
+  if (tid == 0) {
+    const unsigned long long P = hd->pos, N = (unsigned long long)n - P;
+    long long flags = hd->flags;
+    double v;
+    if (P == 0 || N == 0) {
+      flags |= RM_METRIC_ONE_CLASS;
+      v = __builtin_nan("");
+    } else {
+      const unsigned long long two_u = acc - P * (P + 1ull);
+      v = (double)two_u / (2.0 * (double)P * (double)N);
+    }
+    out->value = v;
+    out->pos = (int64_t)P;
+    out->neg = (int64_t)N;
+    out->flags = flags;
+  }
+}
+
+// ----------------------------------------------------------------------------------------- log loss
+// sklearn 1.7.2 binary log_loss on float32 y_pred: p and 1 - p clipped in fp32 to [eps, 1 - eps], the log of
+// the one the label selects taken in fp64, summed in fp64, divided by n.  Probabilities outside [0, 1] are
+// flagged (sklearn raises on them).
+__global__ __launch_bounds__(kThreads) void logloss_kernel(const float *__restrict__ pred,
+                                                           const int64_t *__restrict__ labels, int64_t n,
+                                                           float eps, double *__restrict__ part,
+                                                           unsigned long long *__restrict__ pos,
+                                                           unsigned *__restrict__ flags) {
+  __shared__ double smd[kWaves];
+  __shared__ unsigned long long sml[kWaves];
+  __shared__ unsigned smu[kWaves];
+  const float hi = 1.0f - eps;
+  double acc = 0.0;
+  unsigned long long np = 0;
+  unsigned f = 0;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+    const float x = pred[i];
+    const int64_t y = labels[i];
+    if (!isfinite(x)) f |= RM_METRIC_BAD_SCORE;
+    if (x < 0.0f || x > 1.0f) f |= RM_METRIC_PROB_RANGE;
+    if (y != 0 && y != 1) f |= RM_METRIC_BAD_LABEL;
+    const float c = fminf(fmaxf(x, eps), hi);
+    const float v = y == 1 ? c : 1.0f - c;
+    acc += log((double)v);
+    np += (y == 1);
+  }
+  acc = block_sum(acc, smd);
+  np = block_sum(np, sml);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) f |= __shfl_xor(f, o, 64);
+  if ((threadIdx.x & 63) == 0) smu[threadIdx.x >> 6] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) f |= smu[w];
+    part[blockIdx.x] = acc;
+    pos[blockIdx.x] = np;
+    flags[blockIdx.x] = f;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void logloss_final_kernel(const double *__restrict__ part,
+                                                                 const unsigned long long *__restrict__ pos,
+                                                                 const unsigned *__restrict__ flags, int nb,
+                                                                 int64_t n, rm_metric_result *__restrict__ out) {
+  __shared__ double smd[kWaves];
+  __shared__ unsigned long long sml[kWaves];
+  __shared__ unsigned smu[kWaves];
+  double s = 0.0;
+  unsigned long long p = 0;
+  unsigned f = 0;
+  for (int b = threadIdx.x; b < nb; b += kThreads) {
+    s += part[b];
+    p += pos[b];
+    f |= flags[b];
+  }
+  s = block_sum(s, smd);
+  p = block_sum(p, sml);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) f |= __shfl_xor(f, o, 64);
+  if ((threadIdx.x & 63) == 0) smu[threadIdx.x >> 6] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kWaves; ++w) f |= smu[w];
+    const unsigned long long N = (unsigned long long)n - p;
+    if (p == 0 || N == 0) f |= RM_METRIC_ONE_CLASS;
+    out->value = -s / (double)n;
+    out->pos = (int64_t)p;
+    out->neg = (int64_t)N;
+    out->flags = (int64_t)f;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t rm_metric_workspace(int64_t n) {
+  if (n < 1 || n > 0x7FFFFFFFll) return 0;
+  const Layout L = layout(n);
+  return (int64_t)(L.total > L.loss_total ? L.total : L.loss_total);
+}
+
+extern "C" int rm_roc_auc(const float *scores, const int64_t *labels, int64_t n, void *workspace,
+                          rm_metric_result *out, rm_stream_t stream) {
+  RM_REQUIRE(n >= 1 && n <= 0x7FFFFFFFll, "rm_roc_auc: n = %lld outside [1, 2^31 - 1]", (long long)n);
+  RM_REQUIRE(scores && labels && workspace && out, "rm_roc_auc: NULL pointer");
+  RM_REQUIRE(rm_aligned16(workspace) && rm_aligned16(out), "rm_roc_auc: workspace / out not 16-byte aligned");
+  const Layout L = layout(n);
+  char *ws = (char *)workspace;
+  AucHeader *hd = (AucHeader *)(ws + L.header);
+  unsigned *hist = (unsigned *)(ws + L.hist);
+  unsigned long long *part = (unsigned long long *)(ws + L.part);
+  unsigned *head = (unsigned *)(ws + L.head), *tail = (unsigned *)(ws + L.tail);
+  int *last = (int *)(ws + L.last);
+  unsigned *first = (unsigned *)(ws + L.first);
+  unsigned *k0 = (unsigned *)(ws + L.keys0), *k1 = (unsigned *)(ws + L.keys1);
+  unsigned char *l0 = (unsigned char *)(ws + L.lab0), *l1 = (unsigned char *)(ws + L.lab1);
+  const int64_t tiles = (n + kTile - 1) / kTile;
+  hipStream_t s = (hipStream_t)stream;
+
+  if (hipMemsetAsync(hd, 0, sizeof(AucHeader), s) != hipSuccess) {
+    rm_set_error("rm_roc_auc: hipMemsetAsync failed");
+    return RM_ELAUNCH;
+  }
+  hipLaunchKernelGGL(auc_keys_kernel, dim3(rm_grid_cap((n + kThreads - 1) / kThreads, kKeyBlocks)),
+                     dim3(kThreads), 0, s, scores, labels, n, k0, l0, hd);
+  hipLaunchKernelGGL(auc_plan_kernel, dim3(1), dim3(kThreads), 0, s, hd, n);
+  for (int slot = 0; slot < kPasses; ++slot) {
+    hipLaunchKernelGGL(auc_hist_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, n, tiles,
+                       hist);
+    hipLaunchKernelGGL(auc_scan_kernel, dim3(kRadix), dim3(kThreads), 0, s, hd, slot, tiles, hist);
+    hipLaunchKernelGGL(auc_sort_pass_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, l0,
+                       l1, n, tiles, hist);
+  }
+  hipLaunchKernelGGL(auc_groups_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, k0, k1, l0, l1, n, part,
+                     head, tail, last, first);
+  hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(kThreads), 0, s, hd, n, tiles, part, head, tail, last, first,
+                     out);
+  RM_CHECK_LAUNCH("rm_roc_auc");
+  return RM_OK;
+}
+
+extern "C" int rm_log_loss(const float *pred, const int64_t *labels, int64_t n, float eps, void *workspace,
+                           rm_metric_result *out, rm_stream_t stream) {
+  RM_REQUIRE(n >= 1 && n <= 0x7FFFFFFFll, "rm_log_loss: n = %lld outside [1, 2^31 - 1]", (long long)n);
+  RM_REQUIRE(pred && labels && workspace && out, "rm_log_loss: NULL pointer");
+  RM_REQUIRE(rm_aligned16(workspace) && rm_aligned16(out), "rm_log_loss: workspace / out not 16-byte aligned");
+  RM_REQUIRE(eps > 0.0f && eps < 0.5f, "rm_log_loss: eps must lie in (0, 0.5)");
+  const Layout L = layout(n);
+  char *ws = (char *)workspace;
+  double *part = (double *)(ws + L.loss_part);
+  unsigned long long *pos = (unsigned long long *)(ws + L.loss_pos);
+  unsigned *flags = (unsigned *)(ws + L.loss_flags);
+  const int nb = rm_grid_cap((n + kThreads - 1) / kThreads, kLossBlocks);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(logloss_kernel, dim3(nb), dim3(kThreads), 0, s, pred, labels, n, eps, part, pos, flags);
+  hipLaunchKernelGGL(logloss_final_kernel, dim3(1), dim3(kThreads), 0, s, part, pos, flags, nb, n, out);
+  RM_CHECK_LAUNCH("rm_log_loss");
+  return RM_OK;
+}

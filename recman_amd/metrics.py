@@ -1,0 +1,164 @@
+"""Evaluation metrics computed on the GPU: the counterpart of recman.metrics (recman/metrics/roc_auc.py:4-16,
+logloss.py:4-19) and of the sklearn functions the models score with by default.
+
+    from recman_amd.metrics import RocAucScore, LogLoss, roc_auc_score, log_loss
+
+    model = DeepFM(feat_dict, hparams, metrics=(RocAucScore(), LogLoss()), epoch=3)
+
+| name                         | semantics                                                                   |
+|------------------------------|-----------------------------------------------------------------------------|
+| roc_auc_score(y_true, y_score) | sklearn 1.7.2's binary roc_auc_score with default arguments, exact:       |
+|                              | the Mann-Whitney count in integers, ties one half (rm_roc_auc).  One class  |
+|                              | present: UndefinedMetricWarning and nan, as sklearn.                        |
+| log_loss(y_true, y_pred)     | sklearn 1.7.2's binary log_loss on float32 predictions: clip at FLT_EPSILON |
+|                              | (rm_log_loss).  One class present: ValueError with sklearn's message.       |
+| RocAucScore()                | callable, str / repr "roc_auc", higher_the_better = True                     |
+| LogLoss(eps=1e-7)            | callable, str / repr "logloss", higher_the_better = False; clips at eps     |
+|                              | (the reference class's intent; it passes eps= to sklearn, which 1.7.2 no   |
+|                              | longer accepts)                                                             |
+
+Inputs: torch tensors on the GPU are used in place; numpy arrays, lists and CPU tensors are copied to the GPU once.
+Scores are compared and clipped as float32 (other float types are converted).  Labels are 0 / 1 as int64, int32,
+bool or float; any other label value raises ValueError - a stated narrowing, sklearn accepts any two label values.
+NaN or infinite scores and empty inputs raise ValueError, sklearn's keywords (sample_weight, max_fpr, labels, ...)
+TypeError.  Every function returns a Python float: one device-to-host read per call.
+
+Each of the four carries `on_device = True`: DeepModel.fit() / evaluate() keep predictions and labels on the GPU
+when every configured metric has it (recman_amd/th/DeepModel.py).
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from . import ops
+
+__all__ = ["roc_auc_score", "log_loss", "RocAucScore", "LogLoss"]
+
+
+def _no_extras(name, extra):
+    if extra:
+        raise TypeError(f"{name}: unsupported argument(s) {sorted(extra)} (binary and unweighted only)")
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_tensor(x):
+    if isinstance(x, torch.Tensor):
+        return x.detach()
+    a = np.asarray(x)
+    if a.dtype == object or a.dtype.kind in "USV":
+        raise ValueError("recman_amd.metrics takes numeric inputs")
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _inputs(y_true, y_score):
+    dev = _device_of(y_score, y_true)
+    s, y = _as_tensor(y_score), _as_tensor(y_true)
+    if s.dim() != 1 or y.dim() != 1:
+        raise ValueError(f"expected 1-D y_true and scores, got shapes {tuple(y.shape)} and {tuple(s.shape)}")
+    if s.shape[0] != y.shape[0]:
+        raise ValueError(f"Found input variables with inconsistent numbers of samples: [{y.shape[0]}, {s.shape[0]}]")
+    n = s.shape[0]
+    if n == 0:
+        raise ValueError("Found empty input: 0 samples")
+    if n >= 2 ** 31:
+        raise ValueError(f"at most 2^31 - 1 samples, got {n}")
+    if s.dtype == torch.bool or s.is_complex():
+        raise ValueError(f"scores must be real numbers, got {s.dtype}")
+    s = s.to(device=dev, dtype=torch.float32).contiguous()
+    y = y.to(device=dev)
+    if y.is_floating_point():
+        # 0.0 / 1.0 -> 0 / 1; anything else (0.5, NaN, ...) -> 2, which the kernel flags
+        y = (y == 1).to(torch.int64) + 2 * ((y != 0) & (y != 1)).to(torch.int64)
+    elif y.dtype != torch.int64:
+        if y.is_complex():
+            raise ValueError(f"labels must be real numbers, got {y.dtype}")
+        y = y.to(torch.int64)
+    return s, y.contiguous()
+
+
+def _check(rec, what):
+    v, P, N, flags = ops.read_metric(rec)
+    if flags & ops.METRIC_BAD_SCORE:
+        raise ValueError(f"Input {what} contains NaN or infinity.")
+    if flags & ops.METRIC_BAD_LABEL:
+        raise ValueError("y_true must hold binary labels 0 / 1 (recman_amd.metrics scores 0/1 labels only)")
+    return v, P, N, flags
+
+
+def roc_auc_score(y_true, y_score, **unsupported):
+    """Exact binary ROC AUC on the GPU (sklearn.metrics.roc_auc_score with default arguments)."""
+    _no_extras("roc_auc_score", unsupported)
+    s, y = _inputs(y_true, y_score)
+    with torch.cuda.device(s.device):
+        v, _, _, flags = _check(ops.roc_auc(s, y), "y_score")
+    if flags & ops.METRIC_ONE_CLASS:
+        from sklearn.exceptions import UndefinedMetricWarning
+
+        warnings.warn("Only one class is present in y_true. ROC AUC score is not defined in that case.",
+                      UndefinedMetricWarning, stacklevel=2)
+        return float("nan")
+    return v
+
+
+def _log_loss(y_true, y_pred, eps):
+    p, y = _inputs(y_true, y_pred)
+    with torch.cuda.device(p.device):
+        v, P, _, flags = _check(ops.log_loss(p, y, eps=float(np.float32(eps))), "y_pred")
+    if flags & ops.METRIC_PROB_RANGE:
+        raise ValueError("y_prob contains values outside [0, 1]")
+    if flags & ops.METRIC_ONE_CLASS:
+        raise ValueError("y_true contains only one label ({0}). Please provide the list of all expected class "
+                         "labels explicitly through the labels argument.".format(1 if P else 0))
+    return v
+
+
+def log_loss(y_true, y_pred, **unsupported):
+    """Binary log loss on the GPU (sklearn.metrics.log_loss on float32 predictions: clip at FLT_EPSILON)."""
+    _no_extras("log_loss", unsupported)
+    return _log_loss(y_true, y_pred, ops.FLT_EPSILON)
+
+
+roc_auc_score.on_device = True
+log_loss.on_device = True
+
+
+class RocAucScore:
+    """recman.metrics.RocAucScore on the GPU."""
+
+    on_device = True
+    higher_the_better = True
+
+    def __call__(self, y_true, y_pred):
+        return roc_auc_score(y_true, y_pred)
+
+    def __str__(self):
+        return "roc_auc"
+
+    def __repr__(self):
+        return "roc_auc"
+
+
+class LogLoss:
+    """recman.metrics.LogLoss on the GPU: clips at eps (rounded to float32)."""
+
+    on_device = True
+    higher_the_better = False
+
+    def __init__(self, eps=1e-07):
+        self.eps = eps
+
+    def __call__(self, y_true, y_pred):
+        return _log_loss(y_true, y_pred, self.eps)
+
+    def __str__(self):
+        return "logloss"
+
+    def __repr__(self):
+        return "logloss"

@@ -810,3 +810,55 @@ def dense_wgrad(a1, a2, G, dW, ws, accumulate=False, db=None, ws6=None, G2=None,
         return
     _lib.call("rm_dense_wgrad", p1, lda1, K1, p2, lda2, K2, pg, ldg, N, M, pd, lddw, int(bool(accumulate)),
               _chk(db, "db", F32, (N,), allow_none=True), _chk(ws, "ws", F32), ws.numel(), _stream())
+
+
+# ------------------------------------------------------------------ evaluation metrics (csrc/metrics.hip)
+METRIC_BAD_LABEL, METRIC_BAD_SCORE, METRIC_ONE_CLASS, METRIC_PROB_RANGE = 1, 2, 4, 8
+FLT_EPSILON = 1.1920928955078125e-07
+
+
+def metric_workspace(n):
+    """Bytes of the workspace rm_roc_auc / rm_log_loss need for n elements (0 outside 1 <= n < 2^31)."""
+    return int(_lib.lib().rm_metric_workspace(int(n)))
+
+
+def _metric_args(x, y, workspace, out, name):
+    n = x.shape[0] if x.dim() == 1 else -1
+    xp = _chk(x, name, F32, (n,))
+    yp = _chk(y, "labels", I64, (n,))
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"{name}: need 1 <= n < 2^31 elements, got {n}")
+    need = metric_workspace(n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"metric workspace too small: {need} bytes needed")
+    wp = _chk(workspace, "workspace", workspace.dtype)
+    if out is None:
+        out = torch.empty(4, dtype=I64, device=x.device)
+    op = _chk(out, "out", I64, (4,))
+    if wp % 16 or op % 16:
+        raise ValueError("metric workspace / out must be 16-byte aligned")
+    return n, xp, yp, wp, out, op
+
+
+def roc_auc(scores, labels, workspace=None, out=None):
+    """Exact binary ROC AUC (rm_roc_auc): scores fp32 [n], labels int64 [n] on the GPU.  Returns the device
+    record `out` (int64 [4]: value as float64 bits, P, N, flags); read it with read_metric."""
+    n, xp, yp, wp, out, op = _metric_args(scores, labels, workspace, out, "scores")
+    _lib.call("rm_roc_auc", xp, yp, n, wp, op, _stream())
+    return out
+
+
+def log_loss(pred, labels, eps=FLT_EPSILON, workspace=None, out=None):
+    """Binary log loss (rm_log_loss), clipped in fp32 at eps: pred fp32 [n], labels int64 [n] on the GPU.
+    Returns the device record `out` as roc_auc does."""
+    n, xp, yp, wp, out, op = _metric_args(pred, labels, workspace, out, "pred")
+    _lib.call("rm_log_loss", xp, yp, n, float(eps), wp, op, _stream())
+    return out
+
+
+def read_metric(out):
+    """(value, P, N, flags) of a metric record: one device-to-host copy."""
+    r = out.cpu().numpy()
+    return float(r[:1].view("float64")[0]), int(r[1]), int(r[2]), int(r[3])

@@ -280,10 +280,11 @@ class DeepModel(BaseEstimator, TransformerMixin):
         end = min(start + batch_size, len(y))
         return X[start:end], y[start:end]
 
-    def _predict_encoded(self, idx, dense, training, mv_host=None):
+    def _predict_batches(self, idx, dense, training, mv_host=None):
+        """Yields (s, t, pred) batch by batch: the device prediction of rows [s, t) (a view of an engine
+        buffer, valid until the next batch is enqueued)."""
         e = self._build()
         n = idx.shape[0]
-        out = np.empty((n,), dtype=np.float32)
         mw = None if training else self._manual_weights()
         if mw is not None and self._shard is not None:
             raise NotImplementedError("row-sharded table: manual feature weights are single-GPU only")
@@ -298,14 +299,43 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 ib, db = ib.to(e.device, non_blocking=True), db.to(e.device, non_blocking=True)
             _, pred = e.forward(ib, db, training=training,
                                 masks=masks, manual_weights=mw, mv=self._mv_batch(mv_host, s, t))
+            yield s, t, pred
+
+    def _predict_encoded(self, idx, dense, training, mv_host=None):
+        out = np.empty((idx.shape[0],), dtype=np.float32)
+        for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
             out[s:t] = pred.cpu().numpy()
         return out
+
+    def _predict_device(self, idx, dense, training, mv_host=None):
+        """The predictions of _predict_encoded (same batches, kernels and dropout draws: bitwise equal) in one
+        device fp32 buffer, with no host copy per batch."""
+        e = self._build()
+        out = torch.empty((idx.shape[0],), dtype=torch.float32, device=e.device)
+        for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
+            out[s:t].copy_(pred)
+        return out
+
+    def _metrics_on_device(self):
+        """True when metrics are configured and every one runs on the GPU (recman_amd.metrics): fit() and
+        evaluate() then keep predictions and labels there."""
+        ms = self.metrics
+        return bool(ms) and all(getattr(m, "on_device", False) for m in ms)
+
+    def _labels_on_device(self, y):
+        ya = np.asarray(y)
+        return torch.from_numpy(np.ascontiguousarray(ya)).to(self._build().device)
 
     def predict(self, X, training=False, batch_number_to_show_progress=50):
         idx, dense, _ = self._encode(X)
         return self._predict_encoded(idx, dense, training, self._mv_host)
 
     def evaluate(self, X, y, training=False, batch_number_to_show_progress=50):
+        if self._metrics_on_device():
+            idx, dense, _ = self._encode(X)
+            pred = self._predict_device(idx, dense, training, self._mv_host)
+            yd = self._labels_on_device(y)
+            return [float(metric(yd, pred)) for metric in self.metrics]
         pred = self.predict(X, training, batch_number_to_show_progress)
         return [metric(y, pred) for metric in self.metrics]
 
@@ -369,13 +399,19 @@ class DeepModel(BaseEstimator, TransformerMixin):
         return loss
 
     def _eval_at_epoch(self, enc_train, y_train, enc_valid=None, y_valid=None, start_time=None, epoch=0):
+        """y_train / y_valid: host labels, or device labels when every metric runs on the GPU
+        (_metrics_on_device); the predictions then stay on the GPU too."""
         training = bool(self.strict_reference)  # DeepModel.py:103-111 evaluates with training=True
-        ptr = self._predict_encoded(enc_train[0], enc_train[1], training, enc_train[2])
-        tr = [m(y_train, ptr) for m in self.metrics]
+        if self._metrics_on_device():
+            predict, score = self._predict_device, (lambda m, y, p: float(m(y, p)))
+        else:
+            predict, score = self._predict_encoded, (lambda m, y, p: m(y, p))
+        ptr = predict(enc_train[0], enc_train[1], training, enc_train[2])
+        tr = [score(m, y_train, ptr) for m in self.metrics]
         va = None
         if enc_valid is not None:
-            pva = self._predict_encoded(enc_valid[0], enc_valid[1], training, enc_valid[2])
-            va = [m(y_valid, pva) for m in self.metrics]
+            pva = predict(enc_valid[0], enc_valid[1], training, enc_valid[2])
+            va = [score(m, y_valid, pva) for m in self.metrics]
         log.info("[%d] train-result=%s%s [%.1f s]", epoch, [round(float(r), 4) for r in tr],
                  "" if va is None else ", valid-result=%s" % [round(float(r), 4) for r in va],
                  time() - (start_time or time()))
@@ -399,11 +435,16 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                           for n, c in mv_host.items() if n in self._engine.spec.multi_names})
             self._mv_caps_global = True
         n = len(y_train)
+        on_device = self._metrics_on_device()
+        if on_device and enc_valid is not None:
+            y_valid = self._labels_on_device(y_valid)  # once per fit()
         if pinned:
             return self._fit_pinned(idx, dense, yt, mv_host, y_train, enc_valid, y_valid,
                                     random_seed_for_mini_batch, epoch_callback, X_train,
                                     batch_number_to_show_progress)
-        eval_results = self._eval_at_epoch((idx, dense, mv_host), y_train, enc_valid, y_valid, time())
+        # device metrics score the (shuffled) device labels yt; host metrics the host copy
+        eval_results = self._eval_at_epoch((idx, dense, mv_host), yt if on_device else y_train, enc_valid, y_valid,
+                                           time())
         for epoch in range(1, self.epoch + 1):
             start = time()
             seed = np.random.randint(1, 2019) if random_seed_for_mini_batch else self.random_seed
@@ -432,7 +473,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                   self._mv_batch(mv_host, s, t))
                 if i % batch_number_to_show_progress == 0:
                     log.info(f"Fit: {(i + 1)}/{total_batch} has been completed")
-            eval_results = self._eval_at_epoch((idx, dense, mv_host), y_train, enc_valid, y_valid, start, epoch)
+            eval_results = self._eval_at_epoch((idx, dense, mv_host), yt if on_device else y_train, enc_valid,
+                                               y_valid, start, epoch)
             if epoch_callback:
                 epoch_callback(model=self, eval_results=eval_results, df_all=X_train[:1])
         return None  # the reference's fit returns None
@@ -474,7 +516,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
         n = len(y_train)
         feeder = BatchFeeder(idx, dense, yt, self.batch_size, e.device)
         perm_all = np.arange(n)  # position -> original row: the shuffles compose across epochs
-        eval_results = self._eval_at_epoch((idx, dense, mv_host), y_train, enc_valid, y_valid, time())
+        y_eval = self._labels_on_device(yt) if self._metrics_on_device() else y_train  # (device: copied once)
+        eval_results = self._eval_at_epoch((idx, dense, mv_host), y_eval, enc_valid, y_valid, time())
         for epoch in range(1, self.epoch + 1):
             start = time()
             seed = np.random.randint(1, 2019) if random_seed_for_mini_batch else self.random_seed
@@ -488,7 +531,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 if i % every == 0:
                     log.info(f"Fit: {(i + 1)}/{total_batch} has been completed")
             # evaluation order does not matter for the metrics: the unshuffled host arrays
-            eval_results = self._eval_at_epoch((idx, dense, mv_host), y_train, enc_valid, y_valid, start, epoch)
+            eval_results = self._eval_at_epoch((idx, dense, mv_host), y_eval, enc_valid, y_valid, start, epoch)
             if epoch_callback:
                 epoch_callback(model=self, eval_results=eval_results, df_all=X_train[:1])
         return None
