@@ -78,7 +78,8 @@ int rm_profile_marker(int tag, rm_stream_t stream);
  *   fm_sum   [B,D]    S = sum_f mask_e*E  (saved for the backward)
  *   fm_logit [B]      sum_f mask_b*bias + 0.5*sum_k(S_k^2 - sum_f (mask_e*E)_fk^2)
  *   lin_logit[B]      sum_f lin_w[lin_off[f]+idx] + dense . lin_w[dense block] + lin_w0
- * D must be a multiple of 4 and <= 256; table/E 16-byte aligned.
+ * D must be one of 4, 8, 16, 32, 64, 128, 256 (D/4 lanes own an example and must divide the 64-lane wave; anything
+ * else is RM_EINVAL); table_ld a multiple of 4; table/E/fm_sum/mask_e 16-byte aligned.
  */
 /* flags: RM_EMBED_STREAM_ROWS = load the table rows non-temporally (fused-row layout only).  For ids that
  * touch a row about once per batch (uniformly hashed ids over a table far larger than the caches) the
@@ -108,7 +109,8 @@ int rm_linear_fwd(const int64_t *idx, const int64_t *lin_off, const float *w, co
  *   d_rows[b,f,:] = dE_up[b,f,:] + g_fm[b] * mask_e[b,f,:] * (S[b,:] - mask_e*E[b,f,:])
  *   d_bias[b,f]   = g_fm[b] * mask_b[b,f]
  * dE_up (upstream gradient from DNN / CIN / cross w.r.t. E) may be NULL; g_fm may
- * be NULL (no FM term: d_rows = dE_up).  d_rows may alias dE_up.  d_bias may be NULL.
+ * be NULL (no FM term: d_rows = dE_up, and d_bias is then NOT written - it keeps its prior content).  d_rows may
+ * alias dE_up.  d_bias may be NULL.  D is any multiple of 4 (the pass is elementwise over float4 slices).
  */
 int rm_embed_bwd(const float *E, const float *fm_sum, const float *dE_up, const float *g_fm,
                  const float *mask_b, const float *mask_e, int64_t B, int F, int D,
@@ -267,7 +269,8 @@ int rm_deepfm_step(const int64_t *idx, const float *table, int64_t table_ld, con
                    rm_stream_t stream);
 
 /* Epilogues of the library-GEMM DNN path (wide hidden layers, layers.py:593-601):
- * rm_bias_act: x[b,j] = act(x[b,j] + bias[j]) in place (bias may be NULL);
+ * rm_bias_act: x[b,j] = act(x[b,j] + bias[j]) in place (bias may be NULL = a bias of +0.0: the add is still made,
+ *              so x = -0.0 becomes +0.0);
  * rm_act_bwd:  da[b,j] *= act'(a[b,j]) in place, act' read off the post-activation a. */
 int rm_bias_act(float *x, const float *bias, int64_t B, int N, int act, rm_stream_t stream);
 int rm_act_bwd(float *da, const float *a, int64_t B, int N, int act, rm_stream_t stream);
@@ -483,7 +486,8 @@ int rm_pack_pooled_grad_rows(const float *d_rows, int64_t dr_stride, const float
  * Optimizer steps.  Replace optimizer.minimize(...) of xDeepFM.py:121-126 / create_optimizer
  * (utils.py:201-213): Keras Adam (kind 0: beta1/beta2, epsilon outside the sqrt), Adagrad (kind 1,
  * accumulator starts at 0.1) or SGD (kind 2).  reset != 0 ignores the stored moments (the reference
- * builds a new optimizer for every batch); step >= 1 is the Adam bias-correction step.
+ * builds a new optimizer for every batch) AND the step number: the update is a new optimizer's first step (Adam
+ * bias correction at t = 1, whatever `step` says); otherwise step >= 1 is the Adam bias-correction step.
  *
  * rm_sparse_optimizer_step: ROW-WISE and LAZY step on table rows, straight from the IndexedSlices
  * form the backward produces (LazyAdam - Keras' sparse Adam decays the moments of EVERY row; the two
