@@ -334,6 +334,41 @@ int rm_cross_param_grads(const float *P, const float *colsum, const float *w, co
                          float *d_w_out, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * AFM attention layer (Attentional Factorization Machines), forward and backward fused.
+ * Replaces: AFMLayer(att_factor, att_dropout)(feat_embeds) -> logit [B,1] used at
+ *   AFM.py:119-122 - the class itself is ABSENT from the reference (AFM.py:7 comments the
+ *   import out); arithmetic per arXiv 1708.04617 eq. (4)-(6).  Per example, over the
+ *   P = F(F-1)/2 field pairs i < j (row-major over the upper triangle):
+ *     P_ij = E_i * E_j;  z_ij = W^T P_ij + b;  s_ij = h . relu(z_ij);  a = softmax_ij(s)
+ *     v = sum_ij a_ij P_ij;  logit = p . (mask * v)
+ *   E [B,F,D] (the gathered rows, rm_embed_fwd's E); W [D,T], b [T], h [T], p [D];
+ *   mask [B,D] or NULL: the dropout multiplier (0 or 1/keep); logit [B].
+ *   stats [B,D+2] or NULL (inference): per example the softmax's (max score, sum of exp(s - max))
+ *   and u = mask * v [D] - all the backward keeps of the forward.  The softmax is max-subtracted;
+ *   the logits are the same bits with and without stats.
+ * Supported: D in {8,16,32,64}, 2 <= F <= 40, 1 <= T <= 64 (rm_afm_supported); anything else is
+ *   RM_EINVAL.  The [P,D] pair products, the [P,T] hidden units and the scores never leave the chip.
+ * rm_afm_bwd, given g [B] = dLoss/dlogit and the forward's logit and stats, recomputes the forward
+ *   per pair and writes  d_rows [B,F,D] = dLoss/dE (+ dE_up [B,F,D] when not NULL; dE_up may BE
+ *   d_rows),  dW [D,T], db [T], dh [T], dp [D] (overwritten, summed over the batch):
+ *     c = g (mask * p);  ds_ij = a_ij (c . P_ij - g logit);  dz_ij = ds_ij h [z_ij > 0]
+ *     dP_ij = a_ij c + W dz_ij;  dE_i += dP_ij E_j;  dE_j += dP_ij E_i
+ *     dW = sum P_ij dz_ij^T;  db = sum dz_ij;  dh = sum ds_ij relu(z_ij);  dp = sum g u
+ *   workspace: rm_afm_bwd_workspace(B, F, D, T) floats, 16-byte aligned.
+ * Deterministic: per-block partial sums added in block order, fixed-order sums inside a block,
+ *   no float atomics - two runs on the same inputs are bit-equal.
+ */
+int rm_afm_supported(int F, int D, int T);
+int rm_afm_fwd(const float *E, const float *W, const float *b, const float *h, const float *p,
+               const float *mask, int64_t B, int F, int D, int T, float *logit, float *stats,
+               rm_stream_t stream);
+int64_t rm_afm_bwd_workspace(int64_t B, int F, int D, int T);
+int rm_afm_bwd(const float *E, const float *W, const float *b, const float *h, const float *p,
+               const float *mask, const float *g, const float *logit, const float *stats,
+               const float *dE_up, int64_t B, int F, int D, int T, float *d_rows, float *dW, float *db,
+               float *dh, float *dp, float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CIN (xDeepFM), one layer, on the f32-input MFMA.
  * Replaces the loop body of CIN.__call__ (layers.py:714-752):
  *   Z[b,d,i*H+j] = X0[b,i,d] * Xk[b,j,d];  M = Z @ W + bias;  out = act(M)

@@ -1,4 +1,4 @@
-"""Explicit forward+backward engines for DeepFM / DCN / xDeepFM on one MI355X.
+"""Explicit forward+backward engines for DeepFM / DCN / xDeepFM / AFM on one MI355X.
 
 No autograd and no tracing compiler: each engine owns its parameters (laid out
 for the kernels: ONE concatenated embedding table in HBM, per-feature variables
@@ -379,6 +379,9 @@ def init_reference(engine, seed=2019):
             tn(t, t.shape[1], t.shape[2] if t.dim() == 3 else 1)
         elif name == "cross_w_out":
             tn(t, t.shape[0], 1)
+        elif name in ("afm_attention_w", "afm_attention_h", "afm_projection_p"):
+            # the attention layer is absent from the reference (AFM.py:7): glorot like dnn_w / cross_w_out
+            tn(t, t.shape[0], t.shape[1])
         else:
             t.zero_()
 
@@ -1516,4 +1519,103 @@ class XDeepFMEngine(Engine):
                      symbol="cin_fwd_kernel", fn=fn, work=flops, bound="mfma")]
 
 
-ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine}
+class AFMEngine(Engine):
+    """AFM._init_graph (AFM.py:80-150): final = linear + afm, PredictionLayer(use_bias=False).  The attention
+    layer is absent from the reference (AFM.py:7 comments the import out, AFM.py:119-122 uses it); arithmetic
+    per arXiv 1708.04617 eq. (4)-(6), forward and backward fused in csrc/afm.hip:
+        a_ij = softmax_ij(h . relu(W^T (E_i * E_j) + b)),  afm_logit = p . (m * sum_ij a_ij E_i * E_j)
+    Variables (names chosen here): afm_attention_w [D,T], afm_attention_b [T], afm_attention_h [T,1],
+    afm_projection_p [D,1].  l2: embeddings, linear weights and - as in the paper - the attention matrix W only
+    (att_l2_reg).  The first-order bias tables AFM.py:102-109 gathers are never used: none are created.
+    att_dropout is a KEEP probability (layers.py:461) applied to the pooled vector; masks["afm"] [B,D] carries the
+    multiplier (0 or 1/keep)."""
+
+    model = "afm"
+    use_bias_tables = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.T = int(hp.get("att_factor", 8))
+        if not ops.afm_supported(self.F, self.D, self.T):
+            raise ValueError(f"AFM: {self.F} embedding features, embedding_size={self.D}, att_factor={self.T} is not "
+                             "supported by rm_afm_fwd (2..40 features, embedding_size 8/16/32/64, att_factor 1..64)")
+        dev, D, T = self.device, self.D, self.T
+        for nm, shape in (("afm_attention_w", (D, T)), ("afm_attention_b", (T,)), ("afm_attention_h", (T, 1)),
+                          ("afm_projection_p", (D, 1))):
+            self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
+            self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+
+    def _alloc_model(self, B):
+        dev = self.device
+        self.afm_logit = torch.empty(B, dtype=F32, device=dev)
+        self.afm_stats = torch.empty(B, ops.afm_stats_width(self.D), dtype=F32, device=dev)
+        self.afm_ws = torch.empty(max(4, ops.afm_bwd_workspace(B, self.F, self.D, self.T)), dtype=F32, device=dev)
+
+    def _afm_params(self):
+        p = self.params
+        return (p["afm_attention_w"], p["afm_attention_b"], p["afm_attention_h"].view(-1),
+                p["afm_projection_p"].view(-1))
+
+    def _afm_mask(self, masks, training):
+        m = (masks or {}).get("afm") if training else None
+        return m if (m is not None and self.hp.get("att_dropout", 1) < 1) else None
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        self._mask = self._afm_mask(masks, training)
+        ops.afm_fwd(self.E, *self._afm_params(), self.afm_logit, mask=self._mask,
+                    stats=self.afm_stats if training else None)
+        return [(self.lin_logit, 1.0), (self.afm_logit, 1.0)]
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        gr = self.grads
+        # with no other branch over E, d_rows IS dLoss/dE (the linear term's gradients come from the base class)
+        ops.afm_bwd(self.E, *self._afm_params(), g, self.afm_logit, self.afm_stats, self.d_rows,
+                    gr["afm_attention_w"], gr["afm_attention_b"], gr["afm_attention_h"].view(-1),
+                    gr["afm_projection_p"].view(-1), self.afm_ws, mask=self._mask)
+        reg = self.hp.get("att_l2_reg", 0.0)
+        if reg:
+            gr["afm_attention_w"].add_(self.params["afm_attention_w"], alpha=reg)
+
+    def _add_l2_model(self, total):
+        reg = self.hp.get("att_l2_reg", 0.0)
+        if reg:
+            total = total + reg * 0.5 * self.params["afm_attention_w"].square().sum()
+        return total
+
+    @staticmethod
+    def afm_flops(B, F, D, T):
+        """(forward, backward) flops of the attention kernels: per pair D multiplies, the 2 D T score product,
+        2 T for h . relu, 2 D for the pooling; the backward recomputes that and adds three products of the score
+        product's size (W dz, P dz^T, and dP * E twice)."""
+        P = F * (F - 1) // 2
+        fwd = B * P * (D + 2 * D * T + 2 * T + 2 * D)
+        bwd = fwd + B * P * (2 * (2 * D * T) + 4 * D)
+        return fwd, bwd
+
+    def roofline_probes(self, idx, dense, y):
+        B = idx.shape[0]
+        self._alloc(B)
+        if getattr(self, "_probe_ready", None) != B:
+            self.fwd_bwd(idx, dense, y)  # fills E, stats, dlogit
+            self._probe_ready = B
+        fwd, bwd = self.afm_flops(B, self.F, self.D, self.T)
+        gr = self.grads
+        return [
+            dict(name=f"afm_bwd_kernel (rm_afm_bwd: F={self.F} D={self.D} T={self.T}; recompute + dE + dW, db, dh, "
+                      "dp; flops = forward + W dz, P dz^T, dP * E)", symbol="afm_bwd_kernel",
+                 fn=lambda: ops.afm_bwd(self.E, *self._afm_params(), self.dlogit, self.afm_logit, self.afm_stats,
+                                        self.d_rows, gr["afm_attention_w"], gr["afm_attention_b"],
+                                        gr["afm_attention_h"].view(-1), gr["afm_projection_p"].view(-1),
+                                        self.afm_ws),
+                 work=float(bwd), bound="mfma"),
+            dict(name=f"afm_fwd_kernel (rm_afm_fwd: F={self.F} D={self.D} T={self.T}; flops = P (D + 2 D T + 2 T "
+                      "+ 2 D) per example, on the vector ALU - priced against the fp32 peak both pipes share)",
+                 symbol="afm_fwd_kernel",
+                 fn=lambda: ops.afm_fwd(self.E, *self._afm_params(), self.afm_logit, stats=self.afm_stats),
+                 work=float(fwd), bound="mfma"),
+        ] + super().roofline_probes(idx, dense, y)
+
+
+ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine}

@@ -191,6 +191,50 @@ def cross_param_grads(P, colsum, w, b, w_out, d_w, d_b, d_w_out):
         _chk(d_b, "d_b", F32, (L, d)), _chk(d_w_out, "d_w_out", F32, (d,)), _stream())
 
 
+def afm_supported(F, D, T):
+    """rm_afm_supported: D in {8, 16, 32, 64}, 2 <= F <= 40, 1 <= T <= 64."""
+    return bool(_lib.lib().rm_afm_supported(int(F), int(D), int(T)))
+
+
+def afm_stats_width(D):
+    """Row length of the forward's record stats [B, D + 2]: softmax max, denominator, u = mask * v."""
+    return D + 2
+
+
+def afm_fwd(E, W, b, h, p, logit, mask=None, stats=None):
+    """AFM attention layer forward (rm_afm_fwd): E [B,F,D], W [D,T], b [T], h [T], p [D], mask [B,D] or None
+    -> logit [B]; stats [B, D+2] (training) or None (inference, same logits)."""
+    B, F, D = E.shape
+    T = W.shape[1]
+    _lib.call(
+        "rm_afm_fwd", _chk(E, "E", F32), _chk(W, "W", F32, (D, T)), _chk(b, "b", F32, (T,)),
+        _chk(h, "h", F32, (T,)), _chk(p, "p", F32, (D,)), _chk(mask, "mask", F32, (B, D), allow_none=True),
+        B, F, D, T, _chk(logit, "logit", F32, (B,)),
+        _chk(stats, "stats", F32, (B, D + 2), allow_none=True), _stream())
+
+
+def afm_bwd_workspace(B, F, D, T):
+    """Floats of workspace rm_afm_bwd needs (0: unsupported shape)."""
+    return int(_lib.lib().rm_afm_bwd_workspace(int(B), int(F), int(D), int(T)))
+
+
+def afm_bwd(E, W, b, h, p, g, logit, stats, d_rows, dW, db, dh, dp, workspace, mask=None, dE_up=None):
+    """AFM attention layer backward (rm_afm_bwd): d_rows [B,F,D] = dLoss/dE (+ dE_up, which may be d_rows
+    itself), dW [D,T], db [T], dh [T], dp [D] overwritten.  Deterministic."""
+    B, F, D = E.shape
+    T = W.shape[1]
+    need = afm_bwd_workspace(B, F, D, T)
+    if need and workspace.numel() < need:
+        raise ValueError(f"afm_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _lib.call(
+        "rm_afm_bwd", _chk(E, "E", F32), _chk(W, "W", F32, (D, T)), _chk(b, "b", F32, (T,)),
+        _chk(h, "h", F32, (T,)), _chk(p, "p", F32, (D,)), _chk(mask, "mask", F32, (B, D), allow_none=True),
+        _chk(g, "g", F32, (B,)), _chk(logit, "logit", F32, (B,)), _chk(stats, "stats", F32, (B, D + 2)),
+        _chk(dE_up, "dE_up", F32, (B, F, D), allow_none=True), B, F, D, T,
+        _chk(d_rows, "d_rows", F32, (B, F, D)), _chk(dW, "dW", F32, (D, T)), _chk(db, "db", F32, (T,)),
+        _chk(dh, "dh", F32, (T,)), _chk(dp, "dp", F32, (D,)), _chk(workspace, "workspace", F32), _stream())
+
+
 def gather_rows(table, rows, out):
     """out[i, :] = table[rows[i], :width] with width = out.shape[1] <= table.shape[1] (the shard keeps
     optimizer state behind the exchanged columns).  `table` may live in PINNED host memory (th/feeder.py)."""

@@ -36,7 +36,7 @@ log = logging.getLogger(__name__)
 
 
 class DeepModel(BaseEstimator, TransformerMixin):
-    model = None  # "deepfm" | "dcn" | "xdeepfm"
+    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm"
 
     def __init__(self, feat_dict: FeatureDictionary, hparams: dict, metrics, epoch, batch_size=64,
                  random_seed=2019, task="classification", strict_reference=False, device="cuda"):
@@ -72,6 +72,11 @@ class DeepModel(BaseEstimator, TransformerMixin):
         hp["strict_reference"] = self.strict_reference
         self._shard = self._dist_info()
         if self._shard is not None:
+            if self.model == "afm":
+                self._shard = None
+                raise NotImplementedError(
+                    "AFM runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
+                    "multi-rank torch.distributed job); use table_sharding='none'")
             return self._build_sharded(spec, hp)
         e = eng.ENGINES[self.model](spec, hp["embedding_size"], hp, task=self.task, device=self.device)
         eng.init_reference(e, self.random_seed)
@@ -362,6 +367,9 @@ class DeepModel(BaseEstimator, TransformerMixin):
             shapes = [(B, e.F, e.D)] + [(B, n, e.D) for n in e.units]
             masks["cin"] = [(torch.rand(*sh, device=dev) < k).float() if k < 1 else None
                             for sh, k in zip(shapes, ck)]
+        ak = hp.get("att_dropout", 1)
+        if e.model == "afm" and ak is not None and ak < 1:
+            masks["afm"] = (torch.rand(B, e.D, device=dev) < ak).float() / ak
         return masks or None
 
     def fit_on_batch(self, X, y):

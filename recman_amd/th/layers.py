@@ -16,7 +16,7 @@ DeepFM.py:107-163, DCN.py:99-149).  recman/th/layers.py, the file this fills, is
 
 Each layer is a torch.autograd.Function over recman_amd/ops.py (the C ABI, librecman_hip.so): forward and
 backward are the same hand-written kernels the engines use (csrc/embed.hip, mlp.hip, gemm.hip, cin.hip,
-cross.hip, loss.hip); torch is the plumbing in between - autograd's tape, the l2 terms, the bias-table
+cross.hip, afm.hip, loss.hip); torch is the plumbing in between - autograd's tape, the l2 terms, the bias-table
 lookup and the loss on probabilities are plain torch ops.  Variables are float32 CUDA leaf tensors
 under the reference's names, so `variables` is at once the parameter list of a torch optimizer and the
 state dict of a checkpoint.  There is no CPU path.
@@ -735,6 +735,85 @@ class CrossNet:
 
 
 # ------------------------------------------------------------------------------------------------
+# AFM attention layer
+# ------------------------------------------------------------------------------------------------
+class _AFMFn(torch.autograd.Function):
+    """rm_afm_fwd / rm_afm_bwd (csrc/afm.hip), as the AFM engine runs them."""
+
+    @staticmethod
+    def forward(ctx, E, W, b, h, p, mask):
+        B, F, D = E.shape
+        E_ = E.detach().contiguous()
+        W_, b_, h_, p_ = (W.detach().contiguous(), b.detach().contiguous(), h.detach().reshape(-1).contiguous(),
+                          p.detach().reshape(-1).contiguous())
+        logit = torch.empty(B, device=E.device, dtype=F32)
+        stats = torch.empty(B, ops.afm_stats_width(D), device=E.device, dtype=F32)
+        ops.afm_fwd(E_, W_, b_, h_, p_, logit, mask=mask, stats=stats)
+        ctx.save_for_backward(E_, W_, b_, h_, p_, logit, stats)
+        ctx.mask = mask
+        return logit.view(B, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        E, W, b, h, p, logit, stats = ctx.saved_tensors
+        B, F, D = E.shape
+        T = W.shape[1]
+        dev = E.device
+        dE = torch.empty_like(E)
+        dW, db, dh, dp = torch.empty_like(W), torch.empty_like(b), torch.empty_like(h), torch.empty_like(p)
+        ws = torch.empty(max(4, ops.afm_bwd_workspace(B, F, D, T)), device=dev, dtype=F32)
+        ops.afm_bwd(E, W, b, h, p, g.reshape(-1).contiguous(), logit, stats, dE, dW, db, dh, dp, ws, mask=ctx.mask)
+        return dE, dW, db, dh.view(-1, 1), dp.view(-1, 1), None
+
+
+class AFMLayer:
+    """The class AFM.py:7 imports commented out and AFM.py:119-122 uses: AFMLayer(att_factor, att_dropout)(feat_embeds)
+    -> logit [B,1], `.weights`, `.l2()`.  Arithmetic: arXiv 1708.04617 eq. (4)-(6): over the field pairs i < j,
+    a_ij = softmax(h . relu(W^T (E_i * E_j) + b)), logit = p . dropout(sum_ij a_ij E_i * E_j).  Variables (names
+    chosen here - the reference has none): afm_attention_w [D,T], afm_attention_b [T], afm_attention_h [T,1],
+    afm_projection_p [D,1].  att_dropout is a KEEP probability, applied when called with training=True (or with an
+    explicit `mask` [B,D] of multipliers, 0 or 1/keep).  l2(): the attention matrix only, as in the paper."""
+
+    display_name = "AFM"
+    names = ("afm_attention_w", "afm_attention_b", "afm_attention_h", "afm_projection_p")
+
+    def __init__(self, variables, att_factor, att_dropout=1, l2_reg=0.0, prefix="", seed=2019):
+        self.variables, self.att_factor, self.att_dropout = variables, int(att_factor), att_dropout
+        self.l2_reg, self.prefix, self.seed = l2_reg, prefix, seed
+
+    def _upsert_variables(self, D):
+        T, pre, v = self.att_factor, self.prefix, self.variables
+        if pre + "afm_attention_w" not in v:
+            v[pre + "afm_attention_w"] = _leaf(glorot_normal([D, T], self.seed))
+        if pre + "afm_attention_b" not in v:
+            v[pre + "afm_attention_b"] = _leaf(torch.zeros(T))
+        if pre + "afm_attention_h" not in v:
+            v[pre + "afm_attention_h"] = _leaf(glorot_normal([T, 1], self.seed))
+        if pre + "afm_projection_p" not in v:
+            v[pre + "afm_projection_p"] = _leaf(glorot_normal([D, 1], self.seed))
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.names]
+
+    def __call__(self, E, training=False, mask=None):
+        B, F, D = E.shape
+        if not ops.afm_supported(F, D, self.att_factor):
+            raise ValueError(f"AFMLayer: F={F}, D={D}, att_factor={self.att_factor} unsupported "
+                             "(2..40 fields, D in 8/16/32/64, att_factor 1..64)")
+        self._upsert_variables(D)
+        if mask is None and training and self.att_dropout < 1:
+            mask = _keep_mask((B, D), self.att_dropout) / self.att_dropout
+        if mask is not None:
+            mask = mask.detach().to(E.device, F32).contiguous()
+        W, b, h, p = self.weights
+        return _AFMFn.apply(E, W, b, h, p, mask)
+
+    def l2(self):
+        return self.l2_reg * 0.5 * self.variables[self.prefix + "afm_attention_w"].square().sum()
+
+
+# ------------------------------------------------------------------------------------------------
 # prediction + loss
 # ------------------------------------------------------------------------------------------------
 class _SigmoidFn(torch.autograd.Function):
@@ -787,5 +866,5 @@ def create_loss(y, pred, task="classification"):
 
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
-           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "PredictionLayer",
+           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "AFMLayer", "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
