@@ -369,6 +369,48 @@ int rm_afm_bwd(const float *E, const float *W, const float *b, const float *h, c
                float *dh, float *dp, float *workspace, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
+ * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
+ * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,
+ * inputs.py:443).  CSR input: example b owns history ids ids[offsets[b] .. offsets[b+1]),
+ * offsets[B] == nnz.  rows [*, LD]: the fused table; a history id addresses row row0 + id
+ * (the query feature's block), the example's query is row qrow[b] (absolute).  Per example:
+ *     x_l = [q, k_l, q - k_l, q * k_l] (4D, columns 0..D-1 of the rows)
+ *     z   = act(.. act(x_l W0 + b0) .. )     n_layers = 1 or 2, widths H[], W0 [4D,H0], W1 [H0,H1]
+ *     s_l = z . w + w0;   a_l = s_l (norm = 0)  or  softmax over the example's l (norm = 1, max-
+ *     subtracted);   out_b = sum_l a_l k_l;  no history -> 0
+ *   act: RM_ASP_RELU / RM_ASP_SIGMOID.
+ * rm_asp_fwd writes out [B, LD] (out_b in columns 0..D-1, zeros behind) and scores [nnz] = s_l: the
+ *   one per-position value that reaches HBM and all the backward needs (inference passes the same
+ *   kind of buffer: one code path, the pooled rows are the same bits).  workspace:
+ *   rm_asp_workspace(D, n_layers, H, nnz, 0) floats.
+ * rm_asp_bwd, given d_out (the pooled rows' gradient, row b at d_out + b * do_stride, D floats),
+ *   recomputes x and the hidden layers and writes  d_keys [nnz, D] (the gradient of every history
+ *   occurrence's row), ADDS the query gradient onto d_query[b * dq_stride + 0..D-1] (one example
+ *   per lane group), and overwrites dW0, db0, dW1, db1 (NULL with one layer), dw [H_last], dw0 [1].
+ *   workspace: rm_asp_workspace(D, n_layers, H, nnz, 1) floats, 16-byte aligned.
+ * Supported (rm_asp_supported): D in {8,16,32}, 1 or 2 hidden layers of 1..128 units, max_len
+ *   1..256; anything else is RM_EINVAL before any launch.
+ * Deterministic: per-block partial sums added in block order, fixed-order sums inside a block,
+ *   no float atomics - two runs on the same inputs are bit-equal. */
+#define RM_ASP_RELU 0
+#define RM_ASP_SIGMOID 1
+int rm_asp_supported(int D, int n_layers, const int *H, int max_len);
+int64_t rm_asp_workspace(int D, int n_layers, const int *H, int64_t nnz, int backward);
+int rm_asp_fwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+               const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz, const float *W0,
+               const float *b0, const float *W1, const float *b1, const float *w, const float *w0,
+               int n_layers, const int *H, int act, int norm, float *out, float *scores,
+               float *workspace, rm_stream_t stream);
+int rm_asp_bwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+               const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz, const float *W0,
+               const float *b0, const float *W1, const float *b1, const float *w, const float *w0,
+               int n_layers, const int *H, int act, int norm, const float *scores, const float *d_out,
+               int64_t do_stride, float *d_keys, float *d_query, int64_t dq_stride, float *dW0,
+               float *db0, float *dW1, float *db1, float *dw, float *dw0, float *workspace,
+               rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CIN (xDeepFM), one layer, on the f32-input MFMA.
  * Replaces the loop body of CIN.__call__ (layers.py:714-752):
  *   Z[b,d,i*H+j] = X0[b,i,d] * Xk[b,j,d];  M = Z @ W + bias;  out = act(M)

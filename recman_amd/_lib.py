@@ -62,6 +62,10 @@ SIGNATURES = {
     "rm_afm_supported": [c_int, c_int, c_int],
     "rm_afm_fwd": [P, P, P, P, P, P, I64, c_int, c_int, c_int, P, P, P],
     "rm_afm_bwd": [P, P, P, P, P, P, P, P, P, P, I64, c_int, c_int, c_int, P, P, P, P, P, P, P],
+    "rm_asp_supported": [c_int, c_int, P, c_int],
+    "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
+    "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
+                   I64, P, P, P, P, P, P, P, P],
     "rm_cin_layer_fwd": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
                          c_int, P, P],
     "rm_cin_layer_fwd6": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
@@ -101,6 +105,7 @@ SIGNATURES_I64 = {
     "rm_cin_filter_workspace6": [c_int, c_int, c_int, c_int],
     "rm_cin_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_afm_bwd_workspace": [I64, c_int, c_int, c_int],
+    "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],
     "rm_outer_actgrad_sums_workspace": [I64, c_int],

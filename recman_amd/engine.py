@@ -44,7 +44,7 @@ class FeatureSpec:
     included, inputs.py:166) and the dense feature names."""
 
     def __init__(self, sparse_names, feat_sizes, dense_names=(), multi_names=(), value_names=(),
-                 linear_names=None):
+                 linear_names=None, seq_query=None, seq_max_len=None):
         self.sparse_names = list(sparse_names)
         self.feat_sizes = [int(v) for v in feat_sizes]
         self.dense_names = list(dense_names)
@@ -62,6 +62,16 @@ class FeatureSpec:
         self.value_names = list(value_names)
         if len(self.sparse_names) != len(self.feat_sizes):
             raise ValueError("sparse_names and feat_sizes differ in length")
+        # embedding features that are behaviour histories (SequenceFeat): name -> the feature whose table rows
+        # they look up and whose row of the example is the attention's query; they own no rows (feat_size 0)
+        self.seq_query = dict(seq_query or {})
+        self.seq_max_len = {n: int((seq_max_len or {}).get(n, 256)) for n in self.seq_query}
+        size = dict(zip(self.sparse_names, self.feat_sizes))
+        for n, q in self.seq_query.items():
+            if n not in size or size[n] != 0:
+                raise ValueError(f"sequence feature {n!r} must be an embedding feature with feat_size 0")
+            if q not in size or q in self.seq_query or q in self.multi_names or q in self.value_names:
+                raise ValueError(f"sequence feature {n!r}: its query feature {q!r} must be a plain sparse feature")
 
     @property
     def F(self):
@@ -114,7 +124,11 @@ class FeatureSpec:
     @property
     def scratch_names(self):
         """Features whose per-example row is computed into scratch rows before the gather."""
-        return self.multi_names + self.value_names
+        return self.multi_names + self.value_names + self.seq_names
+
+    @property
+    def seq_names(self):
+        return [n for n in self.sparse_names if n in self.seq_query]
 
 
 class MLP:
@@ -379,6 +393,9 @@ def init_reference(engine, seed=2019):
             tn(t, t.shape[1], t.shape[2] if t.dim() == 3 else 1)
         elif name == "cross_w_out":
             tn(t, t.shape[0], 1)
+        elif name.endswith("_asp_w"):
+            # the attention unit is absent from the reference (DIN.py:6): its output projection like dnn_w
+            tn(t, t.shape[0], t.shape[1])
         elif name in ("afm_attention_w", "afm_attention_h", "afm_projection_p"):
             # the attention layer is absent from the reference (AFM.py:7): glorot like dnn_w / cross_w_out
             tn(t, t.shape[0], t.shape[1])
@@ -408,6 +425,95 @@ class Engine:
         self.grads["linear_w_dense"] = torch.zeros(Dn, dtype=F32, device=dev)
         self._B = None
         self.use_linear = True
+        self._init_seq()
+
+    def _init_seq(self):
+        """The attention unit of every sequence feature (csrc/asp.hip; DIN's local activation unit, arXiv 1706.06978):
+        variables {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w
+        [H_last, 1], {name}_asp_w0 [1].  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's
+        Dice, activation.py, uses undefined names), att_weight_normalization False, att_dropout all ones."""
+        spec, hp, dev, D = self.spec, self.hp, self.device, self.D
+        self._asp_saved = {}
+        if not spec.seq_names:
+            return
+        if not hasattr(self, "rows") or self.rows.dim() != 2 or self.rows.shape[0] != spec.rows:
+            raise NotImplementedError("sequence features (SequenceFeat) need the whole table on one GPU: there is "
+                                      "no row-sharded path for them (use table_sharding='none')")
+        self.asp_hidden = [int(h) for h in hp.get("att_hidden_units", (80, 40))]
+        act = hp.get("att_activation", "sigmoid")
+        act = act if isinstance(act, str) else getattr(act, "__name__", str(act))
+        self.asp_act = act.lower()
+        if self.asp_act == "dice":
+            raise NotImplementedError("att_activation='dice': the reference's Dice (activation.py) uses undefined "
+                                      "names and has no arithmetic to follow; use 'sigmoid' or 'relu'")
+        if self.asp_act not in ops.ASP_ACTS:
+            raise ValueError(f"att_activation {act!r}: 'relu' or 'sigmoid'")
+        drop = hp.get("att_dropout", 1)
+        drop = list(drop) if isinstance(drop, (list, tuple)) else [drop]
+        if any(float(k) != 1.0 for k in drop):
+            raise NotImplementedError("att_dropout: the attention unit runs without dropout (every keep "
+                                      f"probability must be 1, got {hp.get('att_dropout')!r})")
+        self.asp_norm = bool(hp.get("att_weight_normalization", False))
+        for n in spec.seq_names:
+            if not ops.asp_supported(D, self.asp_hidden, spec.seq_max_len[n]):
+                raise ValueError(f"sequence feature {n!r}: embedding_size={D}, att_hidden_units={self.asp_hidden}, "
+                                 f"max_len={spec.seq_max_len[n]} is not supported by rm_asp_fwd (embedding_size 8/16/32, "
+                                 "one or two hidden layers of 1..128 units, max_len 1..256)")
+            dims = [4 * D] + self.asp_hidden
+            shapes = []
+            for i in range(len(self.asp_hidden)):
+                shapes += [(f"{n}_asp_layer_{i}_weights", (dims[i], dims[i + 1])), (f"{n}_asp_layer_{i}_bias", (dims[i + 1],))]
+            shapes += [(f"{n}_asp_w", (dims[-1], 1)), (f"{n}_asp_w0", (1,))]
+            for nm, shape in shapes:
+                self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
+                self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+
+    def _asp_vars(self, d, name):
+        """(Ws, bs, w, w0) of sequence feature `name` out of the params or the grads dict."""
+        m = len(self.asp_hidden)
+        return ([d[f"{name}_asp_layer_{i}_weights"] for i in range(m)], [d[f"{name}_asp_layer_{i}_bias"] for i in range(m)],
+                d[f"{name}_asp_w"].view(-1), d[f"{name}_asp_w0"])
+
+    def _asp_fwd(self, j, f, idx):
+        """Sequence field f (scratch block j): the attention-pooled history rows into the scratch rows."""
+        name = self.spec.sparse_names[f]
+        offsets, ids, _ = self._mv_entry(f)
+        fq = self.spec.sparse_names.index(self.spec.seq_query[name])
+        row0 = int(self.field_off_host[fq])
+        qrow = idx[:, fq] + row0
+        nnz = int(ids.shape[0])
+        buf = self._asp_saved.get(f)
+        if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.asp_workspace(self.D, self.asp_hidden, nnz, True):
+            cap = max(nnz, 1)
+            buf = dict(cap=cap, scores=torch.empty(cap, dtype=F32, device=self.device),
+                       d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
+                       ws=torch.empty(max(4, ops.asp_workspace(self.D, self.asp_hidden, cap, True)), dtype=F32,
+                                      device=self.device))
+            self._asp_saved[f] = buf
+        buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq)
+        ops.asp_fwd(self.rows, row0, self.D, offsets, ids, qrow, *self._asp_vars(self.params, name), self.asp_act,
+                    self.asp_norm, self.mv_scratch[j], buf["scores"][:nnz], buf["ws"])
+
+    def _seq_bwd(self):
+        """After the model's backward filled d_rows: every sequence field's pooled-row gradient goes through the
+        attention unit - key gradients per history occurrence (kept for dense_grads / the row-wise optimizer), the
+        query gradient ADDED onto the query field's rows of d_rows, the unit's parameter gradients."""
+        for f in self.mv_fields:
+            name = self.spec.sparse_names[f]
+            if name not in self.spec.seq_query:
+                continue
+            b = self._asp_saved[f]
+            nnz = b["nnz"]
+            ops.asp_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
+                        *self._asp_vars(self.params, name), self.asp_act, self.asp_norm, b["scores"][:nnz],
+                        self.d_rows[:, f, :], b["d_keys"][:nnz], self.d_rows[:, b["fq"], :],
+                        *self._asp_vars(self.grads, name), b["ws"])
+
+    def seq_key_grads(self, f):
+        """(field of the query feature, history ids [nnz], their gradient rows [nnz, D]) of sequence field f after
+        the last fwd_bwd."""
+        b = self._asp_saved[f]
+        return b["fq"], b["ids"], b["d_keys"][: b["nnz"]]
 
     def _alloc_tables(self):
         """HBM layout: ONE table of fused rows [R, LD], LD = 2*D floats (a power of two, so a
@@ -429,6 +535,8 @@ class Engine:
         self.field_off = torch.tensor(offs, dtype=I64, device=dev)
         self.lin_off = self.field_off  # sparse one-hot blocks share the table's row numbering
         for name, off, V in zip(spec.sparse_names, offs, spec.feat_sizes):
+            if name in spec.seq_query:
+                continue  # a history shares its query feature's rows
             self.params[f"{name}_feat_embed"] = self.rows[off: off + V, :D]
             if self.use_bias_tables:
                 self.params[f"{name}_feat_bias"] = self.rows[off: off + V, D: D + 1]
@@ -570,6 +678,10 @@ class Engine:
                 raise ValueError(f"features {self.spec.scratch_names} need their ids / values (mv=...)")
             self.idx_mv.copy_(idx)
             for j, f in enumerate(self.mv_fields):
+                if self.spec.sparse_names[f] in self.spec.seq_query:
+                    self._asp_fwd(j, f, idx)
+                    self.idx_mv[:, f] = self._arange
+                    continue
                 offsets, ids, vals = self._mv_entry(f)
                 ops.pool_rows(self.rows, int(self.field_off_host[f]), D, offsets, ids, self.mv_scratch[j],
                               vals=vals)
@@ -657,6 +769,7 @@ class Engine:
                 self.dlogit.mul_(scale)
         self._lin_done = False
         self._branches_bwd(idx, dense, self.dlogit, masks)
+        self._seq_bwd()
         if self.use_linear and not self._lin_done:
             ops.linear_dense_bwd(self.dlogit, dense if self.Dn else None,
                                  self.grads["linear_w_dense"] if self.Dn else None,
@@ -867,6 +980,13 @@ class Engine:
         if self.use_linear:
             ops.scatter_add_rows(d_lin, idx, foff, g_row=self.dlogit)
         for f in self.mv_fields:
+            if self.spec.sparse_names[f] in self.spec.seq_query:
+                # history occurrences: their key-gradient rows go to the query feature's block (no bias / linear term)
+                fq, ids, d_keys = self.seq_key_grads(f)
+                if ids.numel():
+                    ops.scatter_add_rows(d_table, ids.view(-1, 1), self.field_off[fq: fq + 1].contiguous(),
+                                         rows=d_keys.view(-1, 1, D))
+                continue
             offsets, ids, vals = self._mv_entry(f)
             gb = None
             if d_bias is not None and self._has_fm():
@@ -885,6 +1005,8 @@ class Engine:
         if reg:
             d_table.add_(self.rows[:, :D], alpha=reg)
         for name, off, V in zip(self.spec.sparse_names, offs, self.spec.feat_sizes):
+            if name in self.spec.seq_query:
+                continue
             out[f"{name}_feat_embed"] = d_table[off: off + V]
             if d_bias is not None:
                 out[f"{name}_feat_bias"] = d_bias[off: off + V].view(V, 1)
@@ -1618,4 +1740,16 @@ class AFMEngine(Engine):
         ] + super().roofline_probes(idx, dense, y)
 
 
-ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine}
+class DINEngine(DeepFMEngine):
+    """DIN._init_graph (DIN.py, which stops after the pooling layer): final = linear + DNN([E | dense]), where E holds
+    the plain features' rows and ONE attention-pooled interest row per sequence feature (Engine._asp_fwd; Deep
+    Interest Network, arXiv 1706.06978) - the DeepFM engine without its FM term and without bias tables."""
+
+    model = "din"
+    use_bias_tables = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, dict(hp, use_fm=False, use_deep=True), task, device)
+
+
+ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine}

@@ -235,6 +235,82 @@ def afm_bwd(E, W, b, h, p, g, logit, stats, d_rows, dW, db, dh, dp, workspace, m
         _chk(dh, "dh", F32, (T,)), _chk(dp, "dp", F32, (D,)), _chk(workspace, "workspace", F32), _stream())
 
 
+ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
+
+
+def asp_supported(D, hidden, max_len):
+    """rm_asp_supported: D in {8, 16, 32}, one or two hidden layers of 1..128 units, 1 <= max_len <= 256."""
+    hidden = [int(h) for h in hidden]
+    if not hidden:
+        return False
+    return bool(_lib.lib().rm_asp_supported(int(D), len(hidden), _int_array(hidden), int(max_len)))
+
+
+def asp_workspace(D, hidden, nnz, backward):
+    """Floats of workspace rm_asp_fwd (backward=False) / rm_asp_bwd need (0: unsupported shape)."""
+    return int(_lib.lib().rm_asp_workspace(int(D), len(hidden), _int_array(hidden), int(nnz), 1 if backward else 0))
+
+
+def _asp_params(D, Ws, bs, w, w0):
+    hidden = [int(W.shape[1]) for W in Ws]
+    dims = [4 * D] + hidden
+    if len(Ws) != len(bs) or not 1 <= len(Ws) <= 2:
+        # (rejected here with the library's word: there is no slot for a third layer in the C signature)
+        raise _lib.RecmanHipError(f"asp: unsupported number of hidden layers {len(Ws)} (1 or 2)")
+    ptr = []
+    for i in range(2):
+        if i < len(Ws):
+            ptr += [_chk(Ws[i], f"W{i}", F32, (dims[i], dims[i + 1])), _chk(bs[i], f"b{i}", F32, (dims[i + 1],))]
+        else:
+            ptr += [None, None]
+    ptr += [_chk(w, "w", F32, (hidden[-1],)), _chk(w0, "w0", F32, (1,))]
+    return hidden, ptr
+
+
+def _asp_csr(rows, offsets, ids, qrow):
+    B = offsets.shape[0] - 1
+    _chk_csr(offsets, ids, None)
+    return B, int(ids.shape[0]), (_chk(rows, "rows", F32), _chk(offsets, "offsets", I64), _chk(ids, "ids", I64),
+                                  _chk(qrow, "qrow", I64, (B,)))
+
+
+def asp_fwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, out, scores, workspace):
+    """Attention-pooled history rows (rm_asp_fwd): rows [R, LD] the fused table, history id -> row row0 + id, the
+    example's query row qrow [B] (absolute); Ws = [W0 [4D,H0]] or [W0, W1 [H0,H1]], bs alike, w [H_last], w0 [1];
+    act "relu" | "sigmoid"; norm: softmax over the example's positions.  -> out [B, LD] (pooled row in columns
+    0..D-1, zeros behind) and scores [nnz] (all the backward keeps).  ids.shape[0] must equal offsets[-1]."""
+    LD = rows.shape[1]
+    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    hidden, pp = _asp_params(D, Ws, bs, w, w0)
+    need = asp_workspace(D, hidden, nnz, False)
+    if need and workspace.numel() < need:
+        raise ValueError(f"asp_fwd: workspace has {workspace.numel()} floats, needs {need}")
+    _lib.call("rm_asp_fwd", rp, LD, int(D), int(row0), op, ip, qp, B, nnz, *pp, len(hidden), _int_array(hidden),
+              ASP_ACTS[act], 1 if norm else 0, _chk(out, "out", F32, (B, LD)),
+              _chk(scores, "scores", F32, (nnz,)), _chk(workspace, "workspace", F32), _stream())
+
+
+def asp_bwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, scores, d_out, d_keys, d_query, dWs, dbs, dw,
+            dw0, workspace):
+    """rm_asp_bwd: d_out [B, D] view (row stride may be larger) = the pooled rows' gradient -> d_keys [nnz, D]
+    overwritten; the query gradient ADDED onto d_query [B, D] (a view, row stride may be larger); dWs, dbs, dw, dw0
+    overwritten.  Deterministic."""
+    LD = rows.shape[1]
+    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    hidden, pp = _asp_params(D, Ws, bs, w, w0)
+    _, gp = _asp_params(D, dWs, dbs, dw, dw0)
+    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
+        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
+            raise ValueError(f"asp_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
+    need = asp_workspace(D, hidden, nnz, True)
+    if need and workspace.numel() < need:
+        raise ValueError(f"asp_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _lib.call("rm_asp_bwd", rp, LD, int(D), int(row0), op, ip, qp, B, nnz, *pp, len(hidden), _int_array(hidden),
+              ASP_ACTS[act], 1 if norm else 0, _chk(scores, "scores", F32, (nnz,)),
+              d_out.data_ptr(), d_out.stride(0), _chk(d_keys, "d_keys", F32, (nnz, D)),
+              d_query.data_ptr(), d_query.stride(0), *gp, _chk(workspace, "workspace", F32), _stream())
+
+
 def gather_rows(table, rows, out):
     """out[i, :] = table[rows[i], :width] with width = out.shape[1] <= table.shape[1] (the shard keeps
     optimizer state behind the exchanged columns).  `table` may live in PINNED host memory (th/feeder.py)."""

@@ -132,7 +132,12 @@ class SparseTableOptimizer:
     Multi-valued (MultiValCsvFeat) and value (SparseValueFeat) features: their column of idx is
     masked out (-1) in the main call and every such feature is handed to the same kernel as an
     expanded one-field occurrence list - one occurrence per tag, its row gradient scaled by the
-    pooling / value factor (rm_pool_rows_bwd's factors)."""
+    pooling / value factor (rm_pool_rows_bwd's factors).
+    Sequence features (SequenceFeat): a history occurrence addresses a row of its QUERY feature's block, so that
+    field's column of idx is masked out as well and the field gets ONE occurrence list - its own B occurrences
+    followed by the history occurrences of every sequence feature that looks it up (their key-gradient rows from
+    rm_asp_bwd, zero bias and zero linear gradient): a row that is a target in one example and a history item in
+    another receives one update with the summed gradient."""
 
     def __init__(self, engine, name="adam", lr=1e-3, l2_embedding=0.0, l2_linear=0.0):
         from . import ops
@@ -209,9 +214,14 @@ class SparseTableOptimizer:
         self._prepared = None
         g_bias = e.dlogit if (e.use_bias_tables and e._has_fm()) else None
         g_lin = e.dlogit if e.use_linear else None
+        seq_of = {}  # query field -> the sequence fields that look its rows up
+        for f in e.mv_fields:
+            if e.spec.sparse_names[f] in e.spec.seq_query:
+                seq_of.setdefault(e.seq_key_grads(f)[0], []).append(f)
         if e.mv_fields:
+            idx_all = idx
             idx = idx.clone()
-            idx[:, e.mv_fields] = -1  # handled below
+            idx[:, e.mv_fields + sorted(seq_of)] = -1  # handled below
         B, F = idx.shape
         self.ops.sparse_optimizer_step(
             idx, e.field_off, e.d_rows, e.rows, self.mom, self._workspace(B * F), self.t,
@@ -219,7 +229,22 @@ class SparseTableOptimizer:
             lin_field_mask=getattr(e, "lin_field_mask", None), prepared=prepared,
             l2_embedding=self.l2_embedding, l2_linear=self.l2_linear if e.use_linear else 0.0,
             max_field_rows=self._max_field_rows())
+        for fq, fields in sorted(seq_of.items()):
+            ids = _t.cat([idx_all[:, fq]] + [e.seq_key_grads(f)[1] for f in fields])
+            rows_g = _t.cat([e.d_rows[:, fq, :]] + [e.seq_key_grads(f)[2] for f in fields]).contiguous()
+            pad = ids.numel() - B
+
+            def occ(g):  # the field's own occurrences carry the bias / linear gradient, the history ones zero
+                return None if g is None else _t.cat([g, g.new_zeros(pad)])
+
+            self.ops.sparse_optimizer_step(
+                ids.view(-1, 1).contiguous(), e.field_off[fq: fq + 1], rows_g.view(-1, 1, e.D), e.rows, self.mom,
+                self._workspace(ids.numel()), self.t, self.name, self.lr, g_bias=occ(g_bias),
+                g_lin=occ(g_lin) if self._lin_on(fq) else None, reset=reset, l2_embedding=self.l2_embedding,
+                l2_linear=self.l2_linear if (e.use_linear and self._lin_on(fq)) else 0.0)
         for f in e.mv_fields:
+            if e.spec.sparse_names[f] in e.spec.seq_query:
+                continue
             offsets, ids, vals = e._mv_entry(f)
             n = offsets[1:] - offsets[:-1]
             seg = _t.repeat_interleave(_t.arange(B, device=ids.device), n)

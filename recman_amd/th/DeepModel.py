@@ -36,7 +36,7 @@ log = logging.getLogger(__name__)
 
 
 class DeepModel(BaseEstimator, TransformerMixin):
-    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm"
+    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din"
 
     def __init__(self, feat_dict: FeatureDictionary, hparams: dict, metrics, epoch, batch_size=64,
                  random_seed=2019, task="classification", strict_reference=False, device="cuda"):
@@ -67,11 +67,23 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                [f.name for f in fd.dense_feats],
                                [f.name for f in fd.multi_val_csv_feats],
                                [f.name for f in fd.sparse_val_feats],
-                               linear_names=self._linear_names())
+                               linear_names=self._linear_names(),
+                               seq_query={f.name: f.id_feat.name for f in fd.sequence_feats},
+                               seq_max_len={f.name: f.max_len for f in fd.sequence_feats})
         hp = dict(self.hparams)
         hp["strict_reference"] = self.strict_reference
         self._shard = self._dist_info()
         if self._shard is not None:
+            if fd.sequence_feats:
+                self._shard = None
+                raise NotImplementedError(
+                    f"sequence features {[f.name for f in fd.sequence_feats]} run on one GPU: the row-sharded table "
+                    "has no attention-pooled lookup (table_sharding='row' or a multi-rank torch.distributed job); "
+                    "use table_sharding='none'")
+            if self.model == "din":
+                self._shard = None
+                raise NotImplementedError("DIN runs on one GPU: there is no row-sharded engine for it; use "
+                                          "table_sharding='none'")
             if self.model == "afm":
                 self._shard = None
                 raise NotImplementedError(

@@ -6,12 +6,14 @@ from .AFM import AFM
 from .BestModelFinder import BestModelFinder
 from .DCN import DCN
 from .DeepFM import DeepFM
+from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
-                     SparseFeat, SparseValueFeat)
+                     SequenceFeat, SparseFeat, SparseValueFeat)
 from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "BestModelFinder", "DCN", "DeepFM", "DeepModel", "xDeepFM", "DataInputs", "DenseFeat", "FeatureDictionary",
-           "MultiValCsvFeat", "ResilientLabelEncoder", "SparseFeat", "SparseValueFeat", "hparams", "layers"]
+__all__ = ["AFM", "BestModelFinder", "DCN", "DIN", "DeepFM", "DeepModel", "xDeepFM", "DataInputs", "DenseFeat",
+           "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
+           "hparams", "layers"]

@@ -300,6 +300,77 @@ class MultiValCsvFeat:
         return f"MultiValCsvFeat({self.name}, {len(self.tags)})"
 
 
+class SequenceFeat:
+    """inputs.py:428-467 (whose __init__ raises): a behaviour history - a list of raw ids of `id_feat` per example.
+    It shares id_feat's encoder and its table rows (layers.py:171-184 looks up `{id_feat.name}_feat_embed`) and owns
+    no rows, no linear and no bias entries: feat_size is 0.  The lookup is attention-pooled with the example's own
+    id_feat row as the query (csrc/asp.hip).  Lists longer than max_len keep their LAST max_len items and are
+    zero-padded at the end (pad_sequences: truncating="pre", padding="post", inputs.py:455); unseen items -> 0."""
+
+    def __init__(self, name, id_feat, max_len=10, dtype=None, description=None):
+        assert id_feat
+        self.name = name
+        self.id_feat = id_feat
+        self.max_len = int(max_len)
+        if self.max_len < 1:
+            raise ValueError(f"SequenceFeat {name!r}: max_len must be at least 1")
+        self.dtype = dtype
+        self.description = description
+        self.feat_size = 0
+
+    @property
+    def encoder(self):
+        return self.id_feat.encoder
+
+    def get_shape(self, for_tf=True):
+        return None if for_tf else -1, self.max_len
+
+    def initialize(self, X):
+        pass  # the vocabulary is id_feat's
+
+    @staticmethod
+    def _cells(x):
+        """The column as a list of item lists; None, NaN and [] are empty histories."""
+        out = []
+        for v in (x.tolist() if isinstance(x, (pd.Series, np.ndarray)) else list(x)):
+            if v is None or (isinstance(v, float) and np.isnan(v)):
+                v = []
+            elif isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+                v = [v]
+            out.append(list(v))
+        return out
+
+    def encode(self, x):
+        """-> CSR of encoded ids with the true lengths min(len, max_len): padding is never looked up."""
+        cells = [c[-self.max_len:] for c in self._cells(x)]
+        n = np.fromiter((len(c) for c in cells), dtype=np.int64, count=len(cells))
+        offsets = np.concatenate(([0], np.cumsum(n)))
+        flat = [v for c in cells for v in c]
+        if not flat:
+            return CSR(offsets, np.zeros(0, np.int64))
+        if self.encoder:
+            numeric = all(isinstance(v, (int, np.integer)) for v in flat)
+            ids = self.encoder.transform(np.asarray(flat, dtype=np.int64 if numeric else object)).reshape(-1)
+        else:
+            ids = np.asarray(flat, dtype=np.int64)
+        return CSR(offsets, np.asarray(ids, dtype=np.int64))
+
+    def __call__(self, x):
+        c = self.encode(x)
+        out = np.zeros((len(c), self.max_len), dtype=np.int64)
+        n = c.offsets[1:] - c.offsets[:-1]
+        rows = np.repeat(np.arange(len(c)), n)
+        cols = np.arange(c.offsets[-1]) - np.repeat(c.offsets[:-1], n)
+        out[rows, cols] = c.ids
+        return out
+
+    def decode(self, x):
+        return self.encoder.inverse_transform(x) if self.encoder else x
+
+    def __repr__(self):
+        return f"SequenceFeat({self.name}, {self.id_feat.name}, max_len={self.max_len})"
+
+
 class FeatureDictionary(OrderedDict):
     """inputs.py:8-43.  Insertion order defines the field axis of E (and therefore the
     row order of the CIN filters): embedding_feats are the non-dense features in order."""
@@ -333,14 +404,24 @@ class FeatureDictionary(OrderedDict):
         for feat in self.values():
             feat.initialize(X[feat.name])
 
+    @property
+    def sequence_feats(self):
+        return [f for f in self.values() if isinstance(f, SequenceFeat)]
+
     def check_supported(self):
-        ok = (SparseFeat, SparseValueFeat, DenseFeat, MultiValCsvFeat)
+        ok = (SparseFeat, SparseValueFeat, DenseFeat, MultiValCsvFeat, SequenceFeat)
         bad = [f for f in self.values() if not isinstance(f, ok)]
         if bad:
             raise NotImplementedError(
-                f"features {[f.name for f in bad]}: SparseFeat, SparseValueFeat, DenseFeat and "
-                "MultiValCsvFeat are on the HIP path (the reference itself raises NotImplementedError "
+                f"features {[f.name for f in bad]}: SparseFeat, SparseValueFeat, DenseFeat, MultiValCsvFeat and "
+                "SequenceFeat are on the HIP path (the reference itself raises NotImplementedError "
                 "for MultiValSparseFeat lookups, utils.py:111-115, and for SequenceFeat, inputs.py:443)")
+        for f in self.sequence_feats:
+            q = f.id_feat
+            if not isinstance(q, SparseFeat) or self.get(getattr(q, "name", None)) is not q:
+                raise ValueError(
+                    f"SequenceFeat {f.name!r}: its id_feat must be a SparseFeat of the same FeatureDictionary "
+                    "(the history is looked up in that feature's table rows and attended over by its row)")
 
 
 class DataInputs(dict):
@@ -357,7 +438,7 @@ class DataInputs(dict):
         n = len(X)
         # multi-valued features: tag ids as CSR; their idx column is a placeholder
         self.mv = {f.name: f.encode(X[f.name]) for f in sparse
-                   if isinstance(f, (MultiValCsvFeat, SparseValueFeat))}
+                   if isinstance(f, (MultiValCsvFeat, SparseValueFeat, SequenceFeat))}
         cols = [np.zeros((n, 1), np.int64) if f.name in self.mv else self[f.name] for f in sparse]
         self.idx = np.concatenate(cols, axis=1) if sparse else np.zeros((n, 0), np.int64)
         self.dense = (np.concatenate([self[f.name] for f in dense], axis=1).astype(np.float32)
@@ -376,10 +457,11 @@ class DataInputs(dict):
             if ids.size == 0:
                 continue
             lo, hi = int(ids.min()), int(ids.max())
-            if lo < 0 or hi >= f.feat_size:
+            size = f.id_feat.feat_size if isinstance(f, SequenceFeat) else f.feat_size  # (a history: id_feat's rows)
+            if lo < 0 or hi >= size:
                 raise ValueError(
-                    f"feature {f.name!r}: encoded id {lo if lo < 0 else hi} outside [0, {f.feat_size}) - "
-                    f"feat_size={f.feat_size - 1} is smaller than the fitted vocabulary")
+                    f"feature {f.name!r}: encoded id {lo if lo < 0 else hi} outside [0, {size}) - "
+                    f"feat_size={size - 1} is smaller than the fitted vocabulary")
 
     @property
     def y(self):
