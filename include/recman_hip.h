@@ -687,6 +687,36 @@ int rm_roc_auc(const float *scores, const int64_t *labels, int64_t n, void *work
 int rm_log_loss(const float *pred, const int64_t *labels, int64_t n, float eps, void *workspace,
                 rm_metric_result *out, rm_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Grouped AUC, GAUC (csrc/gauc.hip): the AUC inside each group (user), averaged over the groups that hold
+ * both classes - the measure of the DIN paper (arXiv 1706.06978, section 6.2).  New: the reference has none.
+ *
+ *   scores [n] fp32 finite, labels [n] int64 0 / 1, groups [n] int64 with 0 <= id < 2^32;  1 <= n <= 2^31 - 1
+ *   weight_kind        0: w_g = n_g (impressions, the paper)   1: w_g = P_g (clicks)
+ *   workspace          rm_group_auc_workspace(n) BYTES, 16-byte aligned
+ *   group_ids / group_n / group_pos / group_2u [n] each, or all NULL: per group, in ascending id order, its id,
+ *                      examples n_g, positives P_g and 2U_g (the Mann-Whitney count inside the group, ties one
+ *                      half; equal scores in different groups never tie).  Only the first out->groups entries
+ *                      are written.
+ *   out                ONE device record, read by the host in one copy
+ * GAUC = sum_g w_g AUC_g / sum_g w_g over the scored groups (P_g > 0 and N_g > 0), AUC_g = 2U_g / (2 P_g N_g).
+ * Every per-group integer is exact; the mean is double, summed in ascending id order by a fixed tree (no float
+ * atomics): bitwise reproducible and independent of the order of the input.  With no scored group the value is
+ * NaN and RM_METRIC_ONE_CLASS is set.  Invalid inputs set bits of out->flags as rm_roc_auc does. */
+#define RM_METRIC_BAD_GROUP 16 /* rm_group_auc: a group id outside [0, 2^32) */
+typedef struct rm_group_auc_result {
+  double value;          /* GAUC, NaN when no group is scored */
+  int64_t groups;        /* distinct group ids                */
+  int64_t scored_groups; /* those with both classes           */
+  int64_t weight;        /* sum of w_g over the scored groups */
+  int64_t pos;           /* P over all examples               */
+  int64_t flags;         /* RM_METRIC_*                       */
+} rm_group_auc_result;
+int64_t rm_group_auc_workspace(int64_t n);
+int rm_group_auc(const float *scores, const int64_t *labels, const int64_t *groups, int64_t n, int weight_kind,
+                 void *workspace, int64_t *group_ids, int64_t *group_n, int64_t *group_pos, uint64_t *group_2u,
+                 rm_group_auc_result *out, rm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,7 @@ SIGNATURES = {
                         I64, P],
     "rm_roc_auc": [P, P, I64, P, P, P],
     "rm_log_loss": [P, P, I64, c_float, P, P, P],
+    "rm_group_auc": [P, P, P, I64, c_int, P, P, P, P, P, P, P],
 }
 
 
@@ -116,6 +117,7 @@ SIGNATURES_I64 = {
     "rm_dense_wgrad_workspace": [c_int, c_int, I64],
     "rm_sparse_optimizer_workspace": [I64],
     "rm_metric_workspace": [I64],
+    "rm_group_auc_workspace": [I64],
 }
 
 

@@ -1,9 +1,10 @@
 """Evaluation metrics computed on the GPU: the counterpart of recman.metrics (recman/metrics/roc_auc.py:4-16,
 logloss.py:4-19) and of the sklearn functions the models score with by default.
 
-    from recman_amd.metrics import RocAucScore, LogLoss, roc_auc_score, log_loss
+    from recman_amd.metrics import RocAucScore, LogLoss, GroupAuc, roc_auc_score, log_loss, group_auc
 
     model = DeepFM(feat_dict, hparams, metrics=(RocAucScore(), LogLoss()), epoch=3)
+    model = DIN(feat_dict, eval_metric=(GroupAuc("user_id"), RocAucScore()))
 
 | name                         | semantics                                                                   |
 |------------------------------|-----------------------------------------------------------------------------|
@@ -16,14 +17,25 @@ logloss.py:4-19) and of the sklearn functions the models score with by default.
 | LogLoss(eps=1e-7)            | callable, str / repr "logloss", higher_the_better = False; clips at eps     |
 |                              | (the reference class's intent; it passes eps= to sklearn, which 1.7.2 no   |
 |                              | longer accepts)                                                             |
+| group_auc(y_true, y_score,   | GAUC of the DIN paper (arXiv 1706.06978): the exact AUC inside each group,  |
+|   groups, weight=...)        | averaged over the groups holding both classes, weighted by their examples   |
+|                              | ("impressions", default) or positives ("clicks") (rm_group_auc).  Equal     |
+|                              | scores in different groups never tie.  No group with both classes:          |
+|                              | UndefinedMetricWarning and nan.  return_groups=True: (value, dict of the    |
+|                              | device tensors ids, n, pos, two_u per group, ascending id)                  |
+| GroupAuc(by, weight=...)     | callable metric(y_true, y_pred, groups=...), str / repr "gauc",              |
+|                              | higher_the_better = True, group_by = by: DeepModel hands it the encoded id  |
+|                              | column of the SparseFeat named `by` (unknown ids encode to 0: one group)    |
 
 Inputs: torch tensors on the GPU are used in place; numpy arrays, lists and CPU tensors are copied to the GPU once.
 Scores are compared and clipped as float32 (other float types are converted).  Labels are 0 / 1 as int64, int32,
 bool or float; any other label value raises ValueError - a stated narrowing, sklearn accepts any two label values.
 NaN or infinite scores and empty inputs raise ValueError, sklearn's keywords (sample_weight, max_fpr, labels, ...)
 TypeError.  Every function returns a Python float: one device-to-host read per call.
+Group ids are integers in [0, 2^32) of an integer dtype (label-encode anything else first): a float, bool or
+string dtype and an id outside the range raise ValueError.
 
-Each of the four carries `on_device = True`: DeepModel.fit() / evaluate() keep predictions and labels on the GPU
+Each of the six carries `on_device = True`: DeepModel.fit() / evaluate() keep predictions and labels on the GPU
 when every configured metric has it (recman_amd/th/DeepModel.py).
 """
 import warnings
@@ -33,7 +45,7 @@ import torch
 
 from . import ops
 
-__all__ = ["roc_auc_score", "log_loss", "RocAucScore", "LogLoss"]
+__all__ = ["roc_auc_score", "log_loss", "group_auc", "RocAucScore", "LogLoss", "GroupAuc"]
 
 
 def _no_extras(name, extra):
@@ -125,8 +137,67 @@ def log_loss(y_true, y_pred, **unsupported):
     return _log_loss(y_true, y_pred, ops.FLT_EPSILON)
 
 
+_WEIGHT_KINDS = {"impressions": 0, "clicks": 1}
+
+
+def _group_ids(groups, n, dev):
+    if isinstance(groups, torch.Tensor):
+        g = groups.detach()
+        if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+            raise ValueError(f"groups must hold integer ids, got {g.dtype}")
+    else:
+        a = np.asarray(groups)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"groups must hold integer ids, got dtype {a.dtype} (label-encode them first)")
+        if a.dtype == np.uint64:
+            if a.size and int(a.max()) >= 2 ** 32:
+                raise ValueError("group ids must lie in [0, 2^32)")
+            a = a.astype(np.int64)
+        elif a.dtype.kind == "u":
+            a = a.astype(np.int64)  # (torch has no wide unsigned types)
+        g = torch.from_numpy(np.ascontiguousarray(a))
+    if g.dim() != 1:
+        raise ValueError(f"expected 1-D groups, got shape {tuple(g.shape)}")
+    if g.shape[0] != n:
+        raise ValueError(f"Found input variables with inconsistent numbers of samples: [{n}, {g.shape[0]}]")
+    return g.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def group_auc(y_true, y_score, groups, weight="impressions", return_groups=False, **unsupported):
+    """GAUC on the GPU: the exact AUC inside each group, averaged over the groups that hold both classes with
+    the weights n_g ("impressions") or P_g ("clicks").  return_groups=True: (value, {"ids", "n", "pos",
+    "two_u"}) - int64 device tensors, one entry per group in ascending id order (AUC_g = two_u / (2 pos (n -
+    pos)); two_u holds uint64 bits)."""
+    _no_extras("group_auc", unsupported)
+    if weight not in _WEIGHT_KINDS:
+        raise ValueError(f"weight must be one of {sorted(_WEIGHT_KINDS)}, got {weight!r}")
+    s, y = _inputs(y_true, y_score)
+    n = s.shape[0]
+    g = _group_ids(groups, n, s.device)
+    with torch.cuda.device(s.device):
+        per = [torch.empty(n, dtype=torch.int64, device=s.device) for _ in range(4)] if return_groups else None
+        rec = ops.group_auc(s, y, g, _WEIGHT_KINDS[weight], per_group=per)
+        v, G, scored, _, _, flags = ops.read_group_auc(rec)
+    if flags & ops.METRIC_BAD_SCORE:
+        raise ValueError("Input y_score contains NaN or infinity.")
+    if flags & ops.METRIC_BAD_LABEL:
+        raise ValueError("y_true must hold binary labels 0 / 1 (recman_amd.metrics scores 0/1 labels only)")
+    if flags & ops.METRIC_BAD_GROUP:
+        raise ValueError("group ids must lie in [0, 2^32) (label-encode them first)")
+    if flags & ops.METRIC_ONE_CLASS:
+        from sklearn.exceptions import UndefinedMetricWarning
+
+        warnings.warn("No group holds both classes. The grouped AUC is not defined in that case.",
+                      UndefinedMetricWarning, stacklevel=2)
+        v = float("nan")
+    if return_groups:
+        return v, dict(zip(("ids", "n", "pos", "two_u"), (t[:G] for t in per)))
+    return v
+
+
 roc_auc_score.on_device = True
 log_loss.on_device = True
+group_auc.on_device = True
 
 
 class RocAucScore:
@@ -162,3 +233,28 @@ class LogLoss:
 
     def __repr__(self):
         return "logloss"
+
+
+class GroupAuc:
+    """GAUC (group_auc) grouped by the feature `by`: DeepModel.fit() / evaluate() call it with groups= the
+    encoded id column of that SparseFeat.  Ids the encoder has not seen encode to 0 and form one group."""
+
+    on_device = True
+    higher_the_better = True
+
+    def __init__(self, by, weight="impressions"):
+        if weight not in _WEIGHT_KINDS:
+            raise ValueError(f"weight must be one of {sorted(_WEIGHT_KINDS)}, got {weight!r}")
+        self.by = self.group_by = by
+        self.weight = weight
+
+    def __call__(self, y_true, y_pred, groups=None):
+        if groups is None:
+            raise TypeError(f"GroupAuc needs groups=: the ids of {self.by!r}, one per example")
+        return group_auc(y_true, y_pred, groups, weight=self.weight)
+
+    def __str__(self):
+        return "gauc"
+
+    def __repr__(self):
+        return "gauc"

@@ -982,3 +982,53 @@ def read_metric(out):
     """(value, P, N, flags) of a metric record: one device-to-host copy."""
     r = out.cpu().numpy()
     return float(r[:1].view("float64")[0]), int(r[1]), int(r[2]), int(r[3])
+
+
+# ------------------------------------------------------------------------- grouped AUC (csrc/gauc.hip)
+METRIC_BAD_GROUP = 16
+
+
+def group_auc_workspace(n):
+    """Bytes of the workspace rm_group_auc needs for n elements (0 outside 1 <= n < 2^31)."""
+    return int(_lib.lib().rm_group_auc_workspace(int(n)))
+
+
+def group_auc(scores, labels, groups, weight_kind=0, workspace=None, out=None, per_group=None):
+    """Grouped AUC (rm_group_auc): scores fp32 [n], labels int64 [n], groups int64 [n] on the GPU; weight_kind 0
+    weighs a group by its examples, 1 by its positives.  per_group: None, or four int64 [n] tensors (ids, n, pos,
+    two_u - the last holds uint64 bits) whose first `groups` entries are written in ascending id order.  Returns
+    the device record `out` (int64 [6]: value as float64 bits, groups, scored groups, weight sum, P, flags); read
+    it with read_group_auc."""
+    n = scores.shape[0] if scores.dim() == 1 else -1
+    xp = _chk(scores, "scores", F32, (n,))
+    yp = _chk(labels, "labels", I64, (n,))
+    gp = _chk(groups, "groups", I64, (n,))
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"scores: need 1 <= n < 2^31 elements, got {n}")
+    if weight_kind not in (0, 1):
+        raise ValueError(f"weight_kind must be 0 (impressions) or 1 (clicks), got {weight_kind!r}")
+    need = group_auc_workspace(n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=scores.device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"group_auc workspace too small: {need} bytes needed")
+    wp = _chk(workspace, "workspace", workspace.dtype)
+    if out is None:
+        out = torch.empty(6, dtype=I64, device=scores.device)
+    op = _chk(out, "out", I64, (6,))
+    if wp % 16 or op % 16:
+        raise ValueError("group_auc workspace / out must be 16-byte aligned")
+    pg = [None] * 4
+    if per_group is not None:
+        if len(per_group) != 4:
+            raise ValueError("per_group: four int64 [n] tensors (ids, n, pos, two_u)")
+        pg = [_chk(t, name, I64, (n,)) for t, name in zip(per_group, ("group_ids", "group_n", "group_pos",
+                                                                      "group_2u"))]
+    _lib.call("rm_group_auc", xp, yp, gp, n, int(weight_kind), wp, *pg, op, _stream())
+    return out
+
+
+def read_group_auc(out):
+    """(value, groups, scored_groups, weight, P, flags) of a grouped-AUC record: one device-to-host copy."""
+    r = out.cpu().numpy()
+    return (float(r[:1].view("float64")[0]),) + tuple(int(v) for v in r[1:6])

@@ -50,6 +50,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
         self.batch_size = batch_size
         self.random_seed = random_seed
         self.metrics = metrics
+        self._group_columns()  # (a metric's group_by must name a SparseFeat: fails here, without a GPU)
         self.strict_reference = strict_reference
         self.device = device
         self._engine = None
@@ -339,6 +340,39 @@ class DeepModel(BaseEstimator, TransformerMixin):
         ms = self.metrics
         return bool(ms) and all(getattr(m, "on_device", False) for m in ms)
 
+    def _group_columns(self):
+        """name -> column of idx for every feature a configured metric groups by (a metric with a `group_by`
+        attribute, recman_amd.metrics.GroupAuc).  Such a metric is called with groups= the ENCODED id column of
+        that feature: ids the encoder has not seen encode to 0 and form one group."""
+        from .inputs import SparseFeat
+
+        cols = {}
+        names = [f.name for f in self.feat_dict.embedding_feats]
+        for m in self.metrics or ():
+            by = getattr(m, "group_by", None)
+            if by is None:
+                continue
+            if by not in self.feat_dict or not isinstance(self.feat_dict[by], SparseFeat):
+                raise ValueError(f"metric {m}: group_by={by!r} must name a SparseFeat of the feature dictionary "
+                                 "(dense, multi-valued, value and sequence features have no id column)")
+            cols[by] = names.index(by)
+        return cols
+
+    def _groups_of(self, idx, on_device):
+        """The id columns the grouped metrics take, from the encoded idx: device tensors when the metrics run
+        on the GPU, numpy arrays for the host path.  None without such a metric."""
+        cols = self._group_columns()
+        if not cols:
+            return None
+        if on_device:
+            return {by: idx[:, j].to(self._build().device).contiguous() for by, j in cols.items()}
+        return {by: idx[:, j].cpu().numpy() for by, j in cols.items()}
+
+    @staticmethod
+    def _score(metric, y, pred, groups):
+        by = getattr(metric, "group_by", None)
+        return metric(y, pred) if by is None else metric(y, pred, groups=groups[by])
+
     def _labels_on_device(self, y):
         ya = np.asarray(y)
         return torch.from_numpy(np.ascontiguousarray(ya)).to(self._build().device)
@@ -352,7 +386,13 @@ class DeepModel(BaseEstimator, TransformerMixin):
             idx, dense, _ = self._encode(X)
             pred = self._predict_device(idx, dense, training, self._mv_host)
             yd = self._labels_on_device(y)
-            return [float(metric(yd, pred)) for metric in self.metrics]
+            gc = self._groups_of(idx, True)
+            return [float(self._score(metric, yd, pred, gc)) for metric in self.metrics]
+        if self._group_columns():
+            idx, dense, _ = self._encode(X)  # (predict(), keeping the id columns)
+            pred = self._predict_encoded(idx, dense, training, self._mv_host)
+            gc = self._groups_of(idx, False)
+            return [self._score(metric, y, pred, gc) for metric in self.metrics]
         pred = self.predict(X, training, batch_number_to_show_progress)
         return [metric(y, pred) for metric in self.metrics]
 
@@ -420,18 +460,22 @@ class DeepModel(BaseEstimator, TransformerMixin):
 
     def _eval_at_epoch(self, enc_train, y_train, enc_valid=None, y_valid=None, start_time=None, epoch=0):
         """y_train / y_valid: host labels, or device labels when every metric runs on the GPU
-        (_metrics_on_device); the predictions then stay on the GPU too."""
+        (_metrics_on_device); the predictions then stay on the GPU too.  enc_*: (idx, dense, mv_host) and,
+        optionally, the id columns of the grouped metrics (_groups_of) where the caller has them already."""
         training = bool(self.strict_reference)  # DeepModel.py:103-111 evaluates with training=True
-        if self._metrics_on_device():
-            predict, score = self._predict_device, (lambda m, y, p: float(m(y, p)))
+        on_device = self._metrics_on_device()
+        if on_device:
+            predict, score = self._predict_device, (lambda m, y, p, g: float(self._score(m, y, p, g)))
         else:
-            predict, score = self._predict_encoded, (lambda m, y, p: m(y, p))
+            predict, score = self._predict_encoded, self._score
         ptr = predict(enc_train[0], enc_train[1], training, enc_train[2])
-        tr = [score(m, y_train, ptr) for m in self.metrics]
+        gtr = enc_train[3] if len(enc_train) > 3 else self._groups_of(enc_train[0], on_device)
+        tr = [score(m, y_train, ptr, gtr) for m in self.metrics]
         va = None
         if enc_valid is not None:
             pva = predict(enc_valid[0], enc_valid[1], training, enc_valid[2])
-            va = [score(m, y_valid, pva) for m in self.metrics]
+            gva = enc_valid[3] if len(enc_valid) > 3 else self._groups_of(enc_valid[0], on_device)
+            va = [score(m, y_valid, pva, gva) for m in self.metrics]
         log.info("[%d] train-result=%s%s [%.1f s]", epoch, [round(float(r), 4) for r in tr],
                  "" if va is None else ", valid-result=%s" % [round(float(r), 4) for r in va],
                  time() - (start_time or time()))
@@ -445,7 +489,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
         enc_valid = None
         if X_valid is not None and y_valid is not None:
             vi, vd, _ = self._encode(X_valid)
-            enc_valid = (vi, vd, self._mv_host)
+            enc_valid = (vi, vd, self._mv_host, self._groups_of(vi, self._metrics_on_device()))  # once per fit()
         pinned = self._use_feeder(len(y_train))
         idx, dense, yt = self._encode(X_train, y_train, on_host=pinned)
         mv_host = self._mv_host
@@ -537,7 +581,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
         feeder = BatchFeeder(idx, dense, yt, self.batch_size, e.device)
         perm_all = np.arange(n)  # position -> original row: the shuffles compose across epochs
         y_eval = self._labels_on_device(yt) if self._metrics_on_device() else y_train  # (device: copied once)
-        eval_results = self._eval_at_epoch((idx, dense, mv_host), y_eval, enc_valid, y_valid, time())
+        g_eval = self._groups_of(idx, self._metrics_on_device())  # (device: one column copied once per fit())
+        eval_results = self._eval_at_epoch((idx, dense, mv_host, g_eval), y_eval, enc_valid, y_valid, time())
         for epoch in range(1, self.epoch + 1):
             start = time()
             seed = np.random.randint(1, 2019) if random_seed_for_mini_batch else self.random_seed
@@ -551,7 +596,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 if i % every == 0:
                     log.info(f"Fit: {(i + 1)}/{total_batch} has been completed")
             # evaluation order does not matter for the metrics: the unshuffled host arrays
-            eval_results = self._eval_at_epoch((idx, dense, mv_host), y_eval, enc_valid, y_valid, start, epoch)
+            eval_results = self._eval_at_epoch((idx, dense, mv_host, g_eval), y_eval, enc_valid, y_valid, start,
+                                               epoch)
             if epoch_callback:
                 epoch_callback(model=self, eval_results=eval_results, df_all=X_train[:1])
         return None
