@@ -369,6 +369,50 @@ int rm_afm_bwd(const float *E, const float *W, const float *b, const float *h, c
                float *dh, float *dp, float *workspace, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * AutoInt interacting layer (multi-head self-attention over the fields, arXiv 1810.11921
+ * eq. (5)-(8)) and the model's last projection.  Nothing in the reference implements it.
+ * One layer maps X [B,F,Din] to Y [B,F,HD], HD = H dk; Wq, Wk, Wv, Wr [Din,HD]; Q, K, V are cut
+ * into H column blocks of width dk:
+ *     Q = X Wq;  K = X Wk;  V = X Wv;  s^h_mk = <Q^h_m, K^h_k> scale;  a^h_m. = softmax_k(s^h_m.)
+ *     O_m = concat_h sum_k a^h_mk V^h_k;  Y_m = relu(O_m + X_m Wr)      (Wr NULL: relu(O_m))
+ *   The softmax is max-subtracted and runs over all F fields (k = m included).
+ *   stats [B,H,F,2] (rm_autoint_stats_floats(B, F, H) floats) or NULL (inference): per (example,
+ *   head, field) the row maximum and the sum of exp(s - max) - all the backward keeps of the
+ *   forward besides X and Y.  Y is the same bits with and without stats.  Q, K, V, the scores and
+ *   the weights never leave the chip.
+ * Supported (rm_autoint_supported): 1 <= F <= 40, Din in {8,16,32,64}, H in {1,2,4,8}, dk >= 4,
+ *   H dk in {8,16,32,64}; anything else is RM_EINVAL ("unsupported") before any launch.
+ * rm_autoint_layer_bwd, given dY [B,F,HD], recomputes Q, K, V and the weights and writes
+ *   dX [B,F,Din] = dLoss/dX (+ dX_up when not NULL; dX_up may BE dX), dWq, dWk, dWv, dWr
+ *   (overwritten, summed over the batch; dWr NULL exactly when Wr is):
+ *     dP = dY [Y > 0];  da_mk = <dP^h_m, V^h_k>;  ds_mk = a_mk (da_mk - sum_k' a_mk' da_mk')
+ *     dQ_m = scale sum_k ds_mk K_k;  dK_k = scale sum_m ds_mk Q_m;  dV_k = sum_m a_mk dP_m
+ *     dW* = X^T d*;  dWr = X^T dP;  dX = dQ Wq^T + dK Wk^T + dV Wv^T + dP Wr^T
+ *   workspace: rm_autoint_layer_bwd_workspace(B, F, Din, H, dk) floats, 16-byte aligned.
+ * rm_autoint_head_fwd:  logit[b] = Y[b,:] . w + w0,  Y [B,K], w [K], w0 [1].
+ * rm_autoint_head_bwd, given g [B]:  dY[b,:] = g[b] w,  dw = sum_b g[b] Y[b,:],  dw0 = sum_b g[b];
+ *   workspace: rm_autoint_head_bwd_workspace(B, K) floats.
+ * Deterministic: per-block partial sums added in block order, fixed-order sums inside a block,
+ *   no float atomics - two runs on the same inputs are bit-equal.
+ */
+int rm_autoint_supported(int F, int Din, int H, int dk);
+int64_t rm_autoint_stats_floats(int64_t B, int F, int H);
+int rm_autoint_layer_fwd(const float *X, const float *Wq, const float *Wk, const float *Wv,
+                         const float *Wr, int64_t B, int F, int Din, int H, int dk, float scale,
+                         float *Y, float *stats, rm_stream_t stream);
+int64_t rm_autoint_layer_bwd_workspace(int64_t B, int F, int Din, int H, int dk);
+int rm_autoint_layer_bwd(const float *X, const float *Wq, const float *Wk, const float *Wv,
+                         const float *Wr, const float *Y, const float *stats, const float *dY,
+                         int64_t B, int F, int Din, int H, int dk, float scale, float *dX,
+                         const float *dX_up, float *dWq, float *dWk, float *dWv, float *dWr,
+                         float *workspace, rm_stream_t stream);
+int rm_autoint_head_fwd(const float *Y, const float *w, const float *w0, int64_t B, int K,
+                        float *logit, rm_stream_t stream);
+int64_t rm_autoint_head_bwd_workspace(int64_t B, int K);
+int rm_autoint_head_bwd(const float *Y, const float *w, const float *g, int64_t B, int K, float *dY,
+                        float *dw, float *dw0, float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

@@ -62,6 +62,12 @@ SIGNATURES = {
     "rm_afm_supported": [c_int, c_int, c_int],
     "rm_afm_fwd": [P, P, P, P, P, P, I64, c_int, c_int, c_int, P, P, P],
     "rm_afm_bwd": [P, P, P, P, P, P, P, P, P, P, I64, c_int, c_int, c_int, P, P, P, P, P, P, P],
+    "rm_autoint_supported": [c_int, c_int, c_int, c_int],
+    "rm_autoint_layer_fwd": [P, P, P, P, P, I64, c_int, c_int, c_int, c_int, c_float, P, P, P],
+    "rm_autoint_layer_bwd": [P, P, P, P, P, P, P, P, I64, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P,
+                             P],
+    "rm_autoint_head_fwd": [P, P, P, I64, c_int, P, P],
+    "rm_autoint_head_bwd": [P, P, P, I64, c_int, P, P, P, P, P],
     "rm_asp_supported": [c_int, c_int, P, c_int],
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
@@ -106,6 +112,9 @@ SIGNATURES_I64 = {
     "rm_cin_filter_workspace6": [c_int, c_int, c_int, c_int],
     "rm_cin_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_afm_bwd_workspace": [I64, c_int, c_int, c_int],
+    "rm_autoint_stats_floats": [I64, c_int, c_int],
+    "rm_autoint_layer_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
+    "rm_autoint_head_bwd_workspace": [I64, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],

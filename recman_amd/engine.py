@@ -399,6 +399,9 @@ def init_reference(engine, seed=2019):
         elif name in ("afm_attention_w", "afm_attention_h", "afm_projection_p"):
             # the attention layer is absent from the reference (AFM.py:7): glorot like dnn_w / cross_w_out
             tn(t, t.shape[0], t.shape[1])
+        elif name == "autoint_w" or (name.startswith("autoint_layer_") and name.endswith("_w")):
+            # the interacting layers are absent from the reference: glorot like dnn_w
+            tn(t, t.shape[0], t.shape[1])
         else:
             t.zero_()
 
@@ -1038,12 +1041,13 @@ class DeepFMEngine(Engine):
 
     model = "deepfm"
     use_bias_tables = True
+    needs_fm_or_deep = True  # DeepFM.py:54; a subclass with a branch of its own over E may run without either
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         super().__init__(spec, embedding_size, hp, task, device)
         self.use_fm = bool(hp.get("use_fm", True))
         self.use_deep = bool(hp.get("use_deep", True))
-        assert self.use_fm or self.use_deep  # DeepFM.py:54
+        assert self.use_fm or self.use_deep or not self.needs_fm_or_deep  # DeepFM.py:54
         self.mlp = None
         if self.use_deep:
             self.mlp = MLP(self.params, self.grads, self.FD, self.Dn, hp["deep_hidden_units"],
@@ -1752,4 +1756,156 @@ class DINEngine(DeepFMEngine):
         super().__init__(spec, embedding_size, dict(hp, use_fm=False, use_deep=True), task, device)
 
 
-ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine}
+class AutoIntEngine(DeepFMEngine):
+    """AutoInt (arXiv 1810.11921): final = linear + autoint (+ DNN([E | dense]) with a non-empty deep_hidden_units:
+    AutoInt+), PredictionLayer(use_bias=False).  Nothing in the reference implements it.  L interacting layers of
+    multi-head self-attention over the F rows of E, forward and backward fused in csrc/autoint.hip:
+        Q, K, V = X Wq, X Wk, X Wv;  a^h_m. = softmax_k(<Q^h_m, K^h_k> c);  Y_m = relu(concat_h sum_k a^h_mk V^h_k + X_m Wr)
+        autoint_logit = flatten(Y_L) . autoint_w + autoint_w0
+    Variables (names chosen here): autoint_layer_{l}_query_w / _key_w / _value_w [Din, H dk], autoint_layer_{l}_res_w
+    (att_res only), autoint_w [F H dk, 1], autoint_w0 [1]; Din = embedding_size for layer 0, H dk after it.
+    l2: att_l2_reg over every matrix above.  No bias tables; the dense features enter the linear term and the DNN
+    only.  The attention needs E in HBM: the one-kernel step is never selected (no FM term) and the DNN runs behind
+    the interacting layers so that its fused head sees the attention's logit."""
+
+    model = "autoint"
+    use_bias_tables = False
+    needs_fm_or_deep = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        n = len(hidden)
+        keep = hp.get("deep_dropout")
+        hp = dict(hp, use_fm=False, use_deep=n > 0, deep_hidden_units=hidden,
+                  deep_dropout=tuple(keep) if keep is not None else (1,) * (n + 1))
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.L = int(hp.get("att_layer_num", 3))
+        self.dk = int(hp.get("att_embedding_size", 8))
+        self.H = int(hp.get("att_head_num", 2))
+        self.res = bool(hp.get("att_res", True))
+        self.HD = self.H * self.dk
+        self.scale = float(self.dk) ** -0.5 if hp.get("att_scaling", False) else 1.0
+        if self.L < 1:
+            raise ValueError(f"AutoInt: att_layer_num={self.L} must be at least 1")
+        dins = [self.D] + [self.HD] * (self.L - 1)
+        for din in dins:
+            if not ops.autoint_supported(self.F, din, self.H, self.dk):
+                raise ValueError(
+                    f"AutoInt: {self.F} embedding features, layer input width {din}, att_head_num={self.H}, "
+                    f"att_embedding_size={self.dk} is not supported by rm_autoint_layer_fwd (1..40 features, "
+                    "embedding_size 8/16/32/64, att_head_num 1/2/4/8, att_embedding_size >= 4, att_head_num * "
+                    "att_embedding_size 8/16/32/64)")
+        self.dins = dins
+        self.att_names = []
+        shapes = []
+        for l, din in enumerate(dins):
+            for kind in ("query", "key", "value") + (("res",) if self.res else ()):
+                shapes.append((f"autoint_layer_{l}_{kind}_w", (din, self.HD)))
+                self.att_names.append(shapes[-1][0])
+        shapes += [("autoint_w", (self.F * self.HD, 1)), ("autoint_w0", (1,))]
+        self.att_names.append("autoint_w")
+        for nm, shape in shapes:
+            self.params[nm] = torch.zeros(shape, dtype=F32, device=self.device)
+            self.grads[nm] = torch.zeros(shape, dtype=F32, device=self.device)
+
+    def _alloc_model(self, B):
+        dev, F, H = self.device, self.F, self.H
+        self.att_Y = [torch.empty(B, F, self.HD, dtype=F32, device=dev) for _ in range(self.L)]
+        self.att_stats = [torch.empty(B, H, F, 2, dtype=F32, device=dev) for _ in range(self.L)]
+        self.att_dY = torch.empty(B, F, self.HD, dtype=F32, device=dev)
+        self.att_dX = torch.empty(B, F, self.HD, dtype=F32, device=dev) if self.L > 1 else None
+        self.att_logit = torch.empty(B, dtype=F32, device=dev)
+        need = max([ops.autoint_layer_bwd_workspace(B, F, din, H, self.dk) for din in self.dins]
+                   + [ops.autoint_head_bwd_workspace(B, F * self.HD), 4])
+        self.att_ws = torch.empty(need, dtype=F32, device=dev)
+
+    def _att_weights(self, l, src):
+        return [src.get(f"autoint_layer_{l}_{kind}_w") for kind in ("query", "key", "value", "res")]
+
+    def _att_fwd(self, training):
+        x = self.E
+        for l in range(self.L):
+            ops.autoint_layer_fwd(x, *self._att_weights(l, self.params), self.H, self.scale, self.att_Y[l],
+                                  stats=self.att_stats[l] if training else None)
+            x = self.att_Y[l]
+        ops.autoint_head_fwd(x, self.params["autoint_w"].view(-1), self.params["autoint_w0"], self.att_logit)
+
+    def _att_bwd(self, g, dx_up):
+        """The head and the layers in reverse; layer 0 writes d_rows (= dx_up + its own when the DNN ran first)."""
+        p, gr = self.params, self.grads
+        ops.autoint_head_bwd(self.att_Y[-1], p["autoint_w"].view(-1), g, self.att_dY, gr["autoint_w"].view(-1),
+                             gr["autoint_w0"], self.att_ws)
+        dy, spare = self.att_dY, self.att_dX  # two buffers of one shape take turns: a layer's dX is the next one's dY
+        for l in reversed(range(self.L)):
+            x = self.att_Y[l - 1] if l else self.E
+            dx = spare if l else self.d_rows
+            ops.autoint_layer_bwd(x, *self._att_weights(l, p), self.att_Y[l], self.att_stats[l], dy, self.H,
+                                  self.scale, dx, *self._att_weights(l, gr), self.att_ws,
+                                  dX_up=dx_up if l == 0 else None)
+            dy, spare = dx, dy
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        hp = self.hp
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        self._att_fwd(training)
+        branches = [(self.lin_logit, 1.0), (self.att_logit, 1.0)]
+        if self.use_deep:
+            n = len(hp["deep_hidden_units"])
+            keep = list(hp.get("deep_dropout", [1] * (n + 1))) if training else [1] * (n + 1)
+            self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
+                                            keep, m.get("dnn"), list(branches))
+            branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        super()._branches_bwd(idx, dense, g, masks)  # the DNN (when there is one) writes d_rows
+        self._att_bwd(g, self.d_rows if self.use_deep else None)
+        reg = self.hp.get("att_l2_reg", 0.0)
+        if reg:
+            for nm in self.att_names:
+                self.grads[nm].add_(self.params[nm], alpha=reg)
+
+    def _add_l2_model(self, total):
+        total = super()._add_l2_model(total)
+        reg = self.hp.get("att_l2_reg", 0.0)
+        if reg:
+            for nm in self.att_names:
+                total = total + reg * 0.5 * self.params[nm].square().sum()
+        return total
+
+    @staticmethod
+    def autoint_flops(B, F, Din, HD):
+        """(forward, backward) flops of one interacting layer: 8 F Din HD for the four projections plus 4 F^2 HD for
+        the scores and the weighted sums; the backward recomputes the forward and adds about twice that."""
+        fwd = B * (8 * F * Din * HD + 4 * F * F * HD)
+        return fwd, 3 * fwd
+
+    def roofline_probes(self, idx, dense, y):
+        B = idx.shape[0]
+        self._alloc(B)
+        if getattr(self, "_probe_ready", None) != B:
+            self.fwd_bwd(idx, dense, y)  # fills E, Y, stats
+            self._probe_ready = B
+        fwd, bwd = self.autoint_flops(B, self.F, self.D, self.HD)
+        p, gr = self.params, self.grads
+        dy = torch.randn(B, self.F, self.HD, dtype=F32, device=self.device)
+        dx = torch.empty_like(self.E)
+        shape = f"F={self.F} Din={self.D} H={self.H} dk={self.dk}"
+        return [
+            dict(name=f"autoint_bwd_kernel (rm_autoint_layer_bwd, layer 0: {shape}; recompute + dX + dWq, dWk, dWv, "
+                      "dWr; flops = 3 x forward)", symbol="autoint_bwd_kernel",
+                 fn=lambda: ops.autoint_layer_bwd(self.E, *self._att_weights(0, p), self.att_Y[0], self.att_stats[0],
+                                                  dy, self.H, self.scale, dx, *self._att_weights(0, gr), self.att_ws),
+                 work=float(bwd), bound="mfma"),
+            dict(name=f"autoint_fwd_kernel (rm_autoint_layer_fwd, layer 0: {shape}; flops = 8 F Din HD + 4 F^2 HD per "
+                      "example, on the vector ALU - priced against the fp32 peak both pipes share)",
+                 symbol="autoint_fwd_kernel",
+                 fn=lambda: ops.autoint_layer_fwd(self.E, *self._att_weights(0, p), self.H, self.scale, self.att_Y[0],
+                                                  stats=self.att_stats[0]),
+                 work=float(fwd), bound="mfma"),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
+ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
+           "autoint": AutoIntEngine}

@@ -235,6 +235,89 @@ def afm_bwd(E, W, b, h, p, g, logit, stats, d_rows, dW, db, dh, dp, workspace, m
         _chk(dh, "dh", F32, (T,)), _chk(dp, "dp", F32, (D,)), _chk(workspace, "workspace", F32), _stream())
 
 
+def autoint_supported(F, Din, H, dk):
+    """rm_autoint_supported: 1 <= F <= 40, Din in {8, 16, 32, 64}, H in {1, 2, 4, 8}, dk >= 4, H dk in {8, 16, 32, 64}."""
+    return bool(_lib.lib().rm_autoint_supported(int(F), int(Din), int(H), int(dk)))
+
+
+def autoint_stats_floats(B, F, H):
+    """Floats of the interacting layer's forward record stats [B, H, F, 2]: softmax row maximum and denominator."""
+    return int(_lib.lib().rm_autoint_stats_floats(int(B), int(F), int(H)))
+
+
+def _autoint_dims(X, Wq, H):
+    if X.dim() != 3 or Wq.dim() != 2:
+        raise ValueError(f"autoint: X must be [B,F,Din] and Wq [Din,HD], got {tuple(X.shape)} and {tuple(Wq.shape)}")
+    B, F, Din = X.shape
+    HD, H = Wq.shape[1], int(H)
+    if H < 1 or HD % H:
+        raise ValueError(f"autoint: {H} heads do not divide HD={HD} (unsupported)")
+    return B, F, Din, H, HD // H, HD
+
+
+def autoint_layer_fwd(X, Wq, Wk, Wv, Wr, H, scale, Y, stats=None):
+    """AutoInt interacting layer forward (rm_autoint_layer_fwd): X [B,F,Din], Wq / Wk / Wv [Din,HD], Wr [Din,HD] or
+    None, H heads, scale on the scores -> Y [B,F,HD]; stats [B,H,F,2] (training) or None (inference, same Y)."""
+    B, F, Din, H, dk, HD = _autoint_dims(X, Wq, H)
+    _lib.call(
+        "rm_autoint_layer_fwd", _chk(X, "X", F32), _chk(Wq, "Wq", F32, (Din, HD)), _chk(Wk, "Wk", F32, (Din, HD)),
+        _chk(Wv, "Wv", F32, (Din, HD)), _chk(Wr, "Wr", F32, (Din, HD), allow_none=True), B, F, Din, H, dk,
+        float(scale), _chk(Y, "Y", F32, (B, F, HD)), _chk(stats, "stats", F32, (B, H, F, 2), allow_none=True),
+        _stream())
+
+
+def autoint_layer_bwd_workspace(B, F, Din, H, dk):
+    """Floats of workspace rm_autoint_layer_bwd needs (0: unsupported shape)."""
+    return int(_lib.lib().rm_autoint_layer_bwd_workspace(int(B), int(F), int(Din), int(H), int(dk)))
+
+
+def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, stats, dY, H, scale, dX, dWq, dWk, dWv, dWr, workspace, dX_up=None):
+    """AutoInt interacting layer backward (rm_autoint_layer_bwd): dX [B,F,Din] = dLoss/dX (+ dX_up, which may be dX
+    itself), dWq, dWk, dWv, dWr [Din,HD] overwritten (dWr None exactly when Wr is).  Deterministic."""
+    B, F, Din, H, dk, HD = _autoint_dims(X, Wq, H)
+    if (Wr is None) != (dWr is None):
+        raise ValueError("autoint_layer_bwd: Wr and dWr go together")
+    need = autoint_layer_bwd_workspace(B, F, Din, H, dk)
+    if need and workspace.numel() < need:
+        raise ValueError(f"autoint_layer_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _lib.call(
+        "rm_autoint_layer_bwd", _chk(X, "X", F32), _chk(Wq, "Wq", F32, (Din, HD)), _chk(Wk, "Wk", F32, (Din, HD)),
+        _chk(Wv, "Wv", F32, (Din, HD)), _chk(Wr, "Wr", F32, (Din, HD), allow_none=True),
+        _chk(Y, "Y", F32, (B, F, HD)), _chk(stats, "stats", F32, (B, H, F, 2)), _chk(dY, "dY", F32, (B, F, HD)),
+        B, F, Din, H, dk, float(scale), _chk(dX, "dX", F32, (B, F, Din)),
+        _chk(dX_up, "dX_up", F32, (B, F, Din), allow_none=True), _chk(dWq, "dWq", F32, (Din, HD)),
+        _chk(dWk, "dWk", F32, (Din, HD)), _chk(dWv, "dWv", F32, (Din, HD)),
+        _chk(dWr, "dWr", F32, (Din, HD), allow_none=True), _chk(workspace, "workspace", F32), _stream())
+
+
+def autoint_head_fwd(Y, w, w0, logit):
+    """AutoInt's last projection (rm_autoint_head_fwd): Y [B, ...] flattened to [B,K], w [K], w0 [1] -> logit [B]."""
+    B, K = Y.shape[0], w.numel()
+    if Y.numel() != B * K:
+        raise ValueError(f"autoint_head_fwd: Y {tuple(Y.shape)} does not flatten to [B, {K}]")
+    _lib.call("rm_autoint_head_fwd", _chk(Y, "Y", F32), _chk(w, "w", F32, (K,)), _chk(w0, "w0", F32, (1,)), B, K,
+              _chk(logit, "logit", F32, (B,)), _stream())
+
+
+def autoint_head_bwd_workspace(B, K):
+    """Floats of workspace rm_autoint_head_bwd needs."""
+    return int(_lib.lib().rm_autoint_head_bwd_workspace(int(B), int(K)))
+
+
+def autoint_head_bwd(Y, w, g, dY, dw, dw0, workspace):
+    """Backward of the last projection (rm_autoint_head_bwd): g [B] -> dY (Y's shape) = g w, dw [K] = sum g Y,
+    dw0 [1] = sum g, overwritten.  Deterministic."""
+    B, K = Y.shape[0], w.numel()
+    if Y.numel() != B * K:
+        raise ValueError(f"autoint_head_bwd: Y {tuple(Y.shape)} does not flatten to [B, {K}]")
+    need = autoint_head_bwd_workspace(B, K)
+    if workspace.numel() < need:
+        raise ValueError(f"autoint_head_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _lib.call("rm_autoint_head_bwd", _chk(Y, "Y", F32), _chk(w, "w", F32, (K,)), _chk(g, "g", F32, (B,)), B, K,
+              _chk(dY, "dY", F32, tuple(Y.shape)), _chk(dw, "dw", F32, (K,)), _chk(dw0, "dw0", F32, (1,)),
+              _chk(workspace, "workspace", F32), _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

@@ -36,7 +36,7 @@ log = logging.getLogger(__name__)
 
 
 class DeepModel(BaseEstimator, TransformerMixin):
-    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din"
+    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din" | "autoint"
 
     def __init__(self, feat_dict: FeatureDictionary, hparams: dict, metrics, epoch, batch_size=64,
                  random_seed=2019, task="classification", strict_reference=False, device="cuda"):
@@ -89,6 +89,11 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 self._shard = None
                 raise NotImplementedError(
                     "AFM runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
+                    "multi-rank torch.distributed job); use table_sharding='none'")
+            if self.model == "autoint":
+                self._shard = None
+                raise NotImplementedError(
+                    "AutoInt runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
                     "multi-rank torch.distributed job); use table_sharding='none'")
             return self._build_sharded(spec, hp)
         e = eng.ENGINES[self.model](spec, hp["embedding_size"], hp, task=self.task, device=self.device)

@@ -3,6 +3,7 @@ stub (recman/th/layers.py is 0 bytes, recman/th/DeepFM.py:12-13 is `pass`), here
 by hand-written gfx950 kernels.  Same class names, constructor arguments and
 fit()/predict()/evaluate() signatures as recman/tf/core."""
 from .AFM import AFM
+from .AutoInt import AutoInt
 from .BestModelFinder import BestModelFinder
 from .DCN import DCN
 from .DeepFM import DeepFM
@@ -14,6 +15,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "BestModelFinder", "DCN", "DIN", "DeepFM", "DeepModel", "xDeepFM", "DataInputs", "DenseFeat",
+__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DeepFM", "DeepModel", "xDeepFM", "DataInputs", "DenseFeat",
            "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]

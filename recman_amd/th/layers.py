@@ -814,6 +814,77 @@ class AFMLayer:
 
 
 # ------------------------------------------------------------------------------------------------
+# AutoInt interacting layer
+# ------------------------------------------------------------------------------------------------
+class _InteractingFn(torch.autograd.Function):
+    """rm_autoint_layer_fwd / rm_autoint_layer_bwd (csrc/autoint.hip), as the AutoInt engine runs them."""
+
+    @staticmethod
+    def forward(ctx, X, Wq, Wk, Wv, Wr, H, scale):
+        B, F, _ = X.shape
+        X_ = X.detach().contiguous()
+        Ws = [None if W is None else W.detach().contiguous() for W in (Wq, Wk, Wv, Wr)]
+        Y = torch.empty(B, F, Ws[0].shape[1], device=X.device, dtype=F32)
+        stats = torch.empty(B, H, F, 2, device=X.device, dtype=F32)
+        ops.autoint_layer_fwd(X_, *Ws, H, scale, Y, stats=stats)
+        ctx.save_for_backward(X_, Y, stats, *[W for W in Ws if W is not None])
+        ctx.H, ctx.scale, ctx.res = H, scale, Ws[3] is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, Y, stats, *Ws = ctx.saved_tensors
+        Ws = list(Ws) + ([] if ctx.res else [None])
+        B, F, Din = X.shape
+        dX = torch.empty_like(X)
+        dWs = [None if W is None else torch.empty_like(W) for W in Ws]
+        ws = torch.empty(max(4, ops.autoint_layer_bwd_workspace(B, F, Din, ctx.H, Ws[0].shape[1] // ctx.H)),
+                         device=X.device, dtype=F32)
+        ops.autoint_layer_bwd(X, *Ws, Y, stats, dY.contiguous(), ctx.H, ctx.scale, dX, *dWs, ws)
+        return (dX, *dWs, None, None)
+
+
+class InteractingLayer:
+    """One interacting layer of AutoInt (arXiv 1810.11921 eq. (5)-(8); nothing in the reference implements it):
+    InteractingLayer(variables, att_embedding_size, head_num, use_res, scaling)(X [B,F,Din]) -> Y [B,F,H dk],
+        Q, K, V = X Wq, X Wk, X Wv;  a^h_m. = softmax_k(<Q^h_m, K^h_k> c);  Y_m = relu(concat_h sum_k a^h_mk V^h_k + X_m Wr)
+    with c = 1, or 1/sqrt(dk) under `scaling`.  Variables (created on the first call, glorot-normal): {prefix}query_w,
+    {prefix}key_w, {prefix}value_w and, with use_res, {prefix}res_w, each [Din, H dk]; the engine's layer l uses the
+    prefix "autoint_layer_{l}_".  l2(): every matrix."""
+
+    display_name = "Interacting"
+
+    def __init__(self, variables, att_embedding_size=8, head_num=2, use_res=True, scaling=False,
+                 prefix="autoint_layer_0_", seed=2019, l2_reg=0.0):
+        self.variables, self.att_embedding_size, self.head_num = variables, int(att_embedding_size), int(head_num)
+        self.use_res, self.scaling, self.prefix, self.seed, self.l2_reg = bool(use_res), bool(scaling), prefix, seed, l2_reg
+
+    @property
+    def names(self):
+        return ("query_w", "key_w", "value_w") + (("res_w",) if self.use_res else ())
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.names]
+
+    def __call__(self, X):
+        B, F, Din = X.shape
+        H, dk = self.head_num, self.att_embedding_size
+        if not ops.autoint_supported(F, Din, H, dk):
+            raise ValueError(f"InteractingLayer: F={F}, Din={Din}, head_num={H}, att_embedding_size={dk} unsupported "
+                             "(1..40 fields, Din in 8/16/32/64, head_num 1/2/4/8, att_embedding_size >= 4, head_num * "
+                             "att_embedding_size in 8/16/32/64)")
+        for i, n in enumerate(self.names):  # (a seed per matrix: equal shapes must not mean equal values)
+            if self.prefix + n not in self.variables:
+                self.variables[self.prefix + n] = _leaf(glorot_normal([Din, H * dk], self.seed + i))
+        W = self.weights + ([] if self.use_res else [None])
+        return _InteractingFn.apply(X, *W, H, float(dk) ** -0.5 if self.scaling else 1.0)
+
+    def l2(self):
+        return self.l2_reg * 0.5 * sum(w.square().sum() for w in self.weights)
+
+
+# ------------------------------------------------------------------------------------------------
 # prediction + loss
 # ------------------------------------------------------------------------------------------------
 class _SigmoidFn(torch.autograd.Function):
@@ -866,5 +937,6 @@ def create_loss(y, pred, task="classification"):
 
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
-           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "AFMLayer", "PredictionLayer",
+           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "AFMLayer", "InteractingLayer",
+           "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
