@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_kernel(
 #pragma unroll
   for (int u = 0; u < kPos; ++u) {
     const int64_t i = base + u;
-    head[u] = i < n && k[u + 1] < R && (i == 0 || k[u] != k[u + 1]);  // k >= R: skipped (sorted last)
+    head[u] = i < n && k[u + 1] < R && (i == 0 || k[u] != k[u + 1]);  // k >= R: skipped (ends the list / field block)
     more[u] = head[u] && i + 1 < n && k[u + 2] == k[u + 1];
   }
   RowState st[kPos];
