@@ -413,6 +413,30 @@ int rm_autoint_head_bwd(const float *Y, const float *w, const float *g, int64_t 
                         float *dw, float *dw0, float *workspace, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * DLRM's dot interaction (arXiv 1906.00091 section 3; the 351-pair layer of MLPerf DLRM at
+ * F = 26), forward and backward fused.  Nothing in the reference implements it.  Per example,
+ * over the T = F + 1 vectors v_0 = z and v_f = E[f-1] (f = 1..F), P = F(F+1)/2:
+ *     X[0:D] = z (the same bits);  X[D + i(i-1)/2 + j] = <v_i, v_j>  for 0 <= j < i <= F
+ *   (the strict lower triangle, row-major: (1,0), (2,0), (2,1), (3,0), ...; no diagonal).
+ *   E [B,F,D] (the gathered rows, rm_embed_fwd's E) and z [B,D] contiguous, 16-byte aligned;
+ *   X [B, ldx], ldx >= D + P, rows need no alignment; columns [D + P, ldx) are set to +0.0.
+ *   Every dot product is a k-ordered fmaf chain.
+ * Supported: D in {8,16,32,64}, 1 <= F <= 40 (rm_dot_interact_supported); anything else is
+ *   RM_EINVAL before any launch.  B = 0 is RM_OK.  The [T,T] Gram matrix never reaches HBM.
+ * rm_dot_interact_bwd, given dX [B, ldx] = dLoss/dX (columns >= D + P are never read), writes
+ *   d_rows [B,F,D] and dz [B,D] (both fully overwritten, 16-byte aligned):
+ *     G_ij = G_ji = dX[D + p(i,j)], G_ii = 0;  dV = G V (summed over j in ascending order)
+ *     d_rows[f-1] = dV_f;  dz = dV_0 + dX[0:D]
+ * Deterministic: no parameters, so no batch reduction; no atomics, no workspace - two runs on
+ *   the same inputs are bit-equal.
+ */
+int rm_dot_interact_supported(int F, int D);
+int rm_dot_interact_fwd(const float *E, const float *z, int64_t B, int F, int D, float *X,
+                        int64_t ldx, rm_stream_t stream);
+int rm_dot_interact_bwd(const float *E, const float *z, const float *dX, int64_t ldx, int64_t B,
+                        int F, int D, float *d_rows, float *dz, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

@@ -68,6 +68,9 @@ SIGNATURES = {
                              P],
     "rm_autoint_head_fwd": [P, P, P, I64, c_int, P, P],
     "rm_autoint_head_bwd": [P, P, P, I64, c_int, P, P, P, P, P],
+    "rm_dot_interact_supported": [c_int, c_int],
+    "rm_dot_interact_fwd": [P, P, I64, c_int, c_int, P, I64, P],
+    "rm_dot_interact_bwd": [P, P, P, I64, I64, c_int, c_int, P, P, P],
     "rm_asp_supported": [c_int, c_int, P, c_int],
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,

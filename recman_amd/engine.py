@@ -402,6 +402,9 @@ def init_reference(engine, seed=2019):
         elif name == "autoint_w" or (name.startswith("autoint_layer_") and name.endswith("_w")):
             # the interacting layers are absent from the reference: glorot like dnn_w
             tn(t, t.shape[0], t.shape[1])
+        elif name == "top_dnn_w":
+            # DLRM's top tower: its output projection like dnn_w (the towers' *_weights are covered above)
+            tn(t, t.shape[0], t.shape[1])
         else:
             t.zero_()
 
@@ -1907,5 +1910,179 @@ class AutoIntEngine(DeepFMEngine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+class Tower:
+    """A plain MLP tower in front of an interaction layer (DLRM's bottom MLP): a_0 = x [B,K0],
+    a_{l+1} = act(a_l W_l + b_l) for every layer, the last one included; no dropout, no output projection.
+    Variables {prefix}dnn_layer_{l}_weights / _bias.  Layer by layer on the wide dense kernels (csrc/gemm.hip,
+    csrc/gemm6.hip): bias and activation in the epilogue, the bf16x6 path where `dense_gemm` allows it and the
+    kernel takes the call - the choice MLP's wide path makes."""
+
+    def __init__(self, params, grads, K0, widths, activation, device, prefix):
+        self.K0, self.widths = int(K0), [int(w) for w in widths]
+        self.act = act_name(activation)
+        if self.act not in ("relu", "leaky_relu", "identity"):
+            raise ValueError(self.act)
+        self.p, self.g, self.prefix = params, grads, prefix
+        self.dims = [self.K0] + self.widths
+        for i in range(len(self.widths)):
+            for nm, shape in ((f"{prefix}dnn_layer_{i}_weights", (self.dims[i], self.dims[i + 1])),
+                              (f"{prefix}dnn_layer_{i}_bias", (self.dims[i + 1],))):
+                params[nm] = torch.zeros(shape, dtype=F32, device=device)
+                grads[nm] = torch.zeros(shape, dtype=F32, device=device)
+        self.dense_gemm = "bf16x6"
+        self._B = None
+
+    def _alloc(self, B, device):
+        if self._B == B:
+            return
+        self._B = B
+        dims, n = self.dims, len(self.widths)
+        self.a = [torch.empty(B, h, dtype=F32, device=device) for h in self.widths]
+        self.da = [torch.empty(B, h, dtype=F32, device=device) for h in self.widths[:-1]]
+        fw = max(ops.dense_filter_workspace(max(dims[i], dims[i + 1]), max(dims[i], dims[i + 1])) for i in range(n))
+        ww = max(ops.dense_wgrad_workspace(dims[i], dims[i + 1], B) for i in range(n))
+        self._fws = torch.empty(fw, dtype=F32, device=device)
+        self._wws = torch.empty(max(ww, 1), dtype=F32, device=device)
+        self._fws6 = self._wws6 = None
+        if self.dense_gemm == "bf16x6":
+            kmax = max(dims)
+            self._fws6 = torch.empty(ops.dense6_workspace(kmax, kmax, B), dtype=F32, device=device)
+            self._wws6 = torch.empty(max(ops.dense_wgrad6_workspace(dims[i], dims[i + 1], B) for i in range(n)),
+                                     dtype=F32, device=device)
+
+    def forward(self, x):
+        """x [B,K0] -> a_last [B, widths[-1]] (an internal buffer)."""
+        self._alloc(x.shape[0], x.device)
+        self.x = x
+        p, pre = self.p, self.prefix
+        prev = x
+        for i in range(len(self.widths)):
+            ops.dense_fwd(prev, None, p[f"{pre}dnn_layer_{i}_weights"], self.a[i], self._fws,
+                          bias=p[f"{pre}dnn_layer_{i}_bias"], act=self.act, ws6=self._fws6)
+            prev = self.a[i]
+        return prev
+
+    def backward(self, dz):
+        """dz [B, widths[-1]] = dLoss/da_last (turned into the last pre-activation's gradient in place); writes
+        the parameter gradients.  No gradient is formed for x."""
+        p, gr, pre = self.p, self.g, self.prefix
+        ident = self.act == "identity"
+        da = dz
+        if not ident:
+            ops.act_bwd_(da, self.a[-1], self.act)
+        for i in range(len(self.widths) - 1, -1, -1):
+            prev = self.a[i - 1] if i else self.x
+            ops.dense_wgrad(prev, None, da, gr[f"{pre}dnn_layer_{i}_weights"], self._wws,
+                            db=gr[f"{pre}dnn_layer_{i}_bias"], ws6=self._wws6)
+            if i:
+                ops.dense_fwd(da, None, p[f"{pre}dnn_layer_{i}_weights"], self.da[i - 1], self._fws, transposed=True,
+                              epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD, act=self.act,
+                              aux1=None if ident else prev, ws6=self._fws6)
+                da = self.da[i - 1]
+
+    def l2(self, reg):
+        return sum(reg * 0.5 * self.p[f"{self.prefix}dnn_layer_{i}_weights"].square().sum()
+                   for i in range(len(self.widths)))
+
+    def add_l2_grads(self, reg):
+        for i in range(len(self.widths)):
+            nm = f"{self.prefix}dnn_layer_{i}_weights"
+            self.g[nm].add_(self.p[nm], alpha=reg)
+
+
+class DLRMEngine(Engine):
+    """DLRM (arXiv 1906.00091, the MLPerf recommendation model): the dense features go through a bottom tower to
+    one embedding-wide vector z; the interaction takes every pairwise dot product among z and the F rows of E;
+    [z | dots] feeds the top MLP.  final = top logit (+ linear if use_linear).  Nothing in the reference implements it.
+        a_0 = dense;  a_{l+1} = act(a_l W_l + b_l), widths bottom_hidden_units + (embedding_size,);  z = a_last
+        v_0 = z, v_f = E[:, f-1];  X = [z | <v_i, v_j> for 0 <= j < i <= F]          (csrc/dot_interact.hip)
+        logit = DNN_top(X)
+    Variables (names chosen here): bot_dnn_layer_{l}_weights / _bias, top_dnn_layer_{l}_weights / _bias, top_dnn_w,
+    top_dnn_w0.  deep_activation applies to both towers, deep_dropout to the top one, deep_l2_reg to every weight
+    matrix of both and top_dnn_w.  No bias tables.  X and dX live in buffers whose rows are padded to a multiple
+    of 4 floats; the top MLP sees the [B, D + P] view."""
+
+    model = "dlrm"
+    use_bias_tables = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", False))
+        limits = "at least one dense feature, 1..40 embedding features, embedding_size 8/16/32/64"
+        if self.Dn < 1:
+            raise ValueError(f"DLRM: the bottom tower needs a dense feature, there is none ({limits})")
+        if not ops.dot_interact_supported(self.F, self.D):
+            raise ValueError(f"DLRM: {self.F} embedding features of embedding_size={self.D} are not supported by "
+                             f"rm_dot_interact_fwd ({limits})")
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        if not hidden:
+            raise ValueError("DLRM: deep_hidden_units must name at least one layer of the top tower")
+        self.W, self.ldx = ops.dot_interact_width(self.F, self.D)
+        self.dnn_input_width = self.W  # (the width of the top tower's input-dropout mask)
+        act = hp.get("deep_activation", "relu")
+        dev = self.device
+        self.bot = Tower(self.params, self.grads, self.Dn, tuple(hp.get("bottom_hidden_units", (64, 32))) + (self.D,),
+                         act, dev, "bot_")
+        self.mlp = MLP(self.params, self.grads, self.W, 0, hidden, act, dev, prefix="top_")
+        self.mlp.stream_d_rows = False
+        self.bot.dense_gemm = self.mlp.dense_gemm = hp.get("dense_gemm", "bf16x6")
+
+    def _alloc_model(self, B):
+        dev = self.device
+        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.dz = torch.empty(B, self.D, dtype=F32, device=dev)
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        hp = self.hp
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        self.z = self.bot.forward(dense)
+        X = self.X[:, : self.W]
+        ops.dot_interact_fwd(self.E, self.z, X)
+        n = len(self.mlp.hidden)
+        keep = list(hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
+        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
+        self.dnn_logit = self._mlp_last(self.mlp, X, None, keep, m.get("dnn"), list(branches))
+        branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        dX = self.dX[:, : self.W]
+        self.mlp.backward(g, dX)
+        # no other branch reads E: d_rows IS dLoss/dE
+        ops.dot_interact_bwd(self.E, self.z, dX, self.d_rows, self.dz)
+        self.bot.backward(self.dz)
+        reg = self.hp.get("deep_l2_reg", 0.0)
+        if reg:
+            self.mlp.add_l2_grads(reg)
+            self.bot.add_l2_grads(reg)
+
+    def _add_l2_model(self, total):
+        reg = self.hp.get("deep_l2_reg", 0.0)
+        if reg:
+            total = total + self.mlp.l2(reg) + self.bot.l2(reg)
+        return total
+
+    def roofline_probes(self, idx, dense, y):
+        B = idx.shape[0]
+        self._alloc(B)
+        if getattr(self, "_probe_ready", None) != B:
+            self.fwd_bwd(idx, dense, y)  # fills E, z, dX
+            self._probe_ready = B
+        F, D, ldx = self.F, self.D, self.ldx
+        X, dX = self.X[:, : self.W], self.dX[:, : self.W]
+        d_rows, dz = torch.empty_like(self.d_rows), torch.empty_like(self.dz)
+        shape = f"F={F} D={D} ldx={ldx}"
+        return [
+            dict(name=f"dot_bwd_kernel (rm_dot_interact_bwd, {shape}: E, z, dX read once, d_rows and dz written once)",
+                 symbol="dot_bwd_kernel", fn=lambda: ops.dot_interact_bwd(self.E, self.z, dX, d_rows, dz),
+                 work=B * 4 * (2 * F * D + 2 * D + ldx), bound="hbm"),
+            dict(name=f"dot_fwd_kernel (rm_dot_interact_fwd, {shape}: E and z read once, X written once)",
+                 symbol="dot_fwd_kernel", fn=lambda: ops.dot_interact_fwd(self.E, self.z, X),
+                 work=B * 4 * (F * D + D + ldx), bound="hbm"),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
-           "autoint": AutoIntEngine}
+           "autoint": AutoIntEngine, "dlrm": DLRMEngine}

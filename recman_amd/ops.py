@@ -318,6 +318,52 @@ def autoint_head_bwd(Y, w, g, dY, dw, dw0, workspace):
               _chk(workspace, "workspace", F32), _stream())
 
 
+def dot_interact_supported(F, D):
+    """rm_dot_interact_supported: D in {8, 16, 32, 64}, 1 <= F <= 40."""
+    return bool(_lib.lib().rm_dot_interact_supported(int(F), int(D)))
+
+
+def dot_interact_width(F, D):
+    """(D + P, ldx): the columns DLRM's interaction writes (z, then the P = F(F+1)/2 pair dot products) and that
+    width rounded up to a multiple of 4 floats (16-byte rows for the dense kernels that read X)."""
+    W = D + F * (F + 1) // 2
+    return W, (W + 3) // 4 * 4
+
+
+def _dot_interact_args(E, z, X, name):
+    if E.dim() != 3:
+        raise ValueError(f"E: expected [B,F,D], got {tuple(E.shape)}")
+    B, F, D = E.shape
+    if not dot_interact_supported(F, D):
+        raise ValueError(f"dot_interact: F={F}, D={D} unsupported (1 <= F <= 40, D in 8, 16, 32, 64)")
+    W, _ = dot_interact_width(F, D)
+    px, ldx, cols = _rows2d(X, name)
+    if X.shape[0] != B or cols < W:
+        raise ValueError(f"{name} {tuple(X.shape)} must be [{B}, >= {W}]")
+    if B > 1 and ldx < cols:
+        raise ValueError(f"{name}: row stride {ldx} < {cols} columns")
+    return B, F, D, _chk(E, "E", F32), _chk(z, "z", F32, (B, D)), px, max(ldx, cols)
+
+
+def dot_interact_fwd(E, z, X):
+    """DLRM's dot interaction (rm_dot_interact_fwd): E [B,F,D], z [B,D] -> X [B, >= D+P] with row stride ldx:
+    X[:, :D] = z, X[:, D + i(i-1)/2 + j] = <v_i, v_j> (v_0 = z, v_f = E[:, f-1]; 0 <= j < i <= F); every column
+    from D + P up to the row stride is set to +0.0."""
+    B, F, D, pe, pz, px, ldx = _dot_interact_args(E, z, X, "X")
+    # the kernel writes whole rows of ldx floats: the last one must lie inside X's storage
+    if B and X.storage_offset() + B * ldx > X.untyped_storage().nbytes() // 4:
+        raise ValueError(f"X: {B} rows of stride {ldx} from offset {X.storage_offset()} exceed its storage")
+    _lib.call("rm_dot_interact_fwd", pe, pz, B, F, D, px, ldx, _stream())
+
+
+def dot_interact_bwd(E, z, dX, d_rows, dz):
+    """rm_dot_interact_bwd: dX [B, >= D+P] (row stride ldx; columns >= D+P are never read) -> d_rows [B,F,D] and
+    dz [B,D], both overwritten.  Deterministic."""
+    B, F, D, pe, pz, px, ldx = _dot_interact_args(E, z, dX, "dX")
+    _lib.call("rm_dot_interact_bwd", pe, pz, px, ldx, B, F, D, _chk(d_rows, "d_rows", F32, (B, F, D)),
+              _chk(dz, "dz", F32, (B, D)), _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

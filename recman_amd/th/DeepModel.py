@@ -36,7 +36,7 @@ log = logging.getLogger(__name__)
 
 
 class DeepModel(BaseEstimator, TransformerMixin):
-    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din" | "autoint"
+    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din" | "autoint" | "dlrm"
 
     def __init__(self, feat_dict: FeatureDictionary, hparams: dict, metrics, epoch, batch_size=64,
                  random_seed=2019, task="classification", strict_reference=False, device="cuda"):
@@ -94,6 +94,11 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 self._shard = None
                 raise NotImplementedError(
                     "AutoInt runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
+                    "multi-rank torch.distributed job); use table_sharding='none'")
+            if self.model == "dlrm":
+                self._shard = None
+                raise NotImplementedError(
+                    "DLRM runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
                     "multi-rank torch.distributed job); use table_sharding='none'")
             return self._build_sharded(spec, hp)
         e = eng.ENGINES[self.model](spec, hp["embedding_size"], hp, task=self.task, device=self.device)
@@ -411,7 +416,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
         n = len(hp.get("deep_hidden_units", ()))
         keep = hp.get("deep_dropout")
         if keep is not None and any(k < 1 for k in keep) and getattr(e, "mlp", None) is not None:
-            dims = [e.FD + e.Dn] + list(hp["deep_hidden_units"])
+            # (DLRM's DNN reads the interaction's output, not [E | dense])
+            dims = [getattr(e, "dnn_input_width", e.FD + e.Dn)] + list(hp["deep_hidden_units"])
             masks["dnn"] = [(torch.rand(B, d, device=dev) < k).float() if k < 1 else None
                             for d, k in zip(dims, keep)]
         fk = hp.get("fm_dropout")

@@ -6,6 +6,7 @@ from .AFM import AFM
 from .AutoInt import AutoInt
 from .BestModelFinder import BestModelFinder
 from .DCN import DCN
+from .DLRM import DLRM
 from .DeepFM import DeepFM
 from .DIN import DIN
 from .DeepModel import DeepModel
@@ -15,6 +16,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DeepFM", "DeepModel", "xDeepFM", "DataInputs", "DenseFeat",
-           "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
+__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "xDeepFM", "DataInputs",
+           "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]

@@ -16,7 +16,7 @@ DeepFM.py:107-163, DCN.py:99-149).  recman/th/layers.py, the file this fills, is
 
 Each layer is a torch.autograd.Function over recman_amd/ops.py (the C ABI, librecman_hip.so): forward and
 backward are the same hand-written kernels the engines use (csrc/embed.hip, mlp.hip, gemm.hip, cin.hip,
-cross.hip, afm.hip, loss.hip); torch is the plumbing in between - autograd's tape, the l2 terms, the bias-table
+cross.hip, afm.hip, autoint.hip, dot_interact.hip, loss.hip); torch is the plumbing in between - autograd's tape, the l2 terms, the bias-table
 lookup and the loss on probabilities are plain torch ops.  Variables are float32 CUDA leaf tensors
 under the reference's names, so `variables` is at once the parameter list of a torch optimizer and the
 state dict of a checkpoint.  There is no CPU path.
@@ -882,6 +882,49 @@ class InteractingLayer:
 
     def l2(self):
         return self.l2_reg * 0.5 * sum(w.square().sum() for w in self.weights)
+
+
+# ------------------------------------------------------------------------------------------------
+# DLRM dot interaction
+# ------------------------------------------------------------------------------------------------
+class _DotInteractFn(torch.autograd.Function):
+    """rm_dot_interact_fwd / rm_dot_interact_bwd (csrc/dot_interact.hip), as the DLRM engine runs them."""
+
+    @staticmethod
+    def forward(ctx, E, z):
+        E_, z_ = E.detach().contiguous(), z.detach().contiguous()
+        B, F, D = E_.shape
+        X = torch.empty(B, ops.dot_interact_width(F, D)[0], device=E.device, dtype=F32)
+        ops.dot_interact_fwd(E_, z_, X)
+        ctx.save_for_backward(E_, z_)
+        return X
+
+    @staticmethod
+    def backward(ctx, dX):
+        E, z = ctx.saved_tensors
+        dE, dz = torch.empty_like(E), torch.empty_like(z)
+        ops.dot_interact_bwd(E, z, dX.contiguous(), dE, dz)
+        return dE, dz
+
+
+class DotInteraction:
+    """DLRM's interaction layer (arXiv 1906.00091; nothing in the reference implements it):
+    DotInteraction()(feat_embeds [B,F,D], z [B,D]) -> [B, D + F(F+1)/2] = [z | <v_i, v_j> for 0 <= j < i <= F] with
+    v_0 = z and v_f = feat_embeds[:, f-1] - the strict lower triangle, row-major, no diagonal.  No variables."""
+
+    display_name = "DotInteraction"
+
+    def __call__(self, feat_embeds, z):
+        if feat_embeds.dim() != 3 or z.dim() != 2 or tuple(z.shape) != (feat_embeds.shape[0], feat_embeds.shape[2]):
+            raise ValueError(f"DotInteraction: feat_embeds [B,F,D] and z [B,D] expected, got "
+                             f"{tuple(feat_embeds.shape)} and {tuple(z.shape)}")
+        _, F, D = feat_embeds.shape
+        if not ops.dot_interact_supported(F, D):
+            raise ValueError(f"DotInteraction: F={F}, D={D} unsupported (1..40 fields, D in 8/16/32/64)")
+        return _DotInteractFn.apply(feat_embeds, z)
+
+    def l2(self):
+        return 0.0
 
 
 # ------------------------------------------------------------------------------------------------
