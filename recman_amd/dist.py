@@ -313,9 +313,6 @@ class ShardedTable:
         return ex.recv_ids, ex.push(bucketed_grads)
 
 
-_DENSE_L2 = ("deep_l2_reg", "cin_l2_reg", "cross_layer_l2_reg")
-
-
 def flatten_grads(grads):
     """Re-homes every dense-parameter gradient as a view of ONE flat buffer (16-byte aligned
     slots) so the data-parallel all_reduce runs in place, without a gather/scatter copy per
@@ -413,6 +410,7 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
     from . import engine as eng
 
     base = eng.ENGINES[model]
+    base.require_shardable()
 
     class Sharded(base):
         sharded = True
@@ -438,6 +436,7 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
             self._pending = None
             self._slot = None
             self._segs = None
+            self._step_pk = None  # whether rm_deepfm_step's packed form takes this engine's shapes (asked once)
             self.micro_batches = int(micro_batches)
             super().__init__(spec, D, hp, device=device)
             self._hp_full = dict(self.hp)
@@ -454,8 +453,8 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
             self.linear_w_dense = torch.zeros(self.Dn, dtype=torch.float32, device=dev)
             self.field_off = torch.tensor(self.spec.offsets(), dtype=torch.int64, device=dev)
             self.lin_off = self.field_off
-            self.params["table_shard"] = self.st.shard
-            self.params["linear_w_dense"] = self.linear_w_dense
+            self._view("table_shard", self.st.shard)  # (filled by ShardedTable.init_reference / load_global)
+            self._view("linear_w_dense", self.linear_w_dense)
 
         def _alloc_mv(self, B):
             # (no scratch block beside a local table: the pooled rows are built behind the received rows)
@@ -717,7 +716,7 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
                 return False
             if not (self.use_fm and self.use_deep and self.use_linear and self.use_bias_tables):
                 return False
-            if getattr(self, "_step_pk", None) is None:
+            if self._step_pk is None:
                 self._step_pk = bool(self.mlp.fused_ok and ops.deepfm_step_supported(
                     self.F, self.D, self.D + PAD, self.Dn, self.mlp.hidden))
             return self._step_pk
@@ -733,28 +732,21 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
                 self._mv = None
                 pos = self._lookup(idx).view(B, self.F)  # runs / finishes the row exchange: self.rows
                 mlp, p, g = self.mlp, self.params, self.grads
-                if getattr(self, "_step_ws", None) is None:
+                if self._step_ws is None:
                     self._step_ws = torch.zeros(ops.deepfm_step_workspace(self.F, self.Dn), dtype=torch.float32,
                                                 device=self.device)
-                pre, n = mlp.prefix, len(mlp.hidden)
                 rows = self.rows
                 ops.deepfm_step(
                     pos, rows, self._zoff, self.D, self.D + PAD, dense if self.Dn else None, y,
-                    [p[f"{pre}dnn_layer_{i}_weights"] for i in range(n)],
-                    [p[f"{pre}dnn_layer_{i}_bias"] for i in range(n)], p[f"{pre}dnn_w"].view(-1), p[f"{pre}dnn_w0"],
-                    self.linear_w_dense if self.Dn else None, p["linear_w0"], mlp.act, self.task, grad_rows,
-                    self.logit, self.pred, self.dlogit, self.loss,
-                    [g[f"{pre}dnn_layer_{i}_weights"] for i in range(n)],
-                    [g[f"{pre}dnn_layer_{i}_bias"] for i in range(n)], g[f"{pre}dnn_w"].view(-1), g[f"{pre}dnn_w0"],
-                    g["linear_w_dense"] if self.Dn else None, g["linear_w0"], self._step_ws,
-                    grad_scale=getattr(self, "grad_scale", 1.0), packed_rows=min(rows.shape[0], grad_rows.shape[0]),
+                    *mlp.vars(p), self.linear_w_dense if self.Dn else None, p["linear_w0"], mlp.act, self.task,
+                    grad_rows, self.logit, self.pred, self.dlogit, self.loss,
+                    *mlp.vars(g), g["linear_w_dense"] if self.Dn else None, g["linear_w0"], self._step_ws,
+                    grad_scale=self.grad_scale, packed_rows=min(rows.shape[0], grad_rows.shape[0]),
                     lin_field_mask=self.lin_field_mask)
                 self.d_bias = None
                 if self.Dn and self.lin_dense_mask is not None:
                     g["linear_w_dense"].mul_(self.lin_dense_mask)
-                reg = self.hp.get("deep_l2_reg", 0.0)
-                if reg:
-                    mlp.add_l2_grads(reg)
+                self._add_l2_grads()
                 return self._add_l2(self.loss)
             loss = base.fwd_bwd(self, idx, dense, y, masks, mv=mv) if mv is not None else base.fwd_bwd(self, idx, dense, y, masks)
             if self.mv_fields:
@@ -811,7 +803,7 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
             # shares add up to reg over ranks and micro-batches.
             w_rank = (1.0 / world) if weight is None else float(weight)
             self.grad_scale = w_rank / M
-            self.hp = dict(self._hp_full, **{k: self._hp_full.get(k, 0.0) * self.grad_scale for k in _DENSE_L2})
+            self.hp = self._hp_scaled()
             if M <= 1:
                 try:
                     self._wide = wide
@@ -869,12 +861,16 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
             allreduce_dense(self.grads, world, group, self._flat_grads, average=False)
             return total.div_(M) + self._l2_once()
 
+        def _hp_scaled(self):
+            """The hyper-parameters with this (micro-)batch's share of the dense parameters' l2 coefficients."""
+            return dict(self._hp_full, **{k: self._hp_full.get(k, 0.0) * self.grad_scale for k in self.l2_groups})
+
         def _add_l2(self, loss):
             return loss  # (the data loss only: the dense parameters' l2 value is added once per step)
 
         def _l2_once(self):
             """The l2 VALUE of the dense parameters with the full coefficients (identical on every rank)."""
-            if not any(self._hp_full.get(k, 0.0) for k in _DENSE_L2):
+            if not any(self._hp_full.get(k, 0.0) for k in self.l2_groups):
                 return 0.0
             keep, self.hp = self.hp, self._hp_full  # (restored: capture_segments runs with the scaled copy)
             try:
@@ -918,7 +914,7 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
             coll = world > 1 or (FORCE and dist.is_initialized())
             self.grad_scale = 1.0 / (world * M)
             # (the dense parameters' l2 shares are baked into the captured kernels: see fwd_bwd)
-            self.hp = dict(self._hp_full, **{k: self._hp_full.get(k, 0.0) * self.grad_scale for k in _DENSE_L2})
+            self.hp = self._hp_scaled()
             self._seg_loss = torch.zeros(1, dtype=torch.float32, device=dev)
             segs = []
             for c in range(M):

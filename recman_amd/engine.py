@@ -131,11 +131,49 @@ class FeatureSpec:
         return [n for n in self.sparse_names if n in self.seq_query]
 
 
+def _declare(params, grads, decl, name, shape, device, init="zeros", l2=None):
+    """One dense variable: its zero-filled params / grads pair and, in `decl`, name -> (init, l2).
+    init: "zeros", ("glorot", fan_in, fan_out) (the +-2 sigma truncated normal) or ("glorot_uniform", fan_in,
+    fan_out) - what init_reference applies; l2: the hyper-parameter key whose coefficient regularises it, or None."""
+    params[name] = torch.zeros(shape, dtype=F32, device=device)
+    grads[name] = torch.zeros(shape, dtype=F32, device=device)
+    decl[name] = (init, l2)
+
+
+def _declare_layers(params, grads, decl, prefix, dims, device):
+    """{prefix}dnn_layer_{i}_weights [dims[i], dims[i+1]] (glorot, deep_l2_reg) and _bias (zeros, no l2)."""
+    for i in range(len(dims) - 1):
+        _declare(params, grads, decl, f"{prefix}dnn_layer_{i}_weights", (dims[i], dims[i + 1]), device,
+                 ("glorot", dims[i], dims[i + 1]), "deep_l2_reg")
+        _declare(params, grads, decl, f"{prefix}dnn_layer_{i}_bias", (dims[i + 1],), device)
+
+
+def _dense_workspaces(dims, B, device, dense_gemm, wgrad6_pad=0):
+    """(fws, wws, fws6, wws6) for a chain of wide dense layers of widths `dims` at batch B: the filter and
+    weight-gradient workspaces of csrc/gemm.hip and - with dense_gemm = "bf16x6", the bf16 matrix pipe with split
+    fp32 operands (rm_dense_fwd6, csrc/gemm6.hip) - those of the split-operand kernels, else None ("f32": the f32
+    MFMA kernel).  wgrad6_pad: further gradient columns the first layer's weight-gradient pass may carry."""
+    n = len(dims) - 1
+    fw = max(ops.dense_filter_workspace(max(dims[i], dims[i + 1]), max(dims[i], dims[i + 1])) for i in range(n))
+    ww = max(ops.dense_wgrad_workspace(dims[i], dims[i + 1], B) for i in range(n))
+    fws = torch.empty(fw, dtype=F32, device=device)
+    wws = torch.empty(max(ww, 1), dtype=F32, device=device)
+    fws6 = wws6 = None
+    if dense_gemm == "bf16x6":
+        kmax = max(dims)
+        fws6 = torch.empty(ops.dense6_workspace(kmax, kmax, B), dtype=F32, device=device)
+        wws6 = torch.empty(max(ops.dense_wgrad6_workspace(dims[i], dims[i + 1] + wgrad6_pad, B) for i in range(n)),
+                           dtype=F32, device=device)
+    return fws, wws, fws6, wws6
+
+
 class MLP:
     """DNN.__call__ (layers.py:576-609) with an explicit backward.  x = [xe | xd] is
-    never concatenated: layer 0 is two GEMMs accumulating into one output."""
+    never concatenated: layer 0 is two GEMMs accumulating into one output.
+    self.decl: its variables' name -> (init rule, l2 key), for the engine that adopts it."""
 
-    def __init__(self, params, grads, FD, Dn, hidden, activation, device, prefix=""):
+    def __init__(self, params, grads, FD, Dn, hidden, activation, device, prefix="", stream_d_rows=False,
+                 dense_gemm="bf16x6"):
         self.FD, self.Dn = FD, Dn
         self.hidden = list(hidden)
         self.act = act_name(activation)
@@ -143,17 +181,14 @@ class MLP:
             raise ValueError(self.act)
         self.p, self.g, self.prefix = params, grads, prefix
         dims = [FD + Dn] + self.hidden
-        for i in range(len(self.hidden)):
-            for nm, shape in ((f"{prefix}dnn_layer_{i}_weights", (dims[i], dims[i + 1])),
-                              (f"{prefix}dnn_layer_{i}_bias", (dims[i + 1],))):
-                params[nm] = torch.zeros(shape, dtype=F32, device=device)
-                grads[nm] = torch.zeros(shape, dtype=F32, device=device)
-        for nm, shape in ((f"{prefix}dnn_w", (dims[-1], 1)), (f"{prefix}dnn_w0", (1,))):
-            params[nm] = torch.zeros(shape, dtype=F32, device=device)
-            grads[nm] = torch.zeros(shape, dtype=F32, device=device)
+        self.decl = {}
+        _declare_layers(params, grads, self.decl, prefix, dims, device)
+        _declare(params, grads, self.decl, f"{prefix}dnn_w", (dims[-1], 1), device, ("glorot", dims[-1], 1),
+                 "deep_l2_reg")
+        _declare(params, grads, self.decl, f"{prefix}dnn_w0", (1,), device)
         self._B = None
-        self._ws = None
-        self._ones = None
+        # the wide path's workspaces (_alloc_dense) and rm_outer_actgrad_sums' (backward): made on first use
+        self._ws = self._ones = self._fws = self._wws = self._fws6 = self._wws6 = self._wws_B = self._sums_ws = None
         # hand-written fused f32-MFMA path for skinny MLPs (csrc/mlp.hip); wider ones (DCN's
         # [400,400]) and any MLP under dropout run layer by layer on the wide dense kernels
         # (csrc/gemm.hip: bias / activation / activation-gradient fused, x = [xe | xd] in place)
@@ -162,7 +197,15 @@ class MLP:
         # hp["d_rows_reuse"] = "stream": the row gradients leave the caches (non-temporal stores) - only
         # for a bare forward+backward; the default keeps them cached for the optimizer step that
         # gathers them right after (fit(), and the benchmark: it times what training runs)
-        self.stream_d_rows = False
+        self.stream_d_rows = bool(stream_d_rows)
+        # wide layers: "bf16x6" (the split-operand kernels) or "f32" (_dense_workspaces)
+        self.dense_gemm = dense_gemm
+
+    def vars(self, d):
+        """(Ws, bs, w_out, w0) out of the params or the grads dict."""
+        pre, n = self.prefix, len(self.hidden)
+        return ([d[f"{pre}dnn_layer_{i}_weights"] for i in range(n)], [d[f"{pre}dnn_layer_{i}_bias"] for i in range(n)],
+                d[f"{pre}dnn_w"].view(-1), d[f"{pre}dnn_w0"])
 
     def _alloc(self, B, device):
         if self._B == B:
@@ -193,7 +236,7 @@ class MLP:
         chain (self.head_done tells the caller; otherwise it runs rm_logit_loss as usual)."""
         B = xe.shape[0]
         self._alloc(B, xe.device)
-        p, pre = self.p, self.prefix
+        Ws, bs, w_out, w0 = self.vars(self.p)
         n = len(self.hidden)
         self.keep = keep if keep is not None else [1] * (n + 1)
         self.masks = masks if masks is not None else [None] * (n + 1)
@@ -205,10 +248,8 @@ class MLP:
             if head is not None:
                 self.tail = ops.mlp_tail(B, dh=self.dhb, **head)
                 self.head_done = True
-            ops.mlp_fwd(xe, xd if self.Dn else None,
-                        [p[f"{pre}dnn_layer_{i}_weights"] for i in range(n)],
-                        [p[f"{pre}dnn_layer_{i}_bias"] for i in range(n)], p[f"{pre}dnn_w"].view(-1),
-                        p[f"{pre}dnn_w0"], self.act, self.hb, self.out.view(B), tail=self.tail)
+            ops.mlp_fwd(xe, xd if self.Dn else None, Ws, bs, w_out, w0, self.act, self.hb, self.out.view(B),
+                        tail=self.tail)
             return self.out.view(B)
         if self.keep[0] < 1 and self.masks[0] is not None:
             m = self.masks[0] / self.keep[0]
@@ -218,7 +259,7 @@ class MLP:
         self._alloc_dense(xe.device)
         dotted = False
         for i in range(n):
-            W, b = p[f"{pre}dnn_layer_{i}_weights"], p[f"{pre}dnn_layer_{i}_bias"]
+            W, b = Ws[i], bs[i]
             a = self.a[i]
             if i == 0:
                 ops.dense_fwd(xe, xd if self.Dn else None, W, a, self._fws, bias=b, act=self.act, ws6=self._fws6)
@@ -226,33 +267,21 @@ class MLP:
                 # the last layer's kernel also forms the output projection a . dnn_w + dnn_w0 from its registers
                 dot = None
                 if i == n - 1 and not (self.keep[n] < 1 and self.masks[n] is not None):
-                    dot = (p[f"{pre}dnn_w"].view(-1), p[f"{pre}dnn_w0"], self.out.view(B))
+                    dot = (w_out, w0, self.out.view(B))
                 dotted = ops.dense_fwd(self.a[i - 1], None, W, a, self._fws, bias=b, act=self.act, ws6=self._fws6,
                                        dot=dot) and dot is not None
             if self.keep[i + 1] < 1 and self.masks[i + 1] is not None:
                 a.mul_(self.masks[i + 1] / self.keep[i + 1])
         if not dotted:
-            ops.rowdot(self.a[-1], p[f"{pre}dnn_w"].view(-1), p[f"{pre}dnn_w0"], self.out.view(B))
+            ops.rowdot(self.a[-1], w_out, w0, self.out.view(B))
         return self.out.view(B)
 
     def _alloc_dense(self, device):
-        if getattr(self, "_fws", None) is not None and self._fws.device == device and self._wws_B == self._B:
+        if self._fws is not None and self._fws.device == device and self._wws_B == self._B:
             return
-        dims = [self.FD + self.Dn] + self.hidden
-        fw = max(ops.dense_filter_workspace(max(dims[i], dims[i + 1]), max(dims[i], dims[i + 1]))
-                 for i in range(len(self.hidden)))
-        ww = max(ops.dense_wgrad_workspace(dims[i], dims[i + 1], self._B) for i in range(len(self.hidden)))
-        self._fws = torch.empty(fw, dtype=F32, device=device)
-        # wide layers on the bf16 matrix pipe with split fp32 operands (rm_dense_fwd6, csrc/gemm6.hip) unless
-        # dense_gemm = "f32" asks for the f32 MFMA kernel
-        self._fws6 = self._wws6 = None
-        if getattr(self, "dense_gemm", "bf16x6") == "bf16x6":
-            kmax = max(dims)
-            self._fws6 = torch.empty(ops.dense6_workspace(kmax, kmax, self._B), dtype=F32, device=device)
-            # (+ 16 columns: DCN rides the cross net's coefficient columns along the first layer's pass, wgrad0)
-            self._wws6 = torch.empty(max(ops.dense_wgrad6_workspace(dims[i], dims[i + 1] + 16, self._B)
-                                         for i in range(len(self.hidden))), dtype=F32, device=device)
-        self._wws = torch.empty(max(ww, 1), dtype=F32, device=device)
+        # (+ 16 columns: DCN rides the cross net's coefficient columns along the first layer's pass, wgrad0)
+        self._fws, self._wws, self._fws6, self._wws6 = _dense_workspaces(
+            [self.FD + self.Dn] + self.hidden, self._B, device, self.dense_gemm, wgrad6_pad=16)
         self._wws_B = self._B
         self._ws = torch.empty(256 * 1024, dtype=F32, device=device)
         self._ones = torch.ones(self._B, dtype=F32, device=device)
@@ -268,7 +297,7 @@ class MLP:
     def can_defer_wgrad0(self):
         """backward(defer_wgrad0=True) + wgrad0(G2, dW2) is available: wide layers on the split-operand path, no input
         dropout (the MLP's x is then the caller's x0 itself)."""
-        return (not self.fused_ok and getattr(self, "_wws6", None) is not None
+        return (not self.fused_ok and self._wws6 is not None
                 and not (self.keep[0] < 1 and self.masks[0] is not None))
 
     def backward(self, g, dxe, fm_sum=None, lin_grads=None, defer_wgrad0=False):
@@ -278,20 +307,17 @@ class MLP:
         returns True when it was added).  lin_grads = (d_w_dense [Dn], d_w0 [1]): the linear
         term's dense-weight gradients g^T xd and sum g ride along too (fused path, Dn <= 32):
         self.lin_done tells the caller whether they were written."""
-        p, gr, pre = self.p, self.g, self.prefix
+        (Ws, _, w_out, _), (gWs, gbs, g_w_out, g_w0) = self.vars(self.p), self.vars(self.g)
         n = len(self.hidden)
         self.lin_done = False
         if self.fused:
-            Ws = [p[f"{pre}dnn_layer_{i}_weights"] for i in range(n)]
-            ops.mlp_bwd(self.xe, self.xd if self.Dn else None, Ws, p[f"{pre}dnn_w"].view(-1), self.act,
-                        g, self.hb, dxe, self.dhb, [gr[f"{pre}dnn_layer_{i}_weights"] for i in range(n)],
-                        self.fws, fm_sum=fm_sum,
-                        db=[gr[f"{pre}dnn_layer_{i}_bias"] for i in range(n)],
-                        d_w_out=gr[f"{pre}dnn_w"].view(-1), d_w0_out=gr[f"{pre}dnn_w0"],
+            ops.mlp_bwd(self.xe, self.xd if self.Dn else None, Ws, w_out, self.act,
+                        g, self.hb, dxe, self.dhb, gWs, self.fws, fm_sum=fm_sum,
+                        db=gbs, d_w_out=g_w_out, d_w0_out=g_w0,
                         d_xd_wsum=lin_grads[0] if (lin_grads and 1 <= self.Dn <= 32) else None,
                         d_g_sum=lin_grads[1] if (lin_grads and 1 <= self.Dn <= 32) else None,
                         tail=self.tail if self.head_done else None,
-                        stream_d_rows=getattr(self, "stream_d_rows", False))
+                        stream_d_rows=self.stream_d_rows)
             self.lin_done = bool(lin_grads and 1 <= self.Dn <= 32)
             return fm_sum is not None
         # d(pre-activation of the last layer) = (g w_out^T) o mask o act'(a): one elementwise pass
@@ -304,19 +330,17 @@ class MLP:
         sums = (not plain) and da.shape[1] % 4 == 0 and da.shape[1] >= 64
         if sums:
             need = ops.outer_actgrad_sums_workspace(da.shape[0], da.shape[1])
-            if getattr(self, "_sums_ws", None) is None or self._sums_ws.numel() < need:
+            if self._sums_ws is None or self._sums_ws.numel() < need:
                 self._sums_ws = torch.empty(need, dtype=F32, device=da.device)
-            ops.outer_actgrad_sums(g, p[f"{pre}dnn_w"].view(-1), self.a[-1], self.act, da,
-                                   gr[f"{pre}dnn_w"].view(-1), gr[f"{pre}dnn_w0"],
-                                   gr[f"{pre}dnn_layer_{n - 1}_bias"], self._sums_ws)
+            ops.outer_actgrad_sums(g, w_out, self.a[-1], self.act, da, g_w_out, g_w0, gbs[n - 1], self._sums_ws)
         else:
-            ops.linear_dense_bwd(g, self.a[-1], gr[f"{pre}dnn_w"].view(-1), gr[f"{pre}dnn_w0"], self._ws)
+            ops.linear_dense_bwd(g, self.a[-1], g_w_out, g_w0, self._ws)
         if sums:
             pass
         elif da.shape[1] % 4 == 0:
-            ops.outer_actgrad(g, p[f"{pre}dnn_w"].view(-1), None if plain else self.a[-1], self.act, da)
+            ops.outer_actgrad(g, w_out, None if plain else self.a[-1], self.act, da)
         else:
-            ops.dense_fwd(g.view(-1, 1), None, p[f"{pre}dnn_w"], da, self._fws, transposed=True,
+            ops.dense_fwd(g.view(-1, 1), None, w_out.view(-1, 1), da, self._fws, transposed=True,
                           epilogue=ops.DENSE_ADD if plain else ops.DENSE_MUL_ACTGRAD,
                           act=self.act, aux1=None if plain else self.a[-1])
         if last_drop:
@@ -325,11 +349,10 @@ class MLP:
                 ops.act_bwd_(da, self.a[-1], self.act) if da.numel() % 4 == 0 else da.mul_(
                     torch.where(self.a[-1] > 0, 1.0, _ACTS[self.act] or 0.0))
         for i in range(n - 1, -1, -1):
-            W = p[f"{pre}dnn_layer_{i}_weights"]
-            gW = gr[f"{pre}dnn_layer_{i}_weights"]
+            W, gW = Ws[i], gWs[i]
             # the bias gradient colsum(da): from rm_outer_actgrad_sums for the last layer, otherwise
             # it rides along in the weight-gradient kernel (which stages da in LDS anyway)
-            db = None if (sums and i == n - 1) else gr[f"{pre}dnn_layer_{i}_bias"]
+            db = None if (sums and i == n - 1) else gbs[i]
             if i == 0:
                 if defer_wgrad0:
                     self._deferred = (da, gW, db)
@@ -354,59 +377,33 @@ class MLP:
                     da.mul_(self.masks[i] / self.keep[i])
         return False
 
-    def l2(self, reg):
-        ws = [self.p[f"{self.prefix}dnn_layer_{i}_weights"] for i in range(len(self.hidden))]
-        ws.append(self.p[f"{self.prefix}dnn_w"])
-        return sum(reg * 0.5 * w.square().sum() for w in ws)  # layers.py:611-628
-
-    def add_l2_grads(self, reg):
-        for i in range(len(self.hidden)):
-            nm = f"{self.prefix}dnn_layer_{i}_weights"
-            self.g[nm].add_(self.p[nm], alpha=reg)
-        nm = f"{self.prefix}dnn_w"
-        self.g[nm].add_(self.p[nm], alpha=reg)
-
 
 def init_reference(engine, seed=2019):
-    """Initial values with the reference's distributions (TF's RNG stream itself cannot
-    be reproduced): embedding tables, DNN and CIN weights truncated-normal glorot
-    (utils.py:180-183; layers.py:99-101,536,551,567,666), cin_w glorot-uniform
-    (layers.py:690), everything else zeros (layers.py:109,321,327,544,561,574,676,695).
-    Cross-net vectors (absent from the reference): glorot-normal weights, zero biases."""
+    """Initial values with the reference's distributions (TF's RNG stream itself cannot be reproduced): every
+    variable of engine.params, in insertion order, by the rule it was declared with (Engine._var) - embedding
+    tables, DNN and CIN weights truncated-normal glorot (utils.py:180-183; layers.py:99-101,536,551,567,666), cin_w
+    glorot-uniform (layers.py:690), biases zeros (layers.py:109,321,327,544,561,574,676,695); the layers absent from
+    the reference (cross net, attention units, interacting layers, DLRM's towers) glorot weights like dnn_w and zero
+    biases.  A variable without a declared rule is a KeyError."""
     import math
 
     g = torch.Generator(device=engine.device).manual_seed(int(seed))
-
-    def tn(t, fan_in, fan_out):
-        std = math.sqrt(2.0 / (fan_in + fan_out))
-        torch.nn.init.trunc_normal_(t, 0.0, std, -2 * std, 2 * std, generator=g)
-
     for name, t in engine.params.items():
-        if name.endswith("_feat_embed") or name.endswith("_weights") or name == "dnn_w":
-            tn(t, t.shape[0], t.shape[1])
-        elif name.startswith("cin_filter_"):
-            tn(t, t.shape[1], t.shape[2])
-        elif name == "cin_w":
-            b = math.sqrt(6.0 / (t.shape[0] + t.shape[1]))
-            t.uniform_(-b, b, generator=g)
-        elif name in ("cross_w",):
-            tn(t, t.shape[1], t.shape[2] if t.dim() == 3 else 1)
-        elif name == "cross_w_out":
-            tn(t, t.shape[0], 1)
-        elif name.endswith("_asp_w"):
-            # the attention unit is absent from the reference (DIN.py:6): its output projection like dnn_w
-            tn(t, t.shape[0], t.shape[1])
-        elif name in ("afm_attention_w", "afm_attention_h", "afm_projection_p"):
-            # the attention layer is absent from the reference (AFM.py:7): glorot like dnn_w / cross_w_out
-            tn(t, t.shape[0], t.shape[1])
-        elif name == "autoint_w" or (name.startswith("autoint_layer_") and name.endswith("_w")):
-            # the interacting layers are absent from the reference: glorot like dnn_w
-            tn(t, t.shape[0], t.shape[1])
-        elif name == "top_dnn_w":
-            # DLRM's top tower: its output projection like dnn_w (the towers' *_weights are covered above)
-            tn(t, t.shape[0], t.shape[1])
-        else:
+        if name not in engine.decl:
+            raise KeyError(f"variable {name!r} was never declared: it has no init rule")
+        init = engine.decl[name][0]
+        if init == "zeros":
             t.zero_()
+            continue
+        kind, fan_in, fan_out = init
+        if kind == "glorot":
+            std = math.sqrt(2.0 / (fan_in + fan_out))
+            torch.nn.init.trunc_normal_(t, 0.0, std, -2 * std, 2 * std, generator=g)
+        elif kind == "glorot_uniform":
+            b = math.sqrt(6.0 / (fan_in + fan_out))
+            t.uniform_(-b, b, generator=g)
+        else:
+            raise ValueError(f"variable {name!r}: unknown init rule {init!r}")
 
 
 class Engine:
@@ -415,6 +412,14 @@ class Engine:
 
     model = "base"
     use_bias_tables = False
+    shardable = False  # recman_amd/dist.py has a row-sharded engine for this model
+
+    @classmethod
+    def require_shardable(cls):
+        if not cls.shardable:
+            raise NotImplementedError(
+                f"{cls.model} runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
+                "multi-rank torch.distributed job); use table_sharding='none'")
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         if not torch.cuda.is_available():
@@ -425,20 +430,61 @@ class Engine:
         F, R, Dn = spec.F, spec.rows, spec.Dn
         self.F, self.Dn, self.FD = F, Dn, F * self.D
         self.params, self.grads = {}, {}
+        # every variable's name -> (init rule, l2 key) in declaration order (_var / _view / _adopt), and the names
+        # each l2 hyper-parameter regularises.  NAMES only: the optimizers and recman_amd/dist.py re-home the
+        # tensors of params / grads, and the sharded engine swaps self.hp for a scaled copy per call
+        self.decl, self.l2_groups = {}, {}
+        self.mlp = None
+        self.grad_scale = 1.0   # this batch's share of a step's gradient (micro-batches, recman_amd/dist.py)
+        self._head_req = None   # fwd_bwd's offer of the fused head to the model's last DNN (_mlp_last)
+        self.d_bias = None      # per-occurrence bias-table gradients [B,F] (FM bias dropout only)
+        self._probe_ready = None
         self._alloc_tables()
-        self.params["linear_w0"] = torch.zeros(1, dtype=F32, device=dev)
-        self.grads["linear_w0"] = torch.zeros(1, dtype=F32, device=dev)
+        self._var("linear_w0", (1,))
         self.grads["linear_w_dense"] = torch.zeros(Dn, dtype=F32, device=dev)
         self._B = None
         self.use_linear = True
         self._init_seq()
+
+    def _var(self, name, shape, init="zeros", l2=None):
+        """Declares a dense variable of this engine (_declare): params / grads pair, init rule, l2 key."""
+        _declare(self.params, self.grads, self.decl, name, shape, self.device, init, l2)
+        if l2 is not None:
+            self.l2_groups.setdefault(l2, []).append(name)
+
+    def _view(self, name, t, init="zeros"):
+        """Declares a variable that is a view of storage laid out elsewhere (the table): no l2 key, no grads entry."""
+        self.params[name] = t
+        self.decl[name] = (init, None)
+
+    def _adopt(self, net):
+        """Takes over the declarations of an MLP / Tower built on self.params / self.grads; returns it."""
+        self.decl.update(net.decl)
+        for name, (_, l2) in net.decl.items():
+            if l2 is not None:
+                self.l2_groups.setdefault(l2, []).append(name)
+        return net
+
+    def _dnn(self, FD, Dn, hidden, default_activation, prefix="", stream_d_rows=None):
+        """The model's DNN on this engine's variables, with the hyper-parameters every model passes it."""
+        hp = self.hp
+        if stream_d_rows is None:
+            stream_d_rows = hp.get("d_rows_reuse", "cache") == "stream"
+        return self._adopt(MLP(self.params, self.grads, FD, Dn, hidden, hp.get("deep_activation", default_activation),
+                               self.device, prefix=prefix, stream_d_rows=stream_d_rows,
+                               dense_gemm=hp.get("dense_gemm", "bf16x6")))
+
+    def _dnn_keep(self, training):
+        """The DNN's keep probabilities for this call (deep_dropout; all ones outside training)."""
+        n = len(self.mlp.hidden)
+        return list(self.hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
 
     def _init_seq(self):
         """The attention unit of every sequence feature (csrc/asp.hip; DIN's local activation unit, arXiv 1706.06978):
         variables {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w
         [H_last, 1], {name}_asp_w0 [1].  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's
         Dice, activation.py, uses undefined names), att_weight_normalization False, att_dropout all ones."""
-        spec, hp, dev, D = self.spec, self.hp, self.device, self.D
+        spec, hp, D = self.spec, self.hp, self.D
         self._asp_saved = {}
         if not spec.seq_names:
             return
@@ -465,14 +511,13 @@ class Engine:
                 raise ValueError(f"sequence feature {n!r}: embedding_size={D}, att_hidden_units={self.asp_hidden}, "
                                  f"max_len={spec.seq_max_len[n]} is not supported by rm_asp_fwd (embedding_size 8/16/32, "
                                  "one or two hidden layers of 1..128 units, max_len 1..256)")
+            # (absent from the reference, DIN.py:6: glorot weights and an output projection like dnn_w; no l2)
             dims = [4 * D] + self.asp_hidden
-            shapes = []
             for i in range(len(self.asp_hidden)):
-                shapes += [(f"{n}_asp_layer_{i}_weights", (dims[i], dims[i + 1])), (f"{n}_asp_layer_{i}_bias", (dims[i + 1],))]
-            shapes += [(f"{n}_asp_w", (dims[-1], 1)), (f"{n}_asp_w0", (1,))]
-            for nm, shape in shapes:
-                self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
-                self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+                self._var(f"{n}_asp_layer_{i}_weights", (dims[i], dims[i + 1]), ("glorot", dims[i], dims[i + 1]))
+                self._var(f"{n}_asp_layer_{i}_bias", (dims[i + 1],))
+            self._var(f"{n}_asp_w", (dims[-1], 1), ("glorot", dims[-1], 1))
+            self._var(f"{n}_asp_w0", (1,))
 
     def _asp_vars(self, d, name):
         """(Ws, bs, w, w0) of sequence feature `name` out of the params or the grads dict."""
@@ -543,11 +588,11 @@ class Engine:
         for name, off, V in zip(spec.sparse_names, offs, spec.feat_sizes):
             if name in spec.seq_query:
                 continue  # a history shares its query feature's rows
-            self.params[f"{name}_feat_embed"] = self.rows[off: off + V, :D]
+            self._view(f"{name}_feat_embed", self.rows[off: off + V, :D], ("glorot", V, D))
             if self.use_bias_tables:
-                self.params[f"{name}_feat_bias"] = self.rows[off: off + V, D: D + 1]
-        self.params["linear_w_sparse"] = self.rows[:, D + 1]
-        self.params["linear_w_dense"] = self.linear_w_dense
+                self._view(f"{name}_feat_bias", self.rows[off: off + V, D: D + 1])
+        self._view("linear_w_sparse", self.rows[:, D + 1])
+        self._view("linear_w_dense", self.linear_w_dense)
         self._set_lin_masks()
 
     def storage(self):
@@ -756,7 +801,7 @@ class Engine:
         self._alloc(B)
         self._mv = mv
         yk = dict(y=y) if y.dtype == I64 else dict(y_f=y)
-        scale = getattr(self, "grad_scale", 1.0)
+        scale = self.grad_scale
         # models whose DNN is the last branch of the forward offer it the fused head (rm_mlp_tail):
         # final logit, prediction, loss and dLoss/dlogit in the MLP kernel's epilogue
         self._head_req = dict(task=self.task, grad_scale=scale, logit=self.logit, pred=self.pred,
@@ -775,6 +820,7 @@ class Engine:
                 self.dlogit.mul_(scale)
         self._lin_done = False
         self._branches_bwd(idx, dense, self.dlogit, masks)
+        self._add_l2_grads()
         self._seq_bwd()
         if self.use_linear and not self._lin_done:
             ops.linear_dense_bwd(self.dlogit, dense if self.Dn else None,
@@ -790,7 +836,7 @@ class Engine:
         """The DNN as the LAST branch of the forward: `others` = the (logit, coefficient) pairs
         already computed.  Hands the fused head to the MLP when fwd_bwd asked for it and at most two
         other branches exist; returns the DNN logit."""
-        req = getattr(self, "_head_req", None) if self.fuse_head else None
+        req = self._head_req if self.fuse_head else None
         head = dict(req, branches=others, coef_mlp=1.0) if (req is not None and len(others) <= 2) else None
         out = mlp.forward(xe, xd, keep, masks, head=head)
         self._head_done = bool(head is not None and mlp.head_done)
@@ -824,7 +870,37 @@ class Engine:
         return self._add_l2_model(total)
 
     def _add_l2_model(self, total):
+        """+ the l2 value of the model's own variables: per declared key, reg / 2 * sum w^2 over its group
+        (layers.py:611-628).  Coefficients from self.hp and tensors from self.params at call time."""
+        for key, names in self.l2_groups.items():
+            reg = self.hp.get(key, 0.0)
+            if reg:
+                total = total + sum(reg * 0.5 * self.params[n].square().sum() for n in names)
         return total
+
+    def _add_l2_grads(self):
+        """+ the l2 gradient reg * w of the same groups onto self.grads."""
+        for key, names in self.l2_groups.items():
+            reg = self.hp.get(key, 0.0)
+            if reg:
+                for n in names:
+                    self.grads[n].add_(self.params[n], alpha=reg)
+
+    # ---------------------------------------------------------------- dropout
+    def dropout_masks(self, B):
+        """0/1 keep masks for the configured keep-probabilities (tf.nn.dropout, layers.py:461,466,589,602), drawn
+        on the GPU: masks["dnn"] for the model's DNN, then the model's own (_model_masks); None when there are none."""
+        masks = {}
+        keep = self.hp.get("deep_dropout")
+        if keep is not None and any(k < 1 for k in keep) and self.mlp is not None:
+            dims = [self.mlp.FD + self.mlp.Dn] + self.mlp.hidden
+            masks["dnn"] = [(torch.rand(B, d, device=self.device) < k).float() if k < 1 else None
+                            for d, k in zip(dims, keep)]
+        self._model_masks(B, masks)
+        return masks or None
+
+    def _model_masks(self, B, masks):
+        pass
 
     # ------------------------------------------------------------ measurement
     def roofline_probes(self, idx, dense, y):
@@ -837,6 +913,14 @@ class Engine:
         return [dict(name="embed_fwd_fused_kernel (rm_embed_fwd: gather + FM + linear)",
                      symbol="embed_fwd_fused_kernel", fn=lambda: self._embed(idx, dense, fm, None),
                      work=self._embed_fwd_bytes(idx.shape[0], fm), bound="hbm")]
+
+    def _probe_fill(self, idx, dense, y):
+        """One fwd_bwd per batch size, so that the kernels a probe launches on their own find their inputs."""
+        B = idx.shape[0]
+        self._alloc(B)
+        if self._probe_ready != B:
+            self.fwd_bwd(idx, dense, y)
+            self._probe_ready = B
 
     def roofline_probe_all(self, idx, dense, y, iters=20):
         """Times every roofline_probes() kernel with HIP events on the stream it is launched on and
@@ -977,7 +1061,7 @@ class Engine:
         if self.use_bias_tables:
             d_bias = torch.zeros(R + 1, dtype=F32, device=self.device)
             if self._has_fm():
-                if getattr(self, "d_bias", None) is not None:
+                if self.d_bias is not None:
                     ops.scatter_add_rows(d_bias, idx, foff, rows=self.d_bias, width=1, ld=1)
                     g_bias_occ = self.d_bias
                 else:
@@ -1044,6 +1128,7 @@ class DeepFMEngine(Engine):
 
     model = "deepfm"
     use_bias_tables = True
+    shardable = True
     needs_fm_or_deep = True  # DeepFM.py:54; a subclass with a branch of its own over E may run without either
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
@@ -1051,12 +1136,18 @@ class DeepFMEngine(Engine):
         self.use_fm = bool(hp.get("use_fm", True))
         self.use_deep = bool(hp.get("use_deep", True))
         assert self.use_fm or self.use_deep or not self.needs_fm_or_deep  # DeepFM.py:54
-        self.mlp = None
         if self.use_deep:
-            self.mlp = MLP(self.params, self.grads, self.FD, self.Dn, hp["deep_hidden_units"],
-                           hp.get("deep_activation", "relu"), self.device)
-            self.mlp.stream_d_rows = hp.get("d_rows_reuse", "cache") == "stream"
-            self.mlp.dense_gemm = hp.get("dense_gemm", "bf16x6")
+            self.mlp = self._dnn(self.FD, self.Dn, hp["deep_hidden_units"], "relu")
+        # whether the one-kernel front / step take this engine's shapes (asked once), and the step's workspace
+        self._front_ok = self._step_ok = self._step_ws = None
+
+    def _model_masks(self, B, masks):
+        fk = self.hp.get("fm_dropout")
+        if fk is not None and any(k < 1 for k in fk):
+            dev = self.device
+            mb = (torch.rand(B, self.F, device=dev) < fk[0]).float() / fk[0] if fk[0] < 1 else None
+            me = (torch.rand(B, self.F, self.D, device=dev) < fk[1]).float() / fk[1] if fk[1] < 1 else None
+            masks["fm"] = (mb, me)
 
     def _has_fm(self):
         return self.use_fm
@@ -1069,7 +1160,7 @@ class DeepFMEngine(Engine):
             return False
         if lin_w is not None or m.get("dnn") is not None or any(x is not None for x in m.get("fm", (None, None))):
             return False
-        if getattr(self, "_front_ok", None) is None:
+        if self._front_ok is None:
             self._front_ok = bool(self.mlp.fused_ok and ops.embed_mlp_fwd_supported(
                 self.F, self.D, self._front_ld(), self.Dn, self.mlp.hidden))
         return self._front_ok
@@ -1087,16 +1178,14 @@ class DeepFMEngine(Engine):
         mlp._alloc(B, idx.device)
         mlp.keep, mlp.masks = [1] * (n + 1), [None] * (n + 1)
         mlp.xe, mlp.xd, mlp.fused = self.E.view(-1, self.FD), (dense if self.Dn else None), True
-        req = getattr(self, "_head_req", None) if self.fuse_head else None
+        req = self._head_req if self.fuse_head else None
         head = dict(req, branches=branches, coef_mlp=1.0) if req is not None else None
         mlp.tail = ops.mlp_tail(B, dh=mlp.dhb, **head) if head is not None else None
         mlp.head_done = head is not None
-        pre = mlp.prefix
         ids, rows, foff, ld, stream_rows = self._front_table(idx)
         ops.embed_mlp_fwd(
-            ids, rows, foff, self.D, ld, dense if self.Dn else None,
-            [p[f"{pre}dnn_layer_{i}_weights"] for i in range(n)], [p[f"{pre}dnn_layer_{i}_bias"] for i in range(n)],
-            p[f"{pre}dnn_w"].view(-1), p[f"{pre}dnn_w0"], mlp.act, self.E, mlp.hb, mlp.out.view(B),
+            ids, rows, foff, self.D, ld, dense if self.Dn else None, *mlp.vars(p), mlp.act, self.E, mlp.hb,
+            mlp.out.view(B),
             want_bias=self.use_fm and self.use_bias_tables, want_lin=True,
             lin_w_dense=self.linear_w_dense if self.Dn else None, lin_w0=p["linear_w0"],
             fm_sum=self.fm_sum if self.use_fm else None, fm_logit=self.fm_logit if self.use_fm else None,
@@ -1114,23 +1203,20 @@ class DeepFMEngine(Engine):
             return False
         if not (self.use_fm and self.use_bias_tables and self._front_fused({}, None)):
             return False
-        if getattr(self, "_step_ok", None) is None:
+        if self._step_ok is None:
             self._step_ok = bool(ops.deepfm_step_supported(self.F, self.D, self.LD, self.Dn, self.mlp.hidden))
         return self._step_ok
 
     def _step_call(self, idx, dense, y, skip_finish=False):
         mlp, p, g = self.mlp, self.params, self.grads
-        if getattr(self, "_step_ws", None) is None:
+        if self._step_ws is None:
             self._step_ws = torch.zeros(ops.deepfm_step_workspace(self.F, self.Dn), dtype=F32, device=self.device)
-        pre, n = mlp.prefix, len(mlp.hidden)
         ops.deepfm_step(
             idx, self.rows, self.field_off, self.D, self.LD, dense if self.Dn else None, y,
-            [p[f"{pre}dnn_layer_{i}_weights"] for i in range(n)], [p[f"{pre}dnn_layer_{i}_bias"] for i in range(n)],
-            p[f"{pre}dnn_w"].view(-1), p[f"{pre}dnn_w0"], self.linear_w_dense if self.Dn else None, p["linear_w0"],
+            *mlp.vars(p), self.linear_w_dense if self.Dn else None, p["linear_w0"],
             mlp.act, self.task, self.d_rows, self.logit, self.pred, self.dlogit, self.loss,
-            [g[f"{pre}dnn_layer_{i}_weights"] for i in range(n)], [g[f"{pre}dnn_layer_{i}_bias"] for i in range(n)],
-            g[f"{pre}dnn_w"].view(-1), g[f"{pre}dnn_w0"], g["linear_w_dense"] if self.Dn else None, g["linear_w0"],
-            self._step_ws, grad_scale=getattr(self, "grad_scale", 1.0),
+            *mlp.vars(g), g["linear_w_dense"] if self.Dn else None, g["linear_w0"],
+            self._step_ws, grad_scale=self.grad_scale,
             # (plain row loads unless asked otherwise: the reason for streaming them - keeping E in the caches for the
             # MLP kernels - is gone with E; measured 97 vs 102 us per step, uniform ids)
             stream_rows=self.hp.get("step_row_loads", "cache") == "stream",
@@ -1148,9 +1234,7 @@ class DeepFMEngine(Engine):
         g = self.grads
         if self.Dn and self.lin_dense_mask is not None:
             g["linear_w_dense"].mul_(self.lin_dense_mask)  # linear_features subset
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            self.mlp.add_l2_grads(reg)
+        self._add_l2_grads()
         return self._add_l2(self.loss)
 
     def roofline_probes(self, idx, dense, y):
@@ -1192,7 +1276,6 @@ class DeepFMEngine(Engine):
                      symbol="embed_mlp_fwd_kernel", fn=run, work=work, bound="hbm")] + probes
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        hp = self.hp
         m = masks or {}
         if not training:
             m = {}
@@ -1208,10 +1291,8 @@ class DeepFMEngine(Engine):
         if self.use_fm:
             branches.append((self.fm_logit, 1.0))
         if self.use_deep:
-            n = len(hp["deep_hidden_units"])
-            keep = list(hp.get("deep_dropout", [1] * (n + 1))) if training else [1] * (n + 1)
             self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
-                                            keep, m.get("dnn"), list(branches))
+                                            self._dnn_keep(training), m.get("dnn"), list(branches))
             branches.append((self.dnn_logit, 1.0))
         return branches
 
@@ -1234,16 +1315,6 @@ class DeepFMEngine(Engine):
         if self.use_fm and not fm_done:
             ops.embed_bwd(self.d_rows, E=self.E, fm_sum=self.fm_sum, dE_up=dE_up, g_fm=g,
                           mask_b=fm_masks[0], mask_e=fm_masks[1], d_bias=self.d_bias)
-        if self.use_deep:
-            reg = self.hp.get("deep_l2_reg", 0.0)
-            if reg:
-                self.mlp.add_l2_grads(reg)
-
-    def _add_l2_model(self, total):
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg and self.use_deep:
-            total = total + self.mlp.l2(reg)
-        return total
 
 
 class DCNEngine(Engine):
@@ -1256,6 +1327,7 @@ class DCNEngine(Engine):
 
     model = "dcn"
     use_bias_tables = False
+    shardable = True
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         super().__init__(spec, embedding_size, hp, task, device)
@@ -1263,19 +1335,16 @@ class DCNEngine(Engine):
         self.L = int(hp.get("cross_layer_num", 3))
         self.dnn_coef = 2.0 if hp.get("strict_reference", False) else 1.0
         d = self.FD + self.Dn
-        dev = self.device
-        self.mlp = MLP(self.params, self.grads, self.FD, self.Dn, hp["deep_hidden_units"],
-                       hp.get("deep_activation", "relu"), dev)
-        self.mlp.stream_d_rows = hp.get("d_rows_reuse", "cache") == "stream"
-        self.mlp.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        self.mlp = self._dnn(self.FD, self.Dn, hp["deep_hidden_units"], "relu")
         self.cross_type = hp.get("cross_type", "vector")
         if self.cross_type not in ("vector", "matrix"):
             raise ValueError(f"cross_type {self.cross_type!r}: 'vector' or 'matrix'")
         self.matrix = self.cross_type == "matrix"
-        wshape = (self.L, d, d) if self.matrix else (self.L, d)
-        for nm, shape in (("cross_w", wshape), ("cross_b", (self.L, d)), ("cross_w_out", (d, 1))):
-            self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
-            self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+        # (absent from the reference: glorot-normal weights, zero biases)
+        self._var("cross_w", (self.L, d, d) if self.matrix else (self.L, d), ("glorot", d, d if self.matrix else 1),
+                  "cross_layer_l2_reg")
+        self._var("cross_b", (self.L, d))
+        self._var("cross_w_out", (d, 1), ("glorot", d, 1), "cross_layer_l2_reg")
 
     def _alloc_model(self, B):
         dev = self.device
@@ -1340,13 +1409,10 @@ class DCNEngine(Engine):
         torch.add(self.cdx0[:, : self.FD], self.dxe_dnn, out=self.d_rows.view(-1, self.FD))
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        hp = self.hp
         m = (masks or {}) if training else {}
         self._embed(idx, dense, False, m, lin_w)
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
-        n = len(hp["deep_hidden_units"])
-        keep = list(hp.get("deep_dropout", [1] * (n + 1))) if training else [1] * (n + 1)
-        self.dnn_logit = self.mlp.forward(xe, xd, keep, m.get("dnn"))
+        self.dnn_logit = self.mlp.forward(xe, xd, self._dnn_keep(training), m.get("dnn"))
         p = self.params
         if self.matrix:
             self._cross_matrix_fwd(xe, xd)
@@ -1370,7 +1436,6 @@ class DCNEngine(Engine):
         self.mlp.backward(g_dnn, self.dxe_dnn, defer_wgrad0=fold)
         if self.matrix:
             self._cross_matrix_bwd(g)
-            self._cross_l2_grads()
             return
         # cross backward adds the DNN's dx and writes straight into the row-gradient
         # buffer: with no FM term d_rows IS dLoss/dE (no separate embed_bwd launch)
@@ -1387,7 +1452,6 @@ class DCNEngine(Engine):
         ops.cross_param_grads(self.P, colsum, p["cross_w"], p["cross_b"],
                               p["cross_w_out"].view(-1), gr["cross_w"], gr["cross_b"],
                               gr["cross_w_out"].view(-1))
-        self._cross_l2_grads()
 
     def roofline_probes(self, idx, dense, y):
         # the MLP GEMMs dominate the DCN step: layer 0 of the wide DNN, x = [xe | xd] -> H0 (bias +
@@ -1395,10 +1459,7 @@ class DCNEngine(Engine):
         if self.mlp.fused_ok:
             return super().roofline_probes(idx, dense, y)
         B = idx.shape[0]
-        self._alloc(B)
-        if getattr(self, "_probe_ready", None) != B:
-            self.fwd_bwd(idx, dense, y)  # fills E, the layer scalars s, dlogit, dxe_dnn
-            self._probe_ready = B
+        self._probe_fill(idx, dense, y)  # E, the layer scalars s, dlogit, dxe_dnn
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
         W, b = self.params["dnn_layer_0_weights"], self.params["dnn_layer_0_bias"]
         m, p, L, d = self.mlp, self.params, self.L, self.FD + self.Dn
@@ -1438,26 +1499,6 @@ class DCNEngine(Engine):
                 work=B * (2 * self.FD * 4 + 4 * (2 * L + 2) + 4 * (L + 1) + 4), bound="hbm"))
         return probes
 
-    def _cross_l2_grads(self):
-        p, gr = self.params, self.grads
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            self.mlp.add_l2_grads(reg)
-        reg = self.hp.get("cross_layer_l2_reg", 0.0)
-        if reg:
-            gr["cross_w"].add_(p["cross_w"], alpha=reg)
-            gr["cross_w_out"].add_(p["cross_w_out"], alpha=reg)
-
-    def _add_l2_model(self, total):
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            total = total + self.mlp.l2(reg)
-        reg = self.hp.get("cross_layer_l2_reg", 0.0)
-        if reg:
-            total = total + reg * 0.5 * (self.params["cross_w"].square().sum()
-                                         + self.params["cross_w_out"].square().sum())
-        return total
-
 
 class XDeepFMEngine(Engine):
     """xDeepFM._out (xDeepFM.py:47-104): embeddings without bias tables,
@@ -1466,20 +1507,18 @@ class XDeepFMEngine(Engine):
 
     model = "xdeepfm"
     use_bias_tables = False
+    shardable = True
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         super().__init__(spec, embedding_size, hp, task, device)
-        dev = self.device
         self.units = [int(u) for u in hp["cin_cross_layer_units"]]
         assert len(self.units) > 0  # layers.py:656
         self.cin_act = act_name(hp.get("cin_activation", "leaky_relu"))
         keep = hp.get("cin_dropout")
         if keep is not None and any(k < 1 for k in keep):
             assert len(keep) == len(self.units) + 1  # layers.py:657 (checked only when it matters)
-        self.mlp = MLP(self.params, self.grads, self.FD, self.Dn, hp["deep_hidden_units"],
-                       hp.get("deep_activation", "leaky_relu"), dev)
-        self.mlp.stream_d_rows = hp.get("d_rows_reuse", "cache") == "stream"
-        self.mlp.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        self.mlp = self._dnn(self.FD, self.Dn, hp["deep_hidden_units"], "leaky_relu")
+        self._cin_drop = None  # (keep, masks, which layers) of the last forward's cin_dropout
         m = self.F
         self.Hs, self.pool_from, self.pool_col0 = [m], [], []
         final = 0
@@ -1488,17 +1527,22 @@ class XDeepFMEngine(Engine):
             if not last and size % 2:
                 raise ValueError("CIN layer sizes before the last must be even (split in halves, layers.py:742-746)")
             H = self.Hs[-1]
-            for nm, shape in ((f"cin_filter_{i}", (1, m * H, size)), (f"cin_bias_{i}", (size,))):
-                self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
-                self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+            self._var(f"cin_filter_{i}", (1, m * H, size), ("glorot", m * H, size), "cin_l2_reg")
+            self._var(f"cin_bias_{i}", (size,))
             self.pool_from.append(0 if last else size // 2)
             self.pool_col0.append(final)
             final += size if last else size // 2
             self.Hs.append(size // 2)
         self.P = final
-        for nm, shape in (("cin_w", (final, 1)), ("cin_w0", (1,))):
-            self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
-            self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+        self._var("cin_w", (final, 1), ("glorot_uniform", final, 1), "cin_l2_reg")
+        self._var("cin_w0", (1,))
+
+    def _model_masks(self, B, masks):
+        ck = self.hp.get("cin_dropout")
+        if ck is not None and any(k < 1 for k in ck):
+            shapes = [(B, self.F, self.D)] + [(B, n, self.D) for n in self.units]
+            masks["cin"] = [(torch.rand(*sh, device=self.device) < k).float() if k < 1 else None
+                            for sh, k in zip(shapes, ck)]
 
     def _alloc_model(self, B):
         dev, m, D = self.device, self.F, self.D
@@ -1553,10 +1597,9 @@ class XDeepFMEngine(Engine):
         self._embed(idx, dense, False, m, lin_w)
         ck = list(hp.get("cin_dropout") or []) if training else []
         self._cin_fwd(ck if ck and any(k < 1 for k in ck) else None, m.get("cin"))
-        n = len(hp["deep_hidden_units"])
-        keep = list(hp.get("deep_dropout", [1] * (n + 1))) if training else [1] * (n + 1)
-        self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None, keep,
-                                        m.get("dnn"), [(self.lin_logit, 1.0), (self.cin_logit, 1.0)])
+        self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
+                                        self._dnn_keep(training), m.get("dnn"),
+                                        [(self.lin_logit, 1.0), (self.cin_logit, 1.0)])
         return [(self.lin_logit, 1.0), (self.cin_logit, 1.0), (self.dnn_logit, 1.0)]
 
     def _branches_bwd(self, idx, dense, g, masks):
@@ -1567,7 +1610,7 @@ class XDeepFMEngine(Engine):
         ops.linear_dense_bwd(g, self.pooled, gr["cin_w"].view(-1), gr["cin_w0"], self.ws)
         cw = p["cin_w"].view(-1)
         L = len(self.units)
-        drop = getattr(self, "_cin_drop", None)
+        drop = self._cin_drop
         keep, cmasks, on = drop if drop else (None, None, [False] * (L + 1))
         X0 = self._cin_x0
         dX0 = self.d_rows
@@ -1597,24 +1640,6 @@ class XDeepFMEngine(Engine):
                 first6=self.hp.get("cin_first_layer", "bf16x6") == "bf16x6")
         if on[0]:
             self.d_rows.addcmul_(self._dx0_cin, cmasks[0] / keep[0])
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            self.mlp.add_l2_grads(reg)
-        reg = self.hp.get("cin_l2_reg", 0.0)
-        if reg:
-            for i in range(L):
-                gr[f"cin_filter_{i}"].add_(p[f"cin_filter_{i}"], alpha=reg)
-            gr["cin_w"].add_(p["cin_w"], alpha=reg)
-
-    def _add_l2_model(self, total):
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            total = total + self.mlp.l2(reg)
-        reg = self.hp.get("cin_l2_reg", 0.0)
-        if reg:
-            ws = [self.params[f"cin_filter_{i}"] for i in range(len(self.units))] + [self.params["cin_w"]]
-            total = total + sum(reg * 0.5 * w.square().sum() for w in ws)
-        return total
 
     def roofline_probes(self, idx, dense, y):
         # the heaviest CIN forward layer on the f32 MFMA roofline
@@ -1668,11 +1693,17 @@ class AFMEngine(Engine):
         if not ops.afm_supported(self.F, self.D, self.T):
             raise ValueError(f"AFM: {self.F} embedding features, embedding_size={self.D}, att_factor={self.T} is not "
                              "supported by rm_afm_fwd (2..40 features, embedding_size 8/16/32/64, att_factor 1..64)")
-        dev, D, T = self.device, self.D, self.T
-        for nm, shape in (("afm_attention_w", (D, T)), ("afm_attention_b", (T,)), ("afm_attention_h", (T, 1)),
-                          ("afm_projection_p", (D, 1))):
-            self.params[nm] = torch.zeros(shape, dtype=F32, device=dev)
-            self.grads[nm] = torch.zeros(shape, dtype=F32, device=dev)
+        # (the attention layer is absent from the reference, AFM.py:7: glorot like dnn_w / cross_w_out)
+        D, T = self.D, self.T
+        self._var("afm_attention_w", (D, T), ("glorot", D, T), "att_l2_reg")
+        self._var("afm_attention_b", (T,))
+        self._var("afm_attention_h", (T, 1), ("glorot", T, 1))
+        self._var("afm_projection_p", (D, 1), ("glorot", D, 1))
+
+    def _model_masks(self, B, masks):
+        ak = self.hp.get("att_dropout", 1)
+        if ak is not None and ak < 1:
+            masks["afm"] = (torch.rand(B, self.D, device=self.device) < ak).float() / ak
 
     def _alloc_model(self, B):
         dev = self.device
@@ -1703,15 +1734,6 @@ class AFMEngine(Engine):
         ops.afm_bwd(self.E, *self._afm_params(), g, self.afm_logit, self.afm_stats, self.d_rows,
                     gr["afm_attention_w"], gr["afm_attention_b"], gr["afm_attention_h"].view(-1),
                     gr["afm_projection_p"].view(-1), self.afm_ws, mask=self._mask)
-        reg = self.hp.get("att_l2_reg", 0.0)
-        if reg:
-            gr["afm_attention_w"].add_(self.params["afm_attention_w"], alpha=reg)
-
-    def _add_l2_model(self, total):
-        reg = self.hp.get("att_l2_reg", 0.0)
-        if reg:
-            total = total + reg * 0.5 * self.params["afm_attention_w"].square().sum()
-        return total
 
     @staticmethod
     def afm_flops(B, F, D, T):
@@ -1725,10 +1747,7 @@ class AFMEngine(Engine):
 
     def roofline_probes(self, idx, dense, y):
         B = idx.shape[0]
-        self._alloc(B)
-        if getattr(self, "_probe_ready", None) != B:
-            self.fwd_bwd(idx, dense, y)  # fills E, stats, dlogit
-            self._probe_ready = B
+        self._probe_fill(idx, dense, y)  # E, stats, dlogit
         fwd, bwd = self.afm_flops(B, self.F, self.D, self.T)
         gr = self.grads
         return [
@@ -1754,6 +1773,8 @@ class DINEngine(DeepFMEngine):
 
     model = "din"
     use_bias_tables = False
+    shardable = False
+    _model_masks = Engine._model_masks  # (no FM term: no fm_dropout masks)
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         super().__init__(spec, embedding_size, dict(hp, use_fm=False, use_deep=True), task, device)
@@ -1773,7 +1794,9 @@ class AutoIntEngine(DeepFMEngine):
 
     model = "autoint"
     use_bias_tables = False
+    shardable = False
     needs_fm_or_deep = False
+    _model_masks = Engine._model_masks  # (no FM term: no fm_dropout masks)
 
     def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
         hidden = tuple(hp.get("deep_hidden_units") or ())
@@ -1799,17 +1822,12 @@ class AutoIntEngine(DeepFMEngine):
                     "embedding_size 8/16/32/64, att_head_num 1/2/4/8, att_embedding_size >= 4, att_head_num * "
                     "att_embedding_size 8/16/32/64)")
         self.dins = dins
-        self.att_names = []
-        shapes = []
+        # (the interacting layers are absent from the reference: glorot like dnn_w)
         for l, din in enumerate(dins):
             for kind in ("query", "key", "value") + (("res",) if self.res else ()):
-                shapes.append((f"autoint_layer_{l}_{kind}_w", (din, self.HD)))
-                self.att_names.append(shapes[-1][0])
-        shapes += [("autoint_w", (self.F * self.HD, 1)), ("autoint_w0", (1,))]
-        self.att_names.append("autoint_w")
-        for nm, shape in shapes:
-            self.params[nm] = torch.zeros(shape, dtype=F32, device=self.device)
-            self.grads[nm] = torch.zeros(shape, dtype=F32, device=self.device)
+                self._var(f"autoint_layer_{l}_{kind}_w", (din, self.HD), ("glorot", din, self.HD), "att_l2_reg")
+        self._var("autoint_w", (self.F * self.HD, 1), ("glorot", self.F * self.HD, 1), "att_l2_reg")
+        self._var("autoint_w0", (1,))
 
     def _alloc_model(self, B):
         dev, F, H = self.device, self.F, self.H
@@ -1848,34 +1866,19 @@ class AutoIntEngine(DeepFMEngine):
             dy, spare = dx, dy
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        hp = self.hp
         m = (masks or {}) if training else {}
         self._embed(idx, dense, False, m, lin_w)
         self._att_fwd(training)
         branches = [(self.lin_logit, 1.0), (self.att_logit, 1.0)]
         if self.use_deep:
-            n = len(hp["deep_hidden_units"])
-            keep = list(hp.get("deep_dropout", [1] * (n + 1))) if training else [1] * (n + 1)
             self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
-                                            keep, m.get("dnn"), list(branches))
+                                            self._dnn_keep(training), m.get("dnn"), list(branches))
             branches.append((self.dnn_logit, 1.0))
         return branches
 
     def _branches_bwd(self, idx, dense, g, masks):
         super()._branches_bwd(idx, dense, g, masks)  # the DNN (when there is one) writes d_rows
         self._att_bwd(g, self.d_rows if self.use_deep else None)
-        reg = self.hp.get("att_l2_reg", 0.0)
-        if reg:
-            for nm in self.att_names:
-                self.grads[nm].add_(self.params[nm], alpha=reg)
-
-    def _add_l2_model(self, total):
-        total = super()._add_l2_model(total)
-        reg = self.hp.get("att_l2_reg", 0.0)
-        if reg:
-            for nm in self.att_names:
-                total = total + reg * 0.5 * self.params[nm].square().sum()
-        return total
 
     @staticmethod
     def autoint_flops(B, F, Din, HD):
@@ -1886,10 +1889,7 @@ class AutoIntEngine(DeepFMEngine):
 
     def roofline_probes(self, idx, dense, y):
         B = idx.shape[0]
-        self._alloc(B)
-        if getattr(self, "_probe_ready", None) != B:
-            self.fwd_bwd(idx, dense, y)  # fills E, Y, stats
-            self._probe_ready = B
+        self._probe_fill(idx, dense, y)  # E, Y, stats
         fwd, bwd = self.autoint_flops(B, self.F, self.D, self.HD)
         p, gr = self.params, self.grads
         dy = torch.randn(B, self.F, self.HD, dtype=F32, device=self.device)
@@ -1917,38 +1917,25 @@ class Tower:
     csrc/gemm6.hip): bias and activation in the epilogue, the bf16x6 path where `dense_gemm` allows it and the
     kernel takes the call - the choice MLP's wide path makes."""
 
-    def __init__(self, params, grads, K0, widths, activation, device, prefix):
+    def __init__(self, params, grads, K0, widths, activation, device, prefix, dense_gemm="bf16x6"):
         self.K0, self.widths = int(K0), [int(w) for w in widths]
         self.act = act_name(activation)
         if self.act not in ("relu", "leaky_relu", "identity"):
             raise ValueError(self.act)
         self.p, self.g, self.prefix = params, grads, prefix
         self.dims = [self.K0] + self.widths
-        for i in range(len(self.widths)):
-            for nm, shape in ((f"{prefix}dnn_layer_{i}_weights", (self.dims[i], self.dims[i + 1])),
-                              (f"{prefix}dnn_layer_{i}_bias", (self.dims[i + 1],))):
-                params[nm] = torch.zeros(shape, dtype=F32, device=device)
-                grads[nm] = torch.zeros(shape, dtype=F32, device=device)
-        self.dense_gemm = "bf16x6"
+        self.decl = {}
+        _declare_layers(params, grads, self.decl, prefix, self.dims, device)
+        self.dense_gemm = dense_gemm
         self._B = None
 
     def _alloc(self, B, device):
         if self._B == B:
             return
         self._B = B
-        dims, n = self.dims, len(self.widths)
         self.a = [torch.empty(B, h, dtype=F32, device=device) for h in self.widths]
         self.da = [torch.empty(B, h, dtype=F32, device=device) for h in self.widths[:-1]]
-        fw = max(ops.dense_filter_workspace(max(dims[i], dims[i + 1]), max(dims[i], dims[i + 1])) for i in range(n))
-        ww = max(ops.dense_wgrad_workspace(dims[i], dims[i + 1], B) for i in range(n))
-        self._fws = torch.empty(fw, dtype=F32, device=device)
-        self._wws = torch.empty(max(ww, 1), dtype=F32, device=device)
-        self._fws6 = self._wws6 = None
-        if self.dense_gemm == "bf16x6":
-            kmax = max(dims)
-            self._fws6 = torch.empty(ops.dense6_workspace(kmax, kmax, B), dtype=F32, device=device)
-            self._wws6 = torch.empty(max(ops.dense_wgrad6_workspace(dims[i], dims[i + 1], B) for i in range(n)),
-                                     dtype=F32, device=device)
+        self._fws, self._wws, self._fws6, self._wws6 = _dense_workspaces(self.dims, B, device, self.dense_gemm)
 
     def forward(self, x):
         """x [B,K0] -> a_last [B, widths[-1]] (an internal buffer)."""
@@ -1980,15 +1967,6 @@ class Tower:
                               aux1=None if ident else prev, ws6=self._fws6)
                 da = self.da[i - 1]
 
-    def l2(self, reg):
-        return sum(reg * 0.5 * self.p[f"{self.prefix}dnn_layer_{i}_weights"].square().sum()
-                   for i in range(len(self.widths)))
-
-    def add_l2_grads(self, reg):
-        for i in range(len(self.widths)):
-            nm = f"{self.prefix}dnn_layer_{i}_weights"
-            self.g[nm].add_(self.p[nm], alpha=reg)
-
 
 class DLRMEngine(Engine):
     """DLRM (arXiv 1906.00091, the MLPerf recommendation model): the dense features go through a bottom tower to
@@ -2018,14 +1996,12 @@ class DLRMEngine(Engine):
         if not hidden:
             raise ValueError("DLRM: deep_hidden_units must name at least one layer of the top tower")
         self.W, self.ldx = ops.dot_interact_width(self.F, self.D)
-        self.dnn_input_width = self.W  # (the width of the top tower's input-dropout mask)
-        act = hp.get("deep_activation", "relu")
-        dev = self.device
-        self.bot = Tower(self.params, self.grads, self.Dn, tuple(hp.get("bottom_hidden_units", (64, 32))) + (self.D,),
-                         act, dev, "bot_")
-        self.mlp = MLP(self.params, self.grads, self.W, 0, hidden, act, dev, prefix="top_")
-        self.mlp.stream_d_rows = False
-        self.bot.dense_gemm = self.mlp.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        self.bot = self._adopt(Tower(self.params, self.grads, self.Dn,
+                                     tuple(hp.get("bottom_hidden_units", (64, 32))) + (self.D,),
+                                     hp.get("deep_activation", "relu"), self.device, "bot_",
+                                     dense_gemm=hp.get("dense_gemm", "bf16x6")))
+        # (the top tower reads the interaction's output, not [E | dense]; its dX is no table-row gradient)
+        self.mlp = self._dnn(self.W, 0, hidden, "relu", prefix="top_", stream_d_rows=False)
 
     def _alloc_model(self, B):
         dev = self.device
@@ -2034,16 +2010,13 @@ class DLRMEngine(Engine):
         self.dz = torch.empty(B, self.D, dtype=F32, device=dev)
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        hp = self.hp
         m = (masks or {}) if training else {}
         self._embed(idx, dense, False, m, lin_w)
         self.z = self.bot.forward(dense)
         X = self.X[:, : self.W]
         ops.dot_interact_fwd(self.E, self.z, X)
-        n = len(self.mlp.hidden)
-        keep = list(hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
         branches = [(self.lin_logit, 1.0)] if self.use_linear else []
-        self.dnn_logit = self._mlp_last(self.mlp, X, None, keep, m.get("dnn"), list(branches))
+        self.dnn_logit = self._mlp_last(self.mlp, X, None, self._dnn_keep(training), m.get("dnn"), list(branches))
         branches.append((self.dnn_logit, 1.0))
         return branches
 
@@ -2053,24 +2026,10 @@ class DLRMEngine(Engine):
         # no other branch reads E: d_rows IS dLoss/dE
         ops.dot_interact_bwd(self.E, self.z, dX, self.d_rows, self.dz)
         self.bot.backward(self.dz)
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            self.mlp.add_l2_grads(reg)
-            self.bot.add_l2_grads(reg)
-
-    def _add_l2_model(self, total):
-        reg = self.hp.get("deep_l2_reg", 0.0)
-        if reg:
-            total = total + self.mlp.l2(reg) + self.bot.l2(reg)
-        return total
 
     def roofline_probes(self, idx, dense, y):
-        B = idx.shape[0]
-        self._alloc(B)
-        if getattr(self, "_probe_ready", None) != B:
-            self.fwd_bwd(idx, dense, y)  # fills E, z, dX
-            self._probe_ready = B
-        F, D, ldx = self.F, self.D, self.ldx
+        self._probe_fill(idx, dense, y)  # E, z, dX
+        B, F, D, ldx = idx.shape[0], self.F, self.D, self.ldx
         X, dX = self.X[:, : self.W], self.dX[:, : self.W]
         d_rows, dz = torch.empty_like(self.d_rows), torch.empty_like(self.dz)
         shape = f"F={F} D={D} ldx={ldx}"

@@ -81,25 +81,9 @@ class DeepModel(BaseEstimator, TransformerMixin):
                     f"sequence features {[f.name for f in fd.sequence_feats]} run on one GPU: the row-sharded table "
                     "has no attention-pooled lookup (table_sharding='row' or a multi-rank torch.distributed job); "
                     "use table_sharding='none'")
-            if self.model == "din":
+            if not eng.ENGINES[self.model].shardable:
                 self._shard = None
-                raise NotImplementedError("DIN runs on one GPU: there is no row-sharded engine for it; use "
-                                          "table_sharding='none'")
-            if self.model == "afm":
-                self._shard = None
-                raise NotImplementedError(
-                    "AFM runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
-                    "multi-rank torch.distributed job); use table_sharding='none'")
-            if self.model == "autoint":
-                self._shard = None
-                raise NotImplementedError(
-                    "AutoInt runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
-                    "multi-rank torch.distributed job); use table_sharding='none'")
-            if self.model == "dlrm":
-                self._shard = None
-                raise NotImplementedError(
-                    "DLRM runs on one GPU: there is no row-sharded engine for it (table_sharding='row' or a "
-                    "multi-rank torch.distributed job); use table_sharding='none'")
+                eng.ENGINES[self.model].require_shardable()
             return self._build_sharded(spec, hp)
         e = eng.ENGINES[self.model](spec, hp["embedding_size"], hp, task=self.task, device=self.device)
         eng.init_reference(e, self.random_seed)
@@ -408,32 +392,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
 
     # ---------------------------------------------------------------------- fit
     def _dropout_masks(self, B):
-        """0/1 keep masks for the configured keep-probabilities (tf.nn.dropout,
-        layers.py:461,466,589,602), drawn on the GPU."""
-        e = self._build()
-        hp, dev = e.hp, e.device
-        masks = {}
-        n = len(hp.get("deep_hidden_units", ()))
-        keep = hp.get("deep_dropout")
-        if keep is not None and any(k < 1 for k in keep) and getattr(e, "mlp", None) is not None:
-            # (DLRM's DNN reads the interaction's output, not [E | dense])
-            dims = [getattr(e, "dnn_input_width", e.FD + e.Dn)] + list(hp["deep_hidden_units"])
-            masks["dnn"] = [(torch.rand(B, d, device=dev) < k).float() if k < 1 else None
-                            for d, k in zip(dims, keep)]
-        fk = hp.get("fm_dropout")
-        if fk is not None and any(k < 1 for k in fk) and e.model == "deepfm":
-            mb = (torch.rand(B, e.F, device=dev) < fk[0]).float() / fk[0] if fk[0] < 1 else None
-            me = (torch.rand(B, e.F, e.D, device=dev) < fk[1]).float() / fk[1] if fk[1] < 1 else None
-            masks["fm"] = (mb, me)
-        ck = hp.get("cin_dropout")
-        if ck is not None and any(k < 1 for k in ck) and e.model == "xdeepfm":
-            shapes = [(B, e.F, e.D)] + [(B, n, e.D) for n in e.units]
-            masks["cin"] = [(torch.rand(*sh, device=dev) < k).float() if k < 1 else None
-                            for sh, k in zip(shapes, ck)]
-        ak = hp.get("att_dropout", 1)
-        if e.model == "afm" and ak is not None and ak < 1:
-            masks["afm"] = (torch.rand(B, e.D, device=dev) < ak).float() / ak
-        return masks or None
+        """0/1 keep masks for the configured keep-probabilities, drawn on the GPU (Engine.dropout_masks)."""
+        return self._build().dropout_masks(B)
 
     def fit_on_batch(self, X, y):
         idx, dense, yt = self._encode(X, y)
@@ -461,7 +421,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
             torch.cuda.current_stream(e.device).wait_stream(side)
         if self.strict_reference:
             self._opt.reset()  # a NEW optimizer every batch (xDeepFM.py:121-126)
-        fm_masked = getattr(e, "d_bias", None) is not None  # FM bias dropout: per-occurrence grads
+        fm_masked = e.d_bias is not None  # FM bias dropout: per-occurrence grads
         if self._sparse_opt is not None and not fm_masked:
             self._sparse_opt.step(idx, reset=self.strict_reference)
             self._dense_fused.step(reset=self.strict_reference)  # dense parameters only

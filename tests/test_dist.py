@@ -183,3 +183,15 @@ def test_gloo_fixed_capacity_exchange(world):
 def test_gloo_lookup_push_allreduce(world):
     port = 29500 + os.getpid() % 2000 + world
     mp.spawn(_worker, args=(world, port, 301, 8, 200), nprocs=world, join=True)
+
+
+@pytest.mark.parametrize("model", ["afm", "din", "autoint", "dlrm"])
+def test_models_without_a_sharded_engine_are_refused(model):
+    """No row-sharded engine exists for these: make_sharded_engine says so before it allocates anything (this
+    runs on a host without a GPU)."""
+    from recman_amd import engine as eng
+
+    spec = eng.FeatureSpec(["C0", "C1"], [7, 5], ["I0"])
+    with pytest.raises(NotImplementedError, match="one GPU") as err:
+        rd.make_sharded_engine(model, spec, 8, dict(deep_hidden_units=(8, 8)), "cuda:0", 0, 1)
+    assert model in str(err.value) and "table_sharding='none'" in str(err.value)
