@@ -437,6 +437,35 @@ int rm_dot_interact_bwd(const float *E, const float *z, const float *dX, int64_t
                         int F, int D, float *d_rows, float *dz, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The core of a DCN-Mix cross layer (DCN-V2, arXiv 2008.13535 eq. 4-5): everything between the
+ * layer's projection GEMM and its output GEMM, fused (csrc/cross_mix.hip).  Nothing in the
+ * reference implements it.  Per example, E experts of rank r, W = E r, expert i owning columns
+ * [i r, i r + r):
+ *     a_i = tanh(t_i);  c_i = tanh(a_i C_i);  p = softmax_i(s), max-subtracted;  m_i = p_i c_i
+ *   T [B, ldt] (W columns used), S [B, lds] (E columns used), M [B, ldm] (W columns written):
+ *   every [B, .] argument is a pointer and a row stride in floats, stride >= width, rows need no
+ *   alignment - T | S may be column ranges of one buffer; columns past the width are never read
+ *   or written.  C [E, r, r] contiguous.  Each r x r product is a k-ordered fmaf chain.
+ * rm_cross_mix_bwd, given dM = dLoss/dM, recomputes a, c and p and writes dT, dS (owned columns
+ *   only) and dC [E, r, r] (overwritten; all zero at B = 0):
+ *     dc_i = p_i dm_i;  dp_i = <dm_i, c_i>;  ds_i = p_i (dp_i - sum_j p_j dp_j)   (+0.0 at E = 1)
+ *     dh_i = dc_i o (1 - c_i^2);  dC_i = sum_b a_i^T dh_i;  da_i = dh_i C_i^T;  dt_i = da_i o (1 - a_i^2)
+ *   workspace: rm_cross_mix_bwd_workspace(B, E, r) floats (per-block partial dC, summed in block
+ *   order by a finish kernel: no atomics, two runs are bit-equal); -1 for an unsupported shape.
+ * Supported: 1 <= E <= 8, r in {8,16,32,64}, E r <= 256 (rm_cross_mix_supported); anything else,
+ *   a NULL pointer or a stride below its width is RM_EINVAL before any launch.  B = 0 is RM_OK.
+ * a, h, c, p and dh never reach HBM: the forward moves 4 (2 W + E) bytes per example, the
+ *   backward reads 4 (2 W + E) and writes 4 (W + E).
+ */
+int rm_cross_mix_supported(int E, int r);
+int rm_cross_mix_fwd(const float *T, int64_t ldt, const float *S, int64_t lds, const float *C, int E,
+                     int r, int64_t B, float *M, int64_t ldm, rm_stream_t stream);
+int64_t rm_cross_mix_bwd_workspace(int64_t B, int E, int r);
+int rm_cross_mix_bwd(const float *T, int64_t ldt, const float *S, int64_t lds, const float *C, int E,
+                     int r, int64_t B, const float *dM, int64_t lddm, float *dT, int64_t lddt,
+                     float *dS, int64_t ldds, float *dC, float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

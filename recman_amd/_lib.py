@@ -71,6 +71,9 @@ SIGNATURES = {
     "rm_dot_interact_supported": [c_int, c_int],
     "rm_dot_interact_fwd": [P, P, I64, c_int, c_int, P, I64, P],
     "rm_dot_interact_bwd": [P, P, P, I64, I64, c_int, c_int, P, P, P],
+    "rm_cross_mix_supported": [c_int, c_int],
+    "rm_cross_mix_fwd": [P, I64, P, I64, P, c_int, c_int, I64, P, I64, P],
+    "rm_cross_mix_bwd": [P, I64, P, I64, P, c_int, c_int, I64, P, I64, P, I64, P, I64, P, P, P],
     "rm_asp_supported": [c_int, c_int, P, c_int],
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
@@ -118,6 +121,7 @@ SIGNATURES_I64 = {
     "rm_autoint_stats_floats": [I64, c_int, c_int],
     "rm_autoint_layer_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_autoint_head_bwd_workspace": [I64, c_int],
+    "rm_cross_mix_bwd_workspace": [I64, c_int, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],

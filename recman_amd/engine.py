@@ -1317,13 +1317,109 @@ class DeepFMEngine(Engine):
                           mask_b=fm_masks[0], mask_e=fm_masks[1], d_bias=self.d_bias)
 
 
+class CrossMix:
+    """The DCN-Mix cross stack (DCN-V2, arXiv 2008.13535 eq. 4-5) with an explicit backward, on the variables
+    {prefix}cross_v [L,d,E r], cross_gate [L,d,E], cross_c [L,E,r,r], cross_u [L,d,E r], cross_b [L,d], cross_w_out
+    [d,1] of a params / grads pair: per layer a projection GEMM x_l -> [t | s] over a packed copy of V_l | G_l
+    (refreshed from the variables every forward, on the device), the fused core (csrc/cross_mix.hip) and the output
+    GEMM m U_l^T with the cross update in its epilogue (RM_DENSE_CROSS).  The GEMMs run on the f32 MFMA kernels, as
+    the matrix form's do.  Every buffer is sized once per batch size (alloc): no allocation inside a step."""
+
+    def __init__(self, params, grads, FD, Dn, L, E, r, device, prefix=""):
+        self.p, self.g, self.prefix = params, grads, prefix
+        self.FD, self.Dn, self.d, self.L, self.E, self.r, self.device = FD, Dn, FD + Dn, L, E, r, device
+        self._B = None
+
+    def alloc(self, B):
+        if self._B == B:
+            return
+        self._B = B
+        dev, L, d, E, r = self.device, self.L, self.d, self.E, self.r
+        W, N = E * r, E * r + E
+        dp, ldp = (d + 3) // 4 * 4, (N + 3) // 4 * 4
+        z = lambda cols: torch.zeros(B, cols, dtype=F32, device=dev)  # noqa: E731
+        self.logit = torch.empty(B, dtype=F32, device=dev)
+        # rows padded to a multiple of 4 floats (16-byte rows for the GEMM loaders); the pad columns stay zero
+        self.cx = [z(dp) for _ in range(L + 1)]   # x_0 .. x_L
+        self.cu = [z(dp) for _ in range(L)]       # u_l = m_l U_l^T + b_l
+        self.cts = [z(ldp) for _ in range(L)]     # [t_l | s_l] = x_l [V_l | G_l]: one projection buffer
+        self.cm = [z(W) for _ in range(L)]        # m_l
+        self.cg = [z(dp), z(dp)]                  # dLoss/dx_l, ping-pong
+        self.cdu, self.cdx0 = z(dp), z(dp)        # dLoss/du_l, dLoss/dx0
+        self.cdm, self.cdts = z(W), z(ldp)        # dLoss/dm_l, [dt_l | ds_l]
+        self.cvg = torch.zeros(L, d, N, dtype=F32, device=dev)   # [V_l | G_l]
+        self.cdvg = torch.zeros(d, N, dtype=F32, device=dev)     # its gradient, one layer at a time
+        self.cdut = torch.zeros(W, d, dtype=F32, device=dev)     # dU_l^T
+        self.w_out_p = torch.zeros(dp, dtype=F32, device=dev)
+        fw = max(ops.dense_filter_workspace(k, n) for k, n in ((d, N), (W, d), (d, W), (N, d)))
+        ww = max(ops.dense_wgrad_workspace(k, n, B) for k, n in ((W, d), (d, N), (d, 1)))
+        self._fws = torch.empty(fw, dtype=F32, device=dev)
+        self._wws = torch.empty(max(1, ww), dtype=F32, device=dev)
+        self._core_ws = torch.empty(max(1, ops.cross_mix_bwd_workspace(B, E, r)), dtype=F32, device=dev)
+
+    def _vars(self, d):
+        return {n: d[self.prefix + "cross_" + n] for n in ("v", "gate", "c", "u", "b", "w_out")}
+
+    def forward(self, xe, xd):
+        """x0 = [xe | xd] -> self.logit [B] (the cross logit)."""
+        p, d, W, N = self._vars(self.p), self.d, self.E * self.r, self.E * self.r + self.E
+        self.alloc(xe.shape[0])
+        x0 = self.cx[0]
+        x0[:, : self.FD].copy_(xe)
+        if self.Dn:
+            x0[:, self.FD: d].copy_(xd)
+        self.cvg[:, :, :W].copy_(p["v"])
+        self.cvg[:, :, W:].copy_(p["gate"])
+        for l in range(self.L):
+            ts = self.cts[l]
+            ops.dense_fwd(self.cx[l][:, :d], None, self.cvg[l], ts[:, :N], self._fws)
+            ops.cross_mix_fwd(ts[:, :W], ts[:, W:N], p["c"][l], self.cm[l])
+            ops.dense_fwd(self.cm[l], None, p["u"][l], self.cx[l + 1][:, :d], self._fws,
+                          transposed=True, bias=p["b"][l], epilogue=ops.DENSE_CROSS,
+                          aux1=x0[:, :d], aux2=self.cx[l][:, :d], out2=self.cu[l][:, :d])
+        self.w_out_p[:d].copy_(p["w_out"].view(-1))
+        ops.rowdot(self.cx[self.L], self.w_out_p, None, self.logit)
+        return self.logit
+
+    def backward(self, g):
+        """g [B] = dLoss/dlogit -> the six variables' gradients (overwritten) and self.cdx0[:, :d] = dLoss/dx0."""
+        p, gr, d, L, W, N = self._vars(self.p), self._vars(self.g), self.d, self.L, self.E * self.r, self.E * self.r + self.E
+        x0 = self.cx[0]
+        ops.dense_wgrad(self.cx[L][:, :d], None, g.view(-1, 1), gr["w_out"], self._wws)  # x_L^T g
+        gc, gn = self.cg
+        torch.mul(g.view(-1, 1), self.w_out_p.view(1, -1), out=gc)  # dLoss/dx_L
+        self.cdx0.zero_()
+        for l in range(L - 1, -1, -1):
+            ts, dts = self.cts[l], self.cdts
+            torch.mul(gc, x0, out=self.cdu)                 # dLoss/du_l = g_{l+1} o x0
+            self.cdx0.addcmul_(gc, self.cu[l])              # dLoss/dx0 += g_{l+1} o u_l
+            # dU_l^T = m_l^T du_l, and db_l = the column sums of du_l from the same pass
+            ops.dense_wgrad(self.cm[l], None, self.cdu[:, :d], self.cdut, self._wws, db=gr["b"][l])
+            gr["u"][l].copy_(self.cdut.t())
+            ops.dense_fwd(self.cdu[:, :d], None, p["u"][l], self.cdm, self._fws)  # dLoss/dm_l = du_l U_l
+            ops.cross_mix_bwd(ts[:, :W], ts[:, W:N], p["c"][l], self.cdm, dts[:, :W], dts[:, W:N], gr["c"][l],
+                              self._core_ws)
+            ops.dense_wgrad(self.cx[l][:, :d], None, dts[:, :N], self.cdvg, self._wws)  # x_l^T [dt | ds]
+            gr["v"][l].copy_(self.cdvg[:, :W])
+            gr["gate"][l].copy_(self.cdvg[:, W:])
+            # dLoss/dx_l = [dt | ds] [V_l | G_l]^T + g_{l+1}
+            ops.dense_fwd(dts[:, :N], None, self.cvg[l], gn[:, :d], self._fws, transposed=True,
+                          epilogue=ops.DENSE_ADD, aux1=gc[:, :d])
+            gc, gn = gn, gc
+        self.cdx0.add_(gc)
+
+
 class DCNEngine(Engine):
     """DCN._init_graph (DCN.py:99-144): dnn_input feeds the DNN and the CrossNet;
     final = dnn + cross (+ dnn again under strict_reference, DCN.py:140-142)
     (+ linear if use_linear).  CrossNet is absent from the reference (DCN.py:7):
     cross_type "vector" = DCN-v1, x_{l+1} = x0 (x_l . w_l) + b_l + x_l, all layers fused in
     csrc/cross.hip; cross_type "matrix" = x_{l+1} = x0 o (W_l x_l + b_l) + x_l, one f32-MFMA
-    GEMM per layer with the cross update as its epilogue (csrc/gemm.hip, RM_DENSE_CROSS)."""
+    GEMM per layer with the cross update as its epilogue (csrc/gemm.hip, RM_DENSE_CROSS);
+    cross_type "mix" = DCN-Mix (DCN-V2, arXiv 2008.13535 eq. 4-5), cross_experts low-rank experts of rank
+    cross_low_rank per layer under a per-layer softmax gate: x_{l+1} = x0 o (m U_l^T + b_l) + x_l with
+    m = [p_i tanh(tanh(x_l V_l,i) C_l,i)]_i, p = softmax(x_l G_l) - two skinny GEMMs per layer around the fused
+    core of csrc/cross_mix.hip."""
 
     model = "dcn"
     use_bias_tables = False
@@ -1337,18 +1433,36 @@ class DCNEngine(Engine):
         d = self.FD + self.Dn
         self.mlp = self._dnn(self.FD, self.Dn, hp["deep_hidden_units"], "relu")
         self.cross_type = hp.get("cross_type", "vector")
-        if self.cross_type not in ("vector", "matrix"):
-            raise ValueError(f"cross_type {self.cross_type!r}: 'vector' or 'matrix'")
+        if self.cross_type not in ("vector", "matrix", "mix"):
+            raise ValueError(f"cross_type {self.cross_type!r}: 'vector', 'matrix' or 'mix'")
         self.matrix = self.cross_type == "matrix"
+        self.mix = self.cross_type == "mix"
         # (absent from the reference: glorot-normal weights, zero biases)
-        self._var("cross_w", (self.L, d, d) if self.matrix else (self.L, d), ("glorot", d, d if self.matrix else 1),
-                  "cross_layer_l2_reg")
+        if self.mix:
+            E, r = int(hp.get("cross_experts", 4)), int(hp.get("cross_low_rank", 32))
+            if not ops.cross_mix_supported(E, r):
+                raise ValueError(f"cross_type 'mix': cross_experts={E}, cross_low_rank={r} is not supported "
+                                 "(1 <= cross_experts <= 8, cross_low_rank in 8, 16, 32, 64, their product <= 256)")
+            self.mix_E, self.mix_r = E, r
+            l2 = "cross_layer_l2_reg"
+            self._var("cross_v", (self.L, d, E * r), ("glorot", d, r), l2)
+            self._var("cross_gate", (self.L, d, E), ("glorot", d, E), l2)
+            self._var("cross_c", (self.L, E, r, r), ("glorot", r, r), l2)
+            self._var("cross_u", (self.L, d, E * r), ("glorot", r, d), l2)
+            self.cmix = CrossMix(self.params, self.grads, self.FD, self.Dn, self.L, E, r, self.device)
+        else:
+            self._var("cross_w", (self.L, d, d) if self.matrix else (self.L, d),
+                      ("glorot", d, d if self.matrix else 1), "cross_layer_l2_reg")
         self._var("cross_b", (self.L, d))
         self._var("cross_w_out", (d, 1), ("glorot", d, 1), "cross_layer_l2_reg")
 
     def _alloc_model(self, B):
         dev = self.device
         L = self.L
+        if self.mix:
+            self.dxe_dnn = torch.empty(B, self.FD, dtype=F32, device=dev)
+            self.cmix.alloc(B)
+            return
         self.cross_logit = torch.empty(B, dtype=F32, device=dev)
         self.cross_p = torch.empty(B, ops.cross_p_ld(L), dtype=F32, device=dev)  # x0.w_l, x0.w_out
         self.coef = torch.empty(B, 2 * L + 2, dtype=F32, device=dev)
@@ -1414,7 +1528,9 @@ class DCNEngine(Engine):
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
         self.dnn_logit = self.mlp.forward(xe, xd, self._dnn_keep(training), m.get("dnn"))
         p = self.params
-        if self.matrix:
+        if self.mix:
+            self.cross_logit = self.cmix.forward(xe, xd)
+        elif self.matrix:
             self._cross_matrix_fwd(xe, xd)
         else:
             ops.cross_fwd(xe, xd, p["cross_w"], p["cross_b"], p["cross_w_out"].view(-1),
@@ -1431,9 +1547,13 @@ class DCNEngine(Engine):
         L = self.L
         # the first dense layer's dW = x0^T dA0 and the cross net's P = x0^T coef read the same x0: one pass
         # (rm_dense_wgrad6 with a second piece of gradient columns) once both operands exist
-        fold = (not self.matrix and L + 1 <= 16 and self.mlp.can_defer_wgrad0()
+        fold = (not self.matrix and not self.mix and L + 1 <= 16 and self.mlp.can_defer_wgrad0()
                 and self.hp.get("dcn_fold_cross_wgrad", True))
         self.mlp.backward(g_dnn, self.dxe_dnn, defer_wgrad0=fold)
+        if self.mix:
+            self.cmix.backward(g)
+            torch.add(self.cmix.cdx0[:, : self.FD], self.dxe_dnn, out=self.d_rows.view(-1, self.FD))
+            return
         if self.matrix:
             self._cross_matrix_bwd(g)
             return
@@ -1483,7 +1603,7 @@ class DCNEngine(Engine):
                            symbol="dense_nn_kernel",
                            fn=lambda: ops.dense_fwd(xe, xd, W, m.a[0], m._fws, bias=b, act=m.act),
                            work=2.0 * B * K * N, bound="mfma")]
-        if not self.matrix:
+        if not self.matrix and not self.mix:
             probes.append(dict(
                 name=f"cross_fwd_kernel (rm_cross_fwd, {L} layers fused: x0 [{B},{d}] read once -> logit, p)",
                 symbol="cross_fwd_kernel",

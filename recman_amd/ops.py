@@ -364,6 +364,78 @@ def dot_interact_bwd(E, z, dX, d_rows, dz):
               _chk(dz, "dz", F32, (B, D)), _stream())
 
 
+# ---- the core of a DCN-Mix cross layer (csrc/cross_mix.hip) -----------------------------------------------------
+# the kernels' launch constants (csrc/cross_mix.hip: kTileFloats, kMaxG, kGE, kFwdBlocks, kBwdBlocks): a block owns
+# tiles of cross_mix_tile(E, r) examples and the grids are capped, so the forward walks the batch a second time from
+# B > CROSS_MIX_FWD_BLOCKS * tile on, the backward from B > CROSS_MIX_BWD_BLOCKS * tile on
+CROSS_MIX_FWD_BLOCKS, CROSS_MIX_BWD_BLOCKS = 2048, 512
+
+
+def cross_mix_tile(E, r):
+    """Examples per tile of the cross_mix kernels (mix_tile of csrc/cross_mix.hip)."""
+    return min(4096 // (E * r), 64) // 4 * 4
+
+
+def cross_mix_supported(E, r):
+    """rm_cross_mix_supported: 1 <= E <= 8, r in {8, 16, 32, 64}, E r <= 256."""
+    return bool(_lib.lib().rm_cross_mix_supported(int(E), int(r)))
+
+
+def _cross_mix_dims(C):
+    if C.dim() != 3 or C.shape[1] != C.shape[2]:
+        raise ValueError(f"C: expected [E,r,r], got {tuple(C.shape)}")
+    E, r = int(C.shape[0]), int(C.shape[1])
+    if not cross_mix_supported(E, r):
+        raise ValueError(f"cross_mix: E={E}, r={r} unsupported (1 <= E <= 8, r in 8, 16, 32, 64, E r <= 256)")
+    return E, r, _chk(C, "C", F32)
+
+
+def _cross_mix_rows(t, name, B, width):
+    """A [B, width] float32 device view with unit column stride and any row stride >= width -> (pointer, stride)."""
+    p, ld, cols = _rows2d(t, name)
+    if t.shape[0] != B or cols != width:
+        raise ValueError(f"{name} {tuple(t.shape)} must be [{B},{width}]")
+    if B > 1 and ld < width:
+        raise ValueError(f"{name}: row stride {ld} < {width} columns")
+    return p, max(ld, width)
+
+
+def cross_mix_fwd(T, S, C, M):
+    """rm_cross_mix_fwd: T [B, E r], S [B, E] (column views of any row stride, e.g. of one projection buffer),
+    C [E,r,r] -> M [B, E r]: a_i = tanh(t_i), c_i = tanh(a_i C_i), p = softmax(s), m_i = p_i c_i.  Only M's own
+    columns are written."""
+    E, r, pc = _cross_mix_dims(C)
+    B = T.shape[0]
+    pt, ldt = _cross_mix_rows(T, "T", B, E * r)
+    ps, lds = _cross_mix_rows(S, "S", B, E)
+    pm, ldm = _cross_mix_rows(M, "M", B, E * r)
+    _lib.call("rm_cross_mix_fwd", pt, ldt, ps, lds, pc, E, r, B, pm, ldm, _stream())
+
+
+def cross_mix_bwd_workspace(B, E, r):
+    """Floats of workspace for cross_mix_bwd (rm_cross_mix_bwd_workspace): the blocks' partial dC."""
+    n = int(_lib.lib().rm_cross_mix_bwd_workspace(int(B), int(E), int(r)))
+    if n < 0:
+        raise ValueError(f"cross_mix: B={B}, E={E}, r={r} unsupported")
+    return n
+
+
+def cross_mix_bwd(T, S, C, dM, dT, dS, dC, workspace):
+    """rm_cross_mix_bwd: dM [B, E r] = dLoss/dM -> dT [B, E r], dS [B, E] (column views of any row stride; only
+    their own columns are written) and dC [E,r,r] (overwritten).  a, c and p are recomputed.  Deterministic."""
+    E, r, pc = _cross_mix_dims(C)
+    B = T.shape[0]
+    pt, ldt = _cross_mix_rows(T, "T", B, E * r)
+    ps, lds = _cross_mix_rows(S, "S", B, E)
+    pdm, lddm = _cross_mix_rows(dM, "dM", B, E * r)
+    pdt, lddt = _cross_mix_rows(dT, "dT", B, E * r)
+    pds, ldds = _cross_mix_rows(dS, "dS", B, E)
+    if workspace.numel() < cross_mix_bwd_workspace(B, E, r):
+        raise ValueError("cross_mix_bwd: workspace too small (rm_cross_mix_bwd_workspace)")
+    _lib.call("rm_cross_mix_bwd", pt, ldt, ps, lds, pc, E, r, B, pdm, lddm, pdt, lddt, pds, ldds,
+              _chk(dC, "dC", F32, (E, r, r)), _chk(workspace, "workspace", F32), _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

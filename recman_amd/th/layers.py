@@ -734,6 +734,80 @@ class CrossNet:
                                     + self.variables[self.prefix + "cross_w_out"].square().sum())
 
 
+class _CrossMixFn(torch.autograd.Function):
+    """engine.CrossMix (rm_dense_fwd / rm_cross_mix_fwd / rm_cross_mix_bwd / rm_dense_wgrad), as the DCN engine runs
+    it under cross_type="mix"."""
+
+    @staticmethod
+    def forward(ctx, layer, xe, xd, v, gate, c, u, b, w_out):
+        names = ("cross_v", "cross_gate", "cross_c", "cross_u", "cross_b", "cross_w_out")
+        params = {n: t.detach().contiguous() for n, t in zip(names, (v, gate, c, u, b, w_out))}
+        grads = {n: torch.empty_like(t) for n, t in params.items()}
+        core = eng.CrossMix(params, grads, xe.shape[1], 0 if xd is None else xd.shape[1], layer.layer_num, layer.experts,
+                        layer.low_rank, xe.device)
+        logit = core.forward(xe.detach().contiguous(), None if xd is None else xd.detach().contiguous())
+        ctx.core, ctx.has_xd = core, xd is not None
+        return logit.clone().view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        core = ctx.core
+        core.backward(g.reshape(-1).contiguous())
+        dx0 = core.cdx0
+        d_xd = dx0[:, core.FD: core.d].clone() if ctx.has_xd else None
+        gr = core.g
+        return (None, dx0[:, : core.FD].clone(), d_xd, gr["cross_v"], gr["cross_gate"], gr["cross_c"], gr["cross_u"],
+                gr["cross_b"], gr["cross_w_out"])
+
+
+class CrossNetMix:
+    """CrossNet's low-rank mixture-of-experts form (DCN-Mix, DCN-V2 arXiv 2008.13535 eq. 4-5):
+    CrossNetMix(variables, layer_num, experts, low_rank, l2_reg)(x) -> logit [B,1], `.weights`, `.l2()`.  Per layer
+    t = x_l V_l, s = x_l G_l, m = [softmax(s)_i tanh(tanh(t_i) C_l,i)]_i, x_{l+1} = x0 o (m U_l^T + b_l) + x_l;
+    logit = x_L . w_out.  The gate G_l is per layer.  Variables: cross_v [L,d,E r] (glorot fans (d, r)), cross_gate
+    [L,d,E] (d, E), cross_c [L,E,r,r] (r, r), cross_u [L,d,E r] (r, d), cross_b [L,d] zeros, cross_w_out [d,1]."""
+
+    display_name = "CrossNetMix"
+    NAMES = ("cross_v", "cross_gate", "cross_c", "cross_u", "cross_b", "cross_w_out")
+
+    def __init__(self, variables, layer_num, experts, low_rank, l2_reg=0.0, prefix="", seed=2019):
+        if not ops.cross_mix_supported(experts, low_rank):
+            raise ValueError(f"CrossNetMix: experts={experts}, low_rank={low_rank} unsupported (1 <= experts <= 8, "
+                             "low_rank in 8, 16, 32, 64, their product <= 256)")
+        self.variables, self.layer_num, self.experts, self.low_rank = variables, int(layer_num), int(experts), int(low_rank)
+        self.l2_reg, self.prefix, self.seed = l2_reg, prefix, seed
+
+    def _upsert_variables(self, d):
+        L, E, r, pre = self.layer_num, self.experts, self.low_rank, self.prefix
+
+        def normal(shape, fan_in, fan_out):
+            std = math.sqrt(2.0 / (fan_in + fan_out))
+            g = torch.Generator(device=_device()).manual_seed(int(self.seed))
+            t = torch.empty(shape, device=_device(), dtype=F32)
+            torch.nn.init.trunc_normal_(t, 0.0, std, -2 * std, 2 * std, generator=g)
+            return t
+
+        made = {"cross_v": lambda: normal((L, d, E * r), d, r), "cross_gate": lambda: normal((L, d, E), d, E),
+                "cross_c": lambda: normal((L, E, r, r), r, r), "cross_u": lambda: normal((L, d, E * r), r, d),
+                "cross_b": lambda: torch.zeros(L, d), "cross_w_out": lambda: glorot_normal([d, 1], self.seed)}
+        for n in self.NAMES:
+            if pre + n not in self.variables:
+                self.variables[pre + n] = _leaf(made[n]())
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.NAMES]
+
+    def __call__(self, x):
+        x = _as_concat(x)
+        self._upsert_variables(x.shape[1])
+        return _CrossMixFn.apply(self, x.xe, x.xd, *self.weights)
+
+    def l2(self):
+        return sum(self.l2_reg * 0.5 * self.variables[self.prefix + n].square().sum()
+                   for n in self.NAMES if n != "cross_b")
+
+
 # ------------------------------------------------------------------------------------------------
 # AFM attention layer
 # ------------------------------------------------------------------------------------------------
@@ -980,6 +1054,6 @@ def create_loss(y, pred, task="classification"):
 
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
-           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "AFMLayer", "InteractingLayer",
+           "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "CrossNetMix", "AFMLayer", "InteractingLayer",
            "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
