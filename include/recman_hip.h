@@ -466,6 +466,51 @@ int rm_cross_mix_bwd(const float *T, int64_t ldt, const float *S, int64_t lds, c
                      float *dS, int64_t ldds, float *dC, float *workspace, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * FiBiNET's interaction (arXiv 1905.09433): a squeeze-excitation gate over the F embedding rows
+ * and a bilinear interaction over every field pair, on the raw and on the re-weighted rows,
+ * fused (csrc/fibinet.hip).  Nothing in the reference implements it.  Per example, E [F, D],
+ * P = F(F-1)/2, pairs p = (i, j), 0 <= i < j < F, i-major (itertools.combinations order):
+ *     z_f = (1/D) sum_d E[f,d];  s = relu(z W1);  a = relu(s W2);  V[f] = a_f E[f]    (no biases)
+ *     bilinear(Y, W)[p, d] = (sum_k Y[i,k] W_(i)[k,d]) Y[j,d]
+ *     X = [ bilinear(E, Wb) | bilinear(V, Wsb) ]           2 P D columns, pair-major, d fastest
+ *   type RM_FIBINET_ALL: W_(i) = W[0], Wb and Wsb [1, D, D];  RM_FIBINET_EACH: W_(i) = W[i] (the
+ *   LEFT field selects the matrix), Wb and Wsb [F-1, D, D].  W1 [F, R], W2 [R, F].  All contiguous.
+ *   E [B, F, D] contiguous, 16-byte aligned (rm_embed_fwd's E).  X [B, ldx], ldx >= 2 P D, rows
+ *   need no alignment; columns [2 P D, ldx) are left untouched.  The gate (z, s, a) and the left
+ *   products sum_k Y[i,k] W_(i)[k,d] are summed in ascending order in float64 and rounded to float
+ *   once (X keeps the D axis: a cancelling left product times a large row entry would otherwise
+ *   carry a relative error of 1e-5 and more); everything else is float32 fmaf chains.
+ * rm_fibinet_bwd, given dX [B, lddx] = dLoss/dX (columns >= 2 P D are never read), recomputes z,
+ *   s, a, V and the left products and writes dE [B, F, D] (overwritten, 16-byte aligned) and the
+ *   four parameter gradients dW1 [F,R], dW2 [R,F], dWb, dWsb (overwritten; all zero at B = 0),
+ *   relu'(0) = 0:
+ *     dU_i[d] = sum_{j>i} dX[p,d] Y[j,d];  dY_j[d] += sum_{i<j} dX[p,d] U_i[d];  dY_i += dU_i W_(i)^T
+ *     dW_(i) += Y_i^T dU_i;  dE = dY(E) + a o dV;  da_f = <dV_f, E_f>;  back through the relus, W2
+ *     and W1;  dE[f,d] += dz_f / D
+ *   workspace: rm_fibinet_bwd_workspace(B, F, D, R, type) floats (per-block partial gradients,
+ *   2 nW D D + 2 F R each over at most 512 blocks - fewer, down to 128, where that would pass
+ *   32 MB -, summed in block order by a finish kernel: no
+ *   atomics, two runs are bit-equal); 0 at B = 0, -1 for an unsupported shape.
+ * rm_fibinet_tile: the examples per tile of the forward (backward = 0) or backward kernel, -1 for
+ *   an unsupported shape; both grids are capped at 512 blocks and grid-stride the rest.
+ * Supported: D in {8,16,32}, 2 <= F <= 40, 1 <= R <= F, type ALL or EACH (rm_fibinet_supported);
+ *   anything else, a NULL pointer or a stride below 2 P D is RM_EINVAL before any launch.  B = 0
+ *   is RM_OK.  z, s, a, V and the left products never reach HBM: the forward moves
+ *   4 (F D + 2 P D) bytes per example, the backward reads 4 (F D + 2 P D) and writes 4 F D.
+ */
+#define RM_FIBINET_ALL 0
+#define RM_FIBINET_EACH 1
+int rm_fibinet_supported(int F, int D, int R, int type);
+int rm_fibinet_tile(int F, int D, int R, int type, int backward);
+int rm_fibinet_fwd(const float *E, const float *W1, const float *W2, const float *Wb, const float *Wsb,
+                   int64_t B, int F, int D, int R, int type, float *X, int64_t ldx, rm_stream_t stream);
+int64_t rm_fibinet_bwd_workspace(int64_t B, int F, int D, int R, int type);
+int rm_fibinet_bwd(const float *E, const float *W1, const float *W2, const float *Wb, const float *Wsb,
+                   const float *dX, int64_t lddx, int64_t B, int F, int D, int R, int type, float *dE,
+                   float *dW1, float *dW2, float *dWb, float *dWsb, float *workspace,
+                   rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

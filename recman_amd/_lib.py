@@ -74,6 +74,10 @@ SIGNATURES = {
     "rm_cross_mix_supported": [c_int, c_int],
     "rm_cross_mix_fwd": [P, I64, P, I64, P, c_int, c_int, I64, P, I64, P],
     "rm_cross_mix_bwd": [P, I64, P, I64, P, c_int, c_int, I64, P, I64, P, I64, P, I64, P, P, P],
+    "rm_fibinet_supported": [c_int, c_int, c_int, c_int],
+    "rm_fibinet_tile": [c_int, c_int, c_int, c_int, c_int],
+    "rm_fibinet_fwd": [P, P, P, P, P, I64, c_int, c_int, c_int, c_int, P, I64, P],
+    "rm_fibinet_bwd": [P, P, P, P, P, P, I64, I64, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
     "rm_asp_supported": [c_int, c_int, P, c_int],
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
@@ -122,6 +126,7 @@ SIGNATURES_I64 = {
     "rm_autoint_layer_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_autoint_head_bwd_workspace": [I64, c_int],
     "rm_cross_mix_bwd_workspace": [I64, c_int, c_int],
+    "rm_fibinet_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],

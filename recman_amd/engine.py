@@ -2163,5 +2163,98 @@ class DLRMEngine(Engine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+class FiBiNETEngine(Engine):
+    """FiBiNET (arXiv 1905.09433): a squeeze-excitation gate re-weights the F rows of E, a bilinear interaction runs
+    over every field pair of the raw and of the re-weighted rows, and the DNN reads both.  final = DNN([X | dense])
+    (+ linear if use_linear, the default).  Nothing in the reference implements it.
+        z_f = mean_d E[f,d];  s = relu(z senet_w1);  a = relu(s senet_w2);  V[f] = a_f E[f]
+        bilinear(Y, W)[(i,j), d] = (Y_i W_(i))[d] Y_j[d], i < j;  W_(i) = W[0] ("all") or W[i] ("each")
+        X = [bilinear(E, bilinear_w) | bilinear(V, senet_bilinear_w)]                    (csrc/fibinet.hip)
+    Variables (names chosen here): senet_w1 [F,R], senet_w2 [R,F], R = max(1, F // reduction_ratio), bilinear_w and
+    senet_bilinear_w [1 | F-1, D, D] - glorot, l2 key interaction_l2_reg.  No bias tables.  X and dX are [B, 2PD]
+    buffers: 2PD = F(F-1)D is a multiple of 8, so their rows need no pad."""
+
+    model = "fibinet"
+    use_bias_tables = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", True))
+        limits = "2..40 embedding features, embedding_size 8/16/32, bilinear_type 'all' or 'each'"
+        self.btype = hp.get("bilinear_type", "each")
+        if self.btype == "interaction":
+            raise ValueError("FiBiNET: bilinear_type='interaction' (one matrix per field pair) is out of scope: "
+                             f"use 'all' or 'each' ({limits})")
+        if self.btype not in ops.FIBINET_TYPES:
+            raise ValueError(f"FiBiNET: bilinear_type {self.btype!r} is not supported ({limits})")
+        ratio = int(hp.get("reduction_ratio", 3))
+        if ratio < 1:
+            raise ValueError(f"FiBiNET: reduction_ratio={ratio} must be at least 1")
+        F, D = self.F, self.D
+        self.R = R = max(1, F // ratio)
+        if not ops.fibinet_supported(F, D, R, self.btype):
+            raise ValueError(f"FiBiNET: {F} embedding features of embedding_size={D} are not supported by "
+                             f"rm_fibinet_fwd ({limits})")
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        if not hidden:
+            raise ValueError("FiBiNET: deep_hidden_units must name at least one layer of the DNN")
+        nW = F - 1 if self.btype == "each" else 1
+        l2 = "interaction_l2_reg"
+        self._var("senet_w1", (F, R), ("glorot", F, R), l2)
+        self._var("senet_w2", (R, F), ("glorot", R, F), l2)
+        self._var("bilinear_w", (nW, D, D), ("glorot", D, D), l2)
+        self._var("senet_bilinear_w", (nW, D, D), ("glorot", D, D), l2)
+        self.W, self.ldx = ops.fibinet_width(F, D)
+        # (the DNN reads the interaction's output, not [E | dense]; its dX is no table-row gradient)
+        self.mlp = self._dnn(self.W, self.Dn, hidden, "relu", stream_d_rows=False)
+
+    def _alloc_model(self, B):
+        dev = self.device
+        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.fib_ws = torch.empty(max(4, ops.fibinet_bwd_workspace(B, self.F, self.D, self.R, self.btype)),
+                                  dtype=F32, device=dev)
+
+    def _fib_vars(self, d):
+        return d["senet_w1"], d["senet_w2"], d["bilinear_w"], d["senet_bilinear_w"]
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        X = self.X[:, : self.W]
+        ops.fibinet_fwd(self.E, *self._fib_vars(self.params), self.btype, X)
+        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
+        self.dnn_logit = self._mlp_last(self.mlp, X, dense if self.Dn else None, self._dnn_keep(training),
+                                        m.get("dnn"), list(branches))
+        branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        dX = self.dX[:, : self.W]
+        self.mlp.backward(g, dX)
+        # no other branch reads E: d_rows IS dLoss/dE
+        ops.fibinet_bwd(self.E, *self._fib_vars(self.params), self.btype, dX, self.d_rows,
+                        *self._fib_vars(self.grads), self.fib_ws)
+
+    def roofline_probes(self, idx, dense, y):
+        self._probe_fill(idx, dense, y)  # E, dX
+        B, F, D, ldx = idx.shape[0], self.F, self.D, self.ldx
+        X, dX = self.X[:, : self.W], self.dX[:, : self.W]
+        d_rows = torch.empty_like(self.d_rows)
+        dws = [torch.empty_like(t) for t in self._fib_vars(self.grads)]
+        shape = f"F={F} D={D} R={self.R} {self.btype} ldx={ldx}"
+        return [
+            dict(name=f"fibinet_bwd_kernel (rm_fibinet_bwd, {shape}: E and dX read once from HBM, d_rows written once)",
+                 symbol="fibinet_bwd_kernel",
+                 fn=lambda: ops.fibinet_bwd(self.E, *self._fib_vars(self.params), self.btype, dX, d_rows, *dws,
+                                            self.fib_ws),
+                 work=B * 4 * (2 * F * D + ldx), bound="hbm"),
+            dict(name=f"fibinet_fwd_kernel (rm_fibinet_fwd, {shape}: E read once, X written once)",
+                 symbol="fibinet_fwd_kernel",
+                 fn=lambda: ops.fibinet_fwd(self.E, *self._fib_vars(self.params), self.btype, X),
+                 work=B * 4 * (F * D + ldx), bound="hbm"),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
-           "autoint": AutoIntEngine, "dlrm": DLRMEngine}
+           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine}

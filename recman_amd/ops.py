@@ -436,6 +436,94 @@ def cross_mix_bwd(T, S, C, dM, dT, dS, dC, workspace):
               _chk(dC, "dC", F32, (E, r, r)), _chk(workspace, "workspace", F32), _stream())
 
 
+# ---- FiBiNET's interaction: SENET gate + bilinear pairs (csrc/fibinet.hip) ---------------------------------------
+# the kernels' grid caps (csrc/fibinet.hip: kFwdBlocks, kBwdBlocks): a block owns tiles of fibinet_tile(...) examples,
+# so the forward walks the batch a second time from B > FIBINET_FWD_BLOCKS * tile on, the backward likewise (the
+# backward's cap is lower, down to 128 blocks, where 512 sets of partial gradients would pass 32 MB of workspace)
+FIBINET_FWD_BLOCKS, FIBINET_BWD_BLOCKS = 512, 512
+FIBINET_TYPES = {"all": 0, "each": 1}  # RM_FIBINET_ALL / RM_FIBINET_EACH
+_FIBINET_LIMITS = "2 <= F <= 40, D in 8, 16, 32, 1 <= R <= F, type 'all' or 'each'"
+
+
+def _fibinet_type(bilinear_type):
+    if bilinear_type not in FIBINET_TYPES:
+        raise ValueError(f"fibinet: bilinear_type {bilinear_type!r} unsupported ({_FIBINET_LIMITS})")
+    return FIBINET_TYPES[bilinear_type]
+
+
+def fibinet_supported(F, D, R, bilinear_type):
+    """rm_fibinet_supported: D in {8, 16, 32}, 2 <= F <= 40, 1 <= R <= F, type "all" or "each"."""
+    if bilinear_type not in FIBINET_TYPES:
+        return False
+    return bool(_lib.lib().rm_fibinet_supported(int(F), int(D), int(R), FIBINET_TYPES[bilinear_type]))
+
+
+def fibinet_width(F, D):
+    """(2 P D, ldx): the columns FiBiNET's interaction writes (both bilinear branches over the P = F(F-1)/2 pairs) and
+    that width rounded up to a multiple of 4 floats (16-byte rows for the dense kernels that read X)."""
+    W = F * (F - 1) * D
+    return W, (W + 3) // 4 * 4
+
+
+def fibinet_tile(F, D, R, bilinear_type, backward=False):
+    """Examples per tile of the forward or the backward kernel (rm_fibinet_tile: what the LDS budget leaves)."""
+    g = int(_lib.lib().rm_fibinet_tile(int(F), int(D), int(R), _fibinet_type(bilinear_type), int(bool(backward))))
+    if g < 0:
+        raise ValueError(f"fibinet: F={F}, D={D}, R={R} unsupported ({_FIBINET_LIMITS})")
+    return g
+
+
+def _fibinet_args(E, W1, W2, Wb, Wsb, bilinear_type, X, name):
+    """-> (B, F, D, R, type, the five input pointers, X's pointer and row stride)."""
+    if E.dim() != 3:
+        raise ValueError(f"E: expected [B,F,D], got {tuple(E.shape)}")
+    if W1.dim() != 2:
+        raise ValueError(f"W1: expected [F,R], got {tuple(W1.shape)}")
+    B, F, D = (int(v) for v in E.shape)
+    R = int(W1.shape[1])
+    typ = _fibinet_type(bilinear_type)
+    if not fibinet_supported(F, D, R, bilinear_type):
+        raise ValueError(f"fibinet: F={F}, D={D}, R={R} unsupported ({_FIBINET_LIMITS})")
+    nW = F - 1 if typ else 1
+    W, _ = fibinet_width(F, D)
+    px, ldx, cols = _rows2d(X, name)
+    if X.shape[0] != B or cols < W:
+        raise ValueError(f"{name} {tuple(X.shape)} must be [{B}, >= {W}]")
+    if B > 1 and ldx < cols:
+        raise ValueError(f"{name}: row stride {ldx} < {cols} columns")
+    ptrs = (_chk(E, "E", F32), _chk(W1, "W1", F32, (F, R)), _chk(W2, "W2", F32, (R, F)),
+            _chk(Wb, "Wb", F32, (nW, D, D)), _chk(Wsb, "Wsb", F32, (nW, D, D)))
+    return B, F, D, R, typ, ptrs, px, max(ldx, cols)
+
+
+def fibinet_fwd(E, W1, W2, Wb, Wsb, bilinear_type, X):
+    """rm_fibinet_fwd: E [B,F,D], senet_w1 [F,R], senet_w2 [R,F], bilinear_w and senet_bilinear_w [1 | F-1, D, D] ->
+    X [B, >= 2PD] (any row stride): [bilinear(E, Wb) | bilinear(a o E, Wsb)], a = relu(relu(mean_d(E) W1) W2); only
+    the first 2PD columns of a row are written."""
+    B, F, D, R, typ, ptrs, px, ldx = _fibinet_args(E, W1, W2, Wb, Wsb, bilinear_type, X, "X")
+    _lib.call("rm_fibinet_fwd", *ptrs, B, F, D, R, typ, px, ldx, _stream())
+
+
+def fibinet_bwd_workspace(B, F, D, R, bilinear_type):
+    """Floats of workspace for fibinet_bwd (rm_fibinet_bwd_workspace): the blocks' partial parameter gradients."""
+    n = int(_lib.lib().rm_fibinet_bwd_workspace(int(B), int(F), int(D), int(R), _fibinet_type(bilinear_type)))
+    if n < 0:
+        raise ValueError(f"fibinet: B={B}, F={F}, D={D}, R={R} unsupported ({_FIBINET_LIMITS})")
+    return n
+
+
+def fibinet_bwd(E, W1, W2, Wb, Wsb, bilinear_type, dX, dE, dW1, dW2, dWb, dWsb, workspace):
+    """rm_fibinet_bwd: dX [B, >= 2PD] (any row stride; columns >= 2PD are never read) -> dE [B,F,D] and the gradients
+    of the four weight arrays, all overwritten.  The gate and the left products are recomputed.  Deterministic."""
+    B, F, D, R, typ, ptrs, px, ldx = _fibinet_args(E, W1, W2, Wb, Wsb, bilinear_type, dX, "dX")
+    if workspace.numel() < fibinet_bwd_workspace(B, F, D, R, bilinear_type):
+        raise ValueError("fibinet_bwd: workspace too small (rm_fibinet_bwd_workspace)")
+    _lib.call("rm_fibinet_bwd", *ptrs, px, ldx, B, F, D, R, typ, _chk(dE, "dE", F32, (B, F, D)),
+              _chk(dW1, "dW1", F32, tuple(W1.shape)), _chk(dW2, "dW2", F32, tuple(W2.shape)),
+              _chk(dWb, "dWb", F32, tuple(Wb.shape)), _chk(dWsb, "dWsb", F32, tuple(Wsb.shape)),
+              _chk(workspace, "workspace", F32), _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

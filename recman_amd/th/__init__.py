@@ -8,6 +8,7 @@ from .BestModelFinder import BestModelFinder
 from .DCN import DCN
 from .DLRM import DLRM
 from .DeepFM import DeepFM
+from .FiBiNET import FiBiNET
 from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
@@ -16,6 +17,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]

@@ -1002,6 +1002,87 @@ class DotInteraction:
 
 
 # ------------------------------------------------------------------------------------------------
+# FiBiNET interaction: SENET gate + bilinear pairs
+# ------------------------------------------------------------------------------------------------
+class _FiBiNETFn(torch.autograd.Function):
+    """rm_fibinet_fwd / rm_fibinet_bwd (csrc/fibinet.hip), as the FiBiNET engine runs them."""
+
+    @staticmethod
+    def forward(ctx, btype, E, w1, w2, wb, wsb):
+        ts = [t.detach().contiguous() for t in (E, w1, w2, wb, wsb)]
+        B, F, D = ts[0].shape
+        X = torch.empty(B, ops.fibinet_width(F, D)[0], device=E.device, dtype=F32)
+        ops.fibinet_fwd(*ts, btype, X)
+        ctx.save_for_backward(*ts)
+        ctx.btype = btype
+        return X
+
+    @staticmethod
+    def backward(ctx, dX):
+        ts = ctx.saved_tensors
+        B, F, D = ts[0].shape
+        grads = [torch.empty_like(t) for t in ts]
+        ws = torch.empty(max(4, ops.fibinet_bwd_workspace(B, F, D, ts[1].shape[1], ctx.btype)), device=dX.device,
+                         dtype=F32)
+        ops.fibinet_bwd(*ts, ctx.btype, dX.contiguous(), *grads, ws)
+        return (None, *grads)
+
+
+class FiBiNETInteraction:
+    """FiBiNET's interaction layer (arXiv 1905.09433; nothing in the reference implements it):
+    FiBiNETInteraction(variables, bilinear_type, reduction_ratio, l2_reg)(feat_embeds [B,F,D]) -> [B, 2 P D] =
+    [bilinear(E) | bilinear(a o E)], P = F(F-1)/2 pairs i < j in itertools.combinations order, d fastest:
+    a = relu(relu(mean_d(E) senet_w1) senet_w2), bilinear(Y)[(i,j)] = (Y_i W_(i)) o Y_j with W_(i) = W[0] ("all") or
+    W[i] ("each").  Variables: senet_w1 [F,R], senet_w2 [R,F], R = max(1, F // reduction_ratio), bilinear_w and
+    senet_bilinear_w [1 | F-1, D, D], all glorot; `.weights`, `.l2()`."""
+
+    display_name = "FiBiNETInteraction"
+    NAMES = ("senet_w1", "senet_w2", "bilinear_w", "senet_bilinear_w")
+
+    def __init__(self, variables, bilinear_type="each", reduction_ratio=3, l2_reg=0.0, prefix="", seed=2019):
+        if bilinear_type not in ops.FIBINET_TYPES:
+            raise ValueError(f"FiBiNETInteraction: bilinear_type {bilinear_type!r} unsupported ('all' or 'each'; "
+                             "'interaction', one matrix per pair, is out of scope)")
+        if int(reduction_ratio) < 1:
+            raise ValueError(f"FiBiNETInteraction: reduction_ratio={reduction_ratio} must be at least 1")
+        self.variables, self.bilinear_type, self.reduction_ratio = variables, bilinear_type, int(reduction_ratio)
+        self.l2_reg, self.prefix, self.seed = l2_reg, prefix, seed
+
+    def _upsert_variables(self, F, D):
+        R = max(1, F // self.reduction_ratio)
+        nW = F - 1 if self.bilinear_type == "each" else 1
+        g = torch.Generator(device=_device()).manual_seed(int(self.seed))  # one stream for the four variables
+
+        def normal(shape, fan_in, fan_out):
+            std = math.sqrt(2.0 / (fan_in + fan_out))
+            t = torch.empty(shape, device=_device(), dtype=F32)
+            torch.nn.init.trunc_normal_(t, 0.0, std, -2 * std, 2 * std, generator=g)
+            return t
+
+        made = {"senet_w1": lambda: normal((F, R), F, R), "senet_w2": lambda: normal((R, F), R, F),
+                "bilinear_w": lambda: normal((nW, D, D), D, D), "senet_bilinear_w": lambda: normal((nW, D, D), D, D)}
+        for n in self.NAMES:
+            if self.prefix + n not in self.variables:
+                self.variables[self.prefix + n] = _leaf(made[n]())
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.NAMES]
+
+    def __call__(self, feat_embeds):
+        if feat_embeds.dim() != 3:
+            raise ValueError(f"FiBiNETInteraction: feat_embeds [B,F,D] expected, got {tuple(feat_embeds.shape)}")
+        _, F, D = feat_embeds.shape
+        if not ops.fibinet_supported(F, D, max(1, F // self.reduction_ratio), self.bilinear_type):
+            raise ValueError(f"FiBiNETInteraction: F={F}, D={D} unsupported (2..40 fields, D in 8/16/32)")
+        self._upsert_variables(F, D)
+        return _FiBiNETFn.apply(self.bilinear_type, feat_embeds, *self.weights)
+
+    def l2(self):
+        return sum(self.l2_reg * 0.5 * self.variables[self.prefix + n].square().sum() for n in self.NAMES)
+
+
+# ------------------------------------------------------------------------------------------------
 # prediction + loss
 # ------------------------------------------------------------------------------------------------
 class _SigmoidFn(torch.autograd.Function):
