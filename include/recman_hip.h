@@ -189,7 +189,9 @@ typedef struct rm_mlp_tail {
   float coef_a;
   const float *logit_b;
   float coef_b;
-  float coef_mlp;       /* coefficient of this MLP's logit in the sum */
+  float coef_mlp;       /* coefficient of this MLP's logit in the sum: MUST be 1 - the dh chain and rm_mlp_bwd's
+                           d_w_out / d_w0_out take dlogit as dLoss/d(this MLP's logit); anything else is refused
+                           (scale the MLP's branch with rm_logit_loss and the plain calls instead) */
   const int64_t *y;     /* labels: int64 (classification) ... */
   const float *y_f;     /* ... or float (regression); exactly one of them */
   int task;             /* 0 = classification (sigmoid + binary cross-entropy), 1 = regression (MSE) */

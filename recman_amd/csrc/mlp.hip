@@ -1508,6 +1508,8 @@ static int mlp_tail_check(const char *fn, const rm_mlp_tail *t, int NL) {
   RM_REQUIRE(t->dlogit && t->loss_partial, "%s: tail needs dlogit and loss_partial", fn);
   RM_REQUIRE((t->y != nullptr) != (t->y_f != nullptr), "%s: tail needs exactly one of y / y_f", fn);
   RM_REQUIRE(t->task == 0 || t->task == 1, "%s: tail task must be 0 or 1", fn);
+  // the dh chain and rm_mlp_bwd's output-projection gradients take dlogit as dLoss/d(this MLP's logit)
+  RM_REQUIRE(t->coef_mlp == 1.0f, "%s: tail coef_mlp must be 1 (got %g)", fn, (double)t->coef_mlp);
   for (int l = 0; l < NL; ++l) RM_REQUIRE(t->dh[l], "%s: tail needs dh[%d]", fn, l);
   return RM_OK;
 }

@@ -717,12 +717,15 @@ def mlp_bwd_workspace(FD, Dn):
 def mlp_tail(B, branches, coef_mlp, *, y=None, y_f=None, task="classification", grad_scale=1.0,
              logit=None, pred=None, dlogit, loss_partial, loss=None, dh):
     """Builds the rm_mlp_tail struct of the fused training head (see include/recman_hip.h):
-    branches = up to two (tensor [B], coefficient) pairs summed BEFORE the MLP's own logit.
+    branches = up to two (tensor [B], coefficient) pairs summed BEFORE the MLP's own logit; coef_mlp must be 1
+    (dlogit then is the MLP's own output gradient, which the dh chain and mlp_bwd take it for).
     Returns the struct; pass it to mlp_fwd and then to mlp_bwd (the tensors must stay alive)."""
     if len(branches) > 2:
         raise ValueError("mlp_tail takes at most two other branch logits")
     if (y is None) == (y_f is None):
         raise ValueError("mlp_tail needs exactly one of y / y_f")
+    if float(coef_mlp) != 1.0:
+        raise ValueError("mlp_tail: coef_mlp must be 1 (dlogit is the MLP's own output gradient: see rm_mlp_tail)")
     if loss_partial.numel() < (B + 31) // 32:
         raise ValueError("mlp_tail: loss_partial needs ceil(B/32) floats")
     t = _lib.MlpTail()
