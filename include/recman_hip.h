@@ -513,6 +513,55 @@ int rm_fibinet_bwd(const float *E, const float *W1, const float *W2, const float
                    rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Field-pair weighted FM: FwFM (arXiv 1806.03514), FvFM and FmFM (arXiv 2102.12994), fused
+ * (csrc/fmfm.hip).  Nothing in the reference implements them.  Per example, E [F, D],
+ * P = F(F-1)/2, pairs p = (i, j), 0 <= i < j < F, i-major (itertools.combinations order):
+ *     logit = sum_p E_i W_(p) E_j^T
+ *   type RM_FMFM_MATRIX: W_(p) = W[p], W [P, D, D] (the LEFT field i on the rows);
+ *   RM_FMFM_VECTOR: W_(p) = diag(W[p]), W [P, D];  RM_FMFM_SCALAR: W_(p) = W[p] I, W [P].
+ *   E [B, F, D] contiguous, 16-byte aligned (rm_embed_fwd's E); W contiguous; logit [B] is
+ *   overwritten.  The matrix type runs on the exact-f32 MFMA (fmaf chains of length D inside a
+ *   pair; pair sums are added in per-lane chains of at most P / 8 and reduced by a tree), the other
+ *   two on the vector ALU (chains of at most F - 1 inside, F - 1 outside): no chain over all
+ *   P D D products exists.
+ * rm_fmfm_bwd, given g [B] = dLoss/dlogit:
+ *     dE_i += g W_(p) E_j;  dE_j += g W_(p)^T E_i;  dW[p] = sum_b g_b E_i (x) E_j  (its diagonal for
+ *     VECTOR, its trace for SCALAR)
+ *   d_rows [B, F, D] = dE_up + dE when dE_up is given (it may be d_rows itself), dE otherwise -
+ *   written once; dW (the shape of W) is overwritten.
+ *   workspace: rm_fmfm_bwd_workspace(B, F, D, type) floats: the partial dW of at most 64 batch
+ *   slices (MATRIX; 512 for VECTOR and SCALAR; fewer where that many sets would pass 32 MB),
+ *   summed in slice order by a finish kernel: no atomics, two runs are bit-equal; 0 at B = 0,
+ *   -1 for an unsupported shape.
+ * rm_fmfm_tile(F, D, type, which): the examples per tile of the forward / dE / dW kernel
+ *   (RM_FMFM_TILE_*) and the cap of the forward's and dE's grids and of the dW kernels' batch
+ *   slices (RM_FMFM_CAP_*): beyond cap x tile examples a block walks the batch with a grid stride.
+ *   -1 for an unsupported shape or `which`.
+ * Supported: D in {8,16,32}, 2 <= F <= 40, type MATRIX, VECTOR or SCALAR (rm_fmfm_supported);
+ *   anything else or a NULL pointer is RM_EINVAL before any launch.  B = 0 is RM_OK and touches
+ *   nothing.  Nothing of size P leaves the chip: the forward reads 4 F D bytes per example and
+ *   writes 4; the backward reads E twice (dE kernel, dW kernel: the matrix dW kernel once per
+ *   chunk of 64 pairs - 16 at D = 32 -, from L2 after the first) and writes d_rows once.
+ */
+#define RM_FMFM_MATRIX 0
+#define RM_FMFM_VECTOR 1
+#define RM_FMFM_SCALAR 2
+#define RM_FMFM_TILE_FWD 0
+#define RM_FMFM_TILE_DE 1
+#define RM_FMFM_TILE_DW 2
+#define RM_FMFM_CAP_FWD 3
+#define RM_FMFM_CAP_DE 4
+#define RM_FMFM_CAP_DW 5
+int rm_fmfm_supported(int F, int D, int type);
+int rm_fmfm_tile(int F, int D, int type, int which);
+int rm_fmfm_fwd(const float *E, const float *W, int type, int64_t B, int F, int D, float *logit,
+                rm_stream_t stream);
+int64_t rm_fmfm_bwd_workspace(int64_t B, int F, int D, int type);
+int rm_fmfm_bwd(const float *E, const float *W, int type, const float *g, const float *dE_up,
+                int64_t B, int F, int D, float *d_rows, float *dW, float *workspace,
+                rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

@@ -384,7 +384,8 @@ def init_reference(engine, seed=2019):
     tables, DNN and CIN weights truncated-normal glorot (utils.py:180-183; layers.py:99-101,536,551,567,666), cin_w
     glorot-uniform (layers.py:690), biases zeros (layers.py:109,321,327,544,561,574,676,695); the layers absent from
     the reference (cross net, attention units, interacting layers, DLRM's towers) glorot weights like dnn_w and zero
-    biases.  A variable without a declared rule is a KeyError."""
+    biases; the field-pair weights of FmFM / FvFM / FwFM ("pair_identity") identity matrices or ones.  A variable
+    without a declared rule is a KeyError."""
     import math
 
     g = torch.Generator(device=engine.device).manual_seed(int(seed))
@@ -394,6 +395,14 @@ def init_reference(engine, seed=2019):
         init = engine.decl[name][0]
         if init == "zeros":
             t.zero_()
+            continue
+        if init == "pair_identity":
+            # the field-pair weights start the model at plain FM: identity matrices [P,D,D], all-ones vectors [P,D]
+            # and scalars [P]
+            if t.dim() == 3:
+                t.copy_(torch.eye(t.shape[1], dtype=t.dtype, device=t.device).expand_as(t))
+            else:
+                t.fill_(1.0)
             continue
         kind, fan_in, fan_out = init
         if kind == "glorot":
@@ -2256,5 +2265,87 @@ class FiBiNETEngine(Engine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+class FmFMEngine(DeepFMEngine):
+    """Field-pair weighted FM - FwFM (arXiv 1806.03514), FvFM and FmFM (arXiv 2102.12994): final = linear (use_linear,
+    the default) + pair (+ DNN([E | dense]) with a non-empty deep_hidden_units: DeepFwFM and its kin),
+    PredictionLayer(use_bias=False).  Nothing in the reference implements them.  Over the P = F(F-1)/2 field pairs
+    i < j in itertools.combinations order, forward and backward fused in csrc/fmfm.hip:
+        pair_logit = sum_{i<j} E_i W_(ij) E_j^T
+        field_interaction "matrix": W_(ij) = field_pair_w[p] [P,D,D] (the left field on the rows);  "vector":
+        diag(field_pair_w[p]) [P,D];  "scalar": field_pair_w[p] I [P]
+    field_pair_w starts at plain FM (identity matrices / ones); l2 key interaction_l2_reg.  No bias tables; the dense
+    features enter the linear term and the DNN only.  The pair kernels need E in HBM: the one-kernel step is never
+    selected (no FM term) and the DNN runs behind them so that its fused head sees the pair logit."""
+
+    model = "fmfm"
+    use_bias_tables = False
+    shardable = False
+    needs_fm_or_deep = False
+    _model_masks = Engine._model_masks  # (no FM term: no fm_dropout masks)
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        n = len(hidden)
+        keep = hp.get("deep_dropout")
+        hp = dict(hp, use_fm=False, use_deep=n > 0, deep_hidden_units=hidden,
+                  deep_dropout=tuple(keep) if keep is not None else (1,) * (n + 1))
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", True))
+        self.ftype = hp.get("field_interaction", "matrix")
+        if self.ftype not in ops.FMFM_TYPES:
+            raise ValueError(f"FmFM: field_interaction {self.ftype!r} is not one of 'matrix', 'vector', 'scalar'")
+        if not ops.fmfm_supported(self.F, self.D, self.ftype):
+            raise ValueError(f"FmFM: {self.F} embedding features of embedding_size={self.D} are not supported by "
+                             "rm_fmfm_fwd (2..40 embedding features, embedding_size 8/16/32)")
+        self.P = self.F * (self.F - 1) // 2
+        self._var("field_pair_w", ops.fmfm_weight_shape(self.F, self.D, self.ftype), "pair_identity",
+                  "interaction_l2_reg")
+
+    def _alloc_model(self, B):
+        dev = self.device
+        self.pair_logit = torch.empty(B, dtype=F32, device=dev)
+        self.pair_ws = torch.empty(max(4, ops.fmfm_bwd_workspace(B, self.F, self.D, self.ftype)), dtype=F32,
+                                   device=dev)
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        ops.fmfm_fwd(self.E, self.params["field_pair_w"], self.ftype, self.pair_logit)
+        branches = ([(self.lin_logit, 1.0)] if self.use_linear else []) + [(self.pair_logit, 1.0)]
+        if self.use_deep:
+            self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
+                                            self._dnn_keep(training), m.get("dnn"), list(branches))
+            branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        super()._branches_bwd(idx, dense, g, masks)  # the DNN (when there is one) writes d_rows
+        ops.fmfm_bwd(self.E, self.params["field_pair_w"], self.ftype, g, self.d_rows, self.grads["field_pair_w"],
+                     self.pair_ws, dE_up=self.d_rows if self.use_deep else None)
+
+    def roofline_probes(self, idx, dense, y):
+        B, F, D, P = idx.shape[0], self.F, self.D, self.P
+        self._probe_fill(idx, dense, y)  # E, dlogit
+        w, dw = self.params["field_pair_w"], torch.empty_like(self.grads["field_pair_w"])
+        d_rows = torch.empty_like(self.d_rows)
+        shape = f"F={F} D={D} {self.ftype}"
+        if self.ftype == "matrix":
+            fwd, bwd, bound = 2.0 * B * P * D * D, 6.0 * B * P * D * D, "mfma"
+            names = ("fmfm_de_kernel", "fmfm_fwd_kernel")
+            what = "flops = 2 B P D^2 forward, three times that backward (dE both ways + dM)"
+        else:
+            # algorithmic bytes: E read once and the logit written; E and g read once, d_rows written once (+ W, dW)
+            fwd, bwd, bound = 4.0 * (B * F * D + B + w.numel()), 4.0 * (2 * B * F * D + B + 2 * w.numel()), "hbm"
+            names = ("fmfm_vs_de_kernel", "fmfm_vs_fwd_kernel")
+            what = "algorithmic bytes: E (+ g) in, logit / d_rows out, the weights and their gradient"
+        return [
+            dict(name=f"{names[0]} + dW kernels (rm_fmfm_bwd, {shape}; {what})", symbol=names[0],
+                 fn=lambda: ops.fmfm_bwd(self.E, w, self.ftype, self.dlogit, d_rows, dw, self.pair_ws),
+                 work=bwd, bound=bound),
+            dict(name=f"{names[1]} (rm_fmfm_fwd, {shape}; {what})", symbol=names[1],
+                 fn=lambda: ops.fmfm_fwd(self.E, w, self.ftype, self.pair_logit), work=fwd, bound=bound),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
-           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine}
+           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine}

@@ -524,6 +524,76 @@ def fibinet_bwd(E, W1, W2, Wb, Wsb, bilinear_type, dX, dE, dW1, dW2, dWb, dWsb, 
               _chk(workspace, "workspace", F32), _stream())
 
 
+# ---- field-pair weighted FM: FmFM / FvFM / FwFM (csrc/fmfm.hip) ----------------------------------------------------
+FMFM_TYPES = {"matrix": 0, "vector": 1, "scalar": 2}  # RM_FMFM_MATRIX / RM_FMFM_VECTOR / RM_FMFM_SCALAR
+FMFM_TILE = {"fwd": 0, "de": 1, "dw": 2, "fwd_cap": 3, "de_cap": 4, "dw_cap": 5}  # RM_FMFM_TILE_* / RM_FMFM_CAP_*
+_FMFM_LIMITS = "2 <= F <= 40, D in 8, 16, 32, type 'matrix', 'vector' or 'scalar'"
+
+
+def _fmfm_type(field_interaction):
+    if field_interaction not in FMFM_TYPES:
+        raise ValueError(f"fmfm: field_interaction {field_interaction!r} unsupported ({_FMFM_LIMITS})")
+    return FMFM_TYPES[field_interaction]
+
+
+def fmfm_supported(F, D, field_interaction):
+    """rm_fmfm_supported: D in {8, 16, 32}, 2 <= F <= 40, type "matrix", "vector" or "scalar"."""
+    if field_interaction not in FMFM_TYPES:
+        return False
+    return bool(_lib.lib().rm_fmfm_supported(int(F), int(D), FMFM_TYPES[field_interaction]))
+
+
+def fmfm_weight_shape(F, D, field_interaction):
+    """The shape of field_pair_w: [P,D,D] (matrix), [P,D] (vector) or [P] (scalar), P = F(F-1)/2."""
+    P = F * (F - 1) // 2
+    return {0: (P, D, D), 1: (P, D), 2: (P,)}[_fmfm_type(field_interaction)]
+
+
+def fmfm_tile(F, D, field_interaction, which):
+    """rm_fmfm_tile: which in FMFM_TILE - the examples per tile of the forward ("fwd"), dE ("de") or dW ("dw") kernel,
+    or the cap of their grids / batch slices ("fwd_cap", "de_cap", "dw_cap")."""
+    v = int(_lib.lib().rm_fmfm_tile(int(F), int(D), _fmfm_type(field_interaction), FMFM_TILE[which]))
+    if v < 0:
+        raise ValueError(f"fmfm: F={F}, D={D} unsupported ({_FMFM_LIMITS})")
+    return v
+
+
+def _fmfm_args(E, W, field_interaction):
+    """-> (B, F, D, type, E's and W's pointers)."""
+    if E.dim() != 3:
+        raise ValueError(f"E: expected [B,F,D], got {tuple(E.shape)}")
+    B, F, D = (int(v) for v in E.shape)
+    typ = _fmfm_type(field_interaction)
+    if not fmfm_supported(F, D, field_interaction):
+        raise ValueError(f"fmfm: F={F}, D={D} unsupported ({_FMFM_LIMITS})")
+    return B, F, D, typ, _chk(E, "E", F32), _chk(W, "W", F32, fmfm_weight_shape(F, D, field_interaction))
+
+
+def fmfm_fwd(E, W, field_interaction, logit):
+    """rm_fmfm_fwd: E [B,F,D], field_pair_w [P,D,D] | [P,D] | [P] -> logit [B] = sum_{i<j} E_i W_(ij) E_j^T."""
+    B, F, D, typ, pe, pw = _fmfm_args(E, W, field_interaction)
+    _lib.call("rm_fmfm_fwd", pe, pw, typ, B, F, D, _chk(logit, "logit", F32, (B,)), _stream())
+
+
+def fmfm_bwd_workspace(B, F, D, field_interaction):
+    """Floats of workspace for fmfm_bwd (rm_fmfm_bwd_workspace): the batch slices' partial weight gradients."""
+    n = int(_lib.lib().rm_fmfm_bwd_workspace(int(B), int(F), int(D), _fmfm_type(field_interaction)))
+    if n < 0:
+        raise ValueError(f"fmfm: B={B}, F={F}, D={D} unsupported ({_FMFM_LIMITS})")
+    return n
+
+
+def fmfm_bwd(E, W, field_interaction, g, d_rows, dW, workspace, dE_up=None):
+    """rm_fmfm_bwd: g [B] = dLoss/dlogit -> d_rows [B,F,D] = dLoss/dE (+ dE_up, which may be d_rows itself) and dW
+    (the shape of W), both overwritten.  Deterministic."""
+    B, F, D, typ, pe, pw = _fmfm_args(E, W, field_interaction)
+    if workspace.numel() < fmfm_bwd_workspace(B, F, D, field_interaction):
+        raise ValueError("fmfm_bwd: workspace too small (rm_fmfm_bwd_workspace)")
+    _lib.call("rm_fmfm_bwd", pe, pw, typ, _chk(g, "g", F32, (B,)), _chk(dE_up, "dE_up", F32, (B, F, D), allow_none=True),
+              B, F, D, _chk(d_rows, "d_rows", F32, (B, F, D)), _chk(dW, "dW", F32, tuple(W.shape)),
+              _chk(workspace, "workspace", F32), _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

@@ -9,6 +9,7 @@ from .DCN import DCN
 from .DLRM import DLRM
 from .DeepFM import DeepFM
 from .FiBiNET import FiBiNET
+from .FmFM import FmFM, FwFM
 from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
@@ -17,6 +18,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]

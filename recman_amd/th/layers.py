@@ -1083,6 +1083,71 @@ class FiBiNETInteraction:
 
 
 # ------------------------------------------------------------------------------------------------
+# field-pair weighted FM: FmFM / FvFM / FwFM
+# ------------------------------------------------------------------------------------------------
+class _FieldPairFn(torch.autograd.Function):
+    """rm_fmfm_fwd / rm_fmfm_bwd (csrc/fmfm.hip), as the FmFM engine runs them."""
+
+    @staticmethod
+    def forward(ctx, ftype, E, w):
+        E, w = E.detach().contiguous(), w.detach().contiguous()
+        logit = torch.empty(E.shape[0], device=E.device, dtype=F32)
+        ops.fmfm_fwd(E, w, ftype, logit)
+        ctx.save_for_backward(E, w)
+        ctx.ftype = ftype
+        return logit
+
+    @staticmethod
+    def backward(ctx, g):
+        E, w = ctx.saved_tensors
+        B, F, D = E.shape
+        dE, dw = torch.empty_like(E), torch.empty_like(w)
+        ws = torch.empty(max(4, ops.fmfm_bwd_workspace(B, F, D, ctx.ftype)), device=g.device, dtype=F32)
+        ops.fmfm_bwd(E, w, ctx.ftype, g.contiguous(), dE, dw, ws)
+        return None, dE, dw
+
+
+class FieldPairInteraction:
+    """The pair term of FmFM / FvFM / FwFM (arXiv 2102.12994, 1806.03514; nothing in the reference implements it):
+    FieldPairInteraction(variables, field_interaction, l2_reg)(feat_embeds [B,F,D]) -> [B] =
+    sum_{i<j} E_i W_(ij) E_j^T over the P = F(F-1)/2 pairs in itertools.combinations order, W_(ij) = field_pair_w[p]
+    ("matrix", [P,D,D], the left field on the rows), diag(field_pair_w[p]) ("vector", [P,D]) or field_pair_w[p] I
+    ("scalar", [P]).  The variable starts at plain FM (identity matrices / ones); `.weights`, `.l2()`."""
+
+    display_name = "FieldPairInteraction"
+    NAMES = ("field_pair_w",)
+
+    def __init__(self, variables, field_interaction="matrix", l2_reg=0.0, prefix=""):
+        if field_interaction not in ops.FMFM_TYPES:
+            raise ValueError(f"FieldPairInteraction: field_interaction {field_interaction!r} is not one of 'matrix', "
+                             "'vector', 'scalar'")
+        self.variables, self.field_interaction, self.l2_reg, self.prefix = variables, field_interaction, l2_reg, prefix
+
+    def _upsert_variables(self, F, D):
+        name = self.prefix + "field_pair_w"
+        if name not in self.variables:
+            shape = ops.fmfm_weight_shape(F, D, self.field_interaction)
+            t = torch.eye(D).expand(shape).clone() if len(shape) == 3 else torch.ones(shape)
+            self.variables[name] = _leaf(t)
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.NAMES]
+
+    def __call__(self, feat_embeds):
+        if feat_embeds.dim() != 3:
+            raise ValueError(f"FieldPairInteraction: feat_embeds [B,F,D] expected, got {tuple(feat_embeds.shape)}")
+        _, F, D = feat_embeds.shape
+        if not ops.fmfm_supported(F, D, self.field_interaction):
+            raise ValueError(f"FieldPairInteraction: F={F}, D={D} unsupported (2..40 fields, D in 8/16/32)")
+        self._upsert_variables(F, D)
+        return _FieldPairFn.apply(self.field_interaction, feat_embeds, *self.weights)
+
+    def l2(self):
+        return sum(self.l2_reg * 0.5 * self.variables[self.prefix + n].square().sum() for n in self.NAMES)
+
+
+# ------------------------------------------------------------------------------------------------
 # prediction + loss
 # ------------------------------------------------------------------------------------------------
 class _SigmoidFn(torch.autograd.Function):
@@ -1136,5 +1201,5 @@ def create_loss(y, pred, task="classification"):
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
            "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "CrossNetMix", "AFMLayer", "InteractingLayer",
-           "PredictionLayer",
+           "FieldPairInteraction", "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
