@@ -562,6 +562,75 @@ int rm_fmfm_bwd(const float *E, const float *W, int type, const float *g, const 
                 rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * MaskNet (arXiv 2102.07619): the normalise-and-mask passes around its dense layers, fused
+ * (csrc/masknet.hip).  Nothing in the reference implements it.  eps = 1e-5 inside the root,
+ * biased variance; a row's mean and centred sum of squares are accumulated in float64 (centred
+ * before squaring) and xhat is rounded to float32 once; the rest is float32 fmaf chains.
+ *
+ * a. Group-LayerNorm times N masks.  Per example, X = E [F, D], gamma / beta [F, D]:
+ *     V[f,:] = gamma[f,:] o (E[f,:] - mean_f) / sqrt(var_f + eps) + beta[f,:];   Y_n = M_n o V
+ *   X [B, F, D] contiguous, 16-byte aligned (rm_embed_fwd's E); M, Y: host arrays of N device
+ *   pointers to [B, F D] buffers of row stride ldm / ldy >= F D floats - any stride and alignment
+ *   (float4 accesses when every pointer is 16-byte aligned and the strides are multiples of 4,
+ *   per-element ones otherwise); each may be a column range of a wider buffer.  V, the means and
+ *   the inverse deviations never reach HBM.
+ * rm_masknet_group_bwd, given dY_n (row stride lddy), recomputes the statistics from X:
+ *     dM_n = dY_n o V (row stride lddm; dM[n] MAY be dY[n] itself, with lddm = lddy: a thread
+ *     reads its elements of dY_n before it writes them; no other overlap is allowed: dM[n] equal
+ *     to a mask or to another dY[k] is RM_EINVAL)
+ *     dV = sum_n dY_n o M_n;  dgamma = sum_b dV o xhat;  dbeta = sum_b dV   ([F, D], overwritten)
+ *     dE = rstd (dxhat - mean(dxhat) - xhat mean(dxhat o xhat)), dxhat = dV o gamma
+ *   d_rows [B, F, D] = dE_up + dE when dE_up is given (it may be d_rows itself), dE otherwise -
+ *   written once.  workspace: rm_masknet_group_bwd_workspace(B, F, D) floats, 16-byte aligned:
+ *   one partial dgamma | dbeta set per (block, example slot) of a grid of at most 512 blocks,
+ *   (fewer where the sets would pass 16 MB), summed in a fixed order in float64 by a finish
+ *   kernel: no atomics, two runs are bit-equal; 0 at B = 0, -1 for an unsupported shape.
+ * normalize = 0 (MaskNet's serial blocks 2..N): X = h_prev [B, H] contiguous, called with F = 1,
+ *   D = H, N = 1; gamma, beta, dgamma, dbeta, workspace NULL:
+ *     Y = M o X;   dM = dY o X;   d_rows [B, H] = (dE_up +) dY o M
+ * Supported (rm_masknet_group_supported(F, D, N, normalize)): normalize = 1: D in {8,16,32},
+ *   1 <= F <= 40, 1 <= N <= 8;  normalize = 0: F = 1, N = 1, D a multiple of 4 in 8..2048.
+ *   Anything else, a short stride or a NULL pointer is RM_EINVAL before any launch; B = 0 is RM_OK
+ *   and touches nothing.
+ * rm_masknet_group_tile(F, D, normalize, which): RM_MASKNET_TILE the examples per block pass,
+ *   RM_MASKNET_CAP the grid cap - beyond cap x tile examples a block walks the batch with a grid
+ *   stride; -1 for an unsupported shape or `which`.
+ * Bytes: forward 4 B F D (1 + 2 N) + 8 F D (X and M_n in, Y_n out, the parameters);
+ *   backward 4 B F D (2 + 3 N) (+ 4 B F D with dE_up) + the partial sets.
+ *
+ * b. Row-LayerNorm + ReLU: Z [B, H] contiguous, gamma / beta [H]:
+ *     h[b, :] = relu(gamma o (Z[b,:] - mean_b) / sqrt(var_b + eps) + beta)     row stride ldh >= H
+ * rm_masknet_row_bwd, given dh (row stride lddh; relu'(0) = 0), recomputes the statistics from Z
+ *   (saving mean and rstd would add 8 bytes per row to the forward and save none in the backward,
+ *   which reads Z for xhat either way) and writes dZ [B, H] contiguous (neither Z nor dh itself:
+ *   RM_EINVAL; no other overlap of an output with an input is supported), dgamma and
+ *   dbeta [H] - deterministic as above, workspace rm_masknet_row_bwd_workspace(B, H) floats.
+ * Supported (rm_masknet_row_supported): H a multiple of 4 in 8..2048; ldh, lddh multiples of 4;
+ *   every pointer 16-byte aligned.  Bytes: forward 8 B H, backward 12 B H + the partial sets.
+ */
+#define RM_MASKNET_TILE 0
+#define RM_MASKNET_CAP 1
+int rm_masknet_group_supported(int F, int D, int N, int normalize);
+int rm_masknet_group_tile(int F, int D, int normalize, int which);
+int rm_masknet_group_fwd(const float *X, const float *gamma, const float *beta, int normalize,
+                         const float *const *M, int64_t ldm, int N, int64_t B, int F, int D,
+                         float *const *Y, int64_t ldy, rm_stream_t stream);
+int64_t rm_masknet_group_bwd_workspace(int64_t B, int F, int D);
+int rm_masknet_group_bwd(const float *X, const float *gamma, const float *beta, int normalize,
+                         const float *const *M, int64_t ldm, const float *const *dY, int64_t lddy,
+                         float *const *dM, int64_t lddm, int N, const float *dE_up, int64_t B, int F,
+                         int D, float *d_rows, float *dgamma, float *dbeta, float *workspace,
+                         rm_stream_t stream);
+int rm_masknet_row_supported(int H);
+int rm_masknet_row_tile(int H, int which);
+int rm_masknet_row_fwd(const float *Z, const float *gamma, const float *beta, int64_t B, int H,
+                       float *h, int64_t ldh, rm_stream_t stream);
+int64_t rm_masknet_row_bwd_workspace(int64_t B, int H);
+int rm_masknet_row_bwd(const float *Z, const float *gamma, const float *beta, const float *dh,
+                       int64_t lddh, int64_t B, int H, float *dZ, float *dgamma, float *dbeta,
+                       float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Attention-pooled behaviour sequences: SequenceFeat + DIN's local activation unit (Deep
  * Interest Network, arXiv 1706.06978 section 4.3).  Replaces ASPCombiner / ASPLayer, which
  * DIN.py:6 imports and which exist nowhere in the reference (SequenceFeat.__init__ raises,

@@ -82,6 +82,14 @@ SIGNATURES = {
     "rm_fmfm_tile": [c_int, c_int, c_int, c_int],
     "rm_fmfm_fwd": [P, P, c_int, I64, c_int, c_int, P, P],
     "rm_fmfm_bwd": [P, P, c_int, P, P, I64, c_int, c_int, P, P, P, P],
+    "rm_masknet_group_supported": [c_int, c_int, c_int, c_int],
+    "rm_masknet_group_tile": [c_int, c_int, c_int, c_int],
+    "rm_masknet_group_fwd": [P, P, P, c_int, P, I64, c_int, I64, c_int, c_int, P, I64, P],
+    "rm_masknet_group_bwd": [P, P, P, c_int, P, I64, P, I64, P, I64, c_int, P, I64, c_int, c_int, P, P, P, P, P],
+    "rm_masknet_row_supported": [c_int],
+    "rm_masknet_row_tile": [c_int, c_int],
+    "rm_masknet_row_fwd": [P, P, P, I64, c_int, P, I64, P],
+    "rm_masknet_row_bwd": [P, P, P, P, I64, I64, c_int, P, P, P, P, P],
     "rm_asp_supported": [c_int, c_int, P, c_int],
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
@@ -132,6 +140,8 @@ SIGNATURES_I64 = {
     "rm_cross_mix_bwd_workspace": [I64, c_int, c_int],
     "rm_fibinet_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_fmfm_bwd_workspace": [I64, c_int, c_int, c_int],
+    "rm_masknet_group_bwd_workspace": [I64, c_int, c_int],
+    "rm_masknet_row_bwd_workspace": [I64, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],

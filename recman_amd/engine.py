@@ -384,8 +384,8 @@ def init_reference(engine, seed=2019):
     tables, DNN and CIN weights truncated-normal glorot (utils.py:180-183; layers.py:99-101,536,551,567,666), cin_w
     glorot-uniform (layers.py:690), biases zeros (layers.py:109,321,327,544,561,574,676,695); the layers absent from
     the reference (cross net, attention units, interacting layers, DLRM's towers) glorot weights like dnn_w and zero
-    biases; the field-pair weights of FmFM / FvFM / FwFM ("pair_identity") identity matrices or ones.  A variable
-    without a declared rule is a KeyError."""
+    biases; the field-pair weights of FmFM / FvFM / FwFM ("pair_identity") identity matrices or ones; MaskNet's
+    LayerNorm gains "ones".  A variable without a declared rule is a KeyError."""
     import math
 
     g = torch.Generator(device=engine.device).manual_seed(int(seed))
@@ -395,6 +395,9 @@ def init_reference(engine, seed=2019):
         init = engine.decl[name][0]
         if init == "zeros":
             t.zero_()
+            continue
+        if init == "ones":
+            t.fill_(1.0)  # LayerNorm gains (MaskNet)
             continue
         if init == "pair_identity":
             # the field-pair weights start the model at plain FM: identity matrices [P,D,D], all-ones vectors [P,D]
@@ -2347,5 +2350,266 @@ class FmFMEngine(DeepFMEngine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+def masknet_limits(hp, F, D):
+    """MaskNet's limits in one place (th.MaskNet checks them at construction, MaskNetEngine when it is built): a
+    ValueError naming the limit, or (block_order, num_blocks, block_hidden_units, reduction_ratio, deep_hidden_units)."""
+    order = hp.get("block_order", "parallel")
+    if order not in ("parallel", "serial"):
+        raise ValueError(f"MaskNet: block_order {order!r} is not one of 'parallel', 'serial'")
+    N = int(hp.get("num_blocks", 3))
+    if not 1 <= N <= 8:
+        raise ValueError(f"MaskNet: num_blocks={N} is outside 1..8")
+    H = int(hp.get("block_hidden_units", 64))
+    if H % 4 or not 8 <= H <= 2048:
+        raise ValueError(f"MaskNet: block_hidden_units={H} must be a multiple of 4 in 8..2048")
+    ratio = float(hp.get("reduction_ratio", 2.0))
+    if not ratio > 0:
+        raise ValueError(f"MaskNet: reduction_ratio={ratio} must be greater than 0")
+    if D not in (8, 16, 32) or not 1 <= F <= 40:
+        raise ValueError(f"MaskNet: {F} embedding features of embedding_size={D} are not supported by "
+                         "rm_masknet_group_fwd (1..40 embedding features, embedding_size 8/16/32)")
+    hidden = tuple(hp.get("deep_hidden_units") or ())
+    if not hidden:
+        raise ValueError("MaskNet: deep_hidden_units must name at least one layer of the DNN")
+    return order, N, H, ratio, hidden
+
+
+class MaskNetEngine(Engine):
+    """MaskNet (arXiv 2102.07619): instance-guided masks multiply a LayerNorm'ed embedding (or the previous block's
+    output), a dense layer, a LayerNorm and a ReLU follow; the blocks feed the DNN.  final = DNN logit (+ linear if
+    use_linear, the default).  Nothing in the reference implements it.  x = [flatten(E) | dense] of width K:
+        mask_n(x) = relu(x agg_n + agg_b_n) proj_n + proj_b_n              [K,A] then [A,Wout], A = max(1,
+                                                                            round(reduction_ratio * Wout))
+        V[f,:]    = ln_emb_gamma[f,:] o LN(E[f,:]) + ln_emb_beta[f,:]       (per field row; eps 1e-5, biased variance)
+        embedding block (Wout = F D):  h_n = relu(LN_H((mask_n(x) o V) hidden_n))          hidden_n [F D, H], no bias
+        block on a block (Wout = H):   h_n = relu(LN_H((mask_n(x) o h_{n-1}) hidden_n))    hidden_n [H, H]
+    block_order "parallel": num_blocks embedding blocks share one V, DNN([h_1 | .. | h_N | dense]);  "serial": block 1
+    on the embedding, blocks 2..N each on their predecessor, DNN([h_N | dense]).
+    Variables (names chosen here): ln_emb_gamma / ln_emb_beta [F,D], block{n}_agg_weights / _agg_bias,
+    block{n}_proj_weights / _proj_bias, block{n}_hidden_weights, block{n}_ln_gamma / _ln_beta [H] (n = 1..N), the DNN's
+    dnn_*.  Gains start at one ("ones"), weights glorot, l2 key deep_l2_reg on the weight matrices.  No bias tables.
+    The normalise-and-mask passes are csrc/masknet.hip; the dense layers run one by one on ops.dense_fwd /
+    ops.dense_wgrad (bias + ReLU in the aggregation layer's epilogue, the bf16x6 path under dense_gemm).  The N
+    aggregation layers are NOT batched into one GEMM: each block's weights are a variable of their own, so no
+    [K, N A] matrix exists to multiply by."""
+
+    model = "masknet"
+    use_bias_tables = False
+    shardable = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", True))
+        F, D, FD, Dn = self.F, self.D, self.FD, self.Dn
+        self.order, self.N, self.H, ratio, hidden = masknet_limits(hp, F, D)
+        self.parallel = self.order == "parallel"
+        N, H = self.N, self.H
+        K = FD + Dn
+        self._var("ln_emb_gamma", (F, D), "ones")
+        self._var("ln_emb_beta", (F, D))
+        l2 = "deep_l2_reg"
+        self.wout, self.A = [], []
+        for n in range(1, N + 1):
+            wout = FD if (self.parallel or n == 1) else H
+            A = max(1, round(ratio * wout))
+            self.wout.append(wout)
+            self.A.append(A)
+            self._var(f"block{n}_agg_weights", (K, A), ("glorot", K, A), l2)
+            self._var(f"block{n}_agg_bias", (A,))
+            self._var(f"block{n}_proj_weights", (A, wout), ("glorot", A, wout), l2)
+            self._var(f"block{n}_proj_bias", (wout,))
+            self._var(f"block{n}_hidden_weights", (wout, H), ("glorot", wout, H), l2)
+            self._var(f"block{n}_ln_gamma", (H,), "ones")
+            self._var(f"block{n}_ln_beta", (H,))
+        self.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        # (the DNN reads the blocks' outputs, not [E | dense]; its dX is no table-row gradient)
+        self.mlp = self._dnn((N if self.parallel else 1) * H, Dn, hidden, "relu", stream_d_rows=False)
+
+    def _alloc_model(self, B):
+        dev, H, N = self.device, self.H, self.N
+        K = self.FD + self.Dn
+
+        def buf(w):
+            return torch.empty(B, w, dtype=F32, device=dev)
+
+        # per block: the aggregation layer's output T (rows padded to a multiple of 4 floats), the mask M, the masked
+        # input Y (later dY, then dM, in place) and the hidden layer's output Z
+        self.T = [buf((a + 3) // 4 * 4)[:, :a] for a in self.A]
+        self.dT = buf((max(self.A) + 3) // 4 * 4)
+        self.M = [buf(w) for w in self.wout]
+        self.Y = [buf(w) for w in self.wout]
+        self.Z = [buf(H) for _ in range(N)]
+        self.dZ = buf(H)
+        nx = N if self.parallel else 1
+        self.X = buf(nx * H)
+        self.dX = buf(nx * H)
+        if not self.parallel:
+            # h_1 .. h_{N-1} (h_N is X) and the gradient that comes back to each
+            self.hs = [buf(H) for _ in range(N - 1)]
+            self.dhs = [buf(H) for _ in range(N - 1)]
+        self.dx_tmp = buf(self.FD)
+        self.group_ws = torch.empty(max(4, ops.masknet_group_bwd_workspace(B, self.F, self.D)), dtype=F32, device=dev)
+        self.row_ws = torch.empty(max(4, ops.masknet_row_bwd_workspace(B, H)), dtype=F32, device=dev)
+        # the dense kernels' workspaces, sized for the widest block of either kind
+        a_e = max(a for a, w in zip(self.A, self.wout) if w == self.FD)
+        chains = [[K, a_e, self.FD, H]]
+        if any(w == H for w in self.wout):
+            chains.append([K, max(a for a, w in zip(self.A, self.wout) if w == H), H, H])
+        wss = [_dense_workspaces(c, B, dev, self.dense_gemm) for c in chains]
+        self._fws, self._wws, self._fws6, self._wws6 = (
+            None if any(w[i] is None for w in wss) else max((w[i] for w in wss), key=lambda t: t.numel())
+            for i in range(4))
+
+    def _bp(self, d, n):
+        """Block n's (1-based) variables out of the params or the grads dict."""
+        p = f"block{n}_"
+        return (d[p + "agg_weights"], d[p + "agg_bias"], d[p + "proj_weights"], d[p + "proj_bias"],
+                d[p + "hidden_weights"], d[p + "ln_gamma"], d[p + "ln_beta"])
+
+    def _mask_fwd(self, n, xe, xd):
+        """M[n-1] = relu(x agg + agg_b) proj + proj_b."""
+        Wa, ba, Wp, bp = self._bp(self.params, n)[:4]
+        T = self.T[n - 1]
+        ops.dense_fwd(xe, xd, Wa, T, self._fws, bias=ba, act="relu", ws6=self._fws6)
+        ops.dense_fwd(T, None, Wp, self.M[n - 1], self._fws, bias=bp, act="identity", ws6=self._fws6)
+
+    def _hidden_fwd(self, n, out):
+        """out = relu(LN_H(Y[n-1] hidden))."""
+        Wh, g, b = self._bp(self.params, n)[4:]
+        ops.dense_fwd(self.Y[n - 1], None, Wh, self.Z[n - 1], self._fws, act="identity", ws6=self._fws6)
+        ops.masknet_row_fwd(self.Z[n - 1], g, b, out)
+
+    def _blocks_fwd(self, dense):
+        B, H, N = self.E.shape[0], self.H, self.N
+        xe, xd = self.E.view(B, self.FD), dense if self.Dn else None
+        p = self.params
+        if self.parallel:
+            for n in range(1, N + 1):
+                self._mask_fwd(n, xe, xd)
+            ops.masknet_group_fwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], self.M, self.Y)
+            for n in range(1, N + 1):
+                self._hidden_fwd(n, self.X[:, (n - 1) * H: n * H])
+            return
+        outs = self.hs + [self.X]
+        self._mask_fwd(1, xe, xd)
+        ops.masknet_group_fwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], self.M[:1], self.Y[:1])
+        self._hidden_fwd(1, outs[0])
+        for n in range(2, N + 1):
+            self._mask_fwd(n, xe, xd)
+            ops.masknet_group_fwd(outs[n - 2], None, None, [self.M[n - 1]], [self.Y[n - 1]], normalize=False)
+            self._hidden_fwd(n, outs[n - 1])
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        self._blocks_fwd(dense)
+        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
+        self.dnn_logit = self._mlp_last(self.mlp, self.X, dense if self.Dn else None, self._dnn_keep(training),
+                                        m.get("dnn"), list(branches))
+        branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _hidden_bwd(self, n, dh):
+        """dh = dLoss/dh_n -> the hidden layer's and LN_H's gradients; Y[n-1] <- dLoss/dY."""
+        Wh, g, b = self._bp(self.params, n)[4:]
+        dWh, dg, db = self._bp(self.grads, n)[4:]
+        ops.masknet_row_bwd(self.Z[n - 1], g, b, dh, self.dZ, dg, db, self.row_ws)
+        ops.dense_wgrad(self.Y[n - 1], None, self.dZ, dWh, self._wws, ws6=self._wws6)
+        ops.dense_fwd(self.dZ, None, Wh, self.Y[n - 1], self._fws, transposed=True, epilogue=ops.DENSE_ADD,
+                      ws6=self._fws6)
+
+    def _dx_next(self):
+        """The buffer the next pass writes the accumulated dLoss/dE to (never the one it reads, self._dx): the two
+        alternate so that the last of the N + 1 passes lands in d_rows."""
+        B = self.E.shape[0]
+        d_rows = self.d_rows.view(B, self.FD)
+        if self._dx is None:
+            return d_rows if self.N % 2 == 0 else self.dx_tmp
+        return self.dx_tmp if self._dx.data_ptr() == d_rows.data_ptr() else d_rows
+
+    def _mask_bwd(self, n, xe, xd):
+        """Y[n-1] holds dLoss/dM_n: the two mask layers' gradients, and the mask's share of dLoss/dE."""
+        Wa, _, Wp, _ = self._bp(self.params, n)[:4]
+        dWa, dba, dWp, dbp = self._bp(self.grads, n)[:4]
+        T, dM = self.T[n - 1], self.Y[n - 1]
+        dT = self.dT[:, : T.shape[1]]
+        ops.dense_wgrad(T, None, dM, dWp, self._wws, db=dbp, ws6=self._wws6)
+        ops.dense_fwd(dM, None, Wp, dT, self._fws, transposed=True, epilogue=ops.DENSE_MUL_ACTGRAD, act="relu",
+                      aux1=T, ws6=self._fws6)
+        ops.dense_wgrad(xe, xd, dT, dWa, self._wws, db=dba, ws6=self._wws6)
+        # (the dense features are inputs: no gradient for them)
+        dst = self._dx_next()
+        ops.dense_fwd(dT, None, Wa[: self.FD], dst, self._fws, transposed=True, epilogue=ops.DENSE_ADD,
+                      aux1=self._dx, ws6=self._fws6)
+        self._dx = dst
+
+    def _group_bwd(self, n_masks):
+        p, gr = self.params, self.grads
+        dst = self._dx_next()
+        shape = tuple(self.E.shape)
+        ops.masknet_group_bwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], self.M[:n_masks], self.Y[:n_masks],
+                              self.Y[:n_masks], dst.view(shape), gr["ln_emb_gamma"], gr["ln_emb_beta"], self.group_ws,
+                              dE_up=None if self._dx is None else self._dx.view(shape))
+        self._dx = dst
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        B, H, N = self.E.shape[0], self.H, self.N
+        xe, xd = self.E.view(B, self.FD), dense if self.Dn else None
+        self.mlp.backward(g, self.dX)
+        self._dx = None
+        if self.parallel:
+            for n in range(1, N + 1):
+                self._hidden_bwd(n, self.dX[:, (n - 1) * H: n * H])
+            self._group_bwd(N)
+            for n in range(1, N + 1):
+                self._mask_bwd(n, xe, xd)
+        else:
+            outs, douts = self.hs + [self.X], self.dhs + [self.dX]
+            for n in range(N, 1, -1):
+                self._hidden_bwd(n, douts[n - 1])
+                ops.masknet_group_bwd(outs[n - 2], None, None, [self.M[n - 1]], [self.Y[n - 1]], [self.Y[n - 1]],
+                                      douts[n - 2], normalize=False)
+                self._mask_bwd(n, xe, xd)
+            self._hidden_bwd(1, douts[0])
+            self._group_bwd(1)
+            self._mask_bwd(1, xe, xd)
+        # no other branch reads E: d_rows IS dLoss/dE
+        assert self._dx.data_ptr() == self.d_rows.data_ptr()
+
+    def roofline_probes(self, idx, dense, y):
+        self._probe_fill(idx, dense, y)  # E, M, Y (= dM), Z, dX
+        B, F, D, H, FD = idx.shape[0], self.F, self.D, self.H, self.FD
+        p = self.params
+        n = self.N if self.parallel else 1
+        M, Y = self.M[:n], [torch.empty_like(t) for t in self.Y[:n]]
+        dY = [torch.randn_like(t) for t in Y]
+        d_rows = torch.empty_like(self.d_rows)
+        dg, db = torch.empty_like(p["ln_emb_gamma"]), torch.empty_like(p["ln_emb_beta"])
+        g1, b1 = p["block1_ln_gamma"], p["block1_ln_beta"]
+        dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
+        h, dZ = torch.empty_like(self.Z[0]), torch.empty_like(self.Z[0])
+        dh = self.dX[:, :H]
+        shape = f"F={F} D={D} N={n}"
+        return [
+            dict(name=f"masknet_group_bwd_kernel (rm_masknet_group_bwd, {shape}: E, M_n, dY_n in, dM_n, d_rows out)",
+                 symbol="masknet_group_bwd_kernel",
+                 fn=lambda: ops.masknet_group_bwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, dY, dY, d_rows, dg, db,
+                                                  self.group_ws),
+                 work=4.0 * (B * FD * (2 + 3 * n) + 4 * FD), bound="hbm"),
+            dict(name=f"masknet_group_fwd_kernel (rm_masknet_group_fwd, {shape}: E and M_n in, Y_n out)",
+                 symbol="masknet_group_fwd_kernel",
+                 fn=lambda: ops.masknet_group_fwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, Y),
+                 work=4.0 * (B * FD * (1 + 2 * n) + 2 * FD), bound="hbm"),
+            dict(name=f"masknet_row_bwd_kernel (rm_masknet_row_bwd, H={H}: Z and dh in, dZ out)",
+                 symbol="masknet_row_bwd_kernel",
+                 fn=lambda: ops.masknet_row_bwd(self.Z[0], g1, b1, dh, dZ, dg1, db1, self.row_ws),
+                 work=4.0 * (3 * B * H + 4 * H), bound="hbm"),
+            dict(name=f"masknet_row_fwd_kernel (rm_masknet_row_fwd, H={H}: Z in, h out)",
+                 symbol="masknet_row_fwd_kernel", fn=lambda: ops.masknet_row_fwd(self.Z[0], g1, b1, h),
+                 work=4.0 * (2 * B * H + 2 * H), bound="hbm"),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
-           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine}
+           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine,
+           "masknet": MaskNetEngine}

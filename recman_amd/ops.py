@@ -594,6 +594,163 @@ def fmfm_bwd(E, W, field_interaction, g, d_rows, dW, workspace, dE_up=None):
               _chk(workspace, "workspace", F32), _stream())
 
 
+# ---- MaskNet: group-LayerNorm times masks, row-LayerNorm + ReLU (csrc/masknet.hip) ----------------------------------
+MASKNET_TILE = {"tile": 0, "cap": 1}  # RM_MASKNET_TILE / RM_MASKNET_CAP
+_MASKNET_GROUP_LIMITS = ("normalize: 1 <= F <= 40, D in 8, 16, 32, 1..8 masks; normalize=False: one [B,H] input, one "
+                         "mask, H a multiple of 4 in 8..2048")
+_MASKNET_ROW_LIMITS = "H a multiple of 4 in 8..2048, row strides multiples of 4"
+
+
+def masknet_group_supported(F, D, N, normalize=True):
+    """rm_masknet_group_supported: normalize: D in {8, 16, 32}, 1 <= F <= 40, 1 <= N <= 8; otherwise F = 1, N = 1 and
+    D (= H) a multiple of 4 in 8..2048."""
+    return bool(_lib.lib().rm_masknet_group_supported(int(F), int(D), int(N), int(bool(normalize))))
+
+
+def masknet_group_tile(F, D, which, normalize=True):
+    """rm_masknet_group_tile: which in MASKNET_TILE - the examples per block pass ("tile") or the grid cap ("cap")."""
+    v = int(_lib.lib().rm_masknet_group_tile(int(F), int(D), int(bool(normalize)), MASKNET_TILE[which]))
+    if v < 0:
+        raise ValueError(f"masknet_group: F={F}, D={D} unsupported ({_MASKNET_GROUP_LIMITS})")
+    return v
+
+
+def _masknet_rows(ts, name, B, W):
+    """A list of [B, W] f32 device tensors with unit column stride and ONE common row stride >= W -> (pointer
+    array, stride)."""
+    ld = None
+    for n, t in enumerate(ts):
+        if t is None or not t.is_cuda or t.dtype != F32 or t.dim() != 2 or tuple(t.shape) != (B, W) or (
+                W > 1 and t.stride(1) != 1):
+            raise ValueError(f"{name}[{n}]: expected a [{B},{W}] float32 device tensor with unit column stride")
+        s = t.stride(0) if B > 1 else W  # (a single row has no stride to speak of)
+        if s < W:
+            raise ValueError(f"{name}[{n}]: unsupported row stride {s} < {W}")
+        if ld is None:
+            ld = s
+        elif s != ld:
+            raise ValueError(f"{name}: unsupported mix of row strides ({s} != {ld}): one stride per list")
+    return _ptr_array(ts), int(W if ld is None else ld)
+
+
+def _masknet_group_args(X, gamma, beta, N, normalize):
+    """-> (B, F, D, X's, gamma's and beta's pointers)."""
+    if normalize:
+        if X.dim() != 3:
+            raise ValueError(f"X: expected [B,F,D], got {tuple(X.shape)}")
+        B, F, D = (int(v) for v in X.shape)
+    else:
+        if X.dim() != 2:
+            raise ValueError(f"X: expected [B,H], got {tuple(X.shape)}")
+        B, F, D = int(X.shape[0]), 1, int(X.shape[1])
+    if not masknet_group_supported(F, D, N, normalize):
+        raise ValueError(f"masknet_group: F={F}, D={D}, {N} masks unsupported ({_MASKNET_GROUP_LIMITS})")
+    px = _chk(X, "X", F32)
+    if not normalize:
+        if gamma is not None or beta is not None:
+            raise ValueError("masknet_group: normalize=False takes no gamma / beta")
+        return B, F, D, px, None, None
+    return B, F, D, px, _chk(gamma, "gamma", F32, (F, D)), _chk(beta, "beta", F32, (F, D))
+
+
+def masknet_group_fwd(X, gamma, beta, M, Y, normalize=True):
+    """rm_masknet_group_fwd: X = E [B,F,D], gamma / beta [F,D], M and Y lists of N [B,FD] tensors (rows of any common
+    stride: column ranges of a wider buffer are fine) -> Y[n] = M[n] o LN_rows(E).  normalize=False: X = h_prev
+    [B,H], one mask: Y[0] = M[0] o X."""
+    if len(M) != len(Y):
+        raise ValueError("masknet_group_fwd: M and Y differ in length")
+    B, F, D, px, pg, pb = _masknet_group_args(X, gamma, beta, len(M), normalize)
+    pm, ldm = _masknet_rows(M, "M", B, F * D)
+    py, ldy = _masknet_rows(Y, "Y", B, F * D)
+    _lib.call("rm_masknet_group_fwd", px, pg, pb, int(bool(normalize)), pm, ldm, len(M), B, F, D, py, ldy, _stream())
+
+
+def masknet_group_bwd_workspace(B, F, D):
+    """Floats of workspace for masknet_group_bwd (rm_masknet_group_bwd_workspace): the partial dgamma | dbeta sets."""
+    n = int(_lib.lib().rm_masknet_group_bwd_workspace(int(B), int(F), int(D)))
+    if n < 0:
+        raise ValueError(f"masknet_group: B={B}, F={F}, D={D} unsupported ({_MASKNET_GROUP_LIMITS})")
+    return n
+
+
+def masknet_group_bwd(X, gamma, beta, M, dY, dM, d_rows, dgamma=None, dbeta=None, workspace=None, dE_up=None,
+                      normalize=True):
+    """rm_masknet_group_bwd: dM[n] = dY[n] o V (dM[n] may be dY[n] itself), d_rows = the LayerNorm backward of
+    sum_n dY[n] o M[n] (+ dE_up, which may be d_rows itself), dgamma / dbeta [F,D]; all overwritten, deterministic.
+    normalize=False: dM[0] = dY[0] o X, d_rows [B,H] = dY[0] o M[0] (+ dE_up); no parameters, no workspace."""
+    if not (len(M) == len(dY) == len(dM)):
+        raise ValueError("masknet_group_bwd: M, dY and dM differ in length")
+    B, F, D, px, pg, pb = _masknet_group_args(X, gamma, beta, len(M), normalize)
+    pm, ldm = _masknet_rows(M, "M", B, F * D)
+    pdy, lddy = _masknet_rows(dY, "dY", B, F * D)
+    pdm, lddm = _masknet_rows(dM, "dM", B, F * D)
+    pdg = pdb = pws = None
+    if normalize:
+        pdg, pdb = _chk(dgamma, "dgamma", F32, (F, D)), _chk(dbeta, "dbeta", F32, (F, D))
+        pws = _chk(workspace, "workspace", F32)
+        if workspace.numel() < masknet_group_bwd_workspace(B, F, D):
+            raise ValueError("masknet_group_bwd: workspace too small (rm_masknet_group_bwd_workspace)")
+    _lib.call("rm_masknet_group_bwd", px, pg, pb, int(bool(normalize)), pm, ldm, pdy, lddy, pdm, lddm, len(M),
+              _chk(dE_up, "dE_up", F32, tuple(X.shape), allow_none=True), B, F, D,
+              _chk(d_rows, "d_rows", F32, tuple(X.shape)), pdg, pdb, pws, _stream())
+
+
+def masknet_row_supported(H):
+    """rm_masknet_row_supported: H a multiple of 4 in 8..2048."""
+    return bool(_lib.lib().rm_masknet_row_supported(int(H)))
+
+
+def masknet_row_tile(H, which):
+    """rm_masknet_row_tile: which in MASKNET_TILE - the rows per block pass ("tile") or the grid cap ("cap")."""
+    v = int(_lib.lib().rm_masknet_row_tile(int(H), MASKNET_TILE[which]))
+    if v < 0:
+        raise ValueError(f"masknet_row: H={H} unsupported ({_MASKNET_ROW_LIMITS})")
+    return v
+
+
+def _masknet_row_args(Z, gamma, beta):
+    if Z.dim() != 2:
+        raise ValueError(f"Z: expected [B,H], got {tuple(Z.shape)}")
+    B, H = (int(v) for v in Z.shape)
+    if not masknet_row_supported(H):
+        raise ValueError(f"masknet_row: H={H} unsupported ({_MASKNET_ROW_LIMITS})")
+    return B, H, _chk(Z, "Z", F32), _chk(gamma, "gamma", F32, (H,)), _chk(beta, "beta", F32, (H,))
+
+
+def _masknet_strided(t, name, B, H):
+    p, ld = _masknet_rows([t], name, B, H)
+    if ld % 4 or t.data_ptr() % 16:
+        raise ValueError(f"{name}: unsupported row stride {ld} or alignment ({_MASKNET_ROW_LIMITS}, 16-byte aligned)")
+    return t.data_ptr(), ld
+
+
+def masknet_row_fwd(Z, gamma, beta, h):
+    """rm_masknet_row_fwd: Z [B,H], gamma / beta [H] -> h [B,H] (row stride >= H, a multiple of 4) = relu(LN(Z))."""
+    B, H, pz, pg, pb = _masknet_row_args(Z, gamma, beta)
+    ph, ldh = _masknet_strided(h, "h", B, H)
+    _lib.call("rm_masknet_row_fwd", pz, pg, pb, B, H, ph, ldh, _stream())
+
+
+def masknet_row_bwd_workspace(B, H):
+    """Floats of workspace for masknet_row_bwd (rm_masknet_row_bwd_workspace)."""
+    n = int(_lib.lib().rm_masknet_row_bwd_workspace(int(B), int(H)))
+    if n < 0:
+        raise ValueError(f"masknet_row: B={B}, H={H} unsupported ({_MASKNET_ROW_LIMITS})")
+    return n
+
+
+def masknet_row_bwd(Z, gamma, beta, dh, dZ, dgamma, dbeta, workspace):
+    """rm_masknet_row_bwd: dh [B,H] (row stride >= H) -> dZ [B,H], dgamma / dbeta [H] of h = relu(LN(Z)); the
+    statistics are recomputed from Z.  Deterministic."""
+    B, H, pz, pg, pb = _masknet_row_args(Z, gamma, beta)
+    pdh, lddh = _masknet_strided(dh, "dh", B, H)
+    if workspace.numel() < masknet_row_bwd_workspace(B, H):
+        raise ValueError("masknet_row_bwd: workspace too small (rm_masknet_row_bwd_workspace)")
+    _lib.call("rm_masknet_row_bwd", pz, pg, pb, pdh, lddh, B, H, _chk(dZ, "dZ", F32, (B, H)),
+              _chk(dgamma, "dgamma", F32, (H,)), _chk(dbeta, "dbeta", F32, (H,)), _chk(workspace, "workspace", F32),
+              _stream())
+
+
 ASP_ACTS = {"relu": 0, "sigmoid": 1}  # RM_ASP_RELU / RM_ASP_SIGMOID
 
 

@@ -10,6 +10,7 @@ from .DLRM import DLRM
 from .DeepFM import DeepFM
 from .FiBiNET import FiBiNET
 from .FmFM import FmFM, FwFM
+from .MaskNet import MaskNet
 from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
@@ -18,6 +19,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]

@@ -1148,6 +1148,139 @@ class FieldPairInteraction:
 
 
 # ------------------------------------------------------------------------------------------------
+# MaskNet's MaskBlock
+# ------------------------------------------------------------------------------------------------
+def _mask_gemm(a, W, out, **kw):
+    """ops.dense_fwd on the f32 kernel with a workspace of its own: allocated per call (a layer for composing models
+    by hand, not the engine's hot path), sized for the square of the larger side as _dense_workspaces does, which
+    covers the layer and its transposed use."""
+    K, N = (W.shape[1], W.shape[0]) if kw.get("transposed") else W.shape
+    fws = torch.empty(ops.dense_filter_workspace(max(K, N), max(K, N)), device=a.device, dtype=F32)
+    ops.dense_fwd(a, None, W, out, fws, **kw)
+    return out
+
+
+def _mask_wgrad(a, G, db=None):
+    dW = torch.empty(a.shape[1], G.shape[1], device=a.device, dtype=F32)
+    ws = torch.empty(max(1, ops.dense_wgrad_workspace(a.shape[1], G.shape[1], a.shape[0])), device=a.device, dtype=F32)
+    ops.dense_wgrad(a, None, G, dW, ws, db=db)
+    return dW
+
+
+class _MaskBlockFn(torch.autograd.Function):
+    """One MaskBlock as the MaskNet engine runs it: the two mask layers and the hidden layer on ops.dense_fwd /
+    ops.dense_wgrad, the normalise-and-mask passes on csrc/masknet.hip."""
+
+    @staticmethod
+    def forward(ctx, x, inp, Wa, ba, Wp, bp, Wh, g, b, eg, eb):
+        x, inp = x.detach().contiguous(), inp.detach().contiguous()
+        Wa, ba, Wp, bp, Wh, g, b = (t.detach().contiguous() for t in (Wa, ba, Wp, bp, Wh, g, b))
+        norm = eg is not None
+        if norm:
+            eg, eb = eg.detach().contiguous(), eb.detach().contiguous()
+        B, dev = x.shape[0], x.device
+        A, wout, H = Wa.shape[1], Wp.shape[1], Wh.shape[1]
+        T = torch.empty(B, (A + 3) // 4 * 4, device=dev, dtype=F32)[:, :A]
+        _mask_gemm(x, Wa, T, bias=ba, act="relu")
+        M = _mask_gemm(T, Wp, torch.empty(B, wout, device=dev, dtype=F32), bias=bp, act="identity")
+        Y = torch.empty_like(M)
+        ops.masknet_group_fwd(inp, eg, eb, [M], [Y], normalize=norm)
+        Z = _mask_gemm(Y, Wh, torch.empty(B, H, device=dev, dtype=F32), act="identity")
+        h = torch.empty_like(Z)
+        ops.masknet_row_fwd(Z, g, b, h)
+        ctx.save_for_backward(x, inp, Wa, Wp, Wh, g, b, T, M, Y, Z, *((eg, eb) if norm else ()))
+        ctx.norm = norm
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        x, inp, Wa, Wp, Wh, g, b, T, M, Y, Z, *e = ctx.saved_tensors
+        B, dev, H = x.shape[0], x.device, Z.shape[1]
+        dh = dh.contiguous()
+        dZ, dg, db = torch.empty_like(Z), torch.empty_like(g), torch.empty_like(b)
+        ops.masknet_row_bwd(Z, g, b, dh, dZ, dg, db,
+                            torch.empty(max(4, ops.masknet_row_bwd_workspace(B, H)), device=dev, dtype=F32))
+        dWh = _mask_wgrad(Y, dZ)
+        dY = _mask_gemm(dZ, Wh, torch.empty_like(Y), transposed=True, epilogue=ops.DENSE_ADD)
+        dinp = torch.empty_like(inp)
+        deg = deb = None
+        if ctx.norm:
+            deg, deb = torch.empty_like(e[0]), torch.empty_like(e[1])
+            ws = torch.empty(max(4, ops.masknet_group_bwd_workspace(*inp.shape)), device=dev, dtype=F32)
+            ops.masknet_group_bwd(inp, e[0], e[1], [M], [dY], [dY], dinp, deg, deb, ws)
+        else:
+            ops.masknet_group_bwd(inp, None, None, [M], [dY], [dY], dinp, normalize=False)
+        dM = dY  # (in place)
+        dbp, dba = torch.empty(Wp.shape[1], device=dev, dtype=F32), torch.empty(Wa.shape[1], device=dev, dtype=F32)
+        dWp = _mask_wgrad(T, dM, dbp)
+        dT = torch.empty(B, (T.shape[1] + 3) // 4 * 4, device=dev, dtype=F32)[:, : T.shape[1]]
+        _mask_gemm(dM, Wp, dT, transposed=True, epilogue=ops.DENSE_MUL_ACTGRAD, act="relu", aux1=T)
+        dWa = _mask_wgrad(x, dT, dba)
+        dx = _mask_gemm(dT, Wa, torch.empty_like(x), transposed=True, epilogue=ops.DENSE_ADD)
+        return dx, dinp, dWa, dba, dWp, dbp, dWh, dg, db, deg, deb
+
+
+class MaskBlock:
+    """MaskNet's block (arXiv 2102.07619; nothing in the reference implements it):
+    MaskBlock(variables, hidden_units, reduction_ratio, l2_reg, prefix)(x [B,K], inputs) -> [B, hidden_units] =
+    relu(LN((mask(x) o V) hidden_weights)), mask(x) = relu(x agg_weights + agg_bias) proj_weights + proj_bias with
+    A = max(1, round(reduction_ratio * width of V)) aggregation units.  inputs [B,F,D] (the embedding rows): V is their
+    per-field LayerNorm with the SHARED variables ln_emb_gamma / ln_emb_beta [F,D]; inputs [B,H'] (a previous
+    block's output): V = inputs.  Variables {prefix}agg_weights / agg_bias / proj_weights / proj_bias /
+    hidden_weights / ln_gamma / ln_beta, created on first use (glorot weights, zero biases, unit gains);
+    `.weights`, `.l2()` over the three weight matrices."""
+
+    display_name = "MaskBlock"
+    NAMES = ("agg_weights", "agg_bias", "proj_weights", "proj_bias", "hidden_weights", "ln_gamma", "ln_beta")
+    L2_NAMES = ("agg_weights", "proj_weights", "hidden_weights")
+
+    def __init__(self, variables, hidden_units=64, reduction_ratio=2.0, l2_reg=0.0, prefix="block1_", seed=2019):
+        if not ops.masknet_row_supported(hidden_units):
+            raise ValueError(f"MaskBlock: hidden_units={hidden_units} must be a multiple of 4 in 8..2048")
+        if not reduction_ratio > 0:
+            raise ValueError(f"MaskBlock: reduction_ratio={reduction_ratio} must be greater than 0")
+        self.variables, self.H, self.ratio, self.l2_reg = variables, int(hidden_units), float(reduction_ratio), l2_reg
+        self.prefix, self.seed = prefix, seed
+
+    def _upsert_variables(self, K, wout, emb_shape):
+        v, pre, H = self.variables, self.prefix, self.H
+        A = max(1, round(self.ratio * wout))
+        made = {"agg_weights": lambda: glorot_normal([K, A], self.seed), "agg_bias": lambda: torch.zeros(A),
+                "proj_weights": lambda: glorot_normal([A, wout], self.seed + 1),
+                "proj_bias": lambda: torch.zeros(wout),
+                "hidden_weights": lambda: glorot_normal([wout, H], self.seed + 2),
+                "ln_gamma": lambda: torch.ones(H), "ln_beta": lambda: torch.zeros(H)}
+        for n in self.NAMES:
+            if pre + n not in v:
+                v[pre + n] = _leaf(made[n]())
+        if emb_shape is not None:
+            if "ln_emb_gamma" not in v:
+                v["ln_emb_gamma"] = _leaf(torch.ones(emb_shape))
+            if "ln_emb_beta" not in v:
+                v["ln_emb_beta"] = _leaf(torch.zeros(emb_shape))
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.NAMES]
+
+    def __call__(self, x, inputs):
+        if x.dim() != 2 or inputs.dim() not in (2, 3) or inputs.shape[0] != x.shape[0]:
+            raise ValueError(f"MaskBlock: x [B,K] and inputs [B,F,D] or [B,H] expected, got {tuple(x.shape)} and "
+                             f"{tuple(inputs.shape)}")
+        emb = inputs.dim() == 3
+        F, D = (inputs.shape[1], inputs.shape[2]) if emb else (1, inputs.shape[1])
+        if not ops.masknet_group_supported(F, D, 1, emb):
+            raise ValueError(f"MaskBlock: inputs {tuple(inputs.shape)} unsupported (1..40 fields of 8/16/32, or a "
+                             "width that is a multiple of 4 in 8..2048)")
+        self._upsert_variables(x.shape[1], F * D, (F, D) if emb else None)
+        ln = (self.variables["ln_emb_gamma"], self.variables["ln_emb_beta"]) if emb else (None, None)
+        return _MaskBlockFn.apply(x, inputs, *self.weights, *ln)
+
+    def l2(self):
+        return sum(self.l2_reg * 0.5 * self.variables[self.prefix + n].square().sum() for n in self.L2_NAMES)
+
+
+# ------------------------------------------------------------------------------------------------
 # prediction + loss
 # ------------------------------------------------------------------------------------------------
 class _SigmoidFn(torch.autograd.Function):
@@ -1201,5 +1334,5 @@ def create_loss(y, pred, task="classification"):
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
            "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "CrossNetMix", "AFMLayer", "InteractingLayer",
-           "FieldPairInteraction", "PredictionLayer",
+           "FieldPairInteraction", "MaskBlock", "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
