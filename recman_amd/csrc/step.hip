@@ -26,6 +26,10 @@
 //    g*S for the workers' backward, and accumulates every small gradient (dW1 on the matrix pipe, db0, db1, d w_out,
 //    sum g, g^T xd) in registers.  It also turns the ids into row numbers two tiles ahead (the workers' DMA addresses)
 //    and stages the dense inputs / labels.
+//  * memory is waited for by count, never drained: the tile barrier waits for LDS only (tile_barrier), the workers'
+//    entry loads and the head's prefetch loads are asm statements behind hand-counted s_waitcnt vmcnt(N) (entry_load),
+//    and every wave issues the same vector-memory operations in every segment so that each count is one constant
+//    (derived where it is used).  The tile loops hold no s_waitcnt vmcnt(0).
 //  * one workgroup barrier per tile.  Segment s (between barriers s-1 and s): workers run backward(s-2) + the DMAs
 //    of tile s+1, then forward(s); the head runs epilogue(s-1) meanwhile.  forward(s) -> [barrier] -> epilogue(s) ->
 //    [barrier] -> backward(s): the head's serial chain (32 dependent MFMAs + the loss) always overlaps the workers'
@@ -137,12 +141,28 @@ __device__ __forceinline__ f32x4 mfma16w(float a, float b, f32x4 c) {  // the wo
 __device__ __forceinline__ int swz(int r) { return ((r >> 3) & 1) * 3; }
 
 // One LDS-DMA piece: lane l's 16 bytes at src land at LDS address lds_dst + 16 l (lds_dst wave-uniform).  Through the
-// builtin, so that hipcc counts it among the wave's vector-memory operations (its own s_waitcnt for the worker's
-// register loads stay exact); hipcc does NOT order LDS reads behind it - that is wait_vm's job.
+// builtin (hipcc sets M0); hipcc does NOT order LDS reads behind it - that is wait_vm's job.
 template <bool NT>
 __device__ __forceinline__ void dma16(const char *src, char *lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                    (__attribute__((address_space(3))) void *)lds_dst, 16, 0, NT ? 2 : 0);
+}
+
+// The workers' bias / linear entry loads: a register load that hipcc must NOT count.  While an LDS-DMA is pending,
+// hipcc's wait for any counted register load is s_waitcnt vmcnt(0) (it takes the counter for out of order as soon as
+// LDS-DMAs, loads and stores are pending together), which drains the rows just requested.  So the load is an asm
+// statement, and entry_wait - the counted wait, naming the register "+v" - stands in front of its only consumer.
+// Between the two hipcc believes the register already holds the value: it must not read, copy or spill it there.
+// The worker keeps the four registers dead between use and reload (see the D phase); check the emitted code of a
+// new compiler for a v_mov or a scratch access of them between the load and the wait.
+template <class T>
+__device__ __forceinline__ void entry_load(T &dst, const void *src) {
+  static_assert(sizeof(T) == 4, "one dword");
+  asm volatile("global_load_dword %0, %1, off" : "=v"(dst) : "v"(src) : "memory");
+}
+template <int YOUNGER>
+__device__ __forceinline__ void entry_wait(float &v) {
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "n"(YOUNGER) : "memory");
 }
 
 // waits until at most `younger` (0..24) of this wave's vector-memory operations are outstanding
@@ -154,6 +174,21 @@ __device__ __forceinline__ void wait_vm(int younger) {
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 #undef RM_WV
+}
+
+// The tile loops' workgroup barrier.  It waits for this wave's LDS operations only (lgkmcnt), NOT for its vector memory:
+// __syncthreads() puts s_waitcnt vmcnt(0) in front of s_barrier while an LDS-DMA is pending, which made every worker
+// await the rows it had just requested for the NEXT tile, and its d_rows stores, in the segment that issued them.
+// Invariant that makes the LDS-only wait sufficient: everything that crosses waves at this barrier is written with
+// ds_write by the wave that owns it - worker -> head: the partial sums (oPart); head -> workers: the published dh0 / g
+// / g*S (oPub), the row numbers (oRow), the dense ring (oDense), the labels (oY, head only).  x never crosses waves:
+// a DMA's rows are read by the wave that issued it alone, behind that wave's own counted wait_vm(); the global stores
+// (d_rows, logit, pred, dlogit) are read by nobody in this kernel.  The clobbers keep hipcc from moving LDS accesses
+// across either instruction.
+__device__ __forceinline__ void tile_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
 }
 
 // Sum over the 4 lanes (n, 0..3) of an example = the xor-16 / xor-32 butterfly, on the gfx950 permlane swaps (VALU;
@@ -242,16 +277,39 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
     rp[0][j] = rp[1][j] = rp[2][j] = rp[3][j] = 0;
     lmask[j] = (PACKED && a.lin_mask != nullptr && sx[j]) ? a.lin_mask[fld[j]] : 1.f;
   }
+  // ---- the two counted waits of a worker.  The tile barrier does not wait for vector memory (tile_barrier) and hipcc
+  // counts none of the worker's operations that it could wait for (the DMAs and stores have no register result, the
+  // entry loads are asm), so these two counts are ALL that stands between a consumer and data still in flight.
+  // A worker issues the SAME vector-memory operations in EVERY segment, in this program order (E_j = slot j's entry
+  // load, D_j = its row DMA, both of tile s + 1; S_j = slot j's d_rows store of tile s - 2, SP instructions: 1, or 2
+  // when PACKED (row + tail); asm volatile / sched_barrier(0) pin the order):
+  //     E_0 D_0 | E_1 D_1 S_0 | E_2 D_2 S_1 | E_3 D_3 S_2 | S_3            = 8 + 4 SP operations per segment
+  // Segments without a tile s + 1 fetch row 0 (DMA into the sink), segments without a backward store into a buffer
+  // resource of zero records, empty slots do both: the sequence never changes - fill (s = -2 ..), steady state and
+  // drain alike - and both counts are constants.  vmcnt retires in issue order: "at most N outstanding" = everything
+  // but the youngest N has landed.
+  //  * kYoungerE, in front of the use of sdv[j] at the top of slot j (before E_j of this segment is issued).  Behind
+  //    E_j of the previous segment:  D_j, the pairs j + 1 .. 3 (2 (3 - j)) and the stores S_max(j-1,0) .. S_3
+  //    (4 - max(j - 1, 0)) of that segment; the pairs 0 .. j - 1 (2 j) and the stores S_0 .. S_(j-2) (max(j - 1, 0)) of
+  //    this one:  1 + 2 (3 - j) + 2 j + 4 SP = 7 + 4 SP for every j  (11; PACKED 15).
+  //  * kYounger, in front of forward(s), which reads the rows that D_0 .. D_3 of segment s - 1 fetched.  Behind D_3:
+  //    S_2 S_3 of segment s - 1 (2 SP) and all of segment s (8 + 4 SP):  8 + 6 SP  (14; PACKED 20).
+  // (Scratch reloads of a spilling build would be vector-memory operations too: more operations behind the awaited
+  // one only make the wait retire more.  The ablation builds drop operations and count wrongly - as their results are.)
+  constexpr int kSP = PACKED ? 2 : 1;
+  constexpr int kYoungerE = 7 + 4 * kSP, kYounger = 8 + 6 * kSP;
+  static_assert(kYounger <= 24, "wait_vm's range");
   ST_DECL;
   ST_ADD(0);  // prologue
 
   for (int s = -2; s <= T + 1; ++s) {
     const bool hasB = s - 2 >= 0 && s - 2 < T;  // backward of tile s - 2 (4 d_rows stores)
     const bool hasD = s + 1 >= 0 && s + 1 < T;  // rows of tile s + 1 (4 DMAs + 4 entry loads)
-    // ---- the bias / linear entries of tile s (loaded a segment ago), before their registers are loaded again
+    // ---- the bias / linear entries of tile s (loaded a segment ago) are summed slot by slot in the D phase below,
+    // each right before its register is loaded again: the register is then dead between its use and its reload, no
+    // loaded value is copied on the loop's back-edge (such a copy made hipcc await ALL vector memory there), and
+    // hipcc's own wait in front of each use is a counted one (same order of the four additions as before)
     float side_sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < kSlots; ++j) side_sum += sx[j] ? sdv[j] : 0.f;
     // ------------------------------------------------------------ backward of tile s - 2, rows of tile s + 1
     // Phases WITHOUT per-slot branches (one basic block each, so that hipcc interleaves the slots' MFMA chains and
     // keeps their LDS reads in flight together): R read everything the backward needs of the 4 slots, D issue the
@@ -261,8 +319,11 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
       const int tb = s - 2, td = s + 1;
       const char *pub = smem + oPub + (tb & 1) * kPubB;
       char *xd = smem + oX + ((td + 3) % 3) * kXBufB;  // (the same buffer: tile s + 1 replaces tile s - 2)
-      f32x4 dhB[2], gS, e4[kSlots];
-      float dT[2][4], g, col[kSlots][4];
+      // (without a backward the S phase still runs and stores - into a buffer resource of zero records: zeros here)
+      f32x4 dhB[2], gS = f32x4{0.f, 0.f, 0.f, 0.f}, e4[kSlots];
+      float dT[2][4], g = 0.f, col[kSlots][4];
+#pragma unroll
+      for (int j = 0; j < kSlots; ++j) e4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (hasB) {  // ---- R
 #pragma unroll
         for (int j = 0; j < kSlots; ++j) {
@@ -295,7 +356,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           rp[1][j] = rp[0][j];
         }
       }
-      if (hasD) {
+      {  // (without a tile s + 1: whatever the buffer holds - such row numbers are never used)
         const unsigned *rowid = reinterpret_cast<const unsigned *>(smem + oRow + (td & 1) * kRowB);
 #pragma unroll
         for (int j = 0; j < kSlots; ++j) {
@@ -331,16 +392,21 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
       f32x4 acc[kSlots];
 #pragma unroll
       for (int j = 0; j < kSlots; ++j) {
-        if (hasD) {
-          // empty slots fetch row 0 into the sink: every worker issues the same operations per tile, so the
-          // hand-counted wait of the forward holds for all of them
-          const char *row = a.table + ((RM_STEP_ABL & 4) || !sx[j] ? 0 : (int64_t)rid[j] * a.row_bytes);
-          if (!(RM_STEP_ABL & 8)) dma16<NT>(row + piece, sx[j] ? xd + fld[j] * kSlotB : smem + oJunk);
-          if (!(RM_STEP_ABL & 1)) sdv[j] = *reinterpret_cast<const float *>(row + side_off);
+        entry_wait<kYoungerE>(sdv[j]);
+        side_sum += sx[j] ? sdv[j] : 0.f;
+        asm volatile("" : "+v"(side_sum)::"memory");  // (the sum is taken HERE, not sunk into the forward behind the reload)
+        {
+          // empty slots, and every slot of a segment without a tile s + 1, fetch row 0 into the sink: every worker
+          // issues the SAME vector-memory operations in EVERY segment, so the hand-counted wait of the forward is one
+          // constant, and hipcc's own counted waits (for sdv) see one path through the loop
+          const bool live = sx[j] && hasD;
+          const char *row = a.table + ((RM_STEP_ABL & 4) || !live ? 0 : (int64_t)rid[j] * a.row_bytes);
+          if (!(RM_STEP_ABL & 1)) entry_load(sdv[j], row + side_off);
+          if (!(RM_STEP_ABL & 8)) dma16<NT>(row + piece, live ? xd + fld[j] * kSlotB : smem + oJunk);
         }
         __builtin_amdgcn_sched_barrier(0);
+        acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (hasB) {
-          acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int es = 0; es < 4; ++es) {
             dw[j][0] = mfma16w(col[j][es], dT[0][es], dw[j][0]);
@@ -350,7 +416,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (hasB && j > 0) {
+        if (j > 0) {
           // the PREVIOUS slot's row gradient: dLoss/dE = dX + g (S - E)   (FM second order, layers.py:468-476);
           // slots without an embedding field: out of range, the store is dropped - every tile issues 4 of them
           const int i = j - 1;
@@ -362,7 +428,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           store_row(i, o);
         }
       }
-      if (hasB) {
+      {
         const int i = kSlots - 1;
         f32x4 o;
         o.x = acc[i].x + (gS.x - g * e4[i].x);
@@ -375,11 +441,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
     ST_ADD(6);  // M + S
     // ------------------------------------------------------------ forward of tile s
     if (s >= 0 && s < T) {
-      // the tile's last DMA (slot 3, segment s - 1) is followed by that slot's entry load and the segment's last two
-      // stores (slots 2 and 3), then by this segment's operations
-      constexpr int SP = PACKED ? 2 : 1;  // stores per slot
-      const int younger = 1 + ((s - 3 >= 0) ? 2 * SP : 0) + 8 * (hasD ? 1 : 0) + 4 * SP * (hasB ? 1 : 0);
-      wait_vm(younger);
+      wait_vm(kYounger);
       ST_ADD(3);  // wait for the tile's rows
       f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0, S = acc0, Q = acc0;
       f32x4 x4[kSlots];
@@ -407,9 +469,11 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
       *reinterpret_cast<float *>(part + kPartSd + lane * 4) = side_sum;
     }
     ST_ADD(4);  // forward
-    __syncthreads();
+    tile_barrier();
     ST_ADD(5);  // barrier
   }
+  // the last segment's entry loads are still in flight: their registers must not be reused before they land
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // ---- this block's dW0 slab: every worker owns the rows of its fields
 #pragma unroll
   for (int j = 0; j < kSlots; ++j)
@@ -474,10 +538,17 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
     const int64_t b = ((int64_t)blockIdx.x + t * tstride) * 16 + n;
     return b < B ? b : B - 1;
   };
-  // prefetch registers.  Everything about this lane's fields q + 4 j is UNCONDITIONAL: fields past F read field
-  // F - 1 again and land in row-number slots nobody reads (per-lane branches around the loads made hipcc serialise
-  // them behind s_waitcnt vmcnt(0): 7 exposed HBM round trips per tile).  Loaded values are used RAW a segment
-  // later: a select or conversion next to a load waits for it - and for every load issued before it.
+  // prefetch registers, loaded a segment before their use by loads that hipcc does not count (entry_load): with
+  // counted loads and the output stores pending together, hipcc's wait in front of every use is s_waitcnt vmcnt(0),
+  // i.e. for the stores just issued too.  The head issues the SAME vector-memory operations in EVERY segment, in this
+  // program order - the three output stores (logit, pred, dlogit; into buffer resources of zero records without an
+  // epilogue), then 4 dense columns, the label, 7 ids:
+  //     St St St | [wait A: dense + label] [wait B: ids] | Dn Dn Dn Dn Y | Id x 7        = 15 operations per segment
+  // Everything about this lane's fields q + 4 j is UNCONDITIONAL: fields past F read field F - 1 again and land in
+  // row-number slots nobody reads, tiles past the block's last read example B - 1 (ex_of clamps), without dense
+  // inputs the four columns read w_out[0].  Behind the label Y of the previous segment: its 7 ids and this segment's
+  // 3 stores = 10 (wait A); behind the last id: the 3 stores (wait B).  The prologue's ids (tile 0) are waited for in
+  // the first segment by the same count B.
   unsigned idr[7];  // ids (low words: row numbers < 2^32) of tile s + 2, loaded one segment earlier
   float dnr[4];     // dense columns 4 q .. 4 q + 3 of tile s + 1
   unsigned yr = 0;  // ... and its label (low word of the int64 / the float's bits)
@@ -488,15 +559,19 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
   auto load_ids = [&](int t) {
     const unsigned *p = reinterpret_cast<const unsigned *>(a.idx + ex_of(t) * F);
 #pragma unroll
-    for (int j = 0; j < 7; ++j) idr[j] = p[2 * (q + 4 * j < F ? q + 4 * j : F - 1)];
+    for (int j = 0; j < 7; ++j) entry_load(idr[j], p + 2 * (q + 4 * j < F ? q + 4 * j : F - 1));
   };
-  if (T > 0) load_ids(0);
+  // (the two scalars above are waited for HERE: a counted load first used inside the loop is a vmcnt(0) per tile)
+  asm volatile("" ::"v"(w0o), "v"(lw0) : "memory");
+  load_ids(0);
   ST_DECL;
   ST_ADD(0);
 
   for (int s = -2; s <= T + 1; ++s) {
+    const bool epi = s - 1 >= 0 && s - 1 < T;
+    float o_z = 0.f, o_p = 0.f, o_g = 0.f;  // logit, pred, dlogit of this lane's example
     // ------------------------------------------------------------ epilogue of tile s - 1
-    if (s - 1 >= 0 && s - 1 < T) {
+    if (epi) {
       const int t = s - 1;
       const int64_t bex = ((int64_t)blockIdx.x + t * tstride) * 16 + n;
       const bool valid = bex < B;
@@ -572,12 +647,10 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
       float gb = dz * (1.0f / (float)B);
       gb *= a.grad_scale;
       gb = valid ? gb : 0.f;
-      if (valid && q == 0) {
-        a.logit[bex] = z;
-        a.pred[bex] = p;
-        a.dlogit[bex] = gb;
-        loss_acc += lt;
-      }
+      o_z = z;
+      o_p = p;
+      o_g = gb;
+      if (valid && q == 0) loss_acc += lt;
       ST_ADD(2);  // layer 1, logits, loss
       // dh chain
       float dh1[2][4], dh0[2][4];
@@ -641,9 +714,22 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
       dxd[3] += gb * dn4.w;
     }
     ST_ADD(4);  // small gradients
+    // ------------------------------------------------------------ the tile's outputs: unconditional stores (a
+    // divergent `if (valid && q == 0)` around them is a branch, and a path without them - no constant count).  The
+    // tile's 16 examples through a buffer resource of the tile's valid rows: examples past B, the lanes q > 0 and
+    // segments without an epilogue are out of range, the store is dropped
+    {
+      const int64_t ex0 = epi ? ((int64_t)blockIdx.x + (s - 1) * tstride) * 16 : 0;
+      const int64_t left = B - ex0;
+      const int nb = epi ? 4 * (left < 16 ? (int)left : 16) : 0;
+      const int off = q == 0 ? 4 * n : 0x7ffffff0;
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o_z), __builtin_amdgcn_make_buffer_rsrc(a.logit + ex0, 0, nb, 0x00020000), off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o_p), __builtin_amdgcn_make_buffer_rsrc(a.pred + ex0, 0, nb, 0x00020000), off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o_g), __builtin_amdgcn_make_buffer_rsrc(a.dlogit + ex0, 0, nb, 0x00020000), off, 0, 0);
+    }
     // ------------------------------------------------------------ the prefetch chain: FIRST everything that consumes
-    // registers loaded one segment ago, THEN this segment's loads (a conservative s_waitcnt vmcnt(0) in front of a
-    // consumer must not find loads that have only just been issued)
+    // registers loaded one segment ago (behind the two counted waits derived above), THEN this segment's loads
+    asm volatile("s_waitcnt vmcnt(10)" : "+v"(dnr[0]), "+v"(dnr[1]), "+v"(dnr[2]), "+v"(dnr[3]), "+v"(yr)::"memory");
     if (s + 1 >= 0 && s + 1 < T) {  // dense inputs / label of tile s + 1 -> LDS (columns past Dn masked here)
       const int t = s + 1;
       if (Dn > 0)
@@ -653,6 +739,8 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
       if (q == 0)
         *reinterpret_cast<float *>(smem + oY + ((t & 3) * 16 + n) * 4) = a.y ? (float)(int)yr : __uint_as_float(yr);
     }
+    asm volatile("s_waitcnt vmcnt(3)"
+                 : "+v"(idr[0]), "+v"(idr[1]), "+v"(idr[2]), "+v"(idr[3]), "+v"(idr[4]), "+v"(idr[5]), "+v"(idr[6])::"memory");
     if (s + 2 < T) {  // row numbers of tile s + 2 -> LDS (slots >= F: never read)
       unsigned *rowid = reinterpret_cast<unsigned *>(smem + oRow + ((s + 2) & 1) * kRowB);
 #pragma unroll
@@ -660,22 +748,22 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
         rowid[(q + 4 * j) * 16 + n] = idr[j] + *reinterpret_cast<const unsigned *>(par + kParFo + (q + 4 * j) * 4);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (s + 2 >= 0 && s + 2 < T) {
+    {
       const int64_t b = ex_of(s + 2);
-      if (Dn > 0) {
-        const float *dp = a.dense + b * Dn;
+      const float *dp = Dn > 0 ? a.dense + b * Dn : a.w_out;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dnr[i] = dp[4 * q + i < Dn ? 4 * q + i : 0];
-      }
+      for (int i = 0; i < 4; ++i) entry_load(dnr[i], dp + (4 * q + i < Dn ? 4 * q + i : 0));
       const unsigned *yp = a.y ? reinterpret_cast<const unsigned *>(a.y + b) : reinterpret_cast<const unsigned *>(a.y_f + b);
-      yr = *yp;
+      entry_load(yr, yp);
     }
-    if (s + 3 < T) load_ids(s + 3);
+    load_ids(s + 3);
     ST_ADD(6);  // prefetch chain
-    __syncthreads();
+    tile_barrier();
     ST_ADD(5);  // barrier
   }
 
+  // the last segment's prefetch loads are still in flight: their registers must not be reused before they land
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // ---- this block's partial of the small gradients and the loss
   float *sgp = a.sg_part + (int64_t)blockIdx.x * kRmSgStride;
 #pragma unroll
