@@ -24,12 +24,12 @@
 // LDS, in lane order.  The parameter gradients dW = sum P dz^T, db = sum dz, dh = sum ds relu(z) are a small GEMM
 // over the pass's pairs: every lane owns D T / 64 elements of dW (+ a db / dh column) in registers for the whole
 // kernel, the pass's P and dz rows go through LDS.  Per-block partial sums land in the workspace and one
-// finishing kernel adds them in block order: no float atomics anywhere, two runs are bit-equal.
+// finishing kernel (rm_sum_partials) adds them in block order: no float atomics anywhere, two runs are bit-equal.
 #include <math.h>
 
 #include <type_traits>
 
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -442,20 +442,6 @@ __global__ __launch_bounds__(64) void afm_bwd_kernel(
   if (lane < D) out[D * T + 2 * T + lane] = dpacc;
 }
 
-// fixed-order sum of the per-block partials
-__global__ void afm_finish_kernel(const float *__restrict__ part, int nblk, int D, int T, float *__restrict__ dW,
-                                  float *__restrict__ db, float *__restrict__ dh, float *__restrict__ dp) {
-  const int n = D * T + 2 * T + D;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < nblk; ++k) s += part[(int64_t)k * n + e];
-  if (e < D * T) dW[e] = s;
-  else if (e < D * T + T) db[e - D * T] = s;
-  else if (e < D * T + 2 * T) dh[e - D * T - T] = s;
-  else dp[e - D * T - 2 * T] = s;
-}
-
 int afm_check(const char *fn, int64_t B, int F, int D, int T) {
   RM_REQUIRE(B >= 0, "%s: bad batch size", fn);
   RM_REQUIRE(afm_d_ok(D), "%s: D=%d unsupported (8, 16, 32, 64)", fn, D);
@@ -540,8 +526,8 @@ extern "C" int rm_afm_bwd(const float *E, const float *W, const float *b, const 
 #undef RM_AFM_BWD
     RM_CHECK_LAUNCH("rm_afm_bwd");
   }
-  const int n = D * T + 2 * T + D;
-  hipLaunchKernelGGL(afm_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, part, nblk, D, T, dW, db, dh, dp);
+  // fixed-order sum of the per-block partials (B == 0: no blocks, all +0.0)
+  rm_sum_partials(part, nblk, D * T + 2 * T + D, rm_sum_dsts(dW, D * T, db, T, dh, T, dp, D), st);
   RM_CHECK_LAUNCH("rm_afm_bwd (finish)");
   return RM_OK;
 }

@@ -29,7 +29,7 @@
 // No float atomics anywhere, every sum in a fixed order: two runs are bit-equal.
 #include <math.h>
 
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -533,14 +533,9 @@ extern "C" int rm_asp_fwd(const float *rows, int64_t LD, int D, int64_t row0, co
     asp_pack(d, W0, b0, W1, b1, w, w0, workspace, st);
     const AspCfg c = asp_cfg(d);
     dim3 grid(asp_blocks(nnz, c.TP));
-#define RM_ASP_SCORE(WL_)                                                                                       \
-  {                                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(asp_score_kernel<WL_>),                           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem);                         \
-    hipLaunchKernelGGL((asp_score_kernel<WL_>), grid, dim3(kThreads), c.smem, st, d, c.TP, in,                  \
-                       (const float *)workspace, act, scores);                                                  \
-  }
-    if (c.wlds) RM_ASP_SCORE(true) else RM_ASP_SCORE(false)
+#define RM_ASP_SCORE(WL_) \
+  rm_launch_lds(asp_score_kernel<WL_>, grid, dim3(kThreads), c.smem, st, d, c.TP, in, workspace, act, scores)
+    if (c.wlds) RM_ASP_SCORE(true); else RM_ASP_SCORE(false);
 #undef RM_ASP_SCORE
     RM_CHECK_LAUNCH("rm_asp_fwd (scores)");
   }
@@ -576,13 +571,9 @@ extern "C" int rm_asp_bwd(const float *rows, int64_t LD, int D, int64_t row0, co
                        do_stride, ds, d_keys);
     RM_CHECK_LAUNCH("rm_asp_bwd (examples)");
 #define RM_ASP_BWD(WL_)                                                                                         \
-  {                                                                                                             \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(asp_bwd_tile_kernel<WL_>),                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem);                         \
-    hipLaunchKernelGGL((asp_bwd_tile_kernel<WL_>), dim3(nblk), dim3(kThreads), c.smem, st, d, c.TP, in,         \
-                       (const float *)workspace, act, (const float *)ds, d_keys, d_q, part);                    \
-  }
-    if (c.wlds) RM_ASP_BWD(true) else RM_ASP_BWD(false)
+  rm_launch_lds(asp_bwd_tile_kernel<WL_>, dim3(nblk), dim3(kThreads), c.smem, st, d, c.TP, in, workspace, act, ds, \
+                d_keys, d_q, part)
+    if (c.wlds) RM_ASP_BWD(true); else RM_ASP_BWD(false);
 #undef RM_ASP_BWD
     RM_CHECK_LAUNCH("rm_asp_bwd (tiles)");
     hipLaunchKernelGGL(asp_bwd_query_kernel, egrid, dim3(kThreads), 0, st, offsets, B, D, (const float *)d_q, d_query,

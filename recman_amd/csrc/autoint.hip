@@ -25,7 +25,7 @@
 // (16 segments, then the segments): no float atomics anywhere, two runs are bit-equal.
 #include <math.h>
 
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -422,15 +422,6 @@ __global__ __launch_bounds__(kThreads) void autoint_head_bwd_kernel(const float 
     out[k] = s;
   }
 }
-__global__ void autoint_head_finish_kernel(const float *__restrict__ seg, int K, float *__restrict__ dw,
-                                           float *__restrict__ dw0) {
-  const int n = K + 1, e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < kSeg; ++k) s += seg[(int64_t)k * n + e];
-  if (e < K) dw[e] = s;
-  else dw0[0] = s;
-}
 
 int ai_check(const char *fn, int64_t B, int F, int Din, int H, int dk) {
   RM_REQUIRE(B >= 0 && B < ((int64_t)1 << 40), "%s: bad batch size", fn);
@@ -438,12 +429,6 @@ int ai_check(const char *fn, int64_t B, int F, int Din, int H, int dk) {
              "%s: F=%d Din=%d H=%d dk=%d unsupported (1 <= F <= %d, Din in {8,16,32,64}, H in {1,2,4,8}, dk >= 4, "
              "H dk in {8,16,32,64})", fn, F, Din, H, dk, kMaxF);
   return RM_OK;
-}
-
-template <class K>
-inline void ai_allow_lds(K kernel, size_t smem) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
 }
 
 }  // namespace
@@ -469,9 +454,8 @@ extern "C" int rm_autoint_layer_fwd(const float *X, const float *Wq, const float
   dim3 grid(rm_grid_cap((B + G - 1) / G, 256 * 8));
   hipStream_t st = (hipStream_t)stream;
 #define RM_AI_FWD(DK_)                                                                                          \
-  ai_allow_lds(autoint_fwd_kernel<DK_>, smem);                                                                  \
-  hipLaunchKernelGGL((autoint_fwd_kernel<DK_>), grid, dim3(kThreads), smem, st, X, Wq, Wk, Wv, Wr, B, F, Din, H, \
-                     G, scale, Y, stats)
+  rm_launch_lds(autoint_fwd_kernel<DK_>, grid, dim3(kThreads), smem, st, X, Wq, Wk, Wv, Wr, B, F, Din, H, G, scale, Y, \
+                stats)
   switch (dk) {
     case 4: RM_AI_FWD(4); break;
     case 8: RM_AI_FWD(8); break;
@@ -513,10 +497,9 @@ extern "C" int rm_autoint_layer_bwd(const float *X, const float *Wq, const float
     const size_t smem = (size_t)ai_bwd_floats(G, F, Din, H, HD) * sizeof(float);
     const int NI = Din * HD >= kThreads ? Din * HD / kThreads : 1;
     dim3 grid(nblk);
-#define RM_AI_BWD(DK_, NI_)                                                                                       \
-  ai_allow_lds(autoint_bwd_kernel<DK_, NI_>, smem);                                                               \
-  hipLaunchKernelGGL((autoint_bwd_kernel<DK_, NI_>), grid, dim3(kThreads), smem, st, X, Wq, Wk, Wv, Wr, Y, stats, \
-                     dY, B, F, Din, H, G, scale, dX, dX_up, part)
+#define RM_AI_BWD(DK_, NI_)                                                                                        \
+  rm_launch_lds(autoint_bwd_kernel<DK_, NI_>, grid, dim3(kThreads), smem, st, X, Wq, Wk, Wv, Wr, Y, stats, dY, B, F, \
+                Din, H, G, scale, dX, dX_up, part)
 #define RM_AI_BWD_N(DK_)                     \
   switch (NI) {                              \
     case 1: RM_AI_BWD(DK_, 1); break;        \
@@ -572,7 +555,7 @@ extern "C" int rm_autoint_head_bwd(const float *Y, const float *w, const float *
     RM_CHECK_LAUNCH("rm_autoint_head_bwd");
   }
   hipLaunchKernelGGL(autoint_seg_kernel, dim3((n + 255) / 256, kSeg), dim3(256), 0, st, part, nblk, n, seg);
-  hipLaunchKernelGGL(autoint_head_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seg, K, dw, dw0);
+  rm_sum_partials(seg, kSeg, n, rm_sum_dsts(dw, K, dw0, 1), st);  // the segments, in order
   RM_CHECK_LAUNCH("rm_autoint_head_bwd (finish)");
   return RM_OK;
 }

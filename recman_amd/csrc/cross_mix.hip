@@ -20,8 +20,8 @@
 //   backward: after h and c are rebuilt the r lanes of one (example, expert) sum <dm_i, c_i> with a butterfly,
 //   dh goes to LDS beside a, and three passes over the tile follow: ds, dt (through da) and the tile's addend to
 //   dC, which a thread keeps in registers for its fixed (j, k) positions across all of the block's tiles.
-//   dC is deterministic: per-block partials in the workspace, summed in block order by a finish kernel; no atomics.
-#include "rm_common.h"
+//   dC is deterministic: per-block partials in the workspace, summed in block order (rm_sum_partials); no atomics.
+#include "rm_launch.h"
 
 namespace {
 
@@ -249,16 +249,6 @@ __global__ __launch_bounds__(kThreads) void cross_mix_bwd_kernel(const float *__
   }
 }
 
-// dC[o] = sum over the blocks' partials, in block order
-__global__ __launch_bounds__(kThreads) void cross_mix_finish_kernel(const float *__restrict__ part, int nblk, int N,
-                                                                    float *__restrict__ dC) {
-  const int o = blockIdx.x * kThreads + threadIdx.x;
-  if (o >= N) return;
-  float s = 0.f;
-  for (int b = 0; b < nblk; ++b) s += part[(int64_t)b * N + o];
-  dC[o] = s;
-}
-
 int mix_check(const char *fn, int E, int r, int64_t B) {
   RM_REQUIRE(mix_r_ok(r), "%s: r=%d unsupported (8, 16, 32, 64)", fn, r);
   RM_REQUIRE(E >= 1 && E <= 8, "%s: E=%d unsupported (1..8)", fn, E);
@@ -268,7 +258,7 @@ int mix_check(const char *fn, int E, int r, int64_t B) {
 }
 
 #define RM_MIX_STRIDE(fn, name, ld, width)                                                                  \
-  RM_REQUIRE((ld) >= (width) && (ld) <= (1 << 24), "%s: %s=%lld must be in [%d, 2^24]", fn, name, (long long)(ld), \
+  RM_REQUIRE((ld) >= (width) && (ld) <= kRmMaxStride, "%s: %s=%lld must be in [%d, 2^24]", fn, name, (long long)(ld), \
              (int)(width))
 
 }  // namespace
@@ -285,21 +275,16 @@ extern "C" int rm_cross_mix_fwd(const float *T, int64_t ldt, const float *S, int
   RM_MIX_STRIDE(fn, "lds", lds, E);
   RM_MIX_STRIDE(fn, "ldm", ldm, W);
   if (B == 0) return RM_OK;
-  RM_REQUIRE(T, "%s: T is NULL", fn);
-  RM_REQUIRE(S, "%s: S is NULL", fn);
-  RM_REQUIRE(C, "%s: C is NULL", fn);
-  RM_REQUIRE(M, "%s: M is NULL", fn);
+  RM_REQUIRE_PTR(fn, T);
+  RM_REQUIRE_PTR(fn, S);
+  RM_REQUIRE_PTR(fn, C);
+  RM_REQUIRE_PTR(fn, M);
   const int G = mix_tile(W);
   const size_t smem = ((size_t)G * W + (size_t)E * r * (r + 1) + (size_t)G * E) * sizeof(float);
   dim3 grid(mix_blocks(B, G, kFwdBlocks));
   hipStream_t st = (hipStream_t)stream;
-#define RM_MIX_FWD(R_)                                                                                   \
-  {                                                                                                      \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cross_mix_fwd_kernel<R_>),                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                    \
-    hipLaunchKernelGGL((cross_mix_fwd_kernel<R_>), grid, dim3(kThreads), smem, st, T, ldt, S, lds, C, E, B, G, M, \
-                       ldm);                                                                             \
-  }
+#define RM_MIX_FWD(R_) \
+  rm_launch_lds(cross_mix_fwd_kernel<R_>, grid, dim3(kThreads), smem, st, T, ldt, S, lds, C, E, B, G, M, ldm);
   switch (r) {
     case 8: RM_MIX_FWD(8) break;
     case 16: RM_MIX_FWD(16) break;
@@ -329,32 +314,22 @@ extern "C" int rm_cross_mix_bwd(const float *T, int64_t ldt, const float *S, int
   RM_MIX_STRIDE(fn, "lddm", lddm, W);
   RM_MIX_STRIDE(fn, "lddt", lddt, W);
   RM_MIX_STRIDE(fn, "ldds", ldds, E);
-  RM_REQUIRE(dC, "%s: dC is NULL", fn);
+  RM_REQUIRE_PTR(fn, dC);
   hipStream_t st = (hipStream_t)stream;
-  if (B == 0) {  // the sum over an empty batch
-    if (hipMemsetAsync(dC, 0, (size_t)N * sizeof(float), st) != hipSuccess) {
-      rm_set_error("%s: clearing dC failed", fn);
-      return RM_ELAUNCH;
-    }
-    return RM_OK;
-  }
-  RM_REQUIRE(T, "%s: T is NULL", fn);
-  RM_REQUIRE(S, "%s: S is NULL", fn);
-  RM_REQUIRE(C, "%s: C is NULL", fn);
-  RM_REQUIRE(dM, "%s: dM is NULL", fn);
-  RM_REQUIRE(dT, "%s: dT is NULL", fn);
-  RM_REQUIRE(dS, "%s: dS is NULL", fn);
-  RM_REQUIRE(workspace, "%s: workspace is NULL", fn);
+  if (B == 0) return rm_clear_async(fn, "dC", dC, N, st);  // the sum over an empty batch
+  RM_REQUIRE_PTR(fn, T);
+  RM_REQUIRE_PTR(fn, S);
+  RM_REQUIRE_PTR(fn, C);
+  RM_REQUIRE_PTR(fn, dM);
+  RM_REQUIRE_PTR(fn, dT);
+  RM_REQUIRE_PTR(fn, dS);
+  RM_REQUIRE_PTR(fn, workspace);
   const int G = mix_tile(W);
   const size_t smem = ((size_t)2 * G * W + (size_t)E * r * (r + 1) + (size_t)2 * G * E) * sizeof(float);
   const int nblk = mix_blocks(B, G, kBwdBlocks);
-#define RM_MIX_BWD(R_)                                                                                    \
-  {                                                                                                       \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cross_mix_bwd_kernel<R_>),                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                     \
-    hipLaunchKernelGGL((cross_mix_bwd_kernel<R_>), dim3(nblk), dim3(kThreads), smem, st, T, ldt, S, lds, C, E, B, G, \
-                       dM, lddm, dT, lddt, dS, ldds, workspace);                                          \
-  }
+#define RM_MIX_BWD(R_)                                                                                         \
+  rm_launch_lds(cross_mix_bwd_kernel<R_>, dim3(nblk), dim3(kThreads), smem, st, T, ldt, S, lds, C, E, B, G, dM, lddm, \
+                dT, lddt, dS, ldds, workspace);
   switch (r) {
     case 8: RM_MIX_BWD(8) break;
     case 16: RM_MIX_BWD(16) break;
@@ -363,8 +338,7 @@ extern "C" int rm_cross_mix_bwd(const float *T, int64_t ldt, const float *S, int
   }
 #undef RM_MIX_BWD
   RM_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(cross_mix_finish_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                     (const float *)workspace, nblk, N, dC);
+  rm_sum_partials(workspace, nblk, N, rm_sum_dsts(dC, N), st);  // dC = the blocks' partials, in block order
   RM_CHECK_LAUNCH(fn);
   return RM_OK;
 }

@@ -19,7 +19,7 @@
 //     four columns of one dV row and sums g_ij v_j over j in ascending order, skipping j = i.  d_rows and dz are
 //     written as float4.
 // No parameters, so no batch reduction: no atomics, no workspace, two runs are bit-equal.
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -152,8 +152,7 @@ int dot_check(const char *fn, int64_t B, int F, int D, int64_t ldx) {
   RM_REQUIRE(B >= 0, "%s: bad batch size", fn);
   RM_REQUIRE(dot_d_ok(D), "%s: D=%d unsupported (8, 16, 32, 64)", fn, D);
   RM_REQUIRE(F >= 1 && F <= kMaxF, "%s: F=%d unsupported (1..%d)", fn, F, kMaxF);
-  RM_REQUIRE(ldx >= D + dot_pairs(F), "%s: ldx=%lld < D + F(F+1)/2 = %d", fn, (long long)ldx, D + dot_pairs(F));
-  RM_REQUIRE(ldx <= (1 << 24), "%s: ldx=%lld too large", fn, (long long)ldx);
+  RM_REQUIRE_STRIDE(fn, "ldx", ldx, D + dot_pairs(F), "D + F(F+1)/2");
   return RM_OK;
 }
 

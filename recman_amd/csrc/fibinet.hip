@@ -29,7 +29,7 @@
 //     a second pass adds dU W^T, folds the gated branch into dE and sums <dV_f, E_f> over a field's D lanes; the
 //     gate's backward runs per example; dE leaves as float4.  The tile's addends to the four parameter gradients go
 //     into the block's own accumulators - in LDS when they fit what the budget leaves, else in the block's slice of
-//     the workspace (each element always touched by the same thread) - and a finish kernel sums the blocks' partials
+//     the workspace (each element always touched by the same thread) - and rm_sum_partials sums the blocks' partials
 //     in block order.  No atomics: two runs are bit-equal.
 // Precision.  X keeps the D axis, so a left product U_i[d] that cancels is multiplied by a row entry that need not be
 // small: summed in float32, a pair whose |X| is far above 1 (an example with large rows) carries the cancellation as
@@ -37,7 +37,7 @@
 // products are therefore summed in float64 and rounded to float once: 2 F D D float64 multiply-adds per example
 // (13 312 at F = 26, D = 16) beside 2 P D floats written (10 400).  Everything else is float32 fmaf chains.
 // Everything is vector-ALU work: D x D products per field against 2 P D floats of X / dX per example.
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -395,21 +395,6 @@ __global__ __launch_bounds__(kThreads) void fibinet_bwd_kernel(const float *__re
   }
 }
 
-// the four gradients = the sum over the blocks' partials [dWb | dWsb | dW1 | dW2], in block order
-__global__ __launch_bounds__(kThreads) void fibinet_finish_kernel(const float *__restrict__ part, int nblk, int NW,
-                                                                  int FR, float *__restrict__ dWb,
-                                                                  float *__restrict__ dWsb, float *__restrict__ dW1,
-                                                                  float *__restrict__ dW2) {
-  const int o = blockIdx.x * kThreads + threadIdx.x, N = 2 * NW + 2 * FR;
-  if (o >= N) return;
-  float s = 0.f;
-  for (int b = 0; b < nblk; ++b) s += part[(int64_t)b * N + o];
-  if (o < NW) dWb[o] = s;
-  else if (o < 2 * NW) dWsb[o - NW] = s;
-  else if (o < 2 * NW + FR) dW1[o - 2 * NW] = s;
-  else dW2[o - 2 * NW - FR] = s;
-}
-
 int fib_check(const char *fn, int64_t B, int F, int D, int R, int type, const char *ldname, int64_t ld) {
   RM_REQUIRE(B >= 0, "%s: bad batch size", fn);
   RM_REQUIRE(fib_d_ok(D), "%s: D=%d unsupported (8, 16, 32)", fn, D);
@@ -417,9 +402,7 @@ int fib_check(const char *fn, int64_t B, int F, int D, int R, int type, const ch
   RM_REQUIRE(R >= 1 && R <= F, "%s: R=%d unsupported (1..F)", fn, R);
   RM_REQUIRE(type == RM_FIBINET_ALL || type == RM_FIBINET_EACH, "%s: type=%d unsupported (RM_FIBINET_ALL, RM_FIBINET_EACH)",
              fn, type);
-  const int W = 2 * fib_pairs(F) * D;
-  RM_REQUIRE(ld >= W, "%s: %s=%lld < 2 P D = %d", fn, ldname, (long long)ld, W);
-  RM_REQUIRE(ld <= (1 << 24), "%s: %s=%lld too large", fn, ldname, (long long)ld);
+  RM_REQUIRE_STRIDE(fn, ldname, ld, 2 * fib_pairs(F) * D, "2 P D");
   return RM_OK;
 }
 
@@ -438,24 +421,20 @@ extern "C" int rm_fibinet_fwd(const float *E, const float *W1, const float *W2, 
   int rc = fib_check(fn, B, F, D, R, type, "ldx", ldx);
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
-  RM_REQUIRE(E, "%s: E is NULL", fn);
-  RM_REQUIRE(W1, "%s: W1 is NULL", fn);
-  RM_REQUIRE(W2, "%s: W2 is NULL", fn);
-  RM_REQUIRE(Wb, "%s: Wb is NULL", fn);
-  RM_REQUIRE(Wsb, "%s: Wsb is NULL", fn);
-  RM_REQUIRE(X, "%s: X is NULL", fn);
+  RM_REQUIRE_PTR(fn, E);
+  RM_REQUIRE_PTR(fn, W1);
+  RM_REQUIRE_PTR(fn, W2);
+  RM_REQUIRE_PTR(fn, Wb);
+  RM_REQUIRE_PTR(fn, Wsb);
+  RM_REQUIRE_PTR(fn, X);
   RM_REQUIRE(rm_aligned16(E), "%s: E must be 16-byte aligned", fn);
   const FibPlan p = fib_plan_fwd(F, D, R, type);
   const int nW = fib_nw(F, type);
   dim3 grid(fib_blocks(B, p.G, kFwdBlocks));
   hipStream_t st = (hipStream_t)stream;
-#define RM_FIB_FWD2(D_, WL_)                                                                                     \
-  {                                                                                                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fibinet_fwd_kernel<D_, WL_>),                       \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.smem);                          \
-    hipLaunchKernelGGL((fibinet_fwd_kernel<D_, WL_>), grid, dim3(kThreads), p.smem, st, E, W1, W2, Wb, Wsb, B, F, R, \
-                       nW, p.G, X, ldx);                                                                         \
-  }
+#define RM_FIB_FWD2(D_, WL_)                                                                                       \
+  rm_launch_lds(fibinet_fwd_kernel<D_, WL_>, grid, dim3(kThreads), p.smem, st, E, W1, W2, Wb, Wsb, B, F, R, nW, p.G, \
+                X, ldx);
 #define RM_FIB_FWD(D_) \
   if (p.w_lds) RM_FIB_FWD2(D_, true) else RM_FIB_FWD2(D_, false)
   switch (D) {
@@ -481,40 +460,33 @@ extern "C" int rm_fibinet_bwd(const float *E, const float *W1, const float *W2, 
   const char *fn = "rm_fibinet_bwd";
   int rc = fib_check(fn, B, F, D, R, type, "lddx", lddx);
   if (rc != RM_OK) return rc;
-  RM_REQUIRE(dW1, "%s: dW1 is NULL", fn);
-  RM_REQUIRE(dW2, "%s: dW2 is NULL", fn);
-  RM_REQUIRE(dWb, "%s: dWb is NULL", fn);
-  RM_REQUIRE(dWsb, "%s: dWsb is NULL", fn);
+  RM_REQUIRE_PTR(fn, dW1);
+  RM_REQUIRE_PTR(fn, dW2);
+  RM_REQUIRE_PTR(fn, dWb);
+  RM_REQUIRE_PTR(fn, dWsb);
   const int nW = fib_nw(F, type), NW = nW * D * D, FR = F * R;
   hipStream_t st = (hipStream_t)stream;
   if (B == 0) {  // the sums over an empty batch
-    if (hipMemsetAsync(dW1, 0, (size_t)FR * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(dW2, 0, (size_t)FR * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(dWb, 0, (size_t)NW * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(dWsb, 0, (size_t)NW * sizeof(float), st) != hipSuccess) {
-      rm_set_error("%s: clearing the parameter gradients failed", fn);
-      return RM_ELAUNCH;
-    }
+    const char *what = "the parameter gradients";
+    float *const grads[4] = {dW1, dW2, dWb, dWsb};
+    for (int k = 0; k < 4; ++k)
+      if (rm_clear_async(fn, what, grads[k], k < 2 ? FR : NW, st) != RM_OK) return RM_ELAUNCH;
     return RM_OK;
   }
-  RM_REQUIRE(E, "%s: E is NULL", fn);
-  RM_REQUIRE(W1, "%s: W1 is NULL", fn);
-  RM_REQUIRE(W2, "%s: W2 is NULL", fn);
-  RM_REQUIRE(Wb, "%s: Wb is NULL", fn);
-  RM_REQUIRE(Wsb, "%s: Wsb is NULL", fn);
-  RM_REQUIRE(dX, "%s: dX is NULL", fn);
-  RM_REQUIRE(dE, "%s: dE is NULL", fn);
-  RM_REQUIRE(workspace, "%s: workspace is NULL", fn);
+  RM_REQUIRE_PTR(fn, E);
+  RM_REQUIRE_PTR(fn, W1);
+  RM_REQUIRE_PTR(fn, W2);
+  RM_REQUIRE_PTR(fn, Wb);
+  RM_REQUIRE_PTR(fn, Wsb);
+  RM_REQUIRE_PTR(fn, dX);
+  RM_REQUIRE_PTR(fn, dE);
+  RM_REQUIRE_PTR(fn, workspace);
   RM_REQUIRE(rm_aligned16(E) && rm_aligned16(dE), "%s: E and dE must be 16-byte aligned", fn);
   const FibPlan p = fib_plan_bwd(F, D, R, type);
   const int nblk = fib_blocks(B, p.G, fib_bwd_cap(F, D, R, type));
-#define RM_FIB_BWD3(D_, WL_, AL_)                                                                                \
-  {                                                                                                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fibinet_bwd_kernel<D_, WL_, AL_>),                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.smem);                          \
-    hipLaunchKernelGGL((fibinet_bwd_kernel<D_, WL_, AL_>), dim3(nblk), dim3(kThreads), p.smem, st, E, W1, W2, Wb, \
-                       Wsb, dX, lddx, B, F, R, nW, p.G, dE, workspace);                                          \
-  }
+#define RM_FIB_BWD3(D_, WL_, AL_)                                                                                  \
+  rm_launch_lds(fibinet_bwd_kernel<D_, WL_, AL_>, dim3(nblk), dim3(kThreads), p.smem, st, E, W1, W2, Wb, Wsb, dX, lddx, \
+                B, F, R, nW, p.G, dE, workspace);
 #define RM_FIB_BWD(D_)                                     \
   if (p.w_lds && p.a_lds) RM_FIB_BWD3(D_, true, true)      \
   else if (p.w_lds) RM_FIB_BWD3(D_, true, false)           \
@@ -528,9 +500,8 @@ extern "C" int rm_fibinet_bwd(const float *E, const float *W1, const float *W2, 
 #undef RM_FIB_BWD
 #undef RM_FIB_BWD3
   RM_CHECK_LAUNCH(fn);
-  const int N = 2 * NW + 2 * FR;
-  hipLaunchKernelGGL(fibinet_finish_kernel, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                     (const float *)workspace, nblk, NW, FR, dWb, dWsb, dW1, dW2);
+  // the four gradients = the blocks' partials [dWb | dWsb | dW1 | dW2], summed in block order
+  rm_sum_partials(workspace, nblk, 2 * NW + 2 * FR, rm_sum_dsts(dWb, NW, dWsb, NW, dW1, FR, dW2, FR), st);
   RM_CHECK_LAUNCH(fn);
   return RM_OK;
 }

@@ -25,14 +25,14 @@
 //     d_rows = dE_up + g acc is written once, without atomics.  At D = 8 two output fields share an MFMA.
 //   dM: the block grid is (pair chunks) x (batch slices): a wave keeps the accumulators of NP pairs (8 at D = 8 / 16,
 //     2 at D = 32: 32 registers) for its whole slice, K = examples on the MFMA (A = g E_i^T, B = E_j), and leaves
-//     them in the slice's part of the workspace; a finish kernel sums the slices in slice order.  E is read
+//     them in the slice's part of the workspace; rm_sum_partials sums the slices in slice order.  E is read
 //     ceil(units / (8 NP)) times (6 at F = 26, D = 16), from L2 after the first.
 // Vector and scalar types: one templated vector-ALU path (weight index p D + d or p), a thread per (example, d) in the
 // forward (inner chain over j, outer over i, butterfly over d), per (example, field, d) for dE, per (pair, d) and batch
 // slice for dW - 16-example tiles (the loops are latency-bound: they want waves, not a large tile), the same workspace
-// layout and finish kernel.
+// layout and sum.
 // Determinism: no atomics anywhere; per-slice partials are summed in slice order: two runs are bit-equal.
-#include "rm_common.h"
+#include "rm_launch.h"
 
 namespace {
 
@@ -534,16 +534,6 @@ __global__ __launch_bounds__(kThreads) void fmfm_vs_dw_kernel(const float *__res
   }
 }
 
-// dW = the sum over the slices' partials, in slice order
-__global__ __launch_bounds__(kThreads) void fmfm_finish_kernel(const float *__restrict__ part, int NS, int N,
-                                                               float *__restrict__ dW) {
-  const int o = blockIdx.x * kThreads + threadIdx.x;
-  if (o >= N) return;
-  float s = 0.f;
-  for (int b = 0; b < NS; ++b) s += part[(int64_t)b * N + o];
-  dW[o] = s;
-}
-
 int fm_check(const char *fn, int64_t B, int F, int D, int type) {
   RM_REQUIRE(B >= 0, "%s: bad batch size", fn);
   RM_REQUIRE(D == 8 || D == 16 || D == 32, "%s: D=%d unsupported (8, 16, 32)", fn, D);
@@ -551,12 +541,6 @@ int fm_check(const char *fn, int64_t B, int F, int D, int type) {
   RM_REQUIRE(type >= RM_FMFM_MATRIX && type <= RM_FMFM_SCALAR,
              "%s: type=%d unsupported (RM_FMFM_MATRIX, RM_FMFM_VECTOR, RM_FMFM_SCALAR)", fn, type);
   return RM_OK;
-}
-
-template <typename K>
-inline void fm_smem(K kernel, size_t smem) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
 }
 
 }  // namespace
@@ -582,25 +566,20 @@ extern "C" int rm_fmfm_fwd(const float *E, const float *W, int type, int64_t B, 
   int rc = fm_check(fn, B, F, D, type);
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
-  RM_REQUIRE(E, "%s: E is NULL", fn);
-  RM_REQUIRE(W, "%s: W is NULL", fn);
-  RM_REQUIRE(logit, "%s: logit is NULL", fn);
+  RM_REQUIRE_PTR(fn, E);
+  RM_REQUIRE_PTR(fn, W);
+  RM_REQUIRE_PTR(fn, logit);
   RM_REQUIRE(rm_aligned16(E), "%s: E must be 16-byte aligned", fn);
   const FmPlan p = fm_plan(F, D, type, 0);
   const dim3 grid(rm_grid_cap((B + p.G - 1) / p.G, fm_fwd_cap(type))), block(kThreads);
   hipStream_t st = (hipStream_t)stream;
-#define RM_FM_FWD(D_)                                                                                              \
-  if (type == RM_FMFM_MATRIX) {                                                                                    \
-    fm_smem(fmfm_fwd_kernel<D_>, p.smem);                                                                          \
-    hipLaunchKernelGGL((fmfm_fwd_kernel<D_>), grid, block, p.smem, st, E, W, B, F, p.G, p.ES, fm_units(F, D_),     \
-                       logit);                                                                                     \
-  } else if (type == RM_FMFM_VECTOR) {                                                                             \
-    fm_smem(fmfm_vs_fwd_kernel<D_, true>, p.smem);                                                                 \
-    hipLaunchKernelGGL((fmfm_vs_fwd_kernel<D_, true>), grid, block, p.smem, st, E, W, B, F, p.G, p.ES, logit);     \
-  } else {                                                                                                         \
-    fm_smem(fmfm_vs_fwd_kernel<D_, false>, p.smem);                                                                \
-    hipLaunchKernelGGL((fmfm_vs_fwd_kernel<D_, false>), grid, block, p.smem, st, E, W, B, F, p.G, p.ES, logit);    \
-  }
+#define RM_FM_FWD(D_)                                                                                           \
+  if (type == RM_FMFM_MATRIX)                                                                                   \
+    rm_launch_lds(fmfm_fwd_kernel<D_>, grid, block, p.smem, st, E, W, B, F, p.G, p.ES, fm_units(F, D_), logit); \
+  else if (type == RM_FMFM_VECTOR)                                                                              \
+    rm_launch_lds(fmfm_vs_fwd_kernel<D_, true>, grid, block, p.smem, st, E, W, B, F, p.G, p.ES, logit);         \
+  else                                                                                                          \
+    rm_launch_lds(fmfm_vs_fwd_kernel<D_, false>, grid, block, p.smem, st, E, W, B, F, p.G, p.ES, logit);
   switch (D) {
     case 8: RM_FM_FWD(8) break;
     case 16: RM_FM_FWD(16) break;
@@ -623,12 +602,12 @@ extern "C" int rm_fmfm_bwd(const float *E, const float *W, int type, const float
   int rc = fm_check(fn, B, F, D, type);
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
-  RM_REQUIRE(E, "%s: E is NULL", fn);
-  RM_REQUIRE(W, "%s: W is NULL", fn);
-  RM_REQUIRE(g, "%s: g is NULL", fn);
-  RM_REQUIRE(d_rows, "%s: d_rows is NULL", fn);
-  RM_REQUIRE(dW, "%s: dW is NULL", fn);
-  RM_REQUIRE(workspace, "%s: workspace is NULL", fn);
+  RM_REQUIRE_PTR(fn, E);
+  RM_REQUIRE_PTR(fn, W);
+  RM_REQUIRE_PTR(fn, g);
+  RM_REQUIRE_PTR(fn, d_rows);
+  RM_REQUIRE_PTR(fn, dW);
+  RM_REQUIRE_PTR(fn, workspace);
   RM_REQUIRE(rm_aligned16(E), "%s: E must be 16-byte aligned", fn);
   hipStream_t st = (hipStream_t)stream;
   const FmPlan pe = fm_plan(F, D, type, 1), pw = fm_plan(F, D, type, 2);
@@ -637,25 +616,18 @@ extern "C" int rm_fmfm_bwd(const float *E, const float *W, int type, const float
 #define RM_FM_BWD(D_)                                                                                              \
   if (type == RM_FMFM_MATRIX) {                                                                                    \
     const int NC = fm_dw_chunks(F, D_);                                                                            \
-    fm_smem(fmfm_de_kernel<D_>, pe.smem);                                                                          \
-    hipLaunchKernelGGL((fmfm_de_kernel<D_>), ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES, d_rows);   \
-    fm_smem(fmfm_dw_kernel<D_>, pw.smem);                                                                          \
-    hipLaunchKernelGGL((fmfm_dw_kernel<D_>), dim3(NC * NS), dim3(kDwThreads), pw.smem, st, E, g, B, F, pw.G, pw.ES,           \
-                       fm_units(F, D_), NC, NS, workspace);                                                        \
+    rm_launch_lds(fmfm_de_kernel<D_>, ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES, d_rows);          \
+    rm_launch_lds(fmfm_dw_kernel<D_>, dim3(NC * NS), dim3(kDwThreads), pw.smem, st, E, g, B, F, pw.G, pw.ES,       \
+                  fm_units(F, D_), NC, NS, workspace);                                                             \
   } else if (type == RM_FMFM_VECTOR) {                                                                             \
-    fm_smem(fmfm_vs_de_kernel<D_, true>, pe.smem);                                                                 \
-    hipLaunchKernelGGL((fmfm_vs_de_kernel<D_, true>), ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES,   \
-                       d_rows);                                                                                    \
-    fm_smem(fmfm_vs_dw_kernel<D_, true>, pw.smem);                                                                 \
-    hipLaunchKernelGGL((fmfm_vs_dw_kernel<D_, true>), dim3(NS), block, pw.smem, st, E, g, B, F, pw.G, pw.ES, NS,   \
-                       workspace);                                                                                 \
+    rm_launch_lds(fmfm_vs_de_kernel<D_, true>, ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES, d_rows); \
+    rm_launch_lds(fmfm_vs_dw_kernel<D_, true>, dim3(NS), block, pw.smem, st, E, g, B, F, pw.G, pw.ES, NS,          \
+                  workspace);                                                                                      \
   } else {                                                                                                         \
-    fm_smem(fmfm_vs_de_kernel<D_, false>, pe.smem);                                                                \
-    hipLaunchKernelGGL((fmfm_vs_de_kernel<D_, false>), ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES,  \
-                       d_rows);                                                                                    \
-    fm_smem(fmfm_vs_dw_kernel<D_, false>, pw.smem);                                                                \
-    hipLaunchKernelGGL((fmfm_vs_dw_kernel<D_, false>), dim3(NS), block, pw.smem, st, E, g, B, F, pw.G, pw.ES, NS,  \
-                       workspace);                                                                                 \
+    rm_launch_lds(fmfm_vs_de_kernel<D_, false>, ge, block, pe.smem, st, E, W, g, dE_up, B, F, pe.G, pe.ES,         \
+                  d_rows);                                                                                         \
+    rm_launch_lds(fmfm_vs_dw_kernel<D_, false>, dim3(NS), block, pw.smem, st, E, g, B, F, pw.G, pw.ES, NS,         \
+                  workspace);                                                                                      \
   }
   switch (D) {
     case 8: RM_FM_BWD(8) break;
@@ -664,8 +636,7 @@ extern "C" int rm_fmfm_bwd(const float *E, const float *W, int type, const float
   }
 #undef RM_FM_BWD
   RM_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(fmfm_finish_kernel, dim3((N + kThreads - 1) / kThreads), block, 0, st,
-                     (const float *)workspace, NS, N, dW);
+  rm_sum_partials(workspace, NS, N, rm_sum_dsts(dW, N), st);  // dW = the slices' partials, in slice order
   RM_CHECK_LAUNCH(fn);
   return RM_OK;
 }

@@ -191,6 +191,23 @@ def cross_param_grads(P, colsum, w, b, w_out, d_w, d_b, d_w_out):
         _chk(d_b, "d_b", F32, (L, d)), _chk(d_w_out, "d_w_out", F32, (d,)), _stream())
 
 
+def _need_workspace(fn, workspace, need):
+    """The caller's workspace must hold the `need` floats the entry point's *_workspace function asks for."""
+    if workspace.numel() < need:
+        raise ValueError(f"{fn}: workspace too small ({workspace.numel()} floats, needs {need})")
+
+
+def _strided_rows(t, name, B, width, exact):
+    """A float32 device view of B rows with unit column stride, exactly `width` columns (exact) or at least `width`,
+    and any row stride >= its columns -> (pointer, stride)."""
+    p, ld, cols = _rows2d(t, name)
+    if t.shape[0] != B or (cols != width if exact else cols < width):
+        raise ValueError(f"{name} {tuple(t.shape)} must be " + (f"[{B},{width}]" if exact else f"[{B}, >= {width}]"))
+    if B > 1 and ld < cols:
+        raise ValueError(f"{name}: row stride {ld} < {cols} columns")
+    return p, max(ld, cols)
+
+
 def afm_supported(F, D, T):
     """rm_afm_supported: D in {8, 16, 32, 64}, 2 <= F <= 40, 1 <= T <= 64."""
     return bool(_lib.lib().rm_afm_supported(int(F), int(D), int(T)))
@@ -223,9 +240,7 @@ def afm_bwd(E, W, b, h, p, g, logit, stats, d_rows, dW, db, dh, dp, workspace, m
     itself), dW [D,T], db [T], dh [T], dp [D] overwritten.  Deterministic."""
     B, F, D = E.shape
     T = W.shape[1]
-    need = afm_bwd_workspace(B, F, D, T)
-    if need and workspace.numel() < need:
-        raise ValueError(f"afm_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _need_workspace("afm_bwd", workspace, afm_bwd_workspace(B, F, D, T))
     _lib.call(
         "rm_afm_bwd", _chk(E, "E", F32), _chk(W, "W", F32, (D, T)), _chk(b, "b", F32, (T,)),
         _chk(h, "h", F32, (T,)), _chk(p, "p", F32, (D,)), _chk(mask, "mask", F32, (B, D), allow_none=True),
@@ -277,9 +292,7 @@ def autoint_layer_bwd(X, Wq, Wk, Wv, Wr, Y, stats, dY, H, scale, dX, dWq, dWk, d
     B, F, Din, H, dk, HD = _autoint_dims(X, Wq, H)
     if (Wr is None) != (dWr is None):
         raise ValueError("autoint_layer_bwd: Wr and dWr go together")
-    need = autoint_layer_bwd_workspace(B, F, Din, H, dk)
-    if need and workspace.numel() < need:
-        raise ValueError(f"autoint_layer_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _need_workspace("autoint_layer_bwd", workspace, autoint_layer_bwd_workspace(B, F, Din, H, dk))
     _lib.call(
         "rm_autoint_layer_bwd", _chk(X, "X", F32), _chk(Wq, "Wq", F32, (Din, HD)), _chk(Wk, "Wk", F32, (Din, HD)),
         _chk(Wv, "Wv", F32, (Din, HD)), _chk(Wr, "Wr", F32, (Din, HD), allow_none=True),
@@ -310,9 +323,7 @@ def autoint_head_bwd(Y, w, g, dY, dw, dw0, workspace):
     B, K = Y.shape[0], w.numel()
     if Y.numel() != B * K:
         raise ValueError(f"autoint_head_bwd: Y {tuple(Y.shape)} does not flatten to [B, {K}]")
-    need = autoint_head_bwd_workspace(B, K)
-    if workspace.numel() < need:
-        raise ValueError(f"autoint_head_bwd: workspace has {workspace.numel()} floats, needs {need}")
+    _need_workspace("autoint_head_bwd", workspace, autoint_head_bwd_workspace(B, K))
     _lib.call("rm_autoint_head_bwd", _chk(Y, "Y", F32), _chk(w, "w", F32, (K,)), _chk(g, "g", F32, (B,)), B, K,
               _chk(dY, "dY", F32, tuple(Y.shape)), _chk(dw, "dw", F32, (K,)), _chk(dw0, "dw0", F32, (1,)),
               _chk(workspace, "workspace", F32), _stream())
@@ -337,12 +348,8 @@ def _dot_interact_args(E, z, X, name):
     if not dot_interact_supported(F, D):
         raise ValueError(f"dot_interact: F={F}, D={D} unsupported (1 <= F <= 40, D in 8, 16, 32, 64)")
     W, _ = dot_interact_width(F, D)
-    px, ldx, cols = _rows2d(X, name)
-    if X.shape[0] != B or cols < W:
-        raise ValueError(f"{name} {tuple(X.shape)} must be [{B}, >= {W}]")
-    if B > 1 and ldx < cols:
-        raise ValueError(f"{name}: row stride {ldx} < {cols} columns")
-    return B, F, D, _chk(E, "E", F32), _chk(z, "z", F32, (B, D)), px, max(ldx, cols)
+    px, ldx = _strided_rows(X, name, B, W, False)
+    return B, F, D, _chk(E, "E", F32), _chk(z, "z", F32, (B, D)), px, ldx
 
 
 def dot_interact_fwd(E, z, X):
@@ -390,25 +397,15 @@ def _cross_mix_dims(C):
     return E, r, _chk(C, "C", F32)
 
 
-def _cross_mix_rows(t, name, B, width):
-    """A [B, width] float32 device view with unit column stride and any row stride >= width -> (pointer, stride)."""
-    p, ld, cols = _rows2d(t, name)
-    if t.shape[0] != B or cols != width:
-        raise ValueError(f"{name} {tuple(t.shape)} must be [{B},{width}]")
-    if B > 1 and ld < width:
-        raise ValueError(f"{name}: row stride {ld} < {width} columns")
-    return p, max(ld, width)
-
-
 def cross_mix_fwd(T, S, C, M):
     """rm_cross_mix_fwd: T [B, E r], S [B, E] (column views of any row stride, e.g. of one projection buffer),
     C [E,r,r] -> M [B, E r]: a_i = tanh(t_i), c_i = tanh(a_i C_i), p = softmax(s), m_i = p_i c_i.  Only M's own
     columns are written."""
     E, r, pc = _cross_mix_dims(C)
     B = T.shape[0]
-    pt, ldt = _cross_mix_rows(T, "T", B, E * r)
-    ps, lds = _cross_mix_rows(S, "S", B, E)
-    pm, ldm = _cross_mix_rows(M, "M", B, E * r)
+    pt, ldt = _strided_rows(T, "T", B, E * r, True)
+    ps, lds = _strided_rows(S, "S", B, E, True)
+    pm, ldm = _strided_rows(M, "M", B, E * r, True)
     _lib.call("rm_cross_mix_fwd", pt, ldt, ps, lds, pc, E, r, B, pm, ldm, _stream())
 
 
@@ -425,13 +422,12 @@ def cross_mix_bwd(T, S, C, dM, dT, dS, dC, workspace):
     their own columns are written) and dC [E,r,r] (overwritten).  a, c and p are recomputed.  Deterministic."""
     E, r, pc = _cross_mix_dims(C)
     B = T.shape[0]
-    pt, ldt = _cross_mix_rows(T, "T", B, E * r)
-    ps, lds = _cross_mix_rows(S, "S", B, E)
-    pdm, lddm = _cross_mix_rows(dM, "dM", B, E * r)
-    pdt, lddt = _cross_mix_rows(dT, "dT", B, E * r)
-    pds, ldds = _cross_mix_rows(dS, "dS", B, E)
-    if workspace.numel() < cross_mix_bwd_workspace(B, E, r):
-        raise ValueError("cross_mix_bwd: workspace too small (rm_cross_mix_bwd_workspace)")
+    pt, ldt = _strided_rows(T, "T", B, E * r, True)
+    ps, lds = _strided_rows(S, "S", B, E, True)
+    pdm, lddm = _strided_rows(dM, "dM", B, E * r, True)
+    pdt, lddt = _strided_rows(dT, "dT", B, E * r, True)
+    pds, ldds = _strided_rows(dS, "dS", B, E, True)
+    _need_workspace("cross_mix_bwd", workspace, cross_mix_bwd_workspace(B, E, r))
     _lib.call("rm_cross_mix_bwd", pt, ldt, ps, lds, pc, E, r, B, pdm, lddm, pdt, lddt, pds, ldds,
               _chk(dC, "dC", F32, (E, r, r)), _chk(workspace, "workspace", F32), _stream())
 
@@ -486,14 +482,10 @@ def _fibinet_args(E, W1, W2, Wb, Wsb, bilinear_type, X, name):
         raise ValueError(f"fibinet: F={F}, D={D}, R={R} unsupported ({_FIBINET_LIMITS})")
     nW = F - 1 if typ else 1
     W, _ = fibinet_width(F, D)
-    px, ldx, cols = _rows2d(X, name)
-    if X.shape[0] != B or cols < W:
-        raise ValueError(f"{name} {tuple(X.shape)} must be [{B}, >= {W}]")
-    if B > 1 and ldx < cols:
-        raise ValueError(f"{name}: row stride {ldx} < {cols} columns")
+    px, ldx = _strided_rows(X, name, B, W, False)
     ptrs = (_chk(E, "E", F32), _chk(W1, "W1", F32, (F, R)), _chk(W2, "W2", F32, (R, F)),
             _chk(Wb, "Wb", F32, (nW, D, D)), _chk(Wsb, "Wsb", F32, (nW, D, D)))
-    return B, F, D, R, typ, ptrs, px, max(ldx, cols)
+    return B, F, D, R, typ, ptrs, px, ldx
 
 
 def fibinet_fwd(E, W1, W2, Wb, Wsb, bilinear_type, X):
@@ -516,8 +508,7 @@ def fibinet_bwd(E, W1, W2, Wb, Wsb, bilinear_type, dX, dE, dW1, dW2, dWb, dWsb, 
     """rm_fibinet_bwd: dX [B, >= 2PD] (any row stride; columns >= 2PD are never read) -> dE [B,F,D] and the gradients
     of the four weight arrays, all overwritten.  The gate and the left products are recomputed.  Deterministic."""
     B, F, D, R, typ, ptrs, px, ldx = _fibinet_args(E, W1, W2, Wb, Wsb, bilinear_type, dX, "dX")
-    if workspace.numel() < fibinet_bwd_workspace(B, F, D, R, bilinear_type):
-        raise ValueError("fibinet_bwd: workspace too small (rm_fibinet_bwd_workspace)")
+    _need_workspace("fibinet_bwd", workspace, fibinet_bwd_workspace(B, F, D, R, bilinear_type))
     _lib.call("rm_fibinet_bwd", *ptrs, px, ldx, B, F, D, R, typ, _chk(dE, "dE", F32, (B, F, D)),
               _chk(dW1, "dW1", F32, tuple(W1.shape)), _chk(dW2, "dW2", F32, tuple(W2.shape)),
               _chk(dWb, "dWb", F32, tuple(Wb.shape)), _chk(dWsb, "dWsb", F32, tuple(Wsb.shape)),
@@ -587,8 +578,7 @@ def fmfm_bwd(E, W, field_interaction, g, d_rows, dW, workspace, dE_up=None):
     """rm_fmfm_bwd: g [B] = dLoss/dlogit -> d_rows [B,F,D] = dLoss/dE (+ dE_up, which may be d_rows itself) and dW
     (the shape of W), both overwritten.  Deterministic."""
     B, F, D, typ, pe, pw = _fmfm_args(E, W, field_interaction)
-    if workspace.numel() < fmfm_bwd_workspace(B, F, D, field_interaction):
-        raise ValueError("fmfm_bwd: workspace too small (rm_fmfm_bwd_workspace)")
+    _need_workspace("fmfm_bwd", workspace, fmfm_bwd_workspace(B, F, D, field_interaction))
     _lib.call("rm_fmfm_bwd", pe, pw, typ, _chk(g, "g", F32, (B,)), _chk(dE_up, "dE_up", F32, (B, F, D), allow_none=True),
               B, F, D, _chk(d_rows, "d_rows", F32, (B, F, D)), _chk(dW, "dW", F32, tuple(W.shape)),
               _chk(workspace, "workspace", F32), _stream())
@@ -688,8 +678,7 @@ def masknet_group_bwd(X, gamma, beta, M, dY, dM, d_rows, dgamma=None, dbeta=None
     if normalize:
         pdg, pdb = _chk(dgamma, "dgamma", F32, (F, D)), _chk(dbeta, "dbeta", F32, (F, D))
         pws = _chk(workspace, "workspace", F32)
-        if workspace.numel() < masknet_group_bwd_workspace(B, F, D):
-            raise ValueError("masknet_group_bwd: workspace too small (rm_masknet_group_bwd_workspace)")
+        _need_workspace("masknet_group_bwd", workspace, masknet_group_bwd_workspace(B, F, D))
     _lib.call("rm_masknet_group_bwd", px, pg, pb, int(bool(normalize)), pm, ldm, pdy, lddy, pdm, lddm, len(M),
               _chk(dE_up, "dE_up", F32, tuple(X.shape), allow_none=True), B, F, D,
               _chk(d_rows, "d_rows", F32, tuple(X.shape)), pdg, pdb, pws, _stream())
@@ -744,8 +733,7 @@ def masknet_row_bwd(Z, gamma, beta, dh, dZ, dgamma, dbeta, workspace):
     statistics are recomputed from Z.  Deterministic."""
     B, H, pz, pg, pb = _masknet_row_args(Z, gamma, beta)
     pdh, lddh = _masknet_strided(dh, "dh", B, H)
-    if workspace.numel() < masknet_row_bwd_workspace(B, H):
-        raise ValueError("masknet_row_bwd: workspace too small (rm_masknet_row_bwd_workspace)")
+    _need_workspace("masknet_row_bwd", workspace, masknet_row_bwd_workspace(B, H))
     _lib.call("rm_masknet_row_bwd", pz, pg, pb, pdh, lddh, B, H, _chk(dZ, "dZ", F32, (B, H)),
               _chk(dgamma, "dgamma", F32, (H,)), _chk(dbeta, "dbeta", F32, (H,)), _chk(workspace, "workspace", F32),
               _stream())
