@@ -877,6 +877,52 @@ int rm_sparse_optimizer_step_rows(const int64_t *row_ids, const float *grad_rows
 int rm_dense_optimizer_step(float *p, const float *g, float *m, float *v, int64_t n, int step, int kind,
                             float lr, float beta1, float beta2, float eps, int reset, rm_stream_t stream);
 
+/* The same steps with the update rule(s) given explicitly, and FTRL-Proximal (kind 3) beside Adam, Adagrad and SGD.
+ * A rule descriptor is read on the host at call time.  Field by kind ("-": ignored):
+ *            kind  lr                   beta1  beta2  eps                 l1   l2   beta
+ *   Adam     0     learning rate        yes    yes    outside the sqrt    -    -    -
+ *   Adagrad  1     learning rate        -      -      outside the sqrt    -    -    -
+ *   SGD      2     learning rate        -      -      -                   -    -    -
+ *   FTRL     3     learning rate, > 0   -      -      -                   L1   L2   beta
+ * l1, l2 and beta must be >= 0 whatever the kind (leave them 0 for kinds 0 - 2).
+ * FTRL is tf.keras.optimizers.Ftrl with learning_rate_power = -0.5, initial accumulator 0.1 and no l2_shrinkage;
+ * per element, in float32, every operation rounded on its own:
+ *   n_new = n + g*g;  sigma = (sqrt(n_new) - sqrt(n)) / lr;  z = z + g - sigma * p;
+ *   q = (sqrt(n_new) + beta) / lr + 2*l2;  p = |z| > l1 ? (copysign(l1, z) - z) / q : 0;  n = n_new
+ * with g the summed gradient after the lazy l2 term, and `reset` setting z = 0, n = 0.1 first.  State: z ("linear"
+ * in TF) lives in the m slot and n (the accumulator) in the v slot - of mom's interleaved row, of the row's state
+ * columns [m_b m_l v_b v_l], of the dense step's m / v arrays.  Keras applies FTRL to IndexedSlices row by row, so
+ * the lazy row-wise step is Keras's own semantics for this kind.
+ *
+ * rm_sparse_optimizer_step_rules / rm_sparse_optimizer_step_rows_rules: emb_rule updates the D embedding entries of
+ * a touched row (state: mom, which must be non-NULL unless emb_rule is SGD, and is not touched when it is), side_rule
+ * its bias and linear entries (state: the row's columns D+2 .. D+5; a rule changes only the columns it keeps: SGD none,
+ * Adagrad v_b v_l).  Both rules see the same `step` and `reset`.  With emb_rule == side_rule of kind 0 - 2 the result
+ * is that of rm_sparse_optimizer_step / _step_rows, which run the same code.  Every other argument as above.
+ * rm_dense_optimizer_step_rule: one rule on a flat buffer; m is needed for Adam and FTRL (z), v unless SGD (FTRL: n).
+ * An invalid rule (kind outside 0..3, negative l1 / l2 / beta, FTRL with lr <= 0, a missing state array) returns
+ * RM_EINVAL before anything is launched. */
+typedef struct rm_opt_rule {
+  int kind;
+  float lr;
+  float beta1, beta2;
+  float eps;
+  float l1, l2, beta;
+} rm_opt_rule;
+int rm_sparse_optimizer_step_rules(const int64_t *idx, const int64_t *field_off, const float *d_rows,
+                                   const float *g_bias, const float *g_lin, int64_t B, int F, int D, int64_t R,
+                                   float *rows, int64_t ld, float *mom, int step, const rm_opt_rule *emb_rule,
+                                   const rm_opt_rule *side_rule, int reset, float l2_embedding, float l2_linear,
+                                   const float *lin_field_mask, int64_t max_field_rows, int prepared,
+                                   void *workspace, int64_t ws_bytes, rm_stream_t stream);
+int rm_sparse_optimizer_step_rows_rules(const int64_t *row_ids, const float *grad_rows, int64_t gw, int64_t n, int D,
+                                        int64_t R, float *rows, int64_t ld, float *mom, int step,
+                                        const rm_opt_rule *emb_rule, const rm_opt_rule *side_rule, int reset,
+                                        float l2_embedding, float l2_linear, int prepared, void *workspace,
+                                        int64_t ws_bytes, rm_stream_t stream);
+int rm_dense_optimizer_step_rule(float *p, const float *g, float *m, float *v, int64_t n, int step,
+                                 const rm_opt_rule *rule, int reset, rm_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Row helpers (owner-side gather and re-ordering for the row-sharded table).
  */

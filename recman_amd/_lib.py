@@ -28,6 +28,12 @@ class MlpTail(ctypes.Structure):
                 ("dh", P * 3)]
 
 
+class OptRule(ctypes.Structure):
+    """rm_opt_rule of include/recman_hip.h: one update rule (kind 0 Adam, 1 Adagrad, 2 SGD, 3 FTRL)."""
+    _fields_ = [("kind", c_int), ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
+                ("l1", c_float), ("l2", c_float), ("beta", c_float)]
+
+
 # name -> argtypes, in the order of include/recman_hip.h
 SIGNATURES = {
     "rm_version": [],
@@ -110,6 +116,11 @@ SIGNATURES = {
     "rm_sparse_optimizer_step_rows": [P, P, I64, I64, c_int, I64, P, I64, P, c_int, c_int,
                                       c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_int, P, I64, P],
     "rm_dense_optimizer_step": [P, P, P, P, I64, c_int, c_int, c_float, c_float, c_float, c_float, c_int, P],
+    "rm_sparse_optimizer_step_rules": [P, P, P, P, P, I64, c_int, c_int, I64, P, I64, P, c_int, P, P, c_int,
+                                       c_float, c_float, P, I64, c_int, P, I64, P],
+    "rm_sparse_optimizer_step_rows_rules": [P, P, I64, I64, c_int, I64, P, I64, P, c_int, P, P, c_int,
+                                            c_float, c_float, c_int, P, I64, P],
+    "rm_dense_optimizer_step_rule": [P, P, P, P, I64, c_int, P, c_int, P],
     "rm_shard_route": [P, P, I64, c_int, c_int, P, P, P, P, P],
     "rm_shard_route_padded": [P, P, I64, c_int, c_int, I64, P, P, P, P, P, P],
     "rm_pack_grad_rows": [P, P, P, P, P, I64, c_int, c_int, c_int, P, P],

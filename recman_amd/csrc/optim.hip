@@ -1,6 +1,10 @@
 // Optimizer steps (the step either side of fwd+bwd).  Keras semantics of
 // create_optimizer (recman/tf/core/utils.py:201-213): Adam(beta1 .9, beta2 .999, epsilon 1e-7 OUTSIDE
-// the sqrt), Adagrad(initial accumulator 0.1), SGD.
+// the sqrt), Adagrad(initial accumulator 0.1), SGD; and FTRL-Proximal (tf.keras.optimizers.Ftrl with
+// learning_rate_power -0.5, initial accumulator 0.1, no l2_shrinkage), which Keras applies to IndexedSlices row by
+// row: for FTRL the lazy row-wise step below IS Keras's semantics.  A step carries TWO rules: one for the embedding
+// entries of a row and one for its side entries (bias, linear) - the Wide&Deep recipe, FTRL with L1 on the wide
+// weights and Adam / Adagrad on the rest, in the same pass over the row.
 //
 // rm_sparse_optimizer_step / rm_sparse_optimizer_step_rows: ROW-WISE and LAZY - only table rows that
 // occur in the batch are touched.  This is LazyAdam, a deliberate deviation from Keras, whose
@@ -65,9 +69,26 @@ struct GradSrc {
   int F;
 };
 
+// One update rule.  State per weight, in the slots (m, v): Adam (m, v); Adagrad (-, v); SGD none; FTRL (z, n) - z is
+// TF's "linear", n its accumulator.
+// Five words, not nine: the two rules of a step live in scalar registers for the whole of an apply kernel, and the
+// long-run kernel has none to spare (a rule with one field per constant cost it a wave of occupancy).
+struct OptRule {
+  int kind;      // 0 Adam, 1 Adagrad, 2 SGD, 3 FTRL
+  float lr;      // the learning rate; Adam: lr_t, the bias-corrected rate of this step
+  float c0, c1;  // Adam: beta1, beta2; FTRL: l1, l2
+  float c2;      // Adam, Adagrad: eps; FTRL: beta
+};
+// EXT = false: the kernels as they were before FTRL and the second rule, for steps that need neither (one rule of
+// kind 0 - 2 for the whole row; sparse_step decides).  With both in one body the long-run kernel took 84 registers
+// instead of 79 and lost a wave of occupancy a SIMD; so Adam, Adagrad and SGD keep their own instantiations.
+template <bool EXT = true>
+__host__ __device__ __forceinline__ bool rule_has_m(int kind) { return kind == 0 || (EXT && kind == 3); }
+__host__ __device__ __forceinline__ bool rule_has_v(int kind) { return kind != 2; }
+
 struct OptArgs {
-  int kind;  // 0 Adam, 1 Adagrad, 2 SGD
-  float lr_t, lr, beta1, beta2, eps;
+  OptRule emb;   // lanes sub < GE: the embedding slices and the [R, 2D] moment array
+  OptRule side;  // lane GE: the bias and linear entries and the row's state columns D+2 .. D+5
   int reset;
   // lazy l2: the gradient of embedding_l2_reg * 1/2 |row|^2 (resp. linear_l2_reg on the linear entry) is added
   // for the rows a batch touches, ONCE per distinct row and step (the reference's dense term, layers.py:188-193,
@@ -102,18 +123,38 @@ __global__ __launch_bounds__(kBlock) void sparse_keys_kernel(const int64_t *__re
   }
 }
 
-__device__ __forceinline__ void opt_update(float &p, float &m, float &v, float g, const OptArgs &a) {
+// FTRL-Proximal, one element: every operation rounded on its own, in the order the float32 restatement of
+// tests/optim_ftrl_ref.py uses (no contraction into an fma: sigma is a difference of two square roots over lr, and
+// the yardstick is only one if it rounds where the kernel does).  The soft threshold is continuous: p -> 0 as
+// |z| -> l1.  A first touch (z = 0, n = 0.1) leaves z = g - sigma p: the initial weight enters through sigma.
+__device__ __forceinline__ void ftrl_update(float &p, float &z, float &n, float g, const OptRule &a, int reset) {
+#pragma clang fp contract(off)
+  if (reset) { z = 0.f; n = 0.1f; }
+  const float n_new = n + g * g;
+  const float l1 = a.c0, l2 = a.c1, beta = a.c2;
+  const float sigma = (sqrtf(n_new) - sqrtf(n)) / a.lr;
+  z = z + g - sigma * p;
+  const float q = (sqrtf(n_new) + beta) / a.lr + 2.f * l2;
+  p = fabsf(z) > l1 ? (copysignf(l1, z) - z) / q : 0.f;
+  n = n_new;
+}
+
+template <bool EXT = true>
+__device__ __forceinline__ void opt_update(float &p, float &m, float &v, float g, const OptRule &a, int reset) {
   if (a.kind == 0) {
-    if (a.reset) { m = 0.f; v = 0.f; }
-    m = a.beta1 * m + (1.f - a.beta1) * g;
-    v = a.beta2 * v + (1.f - a.beta2) * g * g;
-    p -= a.lr_t * m / (sqrtf(v) + a.eps);
+    const float beta1 = a.c0, beta2 = a.c1, eps = a.c2;
+    if (reset) { m = 0.f; v = 0.f; }
+    m = beta1 * m + (1.f - beta1) * g;
+    v = beta2 * v + (1.f - beta2) * g * g;
+    p -= a.lr * m / (sqrtf(v) + eps);
   } else if (a.kind == 1) {
-    if (a.reset) v = 0.1f;
+    if (reset) v = 0.1f;
     v += g * g;
-    p -= a.lr * g / (sqrtf(v) + a.eps);
-  } else {
+    p -= a.lr * g / (sqrtf(v) + a.c2);
+  } else if (!EXT || a.kind == 2) {
     p -= a.lr * g;
+  } else {
+    ftrl_update(p, m, v, g, a, reset);
   }
 }
 
@@ -155,7 +196,7 @@ __device__ __forceinline__ RowState load_row(const float *__restrict__ rows, int
   s.p = s.m = s.v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (sub < GE) {
     s.p = *reinterpret_cast<const float4 *>(rows + (int64_t)r * ld + 4 * sub);
-    if (a.kind != 2) {
+    if (rule_has_v(a.emb.kind)) {  // (the embedding rule alone decides whether there is a moment array)
       const float4 *pm = reinterpret_cast<const float4 *>(mom + (int64_t)r * 2 * D + 8 * sub);
       s.m = pm[0];
       s.v = pm[1];
@@ -168,7 +209,7 @@ __device__ __forceinline__ RowState load_row(const float *__restrict__ rows, int
 
 // applies the summed gradient g (lanes sub < GE: embedding slice; lane GE: (g_bias, g_lin, -, -)) and
 // stores the row back
-template <int G, int GE>
+template <int G, int GE, bool EXT>
 __device__ __forceinline__ void apply_row(float *__restrict__ rows, int64_t ld, float *__restrict__ mom,
                                           int D, uint32_t r, int sub, float4 g, RowState s, const OptArgs &a) {
   // lane GE needs (v_b, v_l) of lane GE + 1, and hands the updated pair back
@@ -180,13 +221,15 @@ __device__ __forceinline__ void apply_row(float *__restrict__ rows, int64_t ld, 
     g.y += a.l2_lin * s.p.y;
   }
   if (sub < GE) {
-    opt_update(s.p.x, s.m.x, s.v.x, g.x, a);
-    opt_update(s.p.y, s.m.y, s.v.y, g.y, a);
-    opt_update(s.p.z, s.m.z, s.v.z, g.z, a);
-    opt_update(s.p.w, s.m.w, s.v.w, g.w, a);
+    opt_update<EXT>(s.p.x, s.m.x, s.v.x, g.x, a.emb, a.reset);
+    opt_update<EXT>(s.p.y, s.m.y, s.v.y, g.y, a.emb, a.reset);
+    opt_update<EXT>(s.p.z, s.m.z, s.v.z, g.z, a.emb, a.reset);
+    opt_update<EXT>(s.p.w, s.m.w, s.v.w, g.w, a.emb, a.reset);
   } else if (sub == GE) {
-    opt_update(s.p.x, s.p.z, vb, g.x, a);  // bias: p.x, m = p.z, v = lane GE+1's .x
-    opt_update(s.p.y, s.p.w, vl, g.y, a);  // lin:  p.y, m = p.w, v = lane GE+1's .y
+    // (the side rule changes, of the state columns, what it keeps: nothing under SGD, v_b v_l under Adagrad)
+    const OptRule &rs = EXT ? a.side : a.emb;
+    opt_update<EXT>(s.p.x, s.p.z, vb, g.x, rs, a.reset);  // bias: p.x, m = p.z, v = lane GE+1's .x
+    opt_update<EXT>(s.p.y, s.p.w, vl, g.y, rs, a.reset);  // lin:  p.y, m = p.w, v = lane GE+1's .y
   }
   const float vb_out = __shfl_up(vb, 1, G), vl_out = __shfl_up(vl, 1, G);
   if (sub == GE + 1) {
@@ -194,9 +237,9 @@ __device__ __forceinline__ void apply_row(float *__restrict__ rows, int64_t ld, 
     s.p.y = vl_out;
   }
   if (sub <= GE + 1) *reinterpret_cast<float4 *>(rows + (int64_t)r * ld + 4 * sub) = s.p;
-  if (sub < GE && a.kind != 2) {
+  if (sub < GE && rule_has_v(a.emb.kind)) {
     float4 *pm = reinterpret_cast<float4 *>(mom + (int64_t)r * 2 * D + 8 * sub);
-    if (a.kind == 0) pm[0] = s.m;
+    if (rule_has_m<EXT>(a.emb.kind)) pm[0] = s.m;
     pm[1] = s.v;
   }
 }
@@ -221,7 +264,7 @@ struct Sorted {
 #endif
 constexpr int kPos = RM_OPT_POS;
 
-template <int G, int GE>
+template <int G, int GE, bool EXT>
 __global__ __launch_bounds__(kBlock) void sparse_apply_kernel(
     const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n, uint32_t R,
     GradSrc src, int D, float *__restrict__ rows, int64_t ld, float *__restrict__ mom, OptArgs a,
@@ -303,7 +346,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_kernel(
   }
 #pragma unroll
   for (int u = 0; u < kPos; ++u)
-    if (head[u]) apply_row<G, GE>(rows, ld, mom, D, k[u + 1], sub, g[u], st[u], a);
+    if (head[u]) apply_row<G, GE, EXT>(rows, ld, mom, D, k[u + 1], sub, g[u], st[u], a);
 }
 
 // one WAVE per SEGMENT (<= kSeg positions) of a long run: its 64 / G lane groups take the members round-robin
@@ -311,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_kernel(
 // in group order through LDS - a fixed order, bit-reproducible.  A run of one segment is applied here; the
 // segments of a longer run (a hot row of a Zipf batch: thousands of occurrences - one block per RUN walked them
 // in 48 dependent rounds) leave their sums in `partials`, combined in segment order by sparse_apply_combine_kernel.
-template <int G, int GE>
+template <int G, int GE, bool EXT>
 __global__ __launch_bounds__(kBlock) void sparse_apply_long_kernel(
     const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, GradSrc src, int D,
     float *__restrict__ rows, int64_t ld, float *__restrict__ mom, OptArgs a,
@@ -353,7 +396,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_long_kernel(
         tot.x += t.x; tot.y += t.y; tot.z += t.z; tot.w += t.w;
       }
       if (e.w == 0xFFFFFFFFu) {
-        apply_row<G, GE>(rows, ld, mom, D, e.z, sub, tot, st, a);
+        apply_row<G, GE, EXT>(rows, ld, mom, D, e.z, sub, tot, st, a);
       } else {
         partials[(int64_t)e.w * G + sub] = tot;
       }
@@ -363,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_long_kernel(
 }
 
 // one lane group per run of several segments: the segment sums in segment order, then the update
-template <int G, int GE>
+template <int G, int GE, bool EXT>
 __global__ __launch_bounds__(kBlock) void sparse_apply_combine_kernel(
     int D, float *__restrict__ rows, int64_t ld, float *__restrict__ mom, OptArgs a,
     const uint4 *__restrict__ multi_list, const float4 *__restrict__ partials, const uint32_t *__restrict__ hdr) {
@@ -387,7 +430,7 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_combine_kernel(
       const float4 t = p[(int64_t)q * G];
       tot.x += t.x; tot.y += t.y; tot.z += t.z; tot.w += t.w;
     }
-    apply_row<G, GE>(rows, ld, mom, D, e.x, sub, tot, st, a);
+    apply_row<G, GE, EXT>(rows, ld, mom, D, e.x, sub, tot, st, a);
   }
 }
 
@@ -395,14 +438,14 @@ __global__ __launch_bounds__(kBlock) void sparse_apply_combine_kernel(
 // of launches for ~20 small tensors)
 __global__ __launch_bounds__(kBlock) void dense_opt_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                           float *__restrict__ m, float *__restrict__ v,
-                                                          int64_t n, OptArgs a) {
+                                                          int64_t n, OptRule a, int reset) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float pi = p[i], mi = a.kind == 0 ? m[i] : 0.f, vi = a.kind != 2 ? v[i] : 0.f;
-    opt_update(pi, mi, vi, g[i], a);
+    float pi = p[i], mi = rule_has_m(a.kind) ? m[i] : 0.f, vi = rule_has_v(a.kind) ? v[i] : 0.f;
+    opt_update(pi, mi, vi, g[i], a, reset);
     p[i] = pi;
-    if (a.kind == 0) m[i] = mi;
-    if (a.kind != 2) v[i] = vi;
+    if (rule_has_m(a.kind)) m[i] = mi;  // (FTRL: m = z, v = n)
+    if (rule_has_v(a.kind)) v[i] = vi;
   }
 }
 
@@ -639,17 +682,37 @@ int ws_layout(int64_t n, WsLayout *w) {
   return RM_OK;
 }
 
-OptArgs opt_args(int step, int kind, float lr, float beta1, float beta2, float eps, int reset, float l2_emb = 0.f,
-                 float l2_lin = 0.f) {
-  OptArgs a;
-  a.kind = kind; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.reset = reset;
-  a.l2_emb = l2_emb; a.l2_lin = l2_lin;
-  a.lr_t = lr;
-  if (kind == 0) {
+// the caller's descriptor, checked (fn: the entry point's name for the message) and with Adam's lr_t of this step
+int opt_rule(const rm_opt_rule *r, int step, int reset, const char *fn, const char *which, OptRule *out) {
+  RM_REQUIRE(r != nullptr, "%s: NULL %s rule", fn, which);
+  RM_REQUIRE(r->kind >= 0 && r->kind <= 3 && step >= 1, "%s: bad kind / step (%s rule: kind %d)", fn, which, r->kind);
+  // (written so that a NaN fails too)
+  RM_REQUIRE(r->l1 >= 0.f && r->l2 >= 0.f && r->beta >= 0.f, "%s: %s rule: l1, l2 and beta must be >= 0", fn, which);
+  RM_REQUIRE(r->kind != 3 || r->lr > 0.f, "%s: %s rule: FTRL divides by the learning rate, lr must be > 0", fn, which);
+  OptRule a;
+  a.kind = r->kind; a.lr = r->lr; a.c0 = r->beta1; a.c1 = r->beta2; a.c2 = r->eps;
+  if (r->kind == 3) { a.c0 = r->l1; a.c1 = r->l2; a.c2 = r->beta; }
+  if (r->kind == 0) {
     const double t = reset ? 1.0 : (double)step;
-    a.lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    a.lr = (float)(r->lr * sqrt(1.0 - pow((double)r->beta2, t)) / (1.0 - pow((double)r->beta1, t)));
   }
-  return a;
+  *out = a;
+  return RM_OK;
+}
+
+int opt_args(const rm_opt_rule *emb, const rm_opt_rule *side, int step, int reset, float l2_emb, float l2_lin,
+             const char *fn, OptArgs *a) {
+  int rc = opt_rule(emb, step, reset, fn, "embedding", &a->emb);
+  if (rc == RM_OK) rc = opt_rule(side, step, reset, fn, "side", &a->side);
+  a->reset = reset; a->l2_emb = l2_emb; a->l2_lin = l2_lin;
+  return rc;
+}
+
+rm_opt_rule plain_rule(int kind, float lr, float beta1, float beta2, float eps) {
+  rm_opt_rule r;
+  r.kind = kind; r.lr = lr; r.beta1 = beta1; r.beta2 = beta2; r.eps = eps;
+  r.l1 = r.l2 = r.beta = 0.f;
+  return r;
 }
 
 // plan of the field-segmented sort, or npass = 0 when it does not apply (then: rocPRIM over all n pairs)
@@ -731,7 +794,8 @@ int sparse_step(const int64_t *idx, const int64_t *field_off, int F, const int64
   RM_REQUIRE(D % 4 == 0 && D >= 8 && D <= 64 && ld % 4 == 0 && ld >= D + 8,
              "%s: need D %% 4 == 0, 8 <= D <= 64 and a row stride ld >= D + 8 floats, ld %% 4 == 0 (D=%d ld=%lld)",
              fn, D, (long long)ld);
-  RM_REQUIRE(rows && rm_aligned16(rows) && (a.kind == 2 || (mom && rm_aligned16(mom))), "%s: rows / mom NULL or unaligned", fn);
+  RM_REQUIRE(rows && rm_aligned16(rows) && (!rule_has_v(a.emb.kind) || (mom && rm_aligned16(mom))),
+             "%s: rows / mom NULL or unaligned (the embedding rule keeps state: mom is needed)", fn);
   RM_REQUIRE(src.rows && rm_aligned16(src.rows) && src.ld % 4 == 0, "%s: gradient rows NULL / unaligned", fn);
   if (!prepared) {
     int rc = sparse_prepare(idx, field_off, F, row_ids, n, R, max_field_rows, workspace, ws_bytes, st, fn);
@@ -756,15 +820,19 @@ int sparse_step(const int64_t *idx, const int64_t *field_off, int F, const int64
   RM_REQUIRE(G <= 64, "%s: D=%d unsupported (<= 248)", fn, D);
   const int64_t pos_per_block = (int64_t)(kBlock / G) * kPos;
   dim3 grid((unsigned)((n + pos_per_block - 1) / pos_per_block));  // kPos positions per lane group
-#define RM_OPT_LAUNCH(G_, GE_)                                                                               \
-  {                                                                                                          \
-    hipLaunchKernelGGL((sparse_apply_kernel<G_, GE_>), grid, dim3(kBlock), 0, st, keys, vals, n, (uint32_t)R, \
-                       src, D, rows, ld, mom, a, seg_list, multi_list, hdr);                                 \
-    hipLaunchKernelGGL((sparse_apply_long_kernel<G_, GE_>), dim3(8192), dim3(kBlock), 0, st, keys, vals, src, \
-                       D, rows, ld, mom, a, seg_list, partials, hdr);                                        \
-    hipLaunchKernelGGL((sparse_apply_combine_kernel<G_, GE_>), dim3(64), dim3(kBlock), 0, st, D, rows, ld,   \
-                       mom, a, multi_list, partials, hdr);                                                   \
+  // FTRL in either role, or two rules that differ: the extended kernels
+  const bool ext = a.emb.kind == 3 || a.side.kind == 3 || memcmp(&a.emb, &a.side, sizeof(OptRule)) != 0;
+#define RM_OPT_LAUNCH_EXT(G_, GE_, EXT_)                                                                         \
+  {                                                                                                              \
+    hipLaunchKernelGGL((sparse_apply_kernel<G_, GE_, EXT_>), grid, dim3(kBlock), 0, st, keys, vals, n,           \
+                       (uint32_t)R, src, D, rows, ld, mom, a, seg_list, multi_list, hdr);                        \
+    hipLaunchKernelGGL((sparse_apply_long_kernel<G_, GE_, EXT_>), dim3(8192), dim3(kBlock), 0, st, keys, vals,   \
+                       src, D, rows, ld, mom, a, seg_list, partials, hdr);                                       \
+    hipLaunchKernelGGL((sparse_apply_combine_kernel<G_, GE_, EXT_>), dim3(64), dim3(kBlock), 0, st, D, rows, ld, \
+                       mom, a, multi_list, partials, hdr);                                                       \
   }
+#define RM_OPT_LAUNCH(G_, GE_) \
+  if (ext) RM_OPT_LAUNCH_EXT(G_, GE_, true) else RM_OPT_LAUNCH_EXT(G_, GE_, false)
   switch (GE) {
     case 2: RM_OPT_LAUNCH(4, 2) break;
     case 3: RM_OPT_LAUNCH(8, 3) break;
@@ -778,6 +846,7 @@ int sparse_step(const int64_t *idx, const int64_t *field_off, int F, const int64
       return RM_EUNSUPPORTED;
   }
 #undef RM_OPT_LAUNCH
+#undef RM_OPT_LAUNCH_EXT
   RM_CHECK_LAUNCH(fn);
   return RM_OK;
 }
@@ -799,6 +868,65 @@ extern "C" int rm_sparse_optimizer_prepare(const int64_t *idx, const int64_t *fi
                         "rm_sparse_optimizer_prepare");
 }
 
+// The three steps behind both generations of entry points; fn: the name of the entry point called, for messages.
+// Checks in the order the entry points always had: sizes, then the rule(s) (kind / step), then the pointers.
+static int step_fields(const int64_t *idx, const int64_t *field_off, const float *d_rows, const float *g_bias,
+                       const float *g_lin, int64_t B, int F, int D, int64_t R, float *rows, int64_t ld, float *mom,
+                       int step, const rm_opt_rule *emb_rule, const rm_opt_rule *side_rule, int reset,
+                       float l2_embedding, float l2_linear, const float *lin_field_mask, int64_t max_field_rows,
+                       int prepared, void *workspace, int64_t ws_bytes, rm_stream_t stream, const char *fn) {
+  RM_REQUIRE(B >= 0 && F > 0, "%s: bad sizes", fn);
+  OptArgs a;
+  const int rc = opt_args(emb_rule, side_rule, step, reset, l2_embedding, l2_linear, fn, &a);
+  if (rc != RM_OK) return rc;
+  if (B == 0) return RM_OK;
+  RM_REQUIRE(prepared || (idx && field_off), "%s: NULL argument", fn);
+  GradSrc src = {0, d_rows, D, g_bias, g_lin, lin_field_mask, F};
+  return sparse_step(idx, field_off, F, nullptr, B * F, src, D, R, max_field_rows, rows, ld, mom, a, prepared,
+                     workspace, ws_bytes, (hipStream_t)stream, fn);
+}
+
+static int step_rows(const int64_t *row_ids, const float *grad_rows, int64_t gw, int64_t n, int D, int64_t R,
+                     float *rows, int64_t ld, float *mom, int step, const rm_opt_rule *emb_rule,
+                     const rm_opt_rule *side_rule, int reset, float l2_embedding, float l2_linear, int prepared,
+                     void *workspace, int64_t ws_bytes, rm_stream_t stream, const char *fn) {
+  RM_REQUIRE(n >= 0 && gw >= D + 2, "%s: gradient rows need D + 2 columns", fn);
+  OptArgs a;
+  const int rc = opt_args(emb_rule, side_rule, step, reset, l2_embedding, l2_linear, fn, &a);
+  if (rc != RM_OK) return rc;
+  if (n == 0) return RM_OK;
+  RM_REQUIRE(prepared || row_ids, "%s: NULL argument", fn);
+  GradSrc src = {1, grad_rows, gw, nullptr, nullptr, nullptr, 1};
+  return sparse_step(nullptr, nullptr, 1, row_ids, n, src, D, R, 0, rows, ld, mom, a, prepared, workspace, ws_bytes,
+                     (hipStream_t)stream, fn);
+}
+
+static int step_dense(float *p, const float *g, float *m, float *v, int64_t n, int step, const rm_opt_rule *rule,
+                      int reset, rm_stream_t stream, const char *fn) {
+  RM_REQUIRE(n >= 0, "%s: bad arguments", fn);
+  OptRule a;
+  const int rc = opt_rule(rule, step, reset, fn, "dense", &a);
+  if (rc != RM_OK) return rc;
+  if (n == 0) return RM_OK;
+  RM_REQUIRE(p && g && (!rule_has_v(a.kind) || v) && (!rule_has_m(a.kind) || m), "%s: NULL argument", fn);
+  hipLaunchKernelGGL(dense_opt_kernel, dim3(rm_grid_cap((n + kBlock - 1) / kBlock, 256 * 4)), dim3(kBlock), 0,
+                     (hipStream_t)stream, p, g, m, v, n, a, reset);
+  RM_CHECK_LAUNCH(fn);
+  return RM_OK;
+}
+
+extern "C" int rm_sparse_optimizer_step_rules(const int64_t *idx, const int64_t *field_off, const float *d_rows,
+                                              const float *g_bias, const float *g_lin, int64_t B, int F, int D,
+                                              int64_t R, float *rows, int64_t ld, float *mom, int step,
+                                              const rm_opt_rule *emb_rule, const rm_opt_rule *side_rule, int reset,
+                                              float l2_embedding, float l2_linear, const float *lin_field_mask,
+                                              int64_t max_field_rows, int prepared, void *workspace,
+                                              int64_t ws_bytes, rm_stream_t stream) {
+  return step_fields(idx, field_off, d_rows, g_bias, g_lin, B, F, D, R, rows, ld, mom, step, emb_rule, side_rule,
+                     reset, l2_embedding, l2_linear, lin_field_mask, max_field_rows, prepared, workspace, ws_bytes,
+                     stream, "rm_sparse_optimizer_step_rules");
+}
+
 extern "C" int rm_sparse_optimizer_step(const int64_t *idx, const int64_t *field_off, const float *d_rows,
                                         const float *g_bias, const float *g_lin, int64_t B, int F, int D,
                                         int64_t R, float *rows, int64_t ld, float *mom, int step, int kind,
@@ -809,12 +937,20 @@ extern "C" int rm_sparse_optimizer_step(const int64_t *idx, const int64_t *field
                                         int64_t ws_bytes, rm_stream_t stream) {
   RM_REQUIRE(B >= 0 && F > 0, "rm_sparse_optimizer_step: bad sizes");
   RM_REQUIRE(kind >= 0 && kind <= 2 && step >= 1, "rm_sparse_optimizer_step: bad kind / step");
-  if (B == 0) return RM_OK;
-  RM_REQUIRE(prepared || (idx && field_off), "rm_sparse_optimizer_step: NULL argument");
-  GradSrc src = {0, d_rows, D, g_bias, g_lin, lin_field_mask, F};
-  return sparse_step(idx, field_off, F, nullptr, B * F, src, D, R, max_field_rows, rows, ld, mom,
-                     opt_args(step, kind, lr, beta1, beta2, eps, reset, l2_embedding, l2_linear), prepared,
-                     workspace, ws_bytes, (hipStream_t)stream, "rm_sparse_optimizer_step");
+  const rm_opt_rule r = plain_rule(kind, lr, beta1, beta2, eps);  // one rule for both parts
+  return step_fields(idx, field_off, d_rows, g_bias, g_lin, B, F, D, R, rows, ld, mom, step, &r, &r, reset,
+                     l2_embedding, l2_linear, lin_field_mask, max_field_rows, prepared, workspace, ws_bytes, stream,
+                     "rm_sparse_optimizer_step");
+}
+
+extern "C" int rm_sparse_optimizer_step_rows_rules(const int64_t *row_ids, const float *grad_rows, int64_t gw,
+                                                   int64_t n, int D, int64_t R, float *rows, int64_t ld, float *mom,
+                                                   int step, const rm_opt_rule *emb_rule,
+                                                   const rm_opt_rule *side_rule, int reset, float l2_embedding,
+                                                   float l2_linear, int prepared, void *workspace, int64_t ws_bytes,
+                                                   rm_stream_t stream) {
+  return step_rows(row_ids, grad_rows, gw, n, D, R, rows, ld, mom, step, emb_rule, side_rule, reset, l2_embedding,
+                   l2_linear, prepared, workspace, ws_bytes, stream, "rm_sparse_optimizer_step_rows_rules");
 }
 
 extern "C" int rm_sparse_optimizer_step_rows(const int64_t *row_ids, const float *grad_rows, int64_t gw,
@@ -824,22 +960,20 @@ extern "C" int rm_sparse_optimizer_step_rows(const int64_t *row_ids, const float
                                              void *workspace, int64_t ws_bytes, rm_stream_t stream) {
   RM_REQUIRE(n >= 0 && gw >= D + 2, "rm_sparse_optimizer_step_rows: gradient rows need D + 2 columns");
   RM_REQUIRE(kind >= 0 && kind <= 2 && step >= 1, "rm_sparse_optimizer_step_rows: bad kind / step");
-  if (n == 0) return RM_OK;
-  RM_REQUIRE(prepared || row_ids, "rm_sparse_optimizer_step_rows: NULL argument");
-  GradSrc src = {1, grad_rows, gw, nullptr, nullptr, nullptr, 1};
-  return sparse_step(nullptr, nullptr, 1, row_ids, n, src, D, R, 0, rows, ld, mom,
-                     opt_args(step, kind, lr, beta1, beta2, eps, reset, l2_embedding, l2_linear), prepared,
-                     workspace, ws_bytes, (hipStream_t)stream, "rm_sparse_optimizer_step_rows");
+  const rm_opt_rule r = plain_rule(kind, lr, beta1, beta2, eps);
+  return step_rows(row_ids, grad_rows, gw, n, D, R, rows, ld, mom, step, &r, &r, reset, l2_embedding, l2_linear,
+                   prepared, workspace, ws_bytes, stream, "rm_sparse_optimizer_step_rows");
+}
+
+extern "C" int rm_dense_optimizer_step_rule(float *p, const float *g, float *m, float *v, int64_t n, int step,
+                                            const rm_opt_rule *rule, int reset, rm_stream_t stream) {
+  return step_dense(p, g, m, v, n, step, rule, reset, stream, "rm_dense_optimizer_step_rule");
 }
 
 extern "C" int rm_dense_optimizer_step(float *p, const float *g, float *m, float *v, int64_t n, int step,
                                        int kind, float lr, float beta1, float beta2, float eps, int reset,
                                        rm_stream_t stream) {
   RM_REQUIRE(n >= 0 && kind >= 0 && kind <= 2 && step >= 1, "rm_dense_optimizer_step: bad arguments");
-  if (n == 0) return RM_OK;
-  RM_REQUIRE(p && g && (kind == 2 || v) && (kind != 0 || m), "rm_dense_optimizer_step: NULL argument");
-  hipLaunchKernelGGL(dense_opt_kernel, dim3(rm_grid_cap((n + kBlock - 1) / kBlock, 256 * 4)), dim3(kBlock), 0,
-                     (hipStream_t)stream, p, g, m, v, n, opt_args(step, kind, lr, beta1, beta2, eps, reset));
-  RM_CHECK_LAUNCH("rm_dense_optimizer_step");
-  return RM_OK;
+  const rm_opt_rule r = plain_rule(kind, lr, beta1, beta2, eps);
+  return step_dense(p, g, m, v, n, step, &r, reset, stream, "rm_dense_optimizer_step");
 }

@@ -1077,9 +1077,9 @@ def make_sharded_engine(model, spec, D, hp, device, rank, world, group=None, cap
                               f"{b} examples per launch)", symbol="embed_fwd_kernel", fn=fn,
                          work=self._embed_fwd_bytes(b, fm), bound="hbm")]
 
-        def optimizer(self, name="adam", lr=1e-3):
+        def optimizer(self, name="adam", lr=1e-3, **rules):
             """The training step's second half for this engine: ShardedOptimizer(self, ...)."""
-            return ShardedOptimizer(self, name, lr)
+            return ShardedOptimizer(self, name, lr, **rules)
 
         def optimizer_probe_sharded(self, idx, dense, y, iters=5):
             """Times the owner-side optimizer step (every rank calls it: no collective inside, but the
@@ -1122,30 +1122,30 @@ class ShardedOptimizer:
     of the dense parameters from the all-reduced gradient (identical on every rank, so the replicas stay
     bit-identical).  Keras Adam / Adagrad / SGD, lazy on the table rows - the same semantics as
     optim.SparseTableOptimizer on one GPU.  The moments of a shard row's embedding live in a second
-    [R_local, 2 D] array, those of its bias / linear entries in the row's own state columns."""
+    [R_local, 2 D] array, those of its bias / linear entries in the row's own state columns.
+    name may be "ftrl" and side / side_lr give the wide part (the rows' bias and linear entries, linear_w_dense) a
+    rule of its own, as in optim.SparseTableOptimizer / FusedDenseOptimizer; the state is initialised per part."""
 
-    def __init__(self, engine, name="adam", lr=1e-3):
-        from . import ops
+    def __init__(self, engine, name="adam", lr=1e-3, side=None, side_lr=None, ftrl_l1=0.0, ftrl_l2=0.0,
+                 ftrl_beta=0.0):
+        from . import ops, optim
         from .optim import FusedDenseOptimizer
 
-        if name not in ("adam", "adagrad", "gd", "sgd"):
-            raise ValueError(f"ShardedOptimizer: {name!r} unsupported (adam, adagrad, sgd)")
+        side = name if side is None else side
+        optim.check_rules("ShardedOptimizer", name, side)
         self.ops, self.e, self.name, self.lr = ops, engine, name, float(lr)
+        self.side, self.side_lr = side, self.lr if side_lr is None else float(side_lr)
+        ftrl = dict(ftrl_l1=float(ftrl_l1), ftrl_l2=float(ftrl_l2), ftrl_beta=float(ftrl_beta))
+        self._rules = dict(l1=ftrl["ftrl_l1"], l2=ftrl["ftrl_l2"], ftrl_beta=ftrl["ftrl_beta"], side_kind=side,
+                           side_lr=self.side_lr)
         st, D = engine.st, engine.D
         n = st.shard.shape[0]
-        self.mom = None
-        if name in ("adam", "adagrad"):
-            self.mom = torch.zeros(n, 2 * D, device=st.shard.device)
-            if name == "adagrad":
-                self.mom.view(n, D // 4, 2, 4)[:, :, 1, :] = 0.1
+        self.mom = optim.init_moment_rows(name, n, D, st.shard.device)  # by the embedding rule
+
         def init_state_columns():
-            st.shard[:, D + 2: D + 6] = 0.0
-            if name == "adagrad":
-                st.shard[:, D + 4: D + 6] = 0.1
+            optim.init_state_columns(st.shard, D, side)  # by the side rule
             if self.mom is not None:
-                self.mom.zero_()
-                if name == "adagrad":
-                    self.mom.view(n, D // 4, 2, 4)[:, :, 1, :] = 0.1
+                optim.fill_moment_rows(self.mom, name)  # (in place: the array is as large as the shard)
             self.t = 0
             if getattr(self, "dense", None) is not None:
                 self.dense.reset()
@@ -1153,7 +1153,7 @@ class ShardedOptimizer:
         self.t = 0
         init_state_columns()
         st.on_load = init_state_columns  # a restored shard starts the optimizer afresh (ShardedTable.load)
-        self.dense = FusedDenseOptimizer(engine, name, lr)
+        self.dense = FusedDenseOptimizer(engine, name, lr, side=side, side_lr=self.side_lr, **ftrl)
         self._ws = None
         self.t = 0
         # embedding_l2_reg / linear_l2_reg, lazily: reg * row for the rows this step touches (once per row: the owner
@@ -1177,5 +1177,6 @@ class ShardedOptimizer:
         if n:
             self.ops.sparse_optimizer_step_rows(ids.contiguous(), rows.contiguous(), e.D, e.st.shard, self.mom,
                                                 self._ws, self.t, self.name, self.lr, reset=reset,
-                                                l2_embedding=self.l2_embedding, l2_linear=self.l2_linear)
+                                                l2_embedding=self.l2_embedding, l2_linear=self.l2_linear,
+                                                **self._rules)
         self.dense.step(reset=reset)

@@ -990,24 +990,28 @@ class Engine:
         """The dominant kernel's roofline record (roofline_probe_all()[0])."""
         return self.roofline_probe_all(idx, dense, y, iters)[0]
 
-    def optimizer_probe(self, idx, iters=10, more_ids=()):
+    def optimizer_probe(self, idx, iters=10, more_ids=(), name="adam", side=None, lr=1e-3, **rules):
         """Times the separately-reported optimizer step on the gradients of the last fwd_bwd: the
         row-wise step on the touched table rows + the dense parameters in one launch; checks that two
         identical steps from the same state give bit-identical tables.  more_ids: further id batches -
-        the timed steps then cycle through all of them (every step touches other rows, as in fit())."""
+        the timed steps then cycle through all of them (every step touches other rows, as in fit()).
+        name / side / lr / rules: the optimizers' arguments (optim.SparseTableOptimizer: side, side_lr, ftrl_l1, ..);
+        the default is Adam for every parameter."""
         from .optim import FusedDenseOptimizer, SparseTableOptimizer
 
         ids = [idx] + list(more_ids)
-        sopt, dopt = SparseTableOptimizer(self, "adam", 1e-3), FusedDenseOptimizer(self, "adam", 1e-3)
+        sopt = SparseTableOptimizer(self, name, lr, side=side, **rules)
+        dopt = FusedDenseOptimizer(self, name, lr, side=side, **rules)
         # determinism: the same step twice from the same state (rows + moments restored in between)
-        rows0, mom0 = self.rows.clone(), sopt.mom.clone()
+        mom = sopt.mom if sopt.mom is not None else self.rows.new_zeros(1)  # (an SGD embedding rule keeps none)
+        rows0, mom0 = self.rows.clone(), mom.clone()
         sopt.step(idx)
-        rows1, mom1 = self.rows.clone(), sopt.mom.clone()
+        rows1, mom1 = self.rows.clone(), mom.clone()
         self.rows.copy_(rows0)
-        sopt.mom.copy_(mom0)
+        mom.copy_(mom0)
         sopt.t = 0
         sopt.step(idx)
-        same = bool(torch.equal(self.rows, rows1) and torch.equal(sopt.mom, mom1))
+        same = bool(torch.equal(self.rows, rows1) and torch.equal(mom, mom1))
         del rows0, mom0, rows1, mom1
         iters = max(iters, 2 * len(ids))
         for i in range(3):
@@ -1031,9 +1035,14 @@ class Engine:
         return {"ms": round(ms_s + ms_d, 4), "sparse_rows_ms": round(ms_s, 4), "dense_params_ms": round(ms_d, 4),
                 "sort_ms": round(ms_p, 4), "apply_ms": round(ms_s - ms_p, 4),
                 "bit_identical_rerun": same, "id_batches_rotated": len(ids),
-                "what": "row-wise lazy Adam on the touched table rows (rm_sparse_optimizer_step: stable sort by "
-                        "row, duplicates summed in occurrence order, no float atomics) + Adam on the dense "
-                        "parameters in one launch (rm_dense_optimizer_step), timed back to back; sort_ms is the "
+                "rules": {"optimizer": name, "linear_optimizer": sopt.side},
+                "dense_launches": len(dopt.ranges),
+                "what": "row-wise lazy step on the touched table rows by the rules under `rules` "
+                        "(rm_sparse_optimizer_step_rules: stable sort by row, duplicates summed in occurrence order, "
+                        "no float atomics), then the step on the dense "
+                        "parameters (rm_dense_optimizer_step_rule: one launch over the flat buffer, or "
+                        "`dense_launches` of them around linear_w_dense when the wide part has a rule of its own), "
+                        "timed back to back; sort_ms is the "
                         "id-only part (rm_sparse_optimizer_prepare) that fit() issues on a side stream beside "
                         "fwd+bwd; NOT part of value",
                 "roofline": sopt.roofline(idx, ms_s)}

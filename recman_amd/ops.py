@@ -1130,7 +1130,25 @@ def pack_grad_rows(d_rows, g_bias, g_lin, pos, out, lin_field_mask=None):
               _chk(pos, "pos", I64, (B * F,)), B, F, D, width, _chk(out, "out", F32), _stream())
 
 
-OPT_KINDS = {"adam": 0, "adagrad": 1, "gd": 2, "sgd": 2}
+OPT_KINDS = {"adam": 0, "adagrad": 1, "gd": 2, "sgd": 2, "ftrl": 3}
+
+
+def _opt_rule(kind, lr, beta1=0.9, beta2=0.999, eps=1e-7, l1=0.0, l2=0.0, ftrl_beta=0.0):
+    """rm_opt_rule of include/recman_hip.h (beta1 / beta2 / eps: Adam, Adagrad; l1 / l2 / ftrl_beta: FTRL)."""
+    return _lib.OptRule(OPT_KINDS[kind], float(lr), float(beta1), float(beta2), float(eps), float(l1), float(l2),
+                        float(ftrl_beta))
+
+
+def _opt_rules(kind, lr, beta1, beta2, eps, l1, l2, ftrl_beta, side_kind, side_lr, side_beta1, side_beta2, side_eps,
+               side_l1, side_l2, side_ftrl_beta):
+    """(embedding rule, side rule) of a row-wise step: every side_* left None takes the embedding rule's value."""
+    def pick(x, d):
+        return d if x is None else x
+
+    emb = _opt_rule(kind, lr, beta1, beta2, eps, l1, l2, ftrl_beta)
+    side = _opt_rule(pick(side_kind, kind), pick(side_lr, lr), pick(side_beta1, beta1), pick(side_beta2, beta2),
+                     pick(side_eps, eps), pick(side_l1, l1), pick(side_l2, l2), pick(side_ftrl_beta, ftrl_beta))
+    return emb, side
 
 
 def sparse_optimizer_workspace(n):
@@ -1165,48 +1183,60 @@ def sparse_optimizer_prepare(workspace, R, idx=None, field_off=None, row_ids=Non
 
 def sparse_optimizer_step(idx, field_off, d_rows, rows, mom, workspace, step, kind, lr, D=None,
                           g_bias=None, g_lin=None, reset=False, beta1=0.9, beta2=0.999, eps=1e-7,
-                          lin_field_mask=None, prepared=False, l2_embedding=0.0, l2_linear=0.0, max_field_rows=0):
-    """Lazy row-wise optimizer step on table rows [R, ld] (see rm_sparse_optimizer_step): rows =
-    [D emb | bias | lin | m_b | m_l | v_b | v_l | pad], mom [R, 2D] = [m | v] of the embedding."""
+                          lin_field_mask=None, prepared=False, l2_embedding=0.0, l2_linear=0.0, max_field_rows=0,
+                          l1=0.0, l2=0.0, ftrl_beta=0.0, side_kind=None, side_lr=None, side_beta1=None,
+                          side_beta2=None, side_eps=None, side_l1=None, side_l2=None, side_ftrl_beta=None):
+    """Lazy row-wise optimizer step on table rows [R, ld] (see rm_sparse_optimizer_step_rules): rows =
+    [D emb | bias | lin | m_b | m_l | v_b | v_l | pad], mom [R, 2D] = [m | v] of the embedding ("ftrl": m = z,
+    v = n; l1 / l2 / ftrl_beta are its constants).  side_*: another rule for the bias and linear entries (and the
+    row's state columns); each one left None takes the value of the embedding rule, so that leaving all of them out
+    is one rule for the whole row.  mom may be None when the EMBEDDING rule is "sgd"."""
     B, F, Dg = d_rows.shape
     D = Dg if D is None else D
     R, ld = rows.shape
     if mom is not None:
         _chk(mom, "mom", F32, (R, 2 * D))
     wp, wn = _opt_ws(workspace, B * F)
-    _lib.call("rm_sparse_optimizer_step", _chk(idx, "idx", I64, (B, F)),
+    emb, side = _opt_rules(kind, lr, beta1, beta2, eps, l1, l2, ftrl_beta, side_kind, side_lr, side_beta1, side_beta2,
+                           side_eps, side_l1, side_l2, side_ftrl_beta)
+    _lib.call("rm_sparse_optimizer_step_rules", _chk(idx, "idx", I64, (B, F)),
               _chk(field_off, "field_off", I64, (F,)), _chk(d_rows, "d_rows", F32, (B, F, D)),
               _chk(g_bias, "g_bias", F32, (B,), allow_none=True),
               _chk(g_lin, "g_lin", F32, (B,), allow_none=True), B, F, D, R, _chk(rows, "rows", F32), ld,
-              None if mom is None else mom.data_ptr(), int(step), OPT_KINDS[kind], float(lr), float(beta1),
-              float(beta2), float(eps), 1 if reset else 0, float(l2_embedding), float(l2_linear),
+              None if mom is None else mom.data_ptr(), int(step), ctypes.byref(emb), ctypes.byref(side),
+              1 if reset else 0, float(l2_embedding), float(l2_linear),
               _chk(lin_field_mask, "lin_field_mask", F32, (F,), allow_none=True), int(max_field_rows),
               1 if prepared else 0, wp, wn, _stream())
 
 
 def sparse_optimizer_step_rows(row_ids, grad_rows, D, rows, mom, workspace, step, kind, lr, reset=False,
-                               beta1=0.9, beta2=0.999, eps=1e-7, prepared=False, l2_embedding=0.0, l2_linear=0.0):
+                               beta1=0.9, beta2=0.999, eps=1e-7, prepared=False, l2_embedding=0.0, l2_linear=0.0,
+                               l1=0.0, l2=0.0, ftrl_beta=0.0, side_kind=None, side_lr=None, side_beta1=None,
+                               side_beta2=None, side_eps=None, side_l1=None, side_l2=None, side_ftrl_beta=None):
     """The same step from gradient rows that carry their (local) table row: row_ids [n] (< 0: skip),
-    grad_rows [n, gw] = [dE | g_bias | g_lin | ...] (rm_sparse_optimizer_step_rows)."""
+    grad_rows [n, gw] = [dE | g_bias | g_lin | ...] (rm_sparse_optimizer_step_rows_rules; the rules as in
+    sparse_optimizer_step)."""
     n, gw = grad_rows.shape
     R, ld = rows.shape
     if mom is not None:
         _chk(mom, "mom", F32, (R, 2 * D))
     wp, wn = _opt_ws(workspace, n)
-    _lib.call("rm_sparse_optimizer_step_rows", _chk(row_ids, "row_ids", I64, (n,)),
+    emb, side = _opt_rules(kind, lr, beta1, beta2, eps, l1, l2, ftrl_beta, side_kind, side_lr, side_beta1, side_beta2,
+                           side_eps, side_l1, side_l2, side_ftrl_beta)
+    _lib.call("rm_sparse_optimizer_step_rows_rules", _chk(row_ids, "row_ids", I64, (n,)),
               _chk(grad_rows, "grad_rows", F32), gw, n, D, R, _chk(rows, "rows", F32), ld,
-              None if mom is None else mom.data_ptr(), int(step), OPT_KINDS[kind], float(lr), float(beta1),
-              float(beta2), float(eps), 1 if reset else 0, float(l2_embedding), float(l2_linear),
-              1 if prepared else 0, wp, wn, _stream())
+              None if mom is None else mom.data_ptr(), int(step), ctypes.byref(emb), ctypes.byref(side),
+              1 if reset else 0, float(l2_embedding), float(l2_linear), 1 if prepared else 0, wp, wn, _stream())
 
 
-def dense_optimizer_step(p, g, m, v, step, kind, lr, reset=False, beta1=0.9, beta2=0.999, eps=1e-7):
-    """One launch over a flat parameter buffer (rm_dense_optimizer_step)."""
+def dense_optimizer_step(p, g, m, v, step, kind, lr, reset=False, beta1=0.9, beta2=0.999, eps=1e-7, l1=0.0, l2=0.0,
+                         ftrl_beta=0.0):
+    """One launch over a flat parameter buffer (rm_dense_optimizer_step_rule; "ftrl": m = z, v = n)."""
     n = p.numel()
-    _lib.call("rm_dense_optimizer_step", _chk(p, "p", F32, (n,)), _chk(g, "g", F32, (n,)),
+    rule = _opt_rule(kind, lr, beta1, beta2, eps, l1, l2, ftrl_beta)
+    _lib.call("rm_dense_optimizer_step_rule", _chk(p, "p", F32, (n,)), _chk(g, "g", F32, (n,)),
               _chk(m, "m", F32, (n,), allow_none=True), _chk(v, "v", F32, (n,), allow_none=True), n,
-              int(step), OPT_KINDS[kind], float(lr), float(beta1), float(beta2), float(eps),
-              1 if reset else 0, _stream())
+              int(step), ctypes.byref(rule), 1 if reset else 0, _stream())
 
 
 def _chk_csr(offsets, ids, vals):

@@ -16,10 +16,68 @@ Three pieces:
                          LazyAdam is a deliberate deviation from Keras' sparse Adam (which decays the
                          moments of every row each step): identical under the reference's
                          new-optimizer-per-batch quirk (reset=True) and when every row is touched every
-                         step; DESIGN.md section 6, tests/test_gpu_optim.py."""
+                         step; DESIGN.md section 6, tests/test_gpu_optim.py.
+
+The two fused pieces also know FTRL-Proximal ("ftrl": tf.keras.optimizers.Ftrl, learning_rate_power -0.5, initial
+accumulator 0.1, constants ftrl_l1 / ftrl_l2 / ftrl_beta) and a SIDE rule - another optimizer name and learning rate
+for the wide part of the model: the bias and linear entries of the table rows and linear_w_dense (the Wide&Deep
+recipe: FTRL with L1 on the wide weights, Adam / Adagrad on the embeddings and the DNN).  Keras applies FTRL to
+IndexedSlices row by row, so under FTRL the lazy row-wise step is Keras's own semantics.
+The dict-walking Optimizer has no FTRL on purpose: on a densified table gradient its first step would set every
+untouched row to zero (g = 0 leaves z = 0, hence p = 0)."""
 import math
 
 import torch
+
+FUSED_RULES = ("adam", "adagrad", "gd", "sgd", "ftrl")
+
+
+def canonical(name):
+    return "sgd" if name == "gd" else name
+
+
+def has_m(name):
+    """Does the rule use the first state slot (Adam: m; FTRL: z)?"""
+    return name in ("adam", "ftrl")
+
+
+def has_v(name):
+    """Does the rule use the second state slot (Adam, Adagrad: v; FTRL: n)?"""
+    return canonical(name) != "sgd"
+
+
+def v_init(name):
+    """Initial value of the second state slot: Keras starts Adagrad's and FTRL's accumulator at 0.1."""
+    return 0.1 if name in ("adagrad", "ftrl") else 0.0
+
+
+def init_moment_rows(name, R, D, device):
+    """The [R, 2 D] interleaved state of the embedding entries under rule `name` (None: the rule keeps none)."""
+    if not has_v(name):
+        return None
+    return fill_moment_rows(torch.empty(R, 2 * D, device=device), name)
+
+
+def fill_moment_rows(mom, name):
+    """Resets an [R, 2 D] interleaved state array in place to rule `name`'s initial values; returns it."""
+    R, D2 = mom.shape
+    mom.zero_()
+    if v_init(name):
+        mom.view(R, D2 // 8, 2, 4)[:, :, 1, :] = v_init(name)  # the v halves ([m4 v4] per float4 slice)
+    return mom
+
+
+def init_state_columns(rows, D, name):
+    """The bias / linear entries' state in the row's padding, [.. bias lin | m_b m_l v_b v_l | ..], under rule `name`."""
+    rows[:, D + 2: D + 6] = 0.0
+    if v_init(name):
+        rows[:, D + 4: D + 6] = v_init(name)
+
+
+def check_rules(who, name, side):
+    for n in (name, side):
+        if n not in FUSED_RULES:
+            raise ValueError(f"{who}: {n!r} unsupported (adam, adagrad, sgd, ftrl)")
 
 
 class Optimizer:
@@ -81,14 +139,21 @@ class FusedDenseOptimizer:
     """Dense parameters of an engine in ONE launch per step.  Construction re-homes the engine's dense
     parameters and their gradients as views of two flat buffers (same values; the kernels read the
     dicts at every call, so nothing else changes - but build it BEFORE capturing a hipGraph of the
-    step).  Adam / Adagrad / SGD with the Keras constants."""
+    step).  Adam / Adagrad / SGD / FTRL with the Keras constants.
+    side / side_lr: another rule for linear_w_dense, the wide weights of the dense features (a 16-byte aligned slot of
+    the flat buffer); when it differs from the main rule the step is up to three launches over the sub-ranges before,
+    of and behind that slot - every element is updated exactly once.  State: m (Adam's m, FTRL's z) and v (Adam's and
+    Adagrad's v, FTRL's n) as flat buffers beside p, allocated when some range needs them."""
 
-    def __init__(self, engine, name="adam", lr=1e-3):
+    def __init__(self, engine, name="adam", lr=1e-3, side=None, side_lr=None, ftrl_l1=0.0, ftrl_l2=0.0,
+                 ftrl_beta=0.0):
         from . import ops
 
-        if name not in ("adam", "adagrad", "gd", "sgd"):
-            raise ValueError(f"FusedDenseOptimizer: {name!r} unsupported (adam, adagrad, sgd)")
+        side = name if side is None else side
+        check_rules("FusedDenseOptimizer", name, side)
         self.ops, self.e, self.name, self.lr = ops, engine, name, float(lr)
+        self.side, self.side_lr = side, self.lr if side_lr is None else float(side_lr)
+        self._ftrl = dict(l1=float(ftrl_l1), l2=float(ftrl_l2), ftrl_beta=float(ftrl_beta))
         flat_g = getattr(engine, "_flat_grads", None)  # the row-sharded engines flattened theirs already
         self.keys = sorted(engine.grads)
         if flat_g is None:
@@ -99,23 +164,38 @@ class FusedDenseOptimizer:
         if "linear_w_dense" in engine.params:
             engine.linear_w_dense = engine.params["linear_w_dense"]  # (the engines also hold it as an attribute)
         assert self.p.numel() == self.g.numel()
-        self.m = torch.zeros_like(self.p) if name == "adam" else None
-        self.v = (torch.zeros_like(self.p) if name == "adam"
-                  else torch.full_like(self.p, 0.1) if name == "adagrad" else None)
-        self.t = 0
+        # (start, end, rule, lr) of every launch: the whole buffer, or split around linear_w_dense's slot
+        n = self.p.numel()
+        self.ranges = [(0, n, name, self.lr)]
+        wide = engine.params["linear_w_dense"] if "linear_w_dense" in self.keys else None
+        if (canonical(side), self.side_lr) != (canonical(name), self.lr) and wide is not None and wide.numel():
+            a = (wide.data_ptr() - self.p.data_ptr()) // 4
+            b = a + (wide.numel() + 3) // 4 * 4  # the slot with its padding (flatten_views)
+            assert 0 <= a < b <= n and a % 4 == 0
+            self.ranges = [r for r in ((0, a, name, self.lr), (a, b, side, self.side_lr), (b, n, name, self.lr))
+                           if r[1] > r[0]]
+        names = [r[2] for r in self.ranges]
+        self.m = torch.zeros_like(self.p) if any(has_m(x) for x in names) else None
+        self.v = torch.zeros_like(self.p) if any(has_v(x) for x in names) else None
+        self._launches = [(self.p[a:b], self.g[a:b], self.m[a:b] if has_m(x) else None,
+                           self.v[a:b] if has_v(x) else None, x, rate, self._ftrl if x == "ftrl" else {})
+                          for a, b, x, rate in self.ranges]
+        self.reset()
 
     def reset(self):
         self.t = 0
         if self.m is not None:
             self.m.zero_()
-        if self.v is not None:
-            self.v.fill_(0.0 if self.name == "adam" else 0.1)
+        for a, b, x, _ in self.ranges:
+            if has_v(x):
+                self.v[a:b] = v_init(x)
 
     def step(self, params=None, grads=None, reset=False):
         """(params / grads are accepted for interface parity with Optimizer.step and ignored: the
         engine's own flat buffers are updated.)"""
         self.t += 1
-        self.ops.dense_optimizer_step(self.p, self.g, self.m, self.v, self.t, self.name, self.lr, reset=reset)
+        for p, g, m, v, x, rate, kw in self._launches:
+            self.ops.dense_optimizer_step(p, g, m, v, self.t, x, rate, reset=reset, **kw)
 
 
 class SparseTableOptimizer:
@@ -137,14 +217,22 @@ class SparseTableOptimizer:
     field's column of idx is masked out as well and the field gets ONE occurrence list - its own B occurrences
     followed by the history occurrences of every sequence feature that looks it up (their key-gradient rows from
     rm_asp_bwd, zero bias and zero linear gradient): a row that is a target in one example and a history item in
-    another receives one update with the summed gradient."""
+    another receives one update with the summed gradient.
+    name may be "ftrl" (constants ftrl_l1 / ftrl_l2 / ftrl_beta; state z, n where Adam keeps m, v - the same bytes
+    per touched row).  side / side_lr: another rule for the bias and linear entries of the rows, applied in the same
+    pass (every call below passes both rules); None: the same as name / lr."""
 
-    def __init__(self, engine, name="adam", lr=1e-3, l2_embedding=0.0, l2_linear=0.0):
+    def __init__(self, engine, name="adam", lr=1e-3, l2_embedding=0.0, l2_linear=0.0, side=None, side_lr=None,
+                 ftrl_l1=0.0, ftrl_l2=0.0, ftrl_beta=0.0):
         from . import ops
 
-        if name not in ("adam", "adagrad", "gd", "sgd"):
-            raise ValueError(f"SparseTableOptimizer: {name!r} unsupported (adam, adagrad, sgd)")
+        side = name if side is None else side
+        check_rules("SparseTableOptimizer", name, side)
         self.ops, self.e, self.name, self.lr = ops, engine, name, float(lr)
+        self.side, self.side_lr = side, self.lr if side_lr is None else float(side_lr)
+        # what every row-wise call is handed beside name / lr
+        self._rules = dict(l1=float(ftrl_l1), l2=float(ftrl_l2), ftrl_beta=float(ftrl_beta), side_kind=side,
+                           side_lr=self.side_lr)
         self.l2_embedding, self.l2_linear = float(l2_embedding), float(l2_linear)
         R, LD = engine.rows.shape
         D = engine.D
@@ -153,21 +241,15 @@ class SparseTableOptimizer:
                              f"(D={D}, LD={LD}): use the dense optimizer for this table")
         dev = engine.device
         self.D = D
-        self.mom = None
-        if name == "adam":
-            self.mom = torch.zeros(R, 2 * D, device=dev)
-        elif name == "adagrad":
-            self.mom = torch.zeros(R, 2 * D, device=dev)
-            self.mom.view(R, D // 4, 2, 4)[:, :, 1, :] = 0.1  # the v halves ([m4 v4] per float4 slice)
-        # the bias / linear columns' moments live in the row's padding: [.. bias lin | m_b m_l v_b v_l | ..]
-        engine.rows[:, D + 2: D + 6] = 0.0
-        if name == "adagrad":
-            engine.rows[:, D + 4: D + 6] = 0.1
+        self.mom = init_moment_rows(name, R, D, dev)  # by the embedding rule (None under SGD)
+        # the bias / linear columns' moments live in the row's padding, by the side rule
+        init_state_columns(engine.rows, D, side)
         self._ws = None
         self.t = 0
 
     def moments(self):
-        """(m [R, D], v [R, D]) of the embedding entries as strided views of the interleaved state."""
+        """(m [R, D], v [R, D]) of the embedding entries as strided views of the interleaved state.  Under FTRL the
+        pair is (z, n): TF's "linear" and its accumulator.  (Adagrad: m is unused.)"""
         R = self.mom.shape[0]
         q = self.mom.view(R, self.D // 4, 2, 4)
         return q[:, :, 0, :].reshape(R, self.D), q[:, :, 1, :].reshape(R, self.D)
@@ -228,7 +310,7 @@ class SparseTableOptimizer:
             self.name, self.lr, g_bias=g_bias, g_lin=g_lin, reset=reset,
             lin_field_mask=getattr(e, "lin_field_mask", None), prepared=prepared,
             l2_embedding=self.l2_embedding, l2_linear=self.l2_linear if e.use_linear else 0.0,
-            max_field_rows=self._max_field_rows())
+            max_field_rows=self._max_field_rows(), **self._rules)
         for fq, fields in sorted(seq_of.items()):
             ids = _t.cat([idx_all[:, fq]] + [e.seq_key_grads(f)[1] for f in fields])
             rows_g = _t.cat([e.d_rows[:, fq, :]] + [e.seq_key_grads(f)[2] for f in fields]).contiguous()
@@ -241,7 +323,7 @@ class SparseTableOptimizer:
                 ids.view(-1, 1).contiguous(), e.field_off[fq: fq + 1], rows_g.view(-1, 1, e.D), e.rows, self.mom,
                 self._workspace(ids.numel()), self.t, self.name, self.lr, g_bias=occ(g_bias),
                 g_lin=occ(g_lin) if self._lin_on(fq) else None, reset=reset, l2_embedding=self.l2_embedding,
-                l2_linear=self.l2_linear if (e.use_linear and self._lin_on(fq)) else 0.0)
+                l2_linear=self.l2_linear if (e.use_linear and self._lin_on(fq)) else 0.0, **self._rules)
         for f in e.mv_fields:
             if e.spec.sparse_names[f] in e.spec.seq_query:
                 continue
@@ -261,7 +343,7 @@ class SparseTableOptimizer:
                 g_bias=(g_bias[seg] * wb).contiguous() if g_bias is not None else None,
                 g_lin=(g_lin[seg] * wl).contiguous() if (g_lin is not None and self._lin_on(f)) else None,
                 reset=reset, l2_embedding=self.l2_embedding,
-                l2_linear=self.l2_linear if (e.use_linear and self._lin_on(f)) else 0.0)
+                l2_linear=self.l2_linear if (e.use_linear and self._lin_on(f)) else 0.0, **self._rules)
 
     def roofline(self, idx, ms):
         """The step against the HBM roofline: bytes a step HAS to move with this layout - per occurrence

@@ -29,7 +29,7 @@ from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_random_state
 
 from .. import engine as eng
-from ..optim import FusedDenseOptimizer, Optimizer, SparseTableOptimizer
+from ..optim import FUSED_RULES, FusedDenseOptimizer, Optimizer, SparseTableOptimizer, canonical
 from .inputs import DataInputs, FeatureDictionary
 
 log = logging.getLogger(__name__)
@@ -88,7 +88,10 @@ class DeepModel(BaseEstimator, TransformerMixin):
         e = eng.ENGINES[self.model](spec, hp["embedding_size"], hp, task=self.task, device=self.device)
         eng.init_reference(e, self.random_seed)
         self._engine = e
-        self._opt = Optimizer(hp.get("optimizer", "adam"), hp.get("learning_rate", 1e-3))
+        rules = self._optimizer_rules(hp)
+        name, lr = rules["name"], rules["lr"]
+        # (FTRL has no dict-walking form - optim.py says why -, and needs none: with it every batch steps row-wise)
+        self._opt = None if name == "ftrl" else Optimizer(name, lr)
         # row-wise sparse step for the table.  embedding_l2_reg / linear_l2_reg (1e-5 in the reference's default
         # hyper-parameters, hparams/xDeepFM.py:22-23) would force a DENSE table gradient (layers.py:188-193): with
         # the row-wise step they are applied lazily - reg * row for the rows a batch touches (hparams["lazy_l2"],
@@ -98,15 +101,94 @@ class DeepModel(BaseEstimator, TransformerMixin):
         lazy = bool(hp.get("lazy_l2", not self.strict_reference))
         self._sparse_opt = None
         fits = e.rows.shape[1] >= e.D + 8 and 8 <= e.D <= 64  # room for the bias / linear moments in the row
-        if want and (lazy or not has_l2) and fits and hp.get("optimizer", "adam") in ("adam", "adagrad", "gd", "sgd"):
+        if rules["rowwise"]:
+            # FTRL, or a wide part with a rule of its own: only the row-wise step can do either, whatever the table's
+            # size - and where it cannot run the build fails, it never falls back to the dense path
+            why = rules["why"]
+            if name not in FUSED_RULES:
+                raise ValueError(f"optimizer={name!r} has no row-wise table step ({', '.join(FUSED_RULES)} have), "
+                                 f"which {why} needs: choose another optimizer or drop linear_optimizer / "
+                                 "linear_learning_rate")
+            if not fits:
+                raise ValueError(f"{why} needs the row-wise table step, which needs 8 <= embedding_size <= 64 and "
+                                 f"table rows of embedding_size + 8 floats (embedding_size={e.D}, row "
+                                 f"{e.rows.shape[1]} floats)")
+            if has_l2 and not lazy:
+                raise ValueError(f"{why} needs the row-wise table step, which applies embedding_l2_reg / "
+                                 "linear_l2_reg lazily; strict_reference (lazy_l2=False) keeps the dense l2 term: "
+                                 "set embedding_l2_reg = linear_l2_reg = 0 or drop strict_reference")
+            fk = hp.get("fm_dropout")
+            if fk is not None and e._has_fm() and fk[0] < 1:
+                raise ValueError(f"{why} needs the row-wise table step, which has no per-occurrence bias gradient: "
+                                 f"fm_dropout[0] = {fk[0]} (FM bias dropout) cannot be combined with it")
+            want = True
+        if want and (lazy or not has_l2) and fits and name in FUSED_RULES:
             e.hp["lazy_l2"] = has_l2
-            self._sparse_opt = SparseTableOptimizer(e, hp.get("optimizer", "adam"), hp.get("learning_rate", 1e-3),
-                                                    l2_embedding=hp.get("embedding_l2_reg", 0.0),
-                                                    l2_linear=hp.get("linear_l2_reg", 0.0))
+            self._sparse_opt = SparseTableOptimizer(e, name, lr, l2_embedding=hp.get("embedding_l2_reg", 0.0),
+                                                    l2_linear=hp.get("linear_l2_reg", 0.0), **rules["kw"])
             # ... and the dense parameters in one launch (the dict-walking Optimizer stays the path
             # for densified table gradients: small tables, strict l2 terms, FM bias dropout)
-            self._dense_fused = FusedDenseOptimizer(e, hp.get("optimizer", "adam"), hp.get("learning_rate", 1e-3))
+            self._dense_fused = FusedDenseOptimizer(e, name, lr, **rules["kw"])
         return e
+
+    @staticmethod
+    def _optimizer_rules(hp):
+        """The two update rules of the hyper-parameters: `optimizer` / `learning_rate` for everything, and
+        `linear_optimizer` / `linear_learning_rate` (None: the same) for the wide part - the table's bias and linear
+        entries and linear_w_dense.  rowwise: the configuration needs the row-wise table step (FTRL in either role,
+        or a wide part whose rule differs); why: the hyper-parameters that say so, for error messages; kw: the
+        keyword arguments of the fused optimizers (empty when none of the new keys is set)."""
+        name, lr = hp.get("optimizer", "adam"), hp.get("learning_rate", 1e-3)
+        side = hp.get("linear_optimizer")
+        side_lr = hp.get("linear_learning_rate")
+        if side is not None and side not in ("adam", "adagrad", "sgd", "gd", "ftrl"):
+            raise ValueError(f"linear_optimizer={side!r}: expected adam, adagrad, sgd, gd or ftrl")
+        ftrl = {k: float(hp.get(k) or 0.0) for k in ("ftrl_l1", "ftrl_l2", "ftrl_beta")}
+        for k, v in ftrl.items():
+            if v < 0:
+                raise ValueError(f"{k}={v}: must be >= 0")
+        s_name, s_lr = (name if side is None else side), (lr if side_lr is None else side_lr)
+        split = (canonical(s_name), float(s_lr)) != (canonical(name), float(lr))
+        uses_ftrl = "ftrl" in (name, s_name)
+        why = (f"optimizer={name!r}" if name == "ftrl" else
+               f"linear_optimizer={s_name!r} (optimizer={name!r}, linear_learning_rate={s_lr})")
+        kw = {}
+        if split or uses_ftrl:
+            kw = dict(side=s_name, side_lr=s_lr, **ftrl)
+        return dict(name=name, lr=lr, rowwise=split or uses_ftrl, why=why, kw=kw)
+
+    def linear_sparsity(self):
+        """Share of table rows whose LINEAR entry is exactly 0.0 - what ftrl_l1 did to the wide weights: {feature
+        name: share, .., "overall": share over all rows} as Python floats.  Every row of a feature counts, slot 0
+        like any other.  Row-sharded table: every rank counts the rows of its shard (local row i is global row
+        i * world + rank; padding rows beyond the table do not count), the counts are summed over the ranks (one
+        all_reduce: every rank calls it), and every rank returns the shares of the whole table."""
+        e = self._build()
+        sizes = torch.tensor(e.spec.feat_sizes, dtype=torch.int64)
+        total = int(sizes.sum())
+        if self._shard is not None:
+            rank, world = self._shard
+            lin = e.st.shard[:, e.D + 1]
+            glob = torch.arange(lin.shape[0], device=lin.device, dtype=torch.int64) * world + rank
+            ends = torch.cumsum(sizes, 0).to(lin.device)
+            feat = torch.searchsorted(ends, glob, right=True)  # (rows at or beyond `total` land in bin F: dropped)
+            zeros = torch.zeros(len(sizes) + 1, dtype=torch.int64, device=lin.device)
+            zeros.index_add_(0, feat.clamp(max=len(sizes)), (lin == 0).to(torch.int64))
+            zeros = zeros[: len(sizes)]
+            if world > 1:
+                import torch.distributed as dist
+
+                if dist.get_backend() != "nccl":
+                    zeros = zeros.cpu()
+                dist.all_reduce(zeros, op=dist.ReduceOp.SUM)
+            zeros = zeros.cpu()
+        else:
+            zero = (e.rows[:total, e.D + 1] == 0).to(torch.int64)
+            feat = torch.repeat_interleave(torch.arange(len(sizes)), sizes).to(zero.device)
+            zeros = torch.zeros(len(sizes), dtype=torch.int64, device=zero.device).index_add_(0, feat, zero).cpu()
+        out = {fname: float(zeros[f]) / float(sizes[f]) for f, fname in enumerate(e.spec.sparse_names)}
+        out["overall"] = float(zeros.sum()) / total
+        return out
 
     # ------------------------------------------------------------ row-sharded table (multi-GPU)
     def _dist_info(self):
@@ -127,7 +209,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
         from .. import dist as rdist
 
         rank, world = self._shard
-        name = hp.get("optimizer", "adam")
+        rules = self._optimizer_rules(hp)
+        name = rules["name"]
         dev = torch.device(self.device)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
@@ -139,7 +222,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
         e.st.init_reference(spec.offsets(), spec.feat_sizes, self.random_seed)
         self._engine = e
         self._opt = self._sparse_opt = None
-        self._shard_opt = e.optimizer(name, hp.get("learning_rate", 1e-3))
+        self._shard_opt = e.optimizer(name, rules["lr"], **rules["kw"])
         return e
 
     def _local_part(self, s, t):
@@ -419,8 +502,8 @@ class DeepModel(BaseEstimator, TransformerMixin):
         loss = e.fwd_bwd(idx, dense, yt, masks=self._dropout_masks(idx.shape[0]), mv=mv)
         if side is not None:
             torch.cuda.current_stream(e.device).wait_stream(side)
-        if self.strict_reference:
-            self._opt.reset()  # a NEW optimizer every batch (xDeepFM.py:121-126)
+        if self.strict_reference and self._opt is not None:
+            self._opt.reset()  # a NEW optimizer every batch (xDeepFM.py:121-126); the fused ones take reset=True
         fm_masked = e.d_bias is not None  # FM bias dropout: per-occurrence grads
         if self._sparse_opt is not None and not fm_masked:
             self._sparse_opt.step(idx, reset=self.strict_reference)

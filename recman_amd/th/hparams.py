@@ -20,10 +20,23 @@ class BaseHyperParameters(dict):
     LearningRate = "learning_rate"
     Optimizer = "optimizer"
 
+    # the wide part (the table's bias and linear entries, linear_w_dense) may train by a rule of its own - the
+    # Wide&Deep recipe: FTRL with L1 there, Adam / Adagrad on the embeddings and the DNN (not in the reference)
+    LinearOptimizer = "linear_optimizer"        # None: the same as `optimizer`; adam | adagrad | sgd | gd | ftrl
+    LinearLearningRate = "linear_learning_rate"  # None: `learning_rate`
+    FtrlL1 = "ftrl_l1"
+    FtrlL2 = "ftrl_l2"
+    FtrlBeta = "ftrl_beta"
+
     def __init__(self):
         dict.__init__(self)
         self.add_param(self.LearningRate, 0.001)
-        self.add_param(self.Optimizer, "adam")
+        self.add_param(self.Optimizer, "adam")  # adam | adagrad | sgd | gd | momentum | ftrl
+        self.add_param(self.LinearOptimizer, None)
+        self.add_param(self.LinearLearningRate, None)
+        self.add_param(self.FtrlL1, 0.0)
+        self.add_param(self.FtrlL2, 0.0)
+        self.add_param(self.FtrlBeta, 0.0)
 
     def add_param(self, name, default_val):
         self[name] = HParam(name, default_val)()
