@@ -673,6 +673,55 @@ int rm_asp_bwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t
                rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Transformer-pooled behaviour sequences: SequenceFeat + one post-norm encoder block (Behavior
+ * Sequence Transformer, arXiv 1905.06874).  New: the reference has none.  CSR input and addressing
+ * as rm_asp_fwd (rows, LD, row0, offsets, ids oldest first, qrow; only columns 0..D-1 of a row are
+ * read).  Per example with n <= max_len history rows k_i and query row q, T = n + 1 tokens, the
+ * candidate LAST:
+ *     x_i = k_i + P[n - i] (i < n),  x_n = q + P[0]       P = pos [max_len + 1, D]: by distance
+ *     Q, K, V = X Wq + bq, X Wk + bk, X Wv + bv            W* [D, D] ([in, out]), dk = D / heads
+ *     a^h = softmax_j(Q^h_i . K^h_j / sqrt(dk))            max-subtracted, no mask
+ *     O = concat_h(a^h V^h) Wo + bo
+ *     Y = LayerNorm(X + O; ln1_gamma, ln1_beta)            eps 1e-5, biased variance, over D
+ *     Z = LayerNorm(Y + relu(Y W1 + c1) W2 + c2; ln2_*)    W1 = ffn_w1 [D, Hf], W2 = ffn_w2 [Hf, D]
+ *     out_b = (1 / T) sum_i Z_i                            no history: T = 1 and out_b = Z_0, not 0
+ *   rm_bst_params: the 17 device pointers, read on the host at call time; the same struct carries
+ *   the 17 gradient destinations.
+ * rm_bst_fwd writes out [B, LD] (out_b in columns 0..D-1, zeros behind).  It saves nothing: no
+ *   per-token value reaches HBM, and inference is the same call (the same bits).  workspace:
+ *   rm_bst_workspace(D, heads, Hf, max_len, B, 0) floats.
+ * rm_bst_bwd, given d_out (the pooled rows' gradient, row b at d_out + b * do_stride, D floats),
+ *   recomputes the block and writes d_keys [nnz, D] (the gradient of every history occurrence's
+ *   row), ADDS the candidate's gradient onto d_query[b * dq_stride + 0..D-1] (d_query may be other
+ *   columns of the buffer that holds d_out) and overwrites all 17 members of grads (all zero at
+ *   B = 0).  workspace: rm_bst_workspace(.., B, 1) floats, 16-byte aligned.
+ * Supported (rm_bst_supported): D in {8,16,32}; heads in {1,2,4,8} with D / heads >= 4; Hf a
+ *   multiple of 4 in 4..128; max_len 1..63; anything else is RM_EINVAL before any launch.  A
+ *   history longer than max_len is a caller error that is made safe: its LAST max_len items are
+ *   used (what th.SequenceFeat keeps) and the d_keys rows of the others are written as zeros.
+ * Deterministic: a fixed assignment of examples to blocks, per-block partial sums added in block
+ *   order, fixed-order sums inside a block, no float atomics - two runs are bit-equal. */
+typedef struct rm_bst_params {
+  float *wq, *wk, *wv, *wo;             /* [D, D] */
+  float *bq, *bk, *bv, *bo;             /* [D] */
+  float *ffn_w1, *ffn_b1;               /* [D, Hf], [Hf] */
+  float *ffn_w2, *ffn_b2;               /* [Hf, D], [D] */
+  float *ln1_gamma, *ln1_beta, *ln2_gamma, *ln2_beta; /* [D] */
+  float *pos;                           /* [max_len + 1, D] */
+} rm_bst_params;
+int rm_bst_supported(int D, int heads, int Hf, int max_len);
+int64_t rm_bst_workspace(int D, int heads, int Hf, int max_len, int64_t B, int backward);
+int rm_bst_fwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+               const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz,
+               const rm_bst_params *params, int heads, int Hf, int max_len, float *out,
+               float *workspace, rm_stream_t stream);
+int rm_bst_bwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+               const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz,
+               const rm_bst_params *params, int heads, int Hf, int max_len, const float *d_out,
+               int64_t do_stride, float *d_keys, float *d_query, int64_t dq_stride,
+               const rm_bst_params *grads, float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CIN (xDeepFM), one layer, on the f32-input MFMA.
  * Replaces the loop body of CIN.__call__ (layers.py:714-752):
  *   Z[b,d,i*H+j] = X0[b,i,d] * Xk[b,j,d];  M = Z @ W + bias;  out = act(M)

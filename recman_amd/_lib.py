@@ -34,6 +34,15 @@ class OptRule(ctypes.Structure):
                 ("l1", c_float), ("l2", c_float), ("beta", c_float)]
 
 
+BST_PARAM_NAMES = ("wq", "wk", "wv", "wo", "bq", "bk", "bv", "bo", "ffn_w1", "ffn_b1", "ffn_w2", "ffn_b2", "ln1_gamma",
+                   "ln1_beta", "ln2_gamma", "ln2_beta", "pos")
+
+
+class BstParams(ctypes.Structure):
+    """rm_bst_params of include/recman_hip.h: the 17 device pointers of the transformer unit (or of its gradients)."""
+    _fields_ = [(n, P) for n in BST_PARAM_NAMES]
+
+
 # name -> argtypes, in the order of include/recman_hip.h
 SIGNATURES = {
     "rm_version": [],
@@ -100,6 +109,9 @@ SIGNATURES = {
     "rm_asp_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, P, P],
     "rm_asp_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, P, P, P, P, P, c_int, P, c_int, c_int, P, P, I64, P, P,
                    I64, P, P, P, P, P, P, P, P],
+    "rm_bst_supported": [c_int, c_int, c_int, c_int],
+    "rm_bst_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, c_int, c_int, P, P, P],
+    "rm_bst_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, c_int, c_int, P, I64, P, P, I64, P, P, P],
     "rm_cin_layer_fwd": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
                          c_int, P, P],
     "rm_cin_layer_fwd6": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
@@ -154,6 +166,7 @@ SIGNATURES_I64 = {
     "rm_masknet_group_bwd_workspace": [I64, c_int, c_int],
     "rm_masknet_row_bwd_workspace": [I64, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
+    "rm_bst_workspace": [c_int, c_int, c_int, c_int, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],
     "rm_outer_actgrad_sums_workspace": [I64, c_int],

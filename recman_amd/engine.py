@@ -492,17 +492,30 @@ class Engine:
         return list(self.hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
 
     def _init_seq(self):
-        """The attention unit of every sequence feature (csrc/asp.hip; DIN's local activation unit, arXiv 1706.06978):
-        variables {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w
-        [H_last, 1], {name}_asp_w0 [1].  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's
-        Dice, activation.py, uses undefined names), att_weight_normalization False, att_dropout all ones."""
+        """The pooling unit of every sequence feature, chosen by hp["seq_pooling"]:
+        "din" (default; csrc/asp.hip, DIN's local activation unit, arXiv 1706.06978): variables
+        {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w [H_last, 1],
+        {name}_asp_w0 [1].  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's Dice,
+        activation.py, uses undefined names), att_weight_normalization False.
+        "transformer" (csrc/bst.hip, one post-norm encoder block over the history and the candidate, mean-pooled;
+        Behavior Sequence Transformer, arXiv 1905.06874): variables {name}_bst_{wq|wk|wv|wo} [D, D],
+        {name}_bst_{bq|bk|bv|bo} [D], {name}_bst_ffn_w1 [D, Hf], _ffn_b1 [Hf], _ffn_w2 [Hf, D], _ffn_b2 [D],
+        {name}_bst_ln{1|2}_{gamma|beta} [D], {name}_bst_pos [max_len + 1, D].  hp: att_head_num 2, att_ffn_units 4 D.
+        att_dropout must be all ones under both."""
         spec, hp, D = self.spec, self.hp, self.D
         self._asp_saved = {}
+        self.seq_pooling = str(hp.get("seq_pooling", "din")).lower()
+        if self.seq_pooling not in ("din", "transformer"):
+            raise ValueError(f"seq_pooling {hp.get('seq_pooling')!r}: 'din' or 'transformer'")
         if not spec.seq_names:
             return
         if not hasattr(self, "rows") or self.rows.dim() != 2 or self.rows.shape[0] != spec.rows:
             raise NotImplementedError("sequence features (SequenceFeat) need the whole table on one GPU: there is "
                                       "no row-sharded path for them (use table_sharding='none')")
+        if self.seq_pooling == "transformer":
+            self._check_att_dropout()
+            self._init_bst()
+            return
         self.asp_hidden = [int(h) for h in hp.get("att_hidden_units", (80, 40))]
         act = hp.get("att_activation", "sigmoid")
         act = act if isinstance(act, str) else getattr(act, "__name__", str(act))
@@ -512,11 +525,7 @@ class Engine:
                                       "names and has no arithmetic to follow; use 'sigmoid' or 'relu'")
         if self.asp_act not in ops.ASP_ACTS:
             raise ValueError(f"att_activation {act!r}: 'relu' or 'sigmoid'")
-        drop = hp.get("att_dropout", 1)
-        drop = list(drop) if isinstance(drop, (list, tuple)) else [drop]
-        if any(float(k) != 1.0 for k in drop):
-            raise NotImplementedError("att_dropout: the attention unit runs without dropout (every keep "
-                                      f"probability must be 1, got {hp.get('att_dropout')!r})")
+        self._check_att_dropout()
         self.asp_norm = bool(hp.get("att_weight_normalization", False))
         for n in spec.seq_names:
             if not ops.asp_supported(D, self.asp_hidden, spec.seq_max_len[n]):
@@ -530,6 +539,37 @@ class Engine:
                 self._var(f"{n}_asp_layer_{i}_bias", (dims[i + 1],))
             self._var(f"{n}_asp_w", (dims[-1], 1), ("glorot", dims[-1], 1))
             self._var(f"{n}_asp_w0", (1,))
+
+    def _check_att_dropout(self):
+        drop = self.hp.get("att_dropout", 1)
+        drop = list(drop) if isinstance(drop, (list, tuple)) else [drop]
+        if any(float(k) != 1.0 for k in drop):
+            raise NotImplementedError("att_dropout: the attention unit runs without dropout (every keep "
+                                      f"probability must be 1, got {self.hp.get('att_dropout')!r})")
+
+    def _init_bst(self):
+        """The transformer unit's variables (absent from the reference: glorot matrices and position table, zero
+        biases, LayerNorm gains "ones"; no l2, as for the attention unit)."""
+        spec, hp, D = self.spec, self.hp, self.D
+        self.bst_heads = int(hp.get("att_head_num", 2))
+        ffn = hp.get("att_ffn_units")
+        self.bst_ffn = int(ffn) if ffn is not None else 4 * D
+        for n in spec.seq_names:
+            ml = int(spec.seq_max_len[n])
+            if not ops.bst_supported(D, self.bst_heads, self.bst_ffn, ml):
+                raise ValueError(f"sequence feature {n!r}: embedding_size={D}, att_head_num={self.bst_heads}, "
+                                 f"att_ffn_units={self.bst_ffn}, max_len={ml} is not supported by rm_bst_fwd "
+                                 f"({ops.BST_LIMITS})")
+            for v, shape in ops.bst_param_shapes(D, self.bst_ffn, ml).items():
+                if len(shape) == 2:
+                    init = ("glorot", shape[0], shape[1])
+                else:
+                    init = "ones" if v.endswith("_gamma") else "zeros"
+                self._var(f"{n}_bst_{v}", shape, init)
+
+    def _bst_vars(self, d, name):
+        """{member: tensor} of sequence feature `name`'s transformer unit out of the params or the grads dict."""
+        return {v: d[f"{name}_bst_{v}"] for v in ops.BST_PARAM_NAMES}
 
     def _asp_vars(self, d, name):
         """(Ws, bs, w, w0) of sequence feature `name` out of the params or the grads dict."""
@@ -546,6 +586,18 @@ class Engine:
         qrow = idx[:, fq] + row0
         nnz = int(ids.shape[0])
         buf = self._asp_saved.get(f)
+        if self.seq_pooling == "transformer":
+            B, ml = int(idx.shape[0]), int(self.spec.seq_max_len[name])
+            need = ops.bst_workspace(self.D, self.bst_heads, self.bst_ffn, ml, B, True)
+            if buf is None or buf["cap"] < nnz or buf["ws"].numel() < need:
+                cap = max(nnz, 1)
+                buf = dict(cap=cap, d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
+                           ws=torch.empty(max(4, need), dtype=F32, device=self.device))
+                self._asp_saved[f] = buf
+            buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq, max_len=ml)
+            ops.bst_fwd(self.rows, row0, self.D, offsets, ids, qrow, self._bst_vars(self.params, name), self.bst_heads,
+                        ml, self.mv_scratch[j], buf["ws"])
+            return
         if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.asp_workspace(self.D, self.asp_hidden, nnz, True):
             cap = max(nnz, 1)
             buf = dict(cap=cap, scores=torch.empty(cap, dtype=F32, device=self.device),
@@ -567,6 +619,11 @@ class Engine:
                 continue
             b = self._asp_saved[f]
             nnz = b["nnz"]
+            if self.seq_pooling == "transformer":
+                ops.bst_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
+                            self._bst_vars(self.params, name), self.bst_heads, b["max_len"], self.d_rows[:, f, :],
+                            b["d_keys"][:nnz], self.d_rows[:, b["fq"], :], self._bst_vars(self.grads, name), b["ws"])
+                continue
             ops.asp_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
                         *self._asp_vars(self.params, name), self.asp_act, self.asp_norm, b["scores"][:nnz],
                         self.d_rows[:, f, :], b["d_keys"][:nnz], self.d_rows[:, b["fq"], :],
@@ -1921,6 +1978,18 @@ class DINEngine(DeepFMEngine):
         super().__init__(spec, embedding_size, dict(hp, use_fm=False, use_deep=True), task, device)
 
 
+class BSTEngine(DINEngine):
+    """Behavior Sequence Transformer (arXiv 1905.06874): final = linear + DNN([E | dense]) as DIN, with every sequence
+    feature pooled by the transformer unit (seq_pooling is forced to "transformer"; csrc/bst.hip): one post-norm
+    encoder block over the history and the candidate with a position table by distance from the candidate, mean
+    over the tokens.  hp: att_head_num 2, att_ffn_units 4 * embedding_size."""
+
+    model = "bst"
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, dict(hp, seq_pooling="transformer"), task, device)
+
+
 class AutoIntEngine(DeepFMEngine):
     """AutoInt (arXiv 1810.11921): final = linear + autoint (+ DNN([E | dense]) with a non-empty deep_hidden_units:
     AutoInt+), PredictionLayer(use_bias=False).  Nothing in the reference implements it.  L interacting layers of
@@ -2621,4 +2690,4 @@ class MaskNetEngine(Engine):
 
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine,
-           "masknet": MaskNetEngine}
+           "masknet": MaskNetEngine, "bst": BSTEngine}

@@ -815,6 +815,85 @@ def asp_bwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, scores,
               d_query.data_ptr(), d_query.stride(0), *gp, _chk(workspace, "workspace", F32), _stream())
 
 
+BST_PARAM_NAMES = _lib.BST_PARAM_NAMES
+BST_LIMITS = ("embedding_size 8/16/32, att_head_num 1/2/4/8 with embedding_size / att_head_num >= 4, att_ffn_units a "
+              "multiple of 4 in 4..128, max_len 1..63")
+
+
+def bst_supported(D, heads, Hf, max_len):
+    """rm_bst_supported: D in {8, 16, 32}, heads in {1, 2, 4, 8} with D / heads >= 4, Hf a multiple of 4 in 4..128,
+    1 <= max_len <= 63."""
+    return bool(_lib.lib().rm_bst_supported(int(D), int(heads), int(Hf), int(max_len)))
+
+
+def bst_workspace(D, heads, Hf, max_len, B, backward):
+    """Floats of workspace rm_bst_fwd (backward=False) / rm_bst_bwd need for B examples (0: unsupported shape)."""
+    return int(_lib.lib().rm_bst_workspace(int(D), int(heads), int(Hf), int(max_len), int(B), 1 if backward else 0))
+
+
+def bst_param_shapes(D, Hf, max_len):
+    """name -> shape of the 17 tensors of the transformer unit, in the order of rm_bst_params."""
+    s = {n: (D, D) for n in ("wq", "wk", "wv", "wo")}
+    s.update({n: (D,) for n in ("bq", "bk", "bv", "bo")})
+    s.update(ffn_w1=(D, Hf), ffn_b1=(Hf,), ffn_w2=(Hf, D), ffn_b2=(D,))
+    s.update({n: (D,) for n in ("ln1_gamma", "ln1_beta", "ln2_gamma", "ln2_beta")})
+    s["pos"] = (max_len + 1, D)
+    return {n: s[n] for n in BST_PARAM_NAMES}
+
+
+def _bst_struct(params, what, D, Hf, max_len):
+    shapes = bst_param_shapes(D, Hf, max_len)
+    if set(params) != set(shapes):
+        raise ValueError(f"bst: {what} must hold exactly {BST_PARAM_NAMES}, got {sorted(params)}")
+    return _lib.BstParams(*[_chk(params[n], f"{what}[{n!r}]", F32, shapes[n]) for n in BST_PARAM_NAMES])
+
+
+def _bst_args(rows, D, offsets, ids, qrow, params, max_len):
+    if "ffn_w1" not in params or params["ffn_w1"].dim() != 2:
+        raise ValueError("bst: params['ffn_w1'] must be a [D, Hf] matrix")
+    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    if rows.dim() != 2:
+        raise ValueError(f"rows: expected [R, LD], got {tuple(rows.shape)}")
+    D, max_len = int(D), int(max_len)
+    Hf = int(params["ffn_w1"].shape[1])
+    ps = _bst_struct(params, "params", D, Hf, max_len)
+    return B, nnz, Hf, (rp, int(rows.shape[1]), D), (op, ip, qp, B, nnz), ps
+
+
+def bst_fwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, out, workspace):
+    """Transformer-pooled history rows (rm_bst_fwd): rows [R, LD] the fused table, history id -> row row0 + id (oldest
+    first), the example's query row qrow [B] (absolute); params: {name: tensor} over BST_PARAM_NAMES (shapes:
+    bst_param_shapes).  -> out [B, LD]: the mean of the encoder block's T = n + 1 output rows in columns 0..D-1, zeros
+    behind.  Nothing is saved for the backward; inference is the same call.  ids.shape[0] must equal offsets[-1]."""
+    B, nnz, Hf, (rp, LD, D), csr, ps = _bst_args(rows, D, offsets, ids, qrow, params, max_len)
+    need = bst_workspace(D, heads, Hf, max_len, B, False)
+    if need:
+        _need_workspace("bst_fwd", workspace, need)
+    _lib.call("rm_bst_fwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(heads), Hf, int(max_len),
+              _chk(out, "out", F32, (B, LD)), _chk(workspace, "workspace", F32), _stream())
+
+
+def bst_bwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, d_out, d_keys, d_query, grads, workspace):
+    """rm_bst_bwd: d_out [B, D] view (row stride may be larger) = the pooled rows' gradient -> d_keys [nnz, D]
+    overwritten; the candidate's gradient ADDED onto d_query [B, D] (a view, row stride may be larger; it may be other
+    columns of d_out's buffer); grads: {name: tensor} over BST_PARAM_NAMES, all overwritten.  Deterministic."""
+    B, nnz, Hf, (rp, LD, D), csr, ps = _bst_args(rows, D, offsets, ids, qrow, params, max_len)
+    gs = _bst_struct(grads, "grads", D, Hf, int(max_len))
+    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
+        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
+            raise ValueError(f"bst_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
+    need = bst_workspace(D, heads, Hf, max_len, B, True)
+    if need:
+        _need_workspace("bst_bwd", workspace, need)
+    if workspace.data_ptr() % 16:
+        raise ValueError("bst_bwd: workspace must be 16-byte aligned")
+    _lib.call("rm_bst_bwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(heads), Hf, int(max_len),
+              d_out.data_ptr(), d_out.stride(0) if B > 1 else max(D, d_out.stride(0)),
+              _chk(d_keys, "d_keys", F32, (nnz, D)), d_query.data_ptr(),
+              d_query.stride(0) if B > 1 else max(D, d_query.stride(0)), ctypes.byref(gs),
+              _chk(workspace, "workspace", F32), _stream())
+
+
 def gather_rows(table, rows, out):
     """out[i, :] = table[rows[i], :width] with width = out.shape[1] <= table.shape[1] (the shard keeps
     optimizer state behind the exchanged columns).  `table` may live in PINNED host memory (th/feeder.py)."""

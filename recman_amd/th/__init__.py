@@ -11,6 +11,7 @@ from .DeepFM import DeepFM
 from .FiBiNET import FiBiNET
 from .FmFM import FmFM, FwFM
 from .MaskNet import MaskNet
+from .BST import BST
 from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
@@ -19,6 +20,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]
