@@ -722,6 +722,62 @@ int rm_bst_bwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t
                const rm_bst_params *grads, float *workspace, rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Interest-evolution pooling of behaviour sequences: SequenceFeat + a GRU, an attention and an
+ * attention-gated GRU over the history (Deep Interest Evolution Network, arXiv 1809.03672).  New:
+ * the reference has none.  CSR input and addressing as rm_asp_fwd (rows, LD, row0, offsets, ids
+ * oldest first, qrow; only columns 0..D-1 of a row are read).  Matrices are [in, out]; the column
+ * blocks of a [D, 3D] matrix are [u | r | c].  Per example with history rows k_1..k_n
+ * (n <= max_len) and query row q:
+ *     cell(x, h; W, U, b, a):                              one bias; r applied AFTER the product
+ *         u = sigmoid(x Wu + h Uu + bu)                    with U (paper eq. 1-4)
+ *         r = sigmoid(x Wr + h Ur + br)
+ *         c = tanh(x Wc + r * (h Uc) + bc)
+ *         u = a u;  return (1 - u) h + u c                 (eq. 15-16; a = 1 in the extractor)
+ *     h_0 = 0,  h_t = cell(k_t, h_{t-1}; gru_w, gru_u, gru_b, 1)
+ *     s_t = h_t . (att_w q)                                att_w [D, D] (eq. 13)
+ *     a = softmax_t(s)                                     max-subtracted, the example's n positions
+ *     g_0 = 0,  g_t = cell(h_t, g_{t-1}; augru_w, augru_u, augru_b, a_t)
+ *     out_b = g_n                                          n = 0: out_b = 0 and no gradient
+ *   The hidden size is D; there is no auxiliary loss, no AIGRU / AGRU variant and no dropout.
+ *   sigmoid and tanh stay finite for pre-activations of any size.  The forward forms h_t and s_t in
+ *   float64 (|att_w q| multiplies h_t's error into the softmax) and stores h_t rounded to float.
+ *   rm_dien_params: the 7 device pointers, read on the host at call time; the same struct carries
+ *   the 7 gradient destinations.
+ * rm_dien_fwd writes out [B, LD] (out_b in columns 0..D-1, zeros behind) and leaves h_t and a_t in
+ *   the workspace; with save != 0 also g_t, which rm_dien_bwd needs.  `out` has the same bits for
+ *   save 0 and 1.  workspace: rm_dien_workspace(D, max_len, B, nnz, save) floats.
+ * rm_dien_bwd, called after a save forward on the same inputs and workspace, given d_out (the
+ *   pooled rows' gradient, row b at d_out + b * do_stride, D floats), writes d_keys [nnz, D] (the
+ *   gradient of every history occurrence's row), ADDS the query gradient onto
+ *   d_query[b * dq_stride + 0..D-1] (d_query may be other columns of the buffer that holds d_out,
+ *   which comes back unchanged) and overwrites all 7 members of grads (all zero at B = 0 or
+ *   nnz = 0).  workspace: rm_dien_workspace(.., 1) floats, 16-byte aligned.
+ * Supported (rm_dien_supported): D in {8,16,32}; max_len 1..256; anything else is RM_EINVAL before
+ *   any launch and a workspace of 0.  A history longer than max_len is a caller error that is made
+ *   safe: its LAST max_len items are used (what th.SequenceFeat keeps) and the d_keys rows of the
+ *   others are written as zeros; offsets are clamped to [0, nnz], so no loop bound comes from
+ *   unchecked input.
+ * Deterministic: a fixed assignment of examples (and, for the weight gradients, of positions) to
+ *   blocks, per-block partial sums added in block order, fixed-order sums inside a block, no float
+ *   atomics - two runs are bit-equal. */
+typedef struct rm_dien_params {
+  float *gru_w, *gru_u, *gru_b;         /* [D, 3D], [D, 3D], [3D] */
+  float *att_w;                         /* [D, D] */
+  float *augru_w, *augru_u, *augru_b;   /* [D, 3D], [D, 3D], [3D] */
+} rm_dien_params;
+int rm_dien_supported(int D, int max_len);
+int64_t rm_dien_workspace(int D, int max_len, int64_t B, int64_t nnz, int backward);
+int rm_dien_fwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+                const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz,
+                const rm_dien_params *params, int max_len, int save, float *out, float *workspace,
+                rm_stream_t stream);
+int rm_dien_bwd(const float *rows, int64_t LD, int D, int64_t row0, const int64_t *offsets,
+                const int64_t *ids, const int64_t *qrow, int64_t B, int64_t nnz,
+                const rm_dien_params *params, int max_len, const float *d_out, int64_t do_stride,
+                float *d_keys, float *d_query, int64_t dq_stride, const rm_dien_params *grads,
+                float *workspace, rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * CIN (xDeepFM), one layer, on the f32-input MFMA.
  * Replaces the loop body of CIN.__call__ (layers.py:714-752):
  *   Z[b,d,i*H+j] = X0[b,i,d] * Xk[b,j,d];  M = Z @ W + bias;  out = act(M)

@@ -43,6 +43,15 @@ class BstParams(ctypes.Structure):
     _fields_ = [(n, P) for n in BST_PARAM_NAMES]
 
 
+DIEN_PARAM_NAMES = ("gru_w", "gru_u", "gru_b", "att_w", "augru_w", "augru_u", "augru_b")
+
+
+class DienParams(ctypes.Structure):
+    """rm_dien_params of include/recman_hip.h: the 7 device pointers of the interest-evolution unit (or of its
+    gradients)."""
+    _fields_ = [(n, P) for n in DIEN_PARAM_NAMES]
+
+
 # name -> argtypes, in the order of include/recman_hip.h
 SIGNATURES = {
     "rm_version": [],
@@ -112,6 +121,9 @@ SIGNATURES = {
     "rm_bst_supported": [c_int, c_int, c_int, c_int],
     "rm_bst_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, c_int, c_int, P, P, P],
     "rm_bst_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, c_int, c_int, P, I64, P, P, I64, P, P, P],
+    "rm_dien_supported": [c_int, c_int],
+    "rm_dien_fwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, c_int, P, P, P],
+    "rm_dien_bwd": [P, I64, c_int, I64, P, P, P, I64, I64, P, c_int, P, I64, P, P, I64, P, P, P],
     "rm_cin_layer_fwd": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
                          c_int, P, P],
     "rm_cin_layer_fwd6": [P, P, I64, P, P, c_int, I64, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
@@ -167,6 +179,7 @@ SIGNATURES_I64 = {
     "rm_masknet_row_bwd_workspace": [I64, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],
     "rm_bst_workspace": [c_int, c_int, c_int, c_int, I64, c_int],
+    "rm_dien_workspace": [c_int, c_int, I64, I64, c_int],
     "rm_mlp_bwd_workspace": [c_int, c_int],
     "rm_deepfm_step_workspace": [c_int, c_int],
     "rm_outer_actgrad_sums_workspace": [I64, c_int],

@@ -501,12 +501,17 @@ class Engine:
         Behavior Sequence Transformer, arXiv 1905.06874): variables {name}_bst_{wq|wk|wv|wo} [D, D],
         {name}_bst_{bq|bk|bv|bo} [D], {name}_bst_ffn_w1 [D, Hf], _ffn_b1 [Hf], _ffn_w2 [Hf, D], _ffn_b2 [D],
         {name}_bst_ln{1|2}_{gamma|beta} [D], {name}_bst_pos [max_len + 1, D].  hp: att_head_num 2, att_ffn_units 4 D.
-        att_dropout must be all ones under both."""
+        "dien" (csrc/dien.hip, a GRU over the history, the candidate's attention over its states and an
+        attention-gated GRU whose last state is the row; Deep Interest Evolution Network, arXiv 1809.03672, hidden
+        size D, no auxiliary loss): variables {name}_dien_{gru|augru}_{w|u} [D, 3D], {name}_dien_{gru|augru}_b [3D],
+        {name}_dien_att_w [D, D].  No hyper-parameter.
+        att_dropout must be all ones under all three."""
         spec, hp, D = self.spec, self.hp, self.D
         self._asp_saved = {}
         self.seq_pooling = str(hp.get("seq_pooling", "din")).lower()
-        if self.seq_pooling not in ("din", "transformer"):
-            raise ValueError(f"seq_pooling {hp.get('seq_pooling')!r}: 'din' or 'transformer'")
+        self._seq_save = False
+        if self.seq_pooling not in ("din", "transformer", "dien"):
+            raise ValueError(f"seq_pooling {hp.get('seq_pooling')!r}: 'din', 'transformer' or 'dien'")
         if not spec.seq_names:
             return
         if not hasattr(self, "rows") or self.rows.dim() != 2 or self.rows.shape[0] != spec.rows:
@@ -515,6 +520,10 @@ class Engine:
         if self.seq_pooling == "transformer":
             self._check_att_dropout()
             self._init_bst()
+            return
+        if self.seq_pooling == "dien":
+            self._check_att_dropout()
+            self._init_dien()
             return
         self.asp_hidden = [int(h) for h in hp.get("att_hidden_units", (80, 40))]
         act = hp.get("att_activation", "sigmoid")
@@ -567,6 +576,21 @@ class Engine:
                     init = "ones" if v.endswith("_gamma") else "zeros"
                 self._var(f"{n}_bst_{v}", shape, init)
 
+    def _init_dien(self):
+        """The interest-evolution unit's variables (absent from the reference: glorot matrices, zero biases; no l2,
+        as for the other two units)."""
+        for n in self.spec.seq_names:
+            ml = int(self.spec.seq_max_len[n])
+            if not ops.dien_supported(self.D, ml):
+                raise ValueError(f"sequence feature {n!r}: embedding_size={self.D}, max_len={ml} is not supported by "
+                                 f"rm_dien_fwd ({ops.DIEN_LIMITS})")
+            for v, shape in ops.dien_param_shapes(self.D).items():
+                self._var(f"{n}_dien_{v}", shape, ("glorot", shape[0], shape[1]) if len(shape) == 2 else "zeros")
+
+    def _dien_vars(self, d, name):
+        """{member: tensor} of sequence feature `name`'s interest-evolution unit out of the params or the grads dict."""
+        return {v: d[f"{name}_dien_{v}"] for v in ops.DIEN_PARAM_NAMES}
+
     def _bst_vars(self, d, name):
         """{member: tensor} of sequence feature `name`'s transformer unit out of the params or the grads dict."""
         return {v: d[f"{name}_bst_{v}"] for v in ops.BST_PARAM_NAMES}
@@ -598,6 +622,18 @@ class Engine:
             ops.bst_fwd(self.rows, row0, self.D, offsets, ids, qrow, self._bst_vars(self.params, name), self.bst_heads,
                         ml, self.mv_scratch[j], buf["ws"])
             return
+        if self.seq_pooling == "dien":
+            B, ml = int(idx.shape[0]), int(self.spec.seq_max_len[name])
+            if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.dien_workspace(self.D, ml, B, nnz, True):
+                cap = max(nnz, 1)
+                buf = dict(cap=cap, d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
+                           ws=torch.empty(max(4, ops.dien_workspace(self.D, ml, B, cap, True)), dtype=F32,
+                                          device=self.device))
+                self._asp_saved[f] = buf
+            buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq, max_len=ml)
+            ops.dien_fwd(self.rows, row0, self.D, offsets, ids, qrow, self._dien_vars(self.params, name), ml,
+                         self._seq_save, self.mv_scratch[j], buf["ws"])
+            return
         if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.asp_workspace(self.D, self.asp_hidden, nnz, True):
             cap = max(nnz, 1)
             buf = dict(cap=cap, scores=torch.empty(cap, dtype=F32, device=self.device),
@@ -623,6 +659,11 @@ class Engine:
                 ops.bst_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
                             self._bst_vars(self.params, name), self.bst_heads, b["max_len"], self.d_rows[:, f, :],
                             b["d_keys"][:nnz], self.d_rows[:, b["fq"], :], self._bst_vars(self.grads, name), b["ws"])
+                continue
+            if self.seq_pooling == "dien":
+                ops.dien_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
+                             self._dien_vars(self.params, name), b["max_len"], self.d_rows[:, f, :],
+                             b["d_keys"][:nnz], self.d_rows[:, b["fq"], :], self._dien_vars(self.grads, name), b["ws"])
                 continue
             ops.asp_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
                         *self._asp_vars(self.params, name), self.asp_act, self.asp_norm, b["scores"][:nnz],
@@ -841,6 +882,7 @@ class Engine:
         multi-valued features."""
         self._alloc(idx.shape[0])
         self._mv = mv
+        self._seq_save = bool(training)
         backup = None
         if manual_weights is not None:
             # W + weights for this call only: exact restore from a copy (an add/subtract pair
@@ -869,6 +911,7 @@ class Engine:
         B = idx.shape[0]
         self._alloc(B)
         self._mv = mv
+        self._seq_save = True
         yk = dict(y=y) if y.dtype == I64 else dict(y_f=y)
         scale = self.grad_scale
         # models whose DNN is the last branch of the forward offer it the fused head (rm_mlp_tail):
@@ -1990,6 +2033,18 @@ class BSTEngine(DINEngine):
         super().__init__(spec, embedding_size, dict(hp, seq_pooling="transformer"), task, device)
 
 
+class DIENEngine(DINEngine):
+    """Deep Interest Evolution Network (arXiv 1809.03672): final = linear + DNN([E | dense]) as DIN, with every
+    sequence feature pooled by the interest-evolution unit (seq_pooling is forced to "dien"; csrc/dien.hip): a GRU
+    over the history, the candidate's softmax attention over its states, and an attention-gated GRU (AUGRU) whose
+    last state is the feature's row.  Hidden size = embedding_size; no auxiliary loss; no hyper-parameter."""
+
+    model = "dien"
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, dict(hp, seq_pooling="dien"), task, device)
+
+
 class AutoIntEngine(DeepFMEngine):
     """AutoInt (arXiv 1810.11921): final = linear + autoint (+ DNN([E | dense]) with a non-empty deep_hidden_units:
     AutoInt+), PredictionLayer(use_bias=False).  Nothing in the reference implements it.  L interacting layers of
@@ -2690,4 +2745,4 @@ class MaskNetEngine(Engine):
 
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine,
-           "masknet": MaskNetEngine, "bst": BSTEngine}
+           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine}

@@ -894,6 +894,82 @@ def bst_bwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, d_out, d_
               _chk(workspace, "workspace", F32), _stream())
 
 
+DIEN_PARAM_NAMES = _lib.DIEN_PARAM_NAMES
+DIEN_LIMITS = "embedding_size 8/16/32, max_len 1..256"
+
+
+def dien_supported(D, max_len):
+    """rm_dien_supported: D in {8, 16, 32}, 1 <= max_len <= 256."""
+    return bool(_lib.lib().rm_dien_supported(int(D), int(max_len)))
+
+
+def dien_workspace(D, max_len, B, nnz, backward):
+    """Floats of workspace rm_dien_fwd needs without (backward=False) / with save, and rm_dien_bwd (backward=True), for
+    B examples and nnz history positions (0: unsupported shape)."""
+    return int(_lib.lib().rm_dien_workspace(int(D), int(max_len), int(B), int(nnz), 1 if backward else 0))
+
+
+def dien_param_shapes(D):
+    """name -> shape of the 7 tensors of the interest-evolution unit, in the order of rm_dien_params."""
+    s = {n: (D, 3 * D) for n in ("gru_w", "gru_u", "augru_w", "augru_u")}
+    s.update(gru_b=(3 * D,), augru_b=(3 * D,), att_w=(D, D))
+    return {n: s[n] for n in DIEN_PARAM_NAMES}
+
+
+def _dien_struct(params, what, D):
+    shapes = dien_param_shapes(D)
+    if set(params) != set(shapes):
+        raise ValueError(f"dien: {what} must hold exactly {DIEN_PARAM_NAMES}, got {sorted(params)}")
+    return _lib.DienParams(*[_chk(params[n], f"{what}[{n!r}]", F32, shapes[n]) for n in DIEN_PARAM_NAMES])
+
+
+def _dien_args(rows, D, offsets, ids, qrow, params):
+    if set(params) != set(DIEN_PARAM_NAMES):
+        raise ValueError(f"dien: params must hold exactly {DIEN_PARAM_NAMES}, got {sorted(params)}")
+    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    if rows.dim() != 2:
+        raise ValueError(f"rows: expected [R, LD], got {tuple(rows.shape)}")
+    D = int(D)
+    ps = _dien_struct(params, "params", D)
+    return B, nnz, (rp, int(rows.shape[1]), D), (op, ip, qp, B, nnz), ps
+
+
+def dien_fwd(rows, row0, D, offsets, ids, qrow, params, max_len, save, out, workspace):
+    """Interest-evolution pooling of the history rows (rm_dien_fwd): rows [R, LD] the fused table, history id -> row
+    row0 + id (oldest first), the example's query row qrow [B] (absolute); params: {name: tensor} over DIEN_PARAM_NAMES
+    (shapes: dien_param_shapes).  -> out [B, LD]: the AUGRU's last state in columns 0..D-1, zeros behind (no history:
+    a zero row).  save: keep what dien_bwd needs in the workspace (dien_workspace(.., backward=save) floats); `out` has
+    the same bits either way.  ids.shape[0] must equal offsets[-1]."""
+    B, nnz, (rp, LD, D), csr, ps = _dien_args(rows, D, offsets, ids, qrow, params)
+    need = dien_workspace(D, max_len, B, nnz, bool(save))
+    if need:
+        _need_workspace("dien_fwd", workspace, need)
+    _lib.call("rm_dien_fwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(max_len), 1 if save else 0,
+              _chk(out, "out", F32, (B, LD)), _chk(workspace, "workspace", F32), _stream())
+
+
+def dien_bwd(rows, row0, D, offsets, ids, qrow, params, max_len, d_out, d_keys, d_query, grads, workspace):
+    """rm_dien_bwd, after dien_fwd(save=True) on the same inputs and workspace: d_out [B, D] view (row stride may be
+    larger) = the pooled rows' gradient -> d_keys [nnz, D] overwritten; the query gradient ADDED onto d_query [B, D]
+    (a view, row stride may be larger; it may be other columns of d_out's buffer); grads: {name: tensor} over
+    DIEN_PARAM_NAMES, all overwritten.  Deterministic."""
+    B, nnz, (rp, LD, D), csr, ps = _dien_args(rows, D, offsets, ids, qrow, params)
+    gs = _dien_struct(grads, "grads", D)
+    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
+        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
+            raise ValueError(f"dien_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
+    need = dien_workspace(D, max_len, B, nnz, True)
+    if need:
+        _need_workspace("dien_bwd", workspace, need)
+    if workspace.data_ptr() % 16:
+        raise ValueError("dien_bwd: workspace must be 16-byte aligned")
+    _lib.call("rm_dien_bwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(max_len),
+              d_out.data_ptr(), d_out.stride(0) if B > 1 else max(D, d_out.stride(0)),
+              _chk(d_keys, "d_keys", F32, (nnz, D)), d_query.data_ptr(),
+              d_query.stride(0) if B > 1 else max(D, d_query.stride(0)), ctypes.byref(gs),
+              _chk(workspace, "workspace", F32), _stream())
+
+
 def gather_rows(table, rows, out):
     """out[i, :] = table[rows[i], :width] with width = out.shape[1] <= table.shape[1] (the shard keeps
     optimizer state behind the exchanged columns).  `table` may live in PINNED host memory (th/feeder.py)."""

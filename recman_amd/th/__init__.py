@@ -12,6 +12,7 @@ from .FiBiNET import FiBiNET
 from .FmFM import FmFM, FwFM
 from .MaskNet import MaskNet
 from .BST import BST
+from .DIEN import DIEN
 from .DIN import DIN
 from .DeepModel import DeepModel
 from .inputs import (DataInputs, DenseFeat, FeatureDictionary, MultiValCsvFeat, ResilientLabelEncoder,
@@ -20,6 +21,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]
