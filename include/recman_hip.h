@@ -562,6 +562,69 @@ int rm_fmfm_bwd(const float *E, const float *W, int type, const float *g, const 
                 rm_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * The product layer of the Product-based Neural Network (PNN, arXiv 1611.00144), fused
+ * (csrc/pnn.hip): the kernel-form layer of the widely used open-source PNN (use_inner,
+ * use_outter, kernel_type mat / vec / num), NOT the paper's sum-pooled outer-product shortcut.
+ * Nothing in the reference implements it.  Per example, E [F, D], P = F(F-1)/2, pairs p = (i, j),
+ * 0 <= i < j < F, i-major (itertools.combinations order):
+ *     inner[p] = <E_i, E_j>
+ *     outer[p] = E_i K_(p) E_j^T
+ *   kernel_type RM_PNN_MAT: K_(p) = K[p], K [P, D, D] (the LEFT field i on the rows);
+ *   RM_PNN_VEC: K_(p) = diag(K[p]), K [P, D];  RM_PNN_NUM: K_(p) = K[p] I, K [P].
+ *     X = [ E flattened (F D columns, the same bits) | inner (P, with RM_PNN_INNER) |
+ *           outer (P, with RM_PNN_OUTER) ]                       W = F D + n P columns
+ *   products: a non-empty bit set of RM_PNN_INNER and RM_PNN_OUTER.  E [B, F, D] contiguous,
+ *   16-byte aligned (rm_embed_fwd's E); K contiguous, may be NULL without OUTER (kernel_type
+ *   must still be one of the three).  X [B, ldx], ldx >= W, rows need no alignment; columns
+ *   [W, ldx) are set to +0.0.  Every product is accumulated in float64 and rounded to float once
+ *   (X keeps every pair: a product of a row of large entries that cancels to below 1 would
+ *   otherwise carry an absolute error of 1e-5 and more at D >= 16).  INNER, VEC and NUM products
+ *   are k-ordered fma chains of length D on the vector ALU.  A MAT product is U = E_i K[p] on
+ *   v_mfma_f64_16x16x4_f64 (per column d a k-ordered chain of length D), then sum_d U[d] E_j[d]:
+ *   per lane a chain over four d (eight at D = 32), the four lane groups added by two shuffle
+ *   steps.  The backward is float32: fmaf chains, and v_mfma_f32_16x16x4_f32 for MAT.
+ * rm_pnn_bwd, given dX [B, lddx] = dLoss/dX (lddx >= W; columns >= W are never read), with G_in
+ *   and G_out its two product column blocks:
+ *     dE_i += G_in[p] E_j + G_out[p] K_(p) E_j;   dE_j += G_in[p] E_i + G_out[p] K_(p)^T E_i
+ *     d_rows [B, F, D] = dX[:, 0:FD] + dE, written once
+ *     dK[p] = sum_b G_out[b,p] E_bi (x) E_bj  (its diagonal for VEC, its trace for NUM)
+ *   d_rows and dK (the shape of K) are overwritten; dK and the workspace may be NULL without
+ *   OUTER.  workspace: rm_pnn_bwd_workspace(B, F, D, products, kernel_type) floats: the partial
+ *   dK of at most 64 batch slices (MAT; 512 for VEC and NUM; fewer where that many sets would
+ *   pass 32 MB), summed in slice order by a finish kernel: no atomics, two runs are bit-equal;
+ *   0 at B = 0 or without OUTER, -1 for an unsupported shape.
+ * rm_pnn_tile(F, D, products, kernel_type, which): the examples per tile of the forward / dE /
+ *   dK kernel (RM_PNN_TILE_*) and the cap of the forward's and dE's grids and of the dK kernels'
+ *   batch slices (RM_PNN_CAP_*): beyond cap x tile examples a block walks the batch with a grid
+ *   stride.  The dK entries are 0 without OUTER.  -1 for an unsupported shape or `which`.
+ * Supported: D in {8,16,32}, 2 <= F <= 40, products 1..3, kernel_type MAT, VEC or NUM
+ *   (rm_pnn_supported); anything else, a NULL pointer or a stride below W is RM_EINVAL before any
+ *   launch.  B = 0 is RM_OK and touches nothing.  Nothing of size P D leaves the chip: the
+ *   forward reads 4 F D bytes per example and writes 4 ldx; the backward reads E and dX twice
+ *   with OUTER (dE kernel, dK kernel: the MAT dK kernel once per chunk of 64 pairs - 16 at
+ *   D = 32 -, from L2 after the first), once without, and writes d_rows once.
+ */
+#define RM_PNN_INNER 1
+#define RM_PNN_OUTER 2
+#define RM_PNN_MAT 0
+#define RM_PNN_VEC 1
+#define RM_PNN_NUM 2
+#define RM_PNN_TILE_FWD 0
+#define RM_PNN_TILE_DE 1
+#define RM_PNN_TILE_DK 2
+#define RM_PNN_CAP_FWD 3
+#define RM_PNN_CAP_DE 4
+#define RM_PNN_CAP_DK 5
+int rm_pnn_supported(int F, int D, int products, int kernel_type);
+int rm_pnn_tile(int F, int D, int products, int kernel_type, int which);
+int rm_pnn_fwd(const float *E, const float *K, int products, int kernel_type, int64_t B, int F, int D,
+               float *X, int64_t ldx, rm_stream_t stream);
+int64_t rm_pnn_bwd_workspace(int64_t B, int F, int D, int products, int kernel_type);
+int rm_pnn_bwd(const float *E, const float *K, int products, int kernel_type, const float *dX,
+               int64_t lddx, int64_t B, int F, int D, float *d_rows, float *dK, float *workspace,
+               rm_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * MaskNet (arXiv 2102.07619): the normalise-and-mask passes around its dense layers, fused
  * (csrc/masknet.hip).  Nothing in the reference implements it.  eps = 1e-5 inside the root,
  * biased variance; a row's mean and centred sum of squares are accumulated in float64 (centred

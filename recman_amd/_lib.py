@@ -106,6 +106,10 @@ SIGNATURES = {
     "rm_fmfm_tile": [c_int, c_int, c_int, c_int],
     "rm_fmfm_fwd": [P, P, c_int, I64, c_int, c_int, P, P],
     "rm_fmfm_bwd": [P, P, c_int, P, P, I64, c_int, c_int, P, P, P, P],
+    "rm_pnn_supported": [c_int, c_int, c_int, c_int],
+    "rm_pnn_tile": [c_int, c_int, c_int, c_int, c_int],
+    "rm_pnn_fwd": [P, P, c_int, c_int, I64, c_int, c_int, P, I64, P],
+    "rm_pnn_bwd": [P, P, c_int, c_int, P, I64, I64, c_int, c_int, P, P, P, P],
     "rm_masknet_group_supported": [c_int, c_int, c_int, c_int],
     "rm_masknet_group_tile": [c_int, c_int, c_int, c_int],
     "rm_masknet_group_fwd": [P, P, P, c_int, P, I64, c_int, I64, c_int, c_int, P, I64, P],
@@ -175,6 +179,7 @@ SIGNATURES_I64 = {
     "rm_cross_mix_bwd_workspace": [I64, c_int, c_int],
     "rm_fibinet_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_fmfm_bwd_workspace": [I64, c_int, c_int, c_int],
+    "rm_pnn_bwd_workspace": [I64, c_int, c_int, c_int, c_int],
     "rm_masknet_group_bwd_workspace": [I64, c_int, c_int],
     "rm_masknet_row_bwd_workspace": [I64, c_int],
     "rm_asp_workspace": [c_int, c_int, P, I64, c_int],

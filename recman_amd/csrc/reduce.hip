@@ -4,7 +4,7 @@
 // Determinism: element o is summed by one thread, over the sets in ascending order, in one float accumulator
 // that starts at +0.0f - no float atomics, so two runs are bit-equal, and neither the block size nor the grid
 // enters the arithmetic.  Callers: rm_afm_bwd, rm_autoint_head_bwd (over its kSeg segments), rm_cross_mix_bwd,
-// rm_fibinet_bwd, rm_fmfm_bwd, rm_bst_bwd (five sets: its 17 destinations).
+// rm_fibinet_bwd, rm_fmfm_bwd, rm_pnn_bwd, rm_bst_bwd (five sets: its 17 destinations).
 //
 // Second stages that are NOT this kernel, on purpose:
 //  - autoint_seg_kernel / autoint_finish_kernel (autoint.hip): a segmented first stage (sets split into kSeg

@@ -1,5 +1,5 @@
 // Host-side launch scaffolding shared by the model kernel files (afm, autoint, dot_interact, cross_mix, fibinet,
-// fmfm, masknet, asp, bst) and the one fixed-order sum of per-block partials (reduce.hip).
+// fmfm, pnn, masknet, asp, bst) and the one fixed-order sum of per-block partials (reduce.hip).
 #pragma once
 #include "rm_common.h"
 

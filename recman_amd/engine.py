@@ -2483,6 +2483,101 @@ class FmFMEngine(DeepFMEngine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+class PNNEngine(Engine):
+    """Product-based Neural Network (PNN, arXiv 1611.00144) with the kernel-form product layer of the widely used
+    open-source PNN (use_inner, use_outter, kernel_type mat / vec / num) - NOT the paper's sum-pooled outer-product
+    shortcut.  final = DNN([X | dense]) (+ linear if use_linear; off by default).  Nothing in the reference implements
+    it.  Over the P = F(F-1)/2 field pairs i < j in itertools.combinations order, fused in csrc/pnn.hip:
+        X = [ E flattened | <E_i, E_j> (use_inner) | E_i K_(ij) E_j^T (use_outer) ]
+        kernel_type "mat": K_(ij) = product_kernel[p] [P,D,D] (the left field on the rows);  "vec":
+        diag(product_kernel[p]) [P,D];  "num": product_kernel[p] I [P]
+    Variable (with use_outer only): product_kernel, glorot with fan D / D for all three kernel types, l2 key
+    interaction_l2_reg.  No bias tables.  X and dX are [B, ldx] buffers, ldx = W rounded up to 4 floats; the pad
+    columns stay +0.0.  The DNN's dX is no table-row gradient: d_rows comes from rm_pnn_bwd, which adds the row part
+    of dX to the products' gradient and writes it once."""
+
+    model = "pnn"
+    use_bias_tables = False
+    shardable = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", False))
+        limits = ("2..40 embedding features, embedding_size 8/16/32, use_inner or use_outer, kernel_type 'mat', 'vec' "
+                  "or 'num'")
+        self.ktype = hp.get("kernel_type", "mat")
+        self.products = ops.pnn_products(hp.get("use_inner", True), hp.get("use_outer", False))
+        if not self.products:
+            raise ValueError(f"PNN: neither use_inner nor use_outer is set: the product layer would be empty ({limits})")
+        if self.ktype not in ops.PNN_KERNELS:
+            raise ValueError(f"PNN: kernel_type {self.ktype!r} is not one of 'mat', 'vec', 'num' ({limits})")
+        F, D = self.F, self.D
+        if not ops.pnn_supported(F, D, self.products, self.ktype):
+            raise ValueError(f"PNN: {F} embedding features of embedding_size={D} are not supported by rm_pnn_fwd "
+                             f"({limits})")
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        if not hidden:
+            raise ValueError("PNN: deep_hidden_units must name at least one layer of the DNN")
+        self.P = F * (F - 1) // 2
+        self.outer = bool(self.products & ops.PNN_OUTER)
+        if self.outer:
+            self._var("product_kernel", ops.pnn_weight_shape(F, D, self.ktype), ("glorot", D, D), "interaction_l2_reg")
+        self.W, self.ldx = ops.pnn_width(F, D, self.products)
+        # (the DNN reads the product layer's output, not [E | dense]; its dX is no table-row gradient)
+        self.mlp = self._dnn(self.W, self.Dn, hidden, "relu", stream_d_rows=False)
+
+    def _alloc_model(self, B):
+        dev = self.device
+        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+        self.pnn_ws = (torch.empty(max(4, ops.pnn_bwd_workspace(B, self.F, self.D, self.products, self.ktype)),
+                                   dtype=F32, device=dev) if self.outer else None)
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        X = self.X[:, : self.W]
+        ops.pnn_fwd(self.E, self.params.get("product_kernel"), self.products, self.ktype, X)
+        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
+        self.dnn_logit = self._mlp_last(self.mlp, X, dense if self.Dn else None, self._dnn_keep(training),
+                                        m.get("dnn"), list(branches))
+        branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        dX = self.dX[:, : self.W]
+        self.mlp.backward(g, dX)
+        # no other branch reads E: d_rows IS dLoss/dE
+        ops.pnn_bwd(self.E, self.params.get("product_kernel"), self.products, self.ktype, dX, self.d_rows,
+                    self.grads.get("product_kernel"), self.pnn_ws)
+
+    def roofline_probes(self, idx, dense, y):
+        self._probe_fill(idx, dense, y)  # E, dX
+        B, F, D, P, ldx = idx.shape[0], self.F, self.D, self.P, self.ldx
+        X, dX = self.X[:, : self.W], self.dX[:, : self.W]
+        k = self.params.get("product_kernel")
+        dk = torch.empty_like(k) if k is not None else None
+        d_rows = torch.empty_like(self.d_rows)
+        shape = f"F={F} D={D} products={self.products} {self.ktype} ldx={ldx}"
+        if self.outer and self.ktype == "mat":
+            fwd, bwd, bound = 2.0 * B * P * D * D, 6.0 * B * P * D * D, "mfma"
+            names = ("pnn_de_mat_kernel", "pnn_fwd_kernel")
+            what = "flops = 2 B P D^2 forward, three times that backward (dE both ways + dK)"
+        else:
+            # algorithmic bytes: E read once and X written; E and dX read once, d_rows written once (+ K, dK)
+            nk = k.numel() if k is not None else 0
+            fwd, bwd, bound = 4.0 * (B * F * D + B * ldx + nk), 4.0 * (2 * B * F * D + B * ldx + 2 * nk), "hbm"
+            names = ("pnn_de_valu_kernel", "pnn_fwd_kernel")
+            what = "algorithmic bytes: E (+ dX) in, X / d_rows out, the kernel and its gradient"
+        return [
+            dict(name=f"{names[0]} + dK kernels (rm_pnn_bwd, {shape}; {what})", symbol=names[0],
+                 fn=lambda: ops.pnn_bwd(self.E, k, self.products, self.ktype, dX, d_rows, dk, self.pnn_ws),
+                 work=bwd, bound=bound),
+            dict(name=f"{names[1]} (rm_pnn_fwd, {shape}; {what})", symbol=names[1],
+                 fn=lambda: ops.pnn_fwd(self.E, k, self.products, self.ktype, X), work=fwd, bound=bound),
+        ] + Engine.roofline_probes(self, idx, dense, y)
+
+
 def masknet_limits(hp, F, D):
     """MaskNet's limits in one place (th.MaskNet checks them at construction, MaskNetEngine when it is built): a
     ValueError naming the limit, or (block_order, num_blocks, block_hidden_units, reduction_ratio, deep_hidden_units)."""
@@ -2744,5 +2839,5 @@ class MaskNetEngine(Engine):
 
 
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
-           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine,
+           "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine, "pnn": PNNEngine,
            "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine}

@@ -584,6 +584,106 @@ def fmfm_bwd(E, W, field_interaction, g, d_rows, dW, workspace, dE_up=None):
               _chk(workspace, "workspace", F32), _stream())
 
 
+# ---- PNN's product layer: inner products and kernel-form outer products per field pair (csrc/pnn.hip) --------------
+PNN_INNER, PNN_OUTER = 1, 2  # RM_PNN_INNER / RM_PNN_OUTER: the bits of `products`
+PNN_KERNELS = {"mat": 0, "vec": 1, "num": 2}  # RM_PNN_MAT / RM_PNN_VEC / RM_PNN_NUM
+PNN_TILE = {"fwd": 0, "de": 1, "dk": 2, "fwd_cap": 3, "de_cap": 4, "dk_cap": 5}  # RM_PNN_TILE_* / RM_PNN_CAP_*
+_PNN_LIMITS = "2 <= F <= 40, D in 8, 16, 32, products 1 (inner), 2 (outer) or 3, kernel_type 'mat', 'vec' or 'num'"
+
+
+def _pnn_kernel(kernel_type):
+    if kernel_type not in PNN_KERNELS:
+        raise ValueError(f"pnn: kernel_type {kernel_type!r} unsupported ({_PNN_LIMITS})")
+    return PNN_KERNELS[kernel_type]
+
+
+def _pnn_products(products):
+    if products not in (1, 2, 3):
+        raise ValueError(f"pnn: products {products!r} unsupported ({_PNN_LIMITS})")
+    return int(products)
+
+
+def pnn_products(use_inner, use_outer):
+    """The `products` bit set of the two switches (0 when neither is on: no entry point takes that)."""
+    return (PNN_INNER if use_inner else 0) | (PNN_OUTER if use_outer else 0)
+
+
+def pnn_supported(F, D, products, kernel_type):
+    """rm_pnn_supported: D in {8, 16, 32}, 2 <= F <= 40, products 1..3, kernel_type "mat", "vec" or "num"."""
+    if kernel_type not in PNN_KERNELS or products not in (1, 2, 3):
+        return False
+    return bool(_lib.lib().rm_pnn_supported(int(F), int(D), int(products), PNN_KERNELS[kernel_type]))
+
+
+def pnn_weight_shape(F, D, kernel_type):
+    """The shape of product_kernel: [P,D,D] (mat), [P,D] (vec) or [P] (num), P = F(F-1)/2."""
+    P = F * (F - 1) // 2
+    return {0: (P, D, D), 1: (P, D), 2: (P,)}[_pnn_kernel(kernel_type)]
+
+
+def pnn_width(F, D, products):
+    """(W, ldx): the columns the product layer writes (the F D row floats, then P = F(F-1)/2 per selected product)
+    and that width rounded up to a multiple of 4 floats (16-byte rows for the dense kernels that read X)."""
+    n = bin(_pnn_products(products)).count("1")
+    W = F * D + n * (F * (F - 1) // 2)
+    return W, (W + 3) // 4 * 4
+
+
+def pnn_tile(F, D, products, kernel_type, which):
+    """rm_pnn_tile: which in PNN_TILE - the examples per tile of the forward ("fwd"), dE ("de") or dK ("dk") kernel,
+    or the cap of their grids / batch slices ("fwd_cap", "de_cap", "dk_cap"); the dK entries are 0 without OUTER."""
+    v = int(_lib.lib().rm_pnn_tile(int(F), int(D), _pnn_products(products), _pnn_kernel(kernel_type), PNN_TILE[which]))
+    if v < 0:
+        raise ValueError(f"pnn: F={F}, D={D} unsupported ({_PNN_LIMITS})")
+    return v
+
+
+def _pnn_args(E, K, products, kernel_type, X, name):
+    """-> (B, F, D, products, kernel type, E's and K's pointers, X's pointer and row stride)."""
+    if E.dim() != 3:
+        raise ValueError(f"E: expected [B,F,D], got {tuple(E.shape)}")
+    B, F, D = (int(v) for v in E.shape)
+    kt, products = _pnn_kernel(kernel_type), _pnn_products(products)
+    if not pnn_supported(F, D, products, kernel_type):
+        raise ValueError(f"pnn: F={F}, D={D} unsupported ({_PNN_LIMITS})")
+    outer = bool(products & PNN_OUTER)
+    pk = _chk(K, "K", F32, pnn_weight_shape(F, D, kernel_type), allow_none=not outer)
+    px, ldx = _strided_rows(X, name, B, pnn_width(F, D, products)[0], False)
+    return B, F, D, products, kt, _chk(E, "E", F32), pk, px, ldx
+
+
+def pnn_fwd(E, K, products, kernel_type, X):
+    """rm_pnn_fwd: E [B,F,D], product_kernel [P,D,D] | [P,D] | [P] (None without OUTER) -> X [B, >= W] with row
+    stride ldx: [E flattened | <E_i, E_j> (INNER) | E_i K_(ij) E_j^T (OUTER)], pairs i < j in combinations order;
+    every column from W up to the row stride is set to +0.0."""
+    B, F, D, products, kt, pe, pk, px, ldx = _pnn_args(E, K, products, kernel_type, X, "X")
+    _lib.call("rm_pnn_fwd", pe, pk, products, kt, B, F, D, px, ldx, _stream())
+
+
+def pnn_bwd_workspace(B, F, D, products, kernel_type):
+    """Floats of workspace for pnn_bwd (rm_pnn_bwd_workspace): the batch slices' partial kernel gradients (0 without
+    OUTER)."""
+    n = int(_lib.lib().rm_pnn_bwd_workspace(int(B), int(F), int(D), _pnn_products(products), _pnn_kernel(kernel_type)))
+    if n < 0:
+        raise ValueError(f"pnn: B={B}, F={F}, D={D} unsupported ({_PNN_LIMITS})")
+    return n
+
+
+def pnn_bwd(E, K, products, kernel_type, dX, d_rows, dK, workspace):
+    """rm_pnn_bwd: dX [B, >= W] (any row stride; columns >= W are never read) -> d_rows [B,F,D] = dX[:, :FD] + dLoss/dE
+    through the products, and dK (the shape of K), both overwritten.  K, dK and workspace may be None without OUTER.
+    Deterministic."""
+    B, F, D, products, kt, pe, pk, px, ldx = _pnn_args(E, K, products, kernel_type, dX, "dX")
+    outer = bool(products & PNN_OUTER)
+    if outer:
+        if workspace is None:
+            raise ValueError("workspace must not be None")
+        _need_workspace("pnn_bwd", workspace, pnn_bwd_workspace(B, F, D, products, kernel_type))
+    _lib.call("rm_pnn_bwd", pe, pk, products, kt, px, ldx, B, F, D, _chk(d_rows, "d_rows", F32, (B, F, D)),
+              _chk(dK, "dK", F32, pnn_weight_shape(F, D, kernel_type), allow_none=not outer),
+              _chk(workspace, "workspace", F32, allow_none=not outer), _stream())
+
+
 # ---- MaskNet: group-LayerNorm times masks, row-LayerNorm + ReLU (csrc/masknet.hip) ----------------------------------
 MASKNET_TILE = {"tile": 0, "cap": 1}  # RM_MASKNET_TILE / RM_MASKNET_CAP
 _MASKNET_GROUP_LIMITS = ("normalize: 1 <= F <= 40, D in 8, 16, 32, 1..8 masks; normalize=False: one [B,H] input, one "

@@ -1,0 +1,58 @@
+"""PNN: the Product-based Neural Network (arXiv 1611.00144) - IPNN, OPNN and both.  Nothing in the reference
+implements it; the constructor follows the pattern of the reference's other classes (recman/tf/core/AFM.py:27-48), the
+product layer is the kernel form of the widely used open-source PNN, fused forward and backward in csrc/pnn.hip."""
+from sklearn.metrics import log_loss, roc_auc_score
+
+from .DeepModel import DeepModel
+
+KERNEL_TYPES = ("mat", "vec", "num")
+
+
+class PNN(DeepModel):
+    """final = DNN([E | inner | outer | dense]) (+ linear with use_linear=True; off by default) over every pair i < j of
+    the F embedding rows (multi-valued, value and sequence features included): inner[(i,j)] = <E_i, E_j> (use_inner,
+    IPNN), outer[(i,j)] = E_i K_(ij) E_j^T (use_outer, OPNN) with one kernel per pair - kernel_type "mat" a D x D
+    matrix, "vec" a vector (K_(ij) = diag(k_ij)), "num" a scalar (K_(ij) = k_ij I).  This is the kernel-form product
+    layer of the widely used open-source PNN, not the paper's sum-pooled outer-product shortcut.  The kernels are
+    glorot; interaction_l2_reg covers them, deep_l2_reg the DNN.  deep_dropout holds KEEP probabilities
+    (layers.py:461), None = no dropout.  Limits: one GPU, 2..40 embedding features, embedding_size 8/16/32, at least
+    one of use_inner / use_outer, a non-empty deep_hidden_units.  The TF-only arguments are stored and used nowhere."""
+
+    model = "pnn"
+
+    def __init__(self, feat_dict, embedding_size=8, use_inner=True, use_outer=False, kernel_type="mat",
+                 deep_hidden_units=(128, 128), deep_dropout=None, deep_l2_reg=0.0, interaction_l2_reg=0.0,
+                 deep_activation="relu", use_linear=False, embedding_l2_reg=0.00001, linear_l2_reg=0.00001, epoch=10,
+                 batch_size=256, learning_rate=0.001, optimizer="adam", random_seed=2019, loss_type="logloss",
+                 eval_metric=(roc_auc_score, log_loss), what_means_greater=None, use_interactive_session=True,
+                 log_dir="./logs", strict_reference=False, device="cuda"):
+        assert loss_type in ["logloss", "mse"], (
+            "loss_type can be either 'logloss' for classification task or 'mse' for regression task")
+        if not (use_inner or use_outer):
+            raise ValueError("PNN: neither use_inner nor use_outer is set: the product layer would be empty")
+        if kernel_type not in KERNEL_TYPES:
+            raise ValueError(f"PNN: kernel_type {kernel_type!r} is not one of 'mat', 'vec', 'num'")
+        hidden = tuple(deep_hidden_units or ())
+        if not hidden:
+            raise ValueError("PNN: deep_hidden_units must name at least one layer of the DNN")
+        keep = tuple(deep_dropout) if deep_dropout is not None else (1,) * (len(hidden) + 1)
+        if len(keep) != len(hidden) + 1:
+            raise ValueError(f"deep_dropout needs {len(hidden) + 1} keep probabilities (input + every hidden layer), "
+                             f"got {deep_dropout!r}")
+        hp = dict(embedding_size=embedding_size, use_inner=use_inner, use_outer=use_outer, kernel_type=kernel_type,
+                  deep_hidden_units=hidden, deep_dropout=keep, deep_l2_reg=deep_l2_reg,
+                  interaction_l2_reg=interaction_l2_reg, deep_activation=deep_activation, use_linear=use_linear,
+                  embedding_l2_reg=embedding_l2_reg, linear_l2_reg=linear_l2_reg, learning_rate=learning_rate,
+                  optimizer=optimizer)
+        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
+                           random_seed=random_seed,
+                           task="classification" if loss_type == "logloss" else "regression",
+                           strict_reference=strict_reference, device=device)
+        # TF-only knobs are accepted and ignored
+        self.what_means_greater, self.use_interactive_session, self.log_dir = (
+            what_means_greater, use_interactive_session, log_dir)
+        self.loss_type, self.eval_metric = loss_type, eval_metric
+        for k, v in hp.items():  # sklearn get_params()/clone() need the ctor arguments back
+            setattr(self, k, v)
+        # (as given: clone() compares the attributes with the arguments)
+        self.deep_dropout, self.deep_hidden_units = deep_dropout, deep_hidden_units

@@ -1148,6 +1148,84 @@ class FieldPairInteraction:
 
 
 # ------------------------------------------------------------------------------------------------
+# PNN's product layer
+# ------------------------------------------------------------------------------------------------
+class _ProductFn(torch.autograd.Function):
+    """rm_pnn_fwd / rm_pnn_bwd (csrc/pnn.hip), as the PNN engine runs them."""
+
+    @staticmethod
+    def forward(ctx, products, ktype, E, k):
+        E = E.detach().contiguous()
+        k = k.detach().contiguous() if k is not None else None
+        B, F, D = E.shape
+        X = torch.empty(B, ops.pnn_width(F, D, products)[0], device=E.device, dtype=F32)
+        ops.pnn_fwd(E, k, products, ktype, X)
+        ctx.save_for_backward(*((E,) if k is None else (E, k)))
+        ctx.products, ctx.ktype = products, ktype
+        return X
+
+    @staticmethod
+    def backward(ctx, dX):
+        E, k = (tuple(ctx.saved_tensors) + (None,))[:2]
+        B, F, D = E.shape
+        dE = torch.empty_like(E)
+        dk = ws = None
+        if k is not None:
+            dk = torch.empty_like(k)
+            ws = torch.empty(max(4, ops.pnn_bwd_workspace(B, F, D, ctx.products, ctx.ktype)), device=dX.device,
+                             dtype=F32)
+        ops.pnn_bwd(E, k, ctx.products, ctx.ktype, dX.contiguous(), dE, dk, ws)
+        return None, None, dE, dk
+
+
+class ProductLayer:
+    """PNN's product layer (arXiv 1611.00144) in the kernel form of the widely used open-source PNN - not the paper's
+    sum-pooled outer-product shortcut; nothing in the reference implements it:
+    ProductLayer(variables, use_inner, use_outer, kernel_type, l2_reg)(feat_embeds [B,F,D]) -> [B, F D + n P] =
+    [E flattened | <E_i, E_j> (use_inner) | E_i K_(ij) E_j^T (use_outer)] over the P = F(F-1)/2 pairs in
+    itertools.combinations order, K_(ij) = product_kernel[p] ("mat", [P,D,D], the left field on the rows),
+    diag(product_kernel[p]) ("vec", [P,D]) or product_kernel[p] I ("num", [P]).  The variable (with use_outer only)
+    is glorot with fan D / D; `.weights`, `.l2()`."""
+
+    display_name = "ProductLayer"
+    NAMES = ("product_kernel",)
+
+    def __init__(self, variables, use_inner=True, use_outer=False, kernel_type="mat", l2_reg=0.0, prefix="", seed=2019):
+        if kernel_type not in ops.PNN_KERNELS:
+            raise ValueError(f"ProductLayer: kernel_type {kernel_type!r} is not one of 'mat', 'vec', 'num'")
+        self.products = ops.pnn_products(use_inner, use_outer)
+        if not self.products:
+            raise ValueError("ProductLayer: neither use_inner nor use_outer is set")
+        self.variables, self.kernel_type, self.l2_reg, self.prefix, self.seed = variables, kernel_type, l2_reg, prefix, seed
+        self.outer = bool(self.products & ops.PNN_OUTER)
+
+    def _upsert_variables(self, F, D):
+        name = self.prefix + "product_kernel"
+        if self.outer and name not in self.variables:
+            std = math.sqrt(2.0 / (D + D))
+            t = torch.empty(ops.pnn_weight_shape(F, D, self.kernel_type), device=_device(), dtype=F32)
+            g = torch.Generator(device=_device()).manual_seed(int(self.seed))
+            torch.nn.init.trunc_normal_(t, 0.0, std, -2 * std, 2 * std, generator=g)
+            self.variables[name] = _leaf(t)
+
+    @property
+    def weights(self):
+        return [self.variables[self.prefix + n] for n in self.NAMES] if self.outer else []
+
+    def __call__(self, feat_embeds):
+        if feat_embeds.dim() != 3:
+            raise ValueError(f"ProductLayer: feat_embeds [B,F,D] expected, got {tuple(feat_embeds.shape)}")
+        _, F, D = feat_embeds.shape
+        if not ops.pnn_supported(F, D, self.products, self.kernel_type):
+            raise ValueError(f"ProductLayer: F={F}, D={D} unsupported (2..40 fields, D in 8/16/32)")
+        self._upsert_variables(F, D)
+        return _ProductFn.apply(self.products, self.kernel_type, feat_embeds, *(self.weights or [None]))
+
+    def l2(self):
+        return sum((self.l2_reg * 0.5 * w.square().sum() for w in self.weights), 0.0)
+
+
+# ------------------------------------------------------------------------------------------------
 # MaskNet's MaskBlock
 # ------------------------------------------------------------------------------------------------
 def _mask_gemm(a, W, out, **kw):
@@ -1334,5 +1412,5 @@ def create_loss(y, pred, task="classification"):
 
 __all__ = ["FeatEmbedding", "FeatEmbeddingLayer", "LinearCombiner", "LinearLayer", "SparseLinearCombiner",
            "SparseLinearLayer", "FMLayer", "DNNCombiner", "DNN", "CIN", "CrossNet", "CrossNetMix", "AFMLayer", "InteractingLayer",
-           "FieldPairInteraction", "MaskBlock", "PredictionLayer",
+           "FieldPairInteraction", "ProductLayer", "MaskBlock", "PredictionLayer",
            "create_loss", "glorot_normal", "glorot_uniform"]
