@@ -492,8 +492,7 @@ int asp_check(const char *fn, int D, int nl, const int *H, int act, int64_t B, i
   RM_REQUIRE(asp_shape_ok(D, nl, H, 1), "%s: unsupported shape (D=%d in {8,16,32}, 1 or 2 hidden layers of 1..%d units)",
              fn, D, kMaxH);
   RM_REQUIRE(act == RM_ASP_RELU || act == RM_ASP_SIGMOID, "%s: unsupported activation %d", fn, act);
-  RM_REQUIRE(B >= 0 && nnz >= 0 && LD >= D, "%s: bad sizes", fn);
-  return RM_OK;
+  return rm_seq_check_sizes(fn, D, B, nnz, LD);
 }
 
 void asp_pack(const AspDims &d, const float *W0, const float *b0, const float *W1, const float *b1, const float *w,
@@ -523,9 +522,8 @@ extern "C" int rm_asp_fwd(const float *rows, int64_t LD, int D, int64_t row0, co
   int rc = asp_check("rm_asp_fwd", D, n_layers, H, act, B, nnz, LD);
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
-  RM_REQUIRE(rows && offsets && qrow && out && W0 && b0 && w && w0 && workspace && (n_layers == 1 || (W1 && b1)),
-             "rm_asp_fwd: NULL argument");
-  RM_REQUIRE(nnz == 0 || (ids && scores), "rm_asp_fwd: NULL argument");
+  if ((rc = rm_seq_check_fwd("rm_asp_fwd", rows, offsets, ids, qrow, nnz, out, workspace)) != RM_OK) return rc;
+  RM_REQUIRE(W0 && b0 && w && w0 && (n_layers == 1 || (W1 && b1)) && (nnz == 0 || scores), "rm_asp_fwd: NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const AspDims d = asp_dims(D, n_layers, H);
   const AspIn in{rows, LD, row0, offsets, ids, qrow, B, nnz};
@@ -553,11 +551,11 @@ extern "C" int rm_asp_bwd(const float *rows, int64_t LD, int D, int64_t row0, co
                           float *dW1, float *db1, float *dw, float *dw0, float *workspace, rm_stream_t stream) {
   int rc = asp_check("rm_asp_bwd", D, n_layers, H, act, B, nnz, LD);
   if (rc != RM_OK) return rc;
-  RM_REQUIRE(W0 && b0 && w && w0 && dW0 && db0 && dw && dw0 && workspace && (n_layers == 1 || (W1 && b1 && dW1 && db1)),
-             "rm_asp_bwd: NULL argument");
-  RM_REQUIRE(nnz == 0 || (rows && offsets && ids && qrow && scores && d_out && d_keys && d_query),
-             "rm_asp_bwd: NULL argument");
-  RM_REQUIRE(do_stride >= D && dq_stride >= D, "rm_asp_bwd: bad strides");
+  if ((rc = rm_seq_check_bwd("rm_asp_bwd", D, rows, offsets, ids, qrow, B, nnz, d_out, do_stride, d_keys, d_query,
+                             dq_stride, workspace)) != RM_OK)
+    return rc;
+  RM_REQUIRE(W0 && b0 && w && w0 && dW0 && db0 && dw && dw0 && (n_layers == 1 || (W1 && b1 && dW1 && db1)) &&
+                 (nnz == 0 || scores), "rm_asp_bwd: NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const AspDims d = asp_dims(D, n_layers, H);
   const AspCfg c = asp_cfg(d);

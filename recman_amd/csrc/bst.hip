@@ -605,9 +605,7 @@ int bst_check(const char *fn, int D, int h, int Hf, int ML, int64_t B, int64_t n
   RM_REQUIRE(bst_shape_ok(D, h, Hf, ML),
              "%s: unsupported shape D=%d heads=%d Hf=%d max_len=%d (D in {8,16,32}, heads in {1,2,4,8} with D / heads >= 4, "
              "Hf a multiple of 4 in 4..128, max_len 1..63)", fn, D, h, Hf, ML);
-  RM_REQUIRE(B >= 0 && B < ((int64_t)1 << 31) && nnz >= 0, "%s: bad sizes", fn);
-  RM_REQUIRE_STRIDE(fn, "LD", LD, D, "D");
-  return RM_OK;
+  return rm_seq_check_sizes(fn, D, B, nnz, LD);
 }
 
 int bst_params_ok(const char *fn, const char *what, const rm_bst_params *p) {
@@ -671,7 +669,7 @@ extern "C" int rm_bst_fwd(const float *rows, int64_t LD, int D, int64_t row0, co
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
   if ((rc = bst_params_ok("rm_bst_fwd", "params", params)) != RM_OK) return rc;
-  RM_REQUIRE(rows && offsets && qrow && out && workspace && (nnz == 0 || ids), "rm_bst_fwd: NULL argument");
+  if ((rc = rm_seq_check_fwd("rm_bst_fwd", rows, offsets, ids, qrow, nnz, out, workspace)) != RM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const BstDims d = bst_dims(D, heads, Hf, max_len);
   const BstCfg c = bst_cfg(d);
@@ -695,13 +693,9 @@ extern "C" int rm_bst_bwd(const float *rows, int64_t LD, int D, int64_t row0, co
   if (rc != RM_OK) return rc;
   if ((rc = bst_params_ok("rm_bst_bwd", "params", params)) != RM_OK) return rc;
   if ((rc = bst_params_ok("rm_bst_bwd", "grads", grads)) != RM_OK) return rc;
-  RM_REQUIRE_PTR("rm_bst_bwd", workspace);
-  RM_REQUIRE(B == 0 || (rows && offsets && qrow && d_out && d_query), "rm_bst_bwd: NULL argument");
-  RM_REQUIRE(nnz == 0 || (ids && d_keys), "rm_bst_bwd: NULL argument");
-  if (B > 0) {
-    RM_REQUIRE_STRIDE("rm_bst_bwd", "do_stride", do_stride, D, "D");
-    RM_REQUIRE_STRIDE("rm_bst_bwd", "dq_stride", dq_stride, D, "D");
-  }
+  if ((rc = rm_seq_check_bwd("rm_bst_bwd", D, rows, offsets, ids, qrow, B, nnz, d_out, do_stride, d_keys, d_query,
+                             dq_stride, workspace)) != RM_OK)
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const BstDims d = bst_dims(D, heads, Hf, max_len);
   const BstCfg c = bst_cfg(d);

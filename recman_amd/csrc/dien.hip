@@ -507,9 +507,8 @@ __global__ __launch_bounds__(kThreads) void dien_attw_kernel(const float *__rest
 
 int dien_check(const char *fn, int D, int ML, int64_t B, int64_t nnz, int64_t LD) {
   RM_REQUIRE(dien_shape_ok(D, ML), "%s: unsupported shape D=%d max_len=%d (D in {8,16,32}, max_len 1..256)", fn, D, ML);
-  RM_REQUIRE(B >= 0 && B < ((int64_t)1 << 31) && nnz >= 0 && nnz < ((int64_t)1 << 40), "%s: bad sizes", fn);
-  RM_REQUIRE_STRIDE(fn, "LD", LD, D, "D");
-  return RM_OK;
+  RM_REQUIRE(nnz < ((int64_t)1 << 40), "%s: bad sizes", fn);
+  return rm_seq_check_sizes(fn, D, B, nnz, LD);
 }
 
 int dien_params_ok(const char *fn, const char *what, const rm_dien_params *p) {
@@ -563,7 +562,7 @@ extern "C" int rm_dien_fwd(const float *rows, int64_t LD, int D, int64_t row0, c
   if (rc != RM_OK) return rc;
   if (B == 0) return RM_OK;
   if ((rc = dien_params_ok("rm_dien_fwd", "params", params)) != RM_OK) return rc;
-  RM_REQUIRE(rows && offsets && qrow && out && workspace && (nnz == 0 || ids), "rm_dien_fwd: NULL argument");
+  if ((rc = rm_seq_check_fwd("rm_dien_fwd", rows, offsets, ids, qrow, nnz, out, workspace)) != RM_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const DienWs w = dien_ws(D, B, nnz);
   const DienIn in{rows, LD, row0, offsets, ids, qrow, B, nnz, max_len};
@@ -582,13 +581,9 @@ extern "C" int rm_dien_bwd(const float *rows, int64_t LD, int D, int64_t row0, c
   if (rc != RM_OK) return rc;
   if ((rc = dien_params_ok("rm_dien_bwd", "params", params)) != RM_OK) return rc;
   if ((rc = dien_params_ok("rm_dien_bwd", "grads", grads)) != RM_OK) return rc;
-  RM_REQUIRE_PTR("rm_dien_bwd", workspace);
-  RM_REQUIRE(B == 0 || (rows && offsets && qrow && d_out && d_query), "rm_dien_bwd: NULL argument");
-  RM_REQUIRE(nnz == 0 || (ids && d_keys), "rm_dien_bwd: NULL argument");
-  if (B > 0) {
-    RM_REQUIRE_STRIDE("rm_dien_bwd", "do_stride", do_stride, D, "D");
-    RM_REQUIRE_STRIDE("rm_dien_bwd", "dq_stride", dq_stride, D, "D");
-  }
+  if ((rc = rm_seq_check_bwd("rm_dien_bwd", D, rows, offsets, ids, qrow, B, nnz, d_out, do_stride, d_keys, d_query,
+                              dq_stride, workspace)) != RM_OK)
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const DienWs w = dien_ws(D, B, nnz);
   const bool work = B > 0 && nnz > 0;

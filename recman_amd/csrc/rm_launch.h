@@ -1,5 +1,6 @@
 // Host-side launch scaffolding shared by the model kernel files (afm, autoint, dot_interact, cross_mix, fibinet,
-// fmfm, pnn, masknet, asp, bst) and the one fixed-order sum of per-block partials (reduce.hip).
+// fmfm, pnn, masknet, asp, bst, dien), the argument checks the three sequence pooling units (asp, bst, dien) share,
+// and the one fixed-order sum of per-block partials (reduce.hip).
 #pragma once
 #include "rm_common.h"
 
@@ -15,6 +16,37 @@ constexpr int64_t kRmMaxStride = 1 << 24;
     RM_REQUIRE((ld) >= (width), "%s: %s=%lld < " what " = %d", fn, name, (long long)(ld), (int)(width)); \
     RM_REQUIRE((ld) <= kRmMaxStride, "%s: %s=%lld too large", fn, name, (long long)(ld));                \
   } while (0)
+
+// The sequence pooling units (asp, bst, dien) begin their entry points with the same arguments - rows, LD, D, row0,
+// offsets, ids, qrow, B, nnz - and check them here, after the file's own shape check.
+// The sizes: the kernels narrow the example index to int and index the table's rows with LD.
+inline int rm_seq_check_sizes(const char *fn, int D, int64_t B, int64_t nnz, int64_t LD) {
+  RM_REQUIRE(B >= 0 && B < ((int64_t)1 << 31) && nnz >= 0, "%s: bad sizes", fn);
+  RM_REQUIRE_STRIDE(fn, "LD", LD, D, "D");
+  return RM_OK;
+}
+
+// The pointers of a forward over B > 0 examples (B == 0 returns before it reads any).
+inline int rm_seq_check_fwd(const char *fn, const float *rows, const int64_t *offsets, const int64_t *ids,
+                            const int64_t *qrow, int64_t nnz, const float *out, const float *workspace) {
+  RM_REQUIRE(rows && offsets && qrow && out && workspace && (nnz == 0 || ids), "%s: NULL argument", fn);
+  return RM_OK;
+}
+
+// The pointers of a backward (the workspace always: the parameter gradients of an empty batch are summed from it)
+// and the row strides of its two [B, D] gradient views.
+inline int rm_seq_check_bwd(const char *fn, int D, const float *rows, const int64_t *offsets, const int64_t *ids,
+                            const int64_t *qrow, int64_t B, int64_t nnz, const float *d_out, int64_t do_stride,
+                            const float *d_keys, const float *d_query, int64_t dq_stride, const float *workspace) {
+  RM_REQUIRE_PTR(fn, workspace);
+  RM_REQUIRE(B == 0 || (rows && offsets && qrow && d_out && d_query), "%s: NULL argument", fn);
+  RM_REQUIRE(nnz == 0 || (ids && d_keys), "%s: NULL argument", fn);
+  if (B > 0) {
+    RM_REQUIRE_STRIDE(fn, "do_stride", do_stride, D, "D");
+    RM_REQUIRE_STRIDE(fn, "dq_stride", dq_stride, D, "D");
+  }
+  return RM_OK;
+}
 
 // Launches a kernel that needs `smem` bytes of dynamic LDS: the limit is raised on every launch (a set attribute,
 // no allocation), then the kernel goes out.  The caller checks the launch (RM_CHECK_LAUNCH).

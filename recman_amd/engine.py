@@ -378,6 +378,132 @@ class MLP:
         return False
 
 
+class DinUnit:
+    """One sequence feature's pooling unit of kind "din": DIN's local activation unit (csrc/asp.hip, arXiv
+    1706.06978).  Variables {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w
+    [H_last, 1], {name}_asp_w0 [1] (absent from the reference, DIN.py:6: glorot weights and an output projection like
+    dnn_w; no l2).  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's Dice, activation.py,
+    uses undefined names), att_weight_normalization False.
+
+    The interface of a pooling unit (SEQ_UNITS): __init__(var, hp, D, name, max_len) reads its hyper-parameters,
+    rejects an unsupported shape and declares its variables through var (Engine._var); workspace(B, nnz) is the
+    floats its backward needs; forward(seq, params, save, out, buf) and backward(seq, params, grads, d_out, d_keys,
+    d_query, buf) take seq = (rows, row0, D, offsets, ids, qrow) and the field's buffers buf (Engine._seq_fwd);
+    keeps_scores asks for buf["scores"], one float per occurrence."""
+    keeps_scores = True
+
+    def __init__(self, var, hp, D, name, max_len):
+        self.D, self.name, self.max_len = D, name, max_len
+        self.hidden = [int(h) for h in hp.get("att_hidden_units", (80, 40))]
+        act = hp.get("att_activation", "sigmoid")
+        act = act if isinstance(act, str) else getattr(act, "__name__", str(act))
+        self.act = act.lower()
+        if self.act == "dice":
+            raise NotImplementedError("att_activation='dice': the reference's Dice (activation.py) uses undefined "
+                                      "names and has no arithmetic to follow; use 'sigmoid' or 'relu'")
+        if self.act not in ops.ASP_ACTS:
+            raise ValueError(f"att_activation {act!r}: 'relu' or 'sigmoid'")
+        self.norm = bool(hp.get("att_weight_normalization", False))
+        if not ops.asp_supported(D, self.hidden, max_len):
+            raise ValueError(f"sequence feature {name!r}: embedding_size={D}, att_hidden_units={self.hidden}, "
+                             f"max_len={max_len} is not supported by rm_asp_fwd (embedding_size 8/16/32, "
+                             "one or two hidden layers of 1..128 units, max_len 1..256)")
+        dims = [4 * D] + self.hidden
+        for i in range(len(self.hidden)):
+            var(f"{name}_asp_layer_{i}_weights", (dims[i], dims[i + 1]), ("glorot", dims[i], dims[i + 1]))
+            var(f"{name}_asp_layer_{i}_bias", (dims[i + 1],))
+        var(f"{name}_asp_w", (dims[-1], 1), ("glorot", dims[-1], 1))
+        var(f"{name}_asp_w0", (1,))
+
+    def _vars(self, d):
+        """(Ws, bs, w, w0) out of the params or the grads dict."""
+        layers, name = range(len(self.hidden)), self.name
+        return ([d[f"{name}_asp_layer_{i}_weights"] for i in layers], [d[f"{name}_asp_layer_{i}_bias"] for i in layers],
+                d[f"{name}_asp_w"].view(-1), d[f"{name}_asp_w0"])
+
+    def workspace(self, B, nnz):
+        return ops.asp_workspace(self.D, self.hidden, nnz, True)
+
+    def forward(self, seq, params, save, out, buf):
+        ops.asp_fwd(*seq, *self._vars(params), self.act, self.norm, out, buf["scores"][: buf["nnz"]], buf["ws"])
+
+    def backward(self, seq, params, grads, d_out, d_keys, d_query, buf):
+        ops.asp_bwd(*seq, *self._vars(params), self.act, self.norm, buf["scores"][: buf["nnz"]], d_out, d_keys, d_query,
+                    *self._vars(grads), buf["ws"])
+
+
+class TransformerUnit:
+    """Kind "transformer" (the interface: DinUnit): one post-norm encoder block over the history and the candidate,
+    mean-pooled (csrc/bst.hip; Behavior Sequence Transformer, arXiv 1905.06874).  Variables {name}_bst_{wq|wk|wv|wo}
+    [D, D], {name}_bst_{bq|bk|bv|bo} [D], {name}_bst_ffn_w1 [D, Hf], _ffn_b1 [Hf], _ffn_w2 [Hf, D], _ffn_b2 [D],
+    {name}_bst_ln{1|2}_{gamma|beta} [D], {name}_bst_pos [max_len + 1, D] (absent from the reference: glorot matrices
+    and position table, zero biases, LayerNorm gains "ones"; no l2).  hp: att_head_num 2, att_ffn_units 4 D."""
+    keeps_scores = False
+
+    def __init__(self, var, hp, D, name, max_len):
+        self.D, self.name, self.max_len = D, name, max_len
+        self.heads = int(hp.get("att_head_num", 2))
+        ffn = hp.get("att_ffn_units")
+        self.ffn = int(ffn) if ffn is not None else 4 * D
+        if not ops.bst_supported(D, self.heads, self.ffn, max_len):
+            raise ValueError(f"sequence feature {name!r}: embedding_size={D}, att_head_num={self.heads}, "
+                             f"att_ffn_units={self.ffn}, max_len={max_len} is not supported by rm_bst_fwd "
+                             f"({ops.BST_LIMITS})")
+        for v, shape in ops.bst_param_shapes(D, self.ffn, max_len).items():
+            if len(shape) == 2:
+                init = ("glorot", shape[0], shape[1])
+            else:
+                init = "ones" if v.endswith("_gamma") else "zeros"
+            var(f"{name}_bst_{v}", shape, init)
+
+    def _vars(self, d):
+        """{member: tensor} out of the params or the grads dict."""
+        return {v: d[f"{self.name}_bst_{v}"] for v in ops.BST_PARAM_NAMES}
+
+    def workspace(self, B, nnz):
+        return ops.bst_workspace(self.D, self.heads, self.ffn, self.max_len, B, True)
+
+    def forward(self, seq, params, save, out, buf):
+        ops.bst_fwd(*seq, self._vars(params), self.heads, self.max_len, out, buf["ws"])
+
+    def backward(self, seq, params, grads, d_out, d_keys, d_query, buf):
+        ops.bst_bwd(*seq, self._vars(params), self.heads, self.max_len, d_out, d_keys, d_query, self._vars(grads),
+                    buf["ws"])
+
+
+class DienUnit:
+    """Kind "dien" (the interface: DinUnit): a GRU over the history, the candidate's attention over its states and an
+    attention-gated GRU whose last state is the row (csrc/dien.hip; Deep Interest Evolution Network, arXiv
+    1809.03672, hidden size D, no auxiliary loss).  Variables {name}_dien_{gru|augru}_{w|u} [D, 3D],
+    {name}_dien_{gru|augru}_b [3D], {name}_dien_att_w [D, D] (absent from the reference: glorot matrices, zero
+    biases; no l2).  No hyper-parameter.  Its forward keeps what the backward needs in the workspace (save)."""
+    keeps_scores = False
+
+    def __init__(self, var, hp, D, name, max_len):
+        self.D, self.name, self.max_len = D, name, max_len
+        if not ops.dien_supported(D, max_len):
+            raise ValueError(f"sequence feature {name!r}: embedding_size={D}, max_len={max_len} is not supported by "
+                             f"rm_dien_fwd ({ops.DIEN_LIMITS})")
+        for v, shape in ops.dien_param_shapes(D).items():
+            var(f"{name}_dien_{v}", shape, ("glorot", shape[0], shape[1]) if len(shape) == 2 else "zeros")
+
+    def _vars(self, d):
+        """{member: tensor} out of the params or the grads dict."""
+        return {v: d[f"{self.name}_dien_{v}"] for v in ops.DIEN_PARAM_NAMES}
+
+    def workspace(self, B, nnz):
+        return ops.dien_workspace(self.D, self.max_len, B, nnz, True)
+
+    def forward(self, seq, params, save, out, buf):
+        ops.dien_fwd(*seq, self._vars(params), self.max_len, save, out, buf["ws"])
+
+    def backward(self, seq, params, grads, d_out, d_keys, d_query, buf):
+        ops.dien_bwd(*seq, self._vars(params), self.max_len, d_out, d_keys, d_query, self._vars(grads), buf["ws"])
+
+
+SEQ_UNITS = {"din": DinUnit, "transformer": TransformerUnit, "dien": DienUnit}
+
+
 def init_reference(engine, seed=2019):
     """Initial values with the reference's distributions (TF's RNG stream itself cannot be reproduced): every
     variable of engine.params, in insertion order, by the rule it was declared with (Engine._var) - embedding
@@ -492,62 +618,22 @@ class Engine:
         return list(self.hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
 
     def _init_seq(self):
-        """The pooling unit of every sequence feature, chosen by hp["seq_pooling"]:
-        "din" (default; csrc/asp.hip, DIN's local activation unit, arXiv 1706.06978): variables
-        {name}_asp_layer_{i}_weights [4D | H_{i-1}, H_i], {name}_asp_layer_{i}_bias, {name}_asp_w [H_last, 1],
-        {name}_asp_w0 [1].  hp: att_hidden_units (80, 40), att_activation "sigmoid" (the reference's Dice,
-        activation.py, uses undefined names), att_weight_normalization False.
-        "transformer" (csrc/bst.hip, one post-norm encoder block over the history and the candidate, mean-pooled;
-        Behavior Sequence Transformer, arXiv 1905.06874): variables {name}_bst_{wq|wk|wv|wo} [D, D],
-        {name}_bst_{bq|bk|bv|bo} [D], {name}_bst_ffn_w1 [D, Hf], _ffn_b1 [Hf], _ffn_w2 [Hf, D], _ffn_b2 [D],
-        {name}_bst_ln{1|2}_{gamma|beta} [D], {name}_bst_pos [max_len + 1, D].  hp: att_head_num 2, att_ffn_units 4 D.
-        "dien" (csrc/dien.hip, a GRU over the history, the candidate's attention over its states and an
-        attention-gated GRU whose last state is the row; Deep Interest Evolution Network, arXiv 1809.03672, hidden
-        size D, no auxiliary loss): variables {name}_dien_{gru|augru}_{w|u} [D, 3D], {name}_dien_{gru|augru}_b [3D],
-        {name}_dien_att_w [D, D].  No hyper-parameter.
-        att_dropout must be all ones under all three."""
-        spec, hp, D = self.spec, self.hp, self.D
-        self._asp_saved = {}
+        """One pooling unit per sequence feature, of the kind hp["seq_pooling"] names (SEQ_UNITS; default "din").
+        att_dropout must be all ones under every kind."""
+        spec, hp = self.spec, self.hp
+        self._seq_units, self._seq_buf, self._seq_save = {}, {}, False
         self.seq_pooling = str(hp.get("seq_pooling", "din")).lower()
-        self._seq_save = False
-        if self.seq_pooling not in ("din", "transformer", "dien"):
+        if self.seq_pooling not in SEQ_UNITS:
             raise ValueError(f"seq_pooling {hp.get('seq_pooling')!r}: 'din', 'transformer' or 'dien'")
         if not spec.seq_names:
             return
         if not hasattr(self, "rows") or self.rows.dim() != 2 or self.rows.shape[0] != spec.rows:
             raise NotImplementedError("sequence features (SequenceFeat) need the whole table on one GPU: there is "
                                       "no row-sharded path for them (use table_sharding='none')")
-        if self.seq_pooling == "transformer":
-            self._check_att_dropout()
-            self._init_bst()
-            return
-        if self.seq_pooling == "dien":
-            self._check_att_dropout()
-            self._init_dien()
-            return
-        self.asp_hidden = [int(h) for h in hp.get("att_hidden_units", (80, 40))]
-        act = hp.get("att_activation", "sigmoid")
-        act = act if isinstance(act, str) else getattr(act, "__name__", str(act))
-        self.asp_act = act.lower()
-        if self.asp_act == "dice":
-            raise NotImplementedError("att_activation='dice': the reference's Dice (activation.py) uses undefined "
-                                      "names and has no arithmetic to follow; use 'sigmoid' or 'relu'")
-        if self.asp_act not in ops.ASP_ACTS:
-            raise ValueError(f"att_activation {act!r}: 'relu' or 'sigmoid'")
         self._check_att_dropout()
-        self.asp_norm = bool(hp.get("att_weight_normalization", False))
         for n in spec.seq_names:
-            if not ops.asp_supported(D, self.asp_hidden, spec.seq_max_len[n]):
-                raise ValueError(f"sequence feature {n!r}: embedding_size={D}, att_hidden_units={self.asp_hidden}, "
-                                 f"max_len={spec.seq_max_len[n]} is not supported by rm_asp_fwd (embedding_size 8/16/32, "
-                                 "one or two hidden layers of 1..128 units, max_len 1..256)")
-            # (absent from the reference, DIN.py:6: glorot weights and an output projection like dnn_w; no l2)
-            dims = [4 * D] + self.asp_hidden
-            for i in range(len(self.asp_hidden)):
-                self._var(f"{n}_asp_layer_{i}_weights", (dims[i], dims[i + 1]), ("glorot", dims[i], dims[i + 1]))
-                self._var(f"{n}_asp_layer_{i}_bias", (dims[i + 1],))
-            self._var(f"{n}_asp_w", (dims[-1], 1), ("glorot", dims[-1], 1))
-            self._var(f"{n}_asp_w0", (1,))
+            self._seq_units[spec.sparse_names.index(n)] = SEQ_UNITS[self.seq_pooling](
+                self._var, hp, self.D, n, int(spec.seq_max_len[n]))
 
     def _check_att_dropout(self):
         drop = self.hp.get("att_dropout", 1)
@@ -556,125 +642,43 @@ class Engine:
             raise NotImplementedError("att_dropout: the attention unit runs without dropout (every keep "
                                       f"probability must be 1, got {self.hp.get('att_dropout')!r})")
 
-    def _init_bst(self):
-        """The transformer unit's variables (absent from the reference: glorot matrices and position table, zero
-        biases, LayerNorm gains "ones"; no l2, as for the attention unit)."""
-        spec, hp, D = self.spec, self.hp, self.D
-        self.bst_heads = int(hp.get("att_head_num", 2))
-        ffn = hp.get("att_ffn_units")
-        self.bst_ffn = int(ffn) if ffn is not None else 4 * D
-        for n in spec.seq_names:
-            ml = int(spec.seq_max_len[n])
-            if not ops.bst_supported(D, self.bst_heads, self.bst_ffn, ml):
-                raise ValueError(f"sequence feature {n!r}: embedding_size={D}, att_head_num={self.bst_heads}, "
-                                 f"att_ffn_units={self.bst_ffn}, max_len={ml} is not supported by rm_bst_fwd "
-                                 f"({ops.BST_LIMITS})")
-            for v, shape in ops.bst_param_shapes(D, self.bst_ffn, ml).items():
-                if len(shape) == 2:
-                    init = ("glorot", shape[0], shape[1])
-                else:
-                    init = "ones" if v.endswith("_gamma") else "zeros"
-                self._var(f"{n}_bst_{v}", shape, init)
-
-    def _init_dien(self):
-        """The interest-evolution unit's variables (absent from the reference: glorot matrices, zero biases; no l2,
-        as for the other two units)."""
-        for n in self.spec.seq_names:
-            ml = int(self.spec.seq_max_len[n])
-            if not ops.dien_supported(self.D, ml):
-                raise ValueError(f"sequence feature {n!r}: embedding_size={self.D}, max_len={ml} is not supported by "
-                                 f"rm_dien_fwd ({ops.DIEN_LIMITS})")
-            for v, shape in ops.dien_param_shapes(self.D).items():
-                self._var(f"{n}_dien_{v}", shape, ("glorot", shape[0], shape[1]) if len(shape) == 2 else "zeros")
-
-    def _dien_vars(self, d, name):
-        """{member: tensor} of sequence feature `name`'s interest-evolution unit out of the params or the grads dict."""
-        return {v: d[f"{name}_dien_{v}"] for v in ops.DIEN_PARAM_NAMES}
-
-    def _bst_vars(self, d, name):
-        """{member: tensor} of sequence feature `name`'s transformer unit out of the params or the grads dict."""
-        return {v: d[f"{name}_bst_{v}"] for v in ops.BST_PARAM_NAMES}
-
-    def _asp_vars(self, d, name):
-        """(Ws, bs, w, w0) of sequence feature `name` out of the params or the grads dict."""
-        m = len(self.asp_hidden)
-        return ([d[f"{name}_asp_layer_{i}_weights"] for i in range(m)], [d[f"{name}_asp_layer_{i}_bias"] for i in range(m)],
-                d[f"{name}_asp_w"].view(-1), d[f"{name}_asp_w0"])
-
-    def _asp_fwd(self, j, f, idx):
-        """Sequence field f (scratch block j): the attention-pooled history rows into the scratch rows."""
-        name = self.spec.sparse_names[f]
+    def _seq_fwd(self, j, f, idx):
+        """Sequence field f (scratch block j): its unit pools the history rows into the scratch rows.  The field's
+        buffers - key gradients (and scores, if the unit keeps them) per occurrence, the unit's workspace - grow when
+        a batch has more occurrences or needs more workspace than any before; the CSR is kept for _seq_bwd."""
+        unit = self._seq_units[f]
         offsets, ids, _ = self._mv_entry(f)
-        fq = self.spec.sparse_names.index(self.spec.seq_query[name])
+        fq = self.spec.sparse_names.index(self.spec.seq_query[unit.name])
         row0 = int(self.field_off_host[fq])
-        qrow = idx[:, fq] + row0
-        nnz = int(ids.shape[0])
-        buf = self._asp_saved.get(f)
-        if self.seq_pooling == "transformer":
-            B, ml = int(idx.shape[0]), int(self.spec.seq_max_len[name])
-            need = ops.bst_workspace(self.D, self.bst_heads, self.bst_ffn, ml, B, True)
-            if buf is None or buf["cap"] < nnz or buf["ws"].numel() < need:
-                cap = max(nnz, 1)
-                buf = dict(cap=cap, d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
-                           ws=torch.empty(max(4, need), dtype=F32, device=self.device))
-                self._asp_saved[f] = buf
-            buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq, max_len=ml)
-            ops.bst_fwd(self.rows, row0, self.D, offsets, ids, qrow, self._bst_vars(self.params, name), self.bst_heads,
-                        ml, self.mv_scratch[j], buf["ws"])
-            return
-        if self.seq_pooling == "dien":
-            B, ml = int(idx.shape[0]), int(self.spec.seq_max_len[name])
-            if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.dien_workspace(self.D, ml, B, nnz, True):
-                cap = max(nnz, 1)
-                buf = dict(cap=cap, d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
-                           ws=torch.empty(max(4, ops.dien_workspace(self.D, ml, B, cap, True)), dtype=F32,
-                                          device=self.device))
-                self._asp_saved[f] = buf
-            buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq, max_len=ml)
-            ops.dien_fwd(self.rows, row0, self.D, offsets, ids, qrow, self._dien_vars(self.params, name), ml,
-                         self._seq_save, self.mv_scratch[j], buf["ws"])
-            return
-        if buf is None or buf["cap"] < nnz or buf["ws"].numel() < ops.asp_workspace(self.D, self.asp_hidden, nnz, True):
+        B, nnz = int(idx.shape[0]), int(ids.shape[0])
+        buf = self._seq_buf.get(f)
+        if buf is None or buf["cap"] < nnz or buf["ws"].numel() < unit.workspace(B, nnz):
             cap = max(nnz, 1)
-            buf = dict(cap=cap, scores=torch.empty(cap, dtype=F32, device=self.device),
-                       d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
-                       ws=torch.empty(max(4, ops.asp_workspace(self.D, self.asp_hidden, cap, True)), dtype=F32,
-                                      device=self.device))
-            self._asp_saved[f] = buf
-        buf.update(offsets=offsets, ids=ids, qrow=qrow, nnz=nnz, row0=row0, fq=fq)
-        ops.asp_fwd(self.rows, row0, self.D, offsets, ids, qrow, *self._asp_vars(self.params, name), self.asp_act,
-                    self.asp_norm, self.mv_scratch[j], buf["scores"][:nnz], buf["ws"])
+            buf = dict(cap=cap, d_keys=torch.empty(cap, self.D, dtype=F32, device=self.device),
+                       ws=torch.empty(max(4, unit.workspace(B, cap)), dtype=F32, device=self.device))
+            if unit.keeps_scores:
+                buf["scores"] = torch.empty(cap, dtype=F32, device=self.device)
+            self._seq_buf[f] = buf
+        buf.update(csr=(offsets, ids, idx[:, fq] + row0), nnz=nnz, row0=row0, fq=fq)
+        unit.forward((self.rows, row0, self.D, *buf["csr"]), self.params, self._seq_save, self.mv_scratch[j], buf)
 
     def _seq_bwd(self):
-        """After the model's backward filled d_rows: every sequence field's pooled-row gradient goes through the
-        attention unit - key gradients per history occurrence (kept for dense_grads / the row-wise optimizer), the
-        query gradient ADDED onto the query field's rows of d_rows, the unit's parameter gradients."""
+        """After the model's backward filled d_rows: every sequence field's pooled-row gradient goes through its
+        unit - key gradients per history occurrence (kept for dense_grads / the row-wise optimizer), the query
+        gradient ADDED onto the query field's rows of d_rows, the unit's parameter gradients."""
         for f in self.mv_fields:
-            name = self.spec.sparse_names[f]
-            if name not in self.spec.seq_query:
+            unit = self._seq_units.get(f)
+            if unit is None:
                 continue
-            b = self._asp_saved[f]
-            nnz = b["nnz"]
-            if self.seq_pooling == "transformer":
-                ops.bst_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
-                            self._bst_vars(self.params, name), self.bst_heads, b["max_len"], self.d_rows[:, f, :],
-                            b["d_keys"][:nnz], self.d_rows[:, b["fq"], :], self._bst_vars(self.grads, name), b["ws"])
-                continue
-            if self.seq_pooling == "dien":
-                ops.dien_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
-                             self._dien_vars(self.params, name), b["max_len"], self.d_rows[:, f, :],
-                             b["d_keys"][:nnz], self.d_rows[:, b["fq"], :], self._dien_vars(self.grads, name), b["ws"])
-                continue
-            ops.asp_bwd(self.rows, b["row0"], self.D, b["offsets"], b["ids"], b["qrow"],
-                        *self._asp_vars(self.params, name), self.asp_act, self.asp_norm, b["scores"][:nnz],
-                        self.d_rows[:, f, :], b["d_keys"][:nnz], self.d_rows[:, b["fq"], :],
-                        *self._asp_vars(self.grads, name), b["ws"])
+            b = self._seq_buf[f]
+            unit.backward((self.rows, b["row0"], self.D, *b["csr"]), self.params, self.grads, self.d_rows[:, f, :],
+                          b["d_keys"][: b["nnz"]], self.d_rows[:, b["fq"], :], b)
 
     def seq_key_grads(self, f):
         """(field of the query feature, history ids [nnz], their gradient rows [nnz, D]) of sequence field f after
         the last fwd_bwd."""
-        b = self._asp_saved[f]
-        return b["fq"], b["ids"], b["d_keys"][: b["nnz"]]
+        b = self._seq_buf[f]
+        return b["fq"], b["csr"][1], b["d_keys"][: b["nnz"]]
 
     def _alloc_tables(self):
         """HBM layout: ONE table of fused rows [R, LD], LD = 2*D floats (a power of two, so a
@@ -840,7 +844,7 @@ class Engine:
             self.idx_mv.copy_(idx)
             for j, f in enumerate(self.mv_fields):
                 if self.spec.sparse_names[f] in self.spec.seq_query:
-                    self._asp_fwd(j, f, idx)
+                    self._seq_fwd(j, f, idx)
                     self.idx_mv[:, f] = self._arange
                     continue
                 offsets, ids, vals = self._mv_entry(f)
@@ -2009,7 +2013,7 @@ class AFMEngine(Engine):
 
 class DINEngine(DeepFMEngine):
     """DIN._init_graph (DIN.py, which stops after the pooling layer): final = linear + DNN([E | dense]), where E holds
-    the plain features' rows and ONE attention-pooled interest row per sequence feature (Engine._asp_fwd; Deep
+    the plain features' rows and ONE attention-pooled interest row per sequence feature (Engine._seq_fwd; Deep
     Interest Network, arXiv 1706.06978) - the DeepFM engine without its FM term and without bias tables."""
 
     model = "din"

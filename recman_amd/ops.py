@@ -871,11 +871,42 @@ def _asp_params(D, Ws, bs, w, w0):
     return hidden, ptr
 
 
-def _asp_csr(rows, offsets, ids, qrow):
-    B = offsets.shape[0] - 1
+def _seq_args(rows, row0, D, offsets, ids, qrow):
+    """The arguments every sequence unit's entry points begin with: the fused table, the history's CSR and the query
+    rows -> (B, nnz, LD, [rows, LD, D, row0, offsets, ids, qrow, B, nnz] for the call)."""
+    if rows.dim() != 2:
+        raise ValueError(f"rows: expected [R, LD], got {tuple(rows.shape)}")
+    B, nnz, LD = offsets.shape[0] - 1, int(ids.shape[0]), int(rows.shape[1])
     _chk_csr(offsets, ids, None)
-    return B, int(ids.shape[0]), (_chk(rows, "rows", F32), _chk(offsets, "offsets", I64), _chk(ids, "ids", I64),
-                                  _chk(qrow, "qrow", I64, (B,)))
+    return B, nnz, LD, [_chk(rows, "rows", F32), LD, int(D), int(row0), _chk(offsets, "offsets", I64),
+                        _chk(ids, "ids", I64), _chk(qrow, "qrow", I64, (B,)), B, nnz]
+
+
+def _seq_workspace(fn, workspace, need, aligned=False):
+    """A sequence unit's workspace of `need` floats (0: an unsupported shape, which the library names) -> pointer."""
+    if need:
+        _need_workspace(fn, workspace, need)
+    if aligned and workspace.data_ptr() % 16:
+        raise ValueError(f"{fn}: workspace must be 16-byte aligned")
+    return _chk(workspace, "workspace", F32)
+
+
+def _seq_grad_views(fn, B, D, d_out, d_query):
+    """The two [B, D] gradient views of a sequence unit's backward (column ranges of a wider buffer) -> [d_out's
+    pointer, its row stride, d_query's pointer, its row stride]; a single row has no stride to speak of."""
+    ptrs = []
+    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
+        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
+            raise ValueError(f"{fn}: {name} must be a float32 [B, D] GPU view with unit stride along D")
+        ptrs += [t.data_ptr(), t.stride(0) if B > 1 else max(D, t.stride(0))]
+    return ptrs
+
+
+def _param_struct(struct_cls, names, shapes, params, what, unit):
+    """{name: tensor} over exactly `names`, each of its shape in `shapes` -> the C struct of their pointers."""
+    if set(params) != set(names):
+        raise ValueError(f"{unit}: {what} must hold exactly {names}, got {sorted(params)}")
+    return struct_cls(*[_chk(params[n], f"{what}[{n!r}]", F32, shapes[n]) for n in names])
 
 
 def asp_fwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, out, scores, workspace):
@@ -883,15 +914,11 @@ def asp_fwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, out, sc
     example's query row qrow [B] (absolute); Ws = [W0 [4D,H0]] or [W0, W1 [H0,H1]], bs alike, w [H_last], w0 [1];
     act "relu" | "sigmoid"; norm: softmax over the example's positions.  -> out [B, LD] (pooled row in columns
     0..D-1, zeros behind) and scores [nnz] (all the backward keeps).  ids.shape[0] must equal offsets[-1]."""
-    LD = rows.shape[1]
-    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    B, nnz, LD, seq = _seq_args(rows, row0, D, offsets, ids, qrow)
     hidden, pp = _asp_params(D, Ws, bs, w, w0)
-    need = asp_workspace(D, hidden, nnz, False)
-    if need and workspace.numel() < need:
-        raise ValueError(f"asp_fwd: workspace has {workspace.numel()} floats, needs {need}")
-    _lib.call("rm_asp_fwd", rp, LD, int(D), int(row0), op, ip, qp, B, nnz, *pp, len(hidden), _int_array(hidden),
-              ASP_ACTS[act], 1 if norm else 0, _chk(out, "out", F32, (B, LD)),
-              _chk(scores, "scores", F32, (nnz,)), _chk(workspace, "workspace", F32), _stream())
+    ws = _seq_workspace("asp_fwd", workspace, asp_workspace(D, hidden, nnz, False))
+    _lib.call("rm_asp_fwd", *seq, *pp, len(hidden), _int_array(hidden), ASP_ACTS[act], 1 if norm else 0,
+              _chk(out, "out", F32, (B, LD)), _chk(scores, "scores", F32, (nnz,)), ws, _stream())
 
 
 def asp_bwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, scores, d_out, d_keys, d_query, dWs, dbs, dw,
@@ -899,20 +926,14 @@ def asp_bwd(rows, row0, D, offsets, ids, qrow, Ws, bs, w, w0, act, norm, scores,
     """rm_asp_bwd: d_out [B, D] view (row stride may be larger) = the pooled rows' gradient -> d_keys [nnz, D]
     overwritten; the query gradient ADDED onto d_query [B, D] (a view, row stride may be larger); dWs, dbs, dw, dw0
     overwritten.  Deterministic."""
-    LD = rows.shape[1]
-    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
+    B, nnz, _, seq = _seq_args(rows, row0, D, offsets, ids, qrow)
     hidden, pp = _asp_params(D, Ws, bs, w, w0)
     _, gp = _asp_params(D, dWs, dbs, dw, dw0)
-    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
-        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
-            raise ValueError(f"asp_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
-    need = asp_workspace(D, hidden, nnz, True)
-    if need and workspace.numel() < need:
-        raise ValueError(f"asp_bwd: workspace has {workspace.numel()} floats, needs {need}")
-    _lib.call("rm_asp_bwd", rp, LD, int(D), int(row0), op, ip, qp, B, nnz, *pp, len(hidden), _int_array(hidden),
-              ASP_ACTS[act], 1 if norm else 0, _chk(scores, "scores", F32, (nnz,)),
-              d_out.data_ptr(), d_out.stride(0), _chk(d_keys, "d_keys", F32, (nnz, D)),
-              d_query.data_ptr(), d_query.stride(0), *gp, _chk(workspace, "workspace", F32), _stream())
+    do, do_ld, dq, dq_ld = _seq_grad_views("asp_bwd", B, D, d_out, d_query)
+    ws = _seq_workspace("asp_bwd", workspace, asp_workspace(D, hidden, nnz, True), aligned=True)
+    _lib.call("rm_asp_bwd", *seq, *pp, len(hidden), _int_array(hidden), ASP_ACTS[act], 1 if norm else 0,
+              _chk(scores, "scores", F32, (nnz,)), do, do_ld, _chk(d_keys, "d_keys", F32, (nnz, D)), dq, dq_ld, *gp, ws,
+              _stream())
 
 
 BST_PARAM_NAMES = _lib.BST_PARAM_NAMES
@@ -942,22 +963,17 @@ def bst_param_shapes(D, Hf, max_len):
 
 
 def _bst_struct(params, what, D, Hf, max_len):
-    shapes = bst_param_shapes(D, Hf, max_len)
-    if set(params) != set(shapes):
-        raise ValueError(f"bst: {what} must hold exactly {BST_PARAM_NAMES}, got {sorted(params)}")
-    return _lib.BstParams(*[_chk(params[n], f"{what}[{n!r}]", F32, shapes[n]) for n in BST_PARAM_NAMES])
+    return _param_struct(_lib.BstParams, BST_PARAM_NAMES, bst_param_shapes(D, Hf, max_len), params, what, "bst")
 
 
-def _bst_args(rows, D, offsets, ids, qrow, params, max_len):
+def _bst_args(rows, row0, D, offsets, ids, qrow, params, heads, max_len):
+    """-> (B, nnz, LD, Hf, the call's arguments up to max_len)."""
     if "ffn_w1" not in params or params["ffn_w1"].dim() != 2:
         raise ValueError("bst: params['ffn_w1'] must be a [D, Hf] matrix")
-    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
-    if rows.dim() != 2:
-        raise ValueError(f"rows: expected [R, LD], got {tuple(rows.shape)}")
-    D, max_len = int(D), int(max_len)
     Hf = int(params["ffn_w1"].shape[1])
-    ps = _bst_struct(params, "params", D, Hf, max_len)
-    return B, nnz, Hf, (rp, int(rows.shape[1]), D), (op, ip, qp, B, nnz), ps
+    ps = _bst_struct(params, "params", int(D), Hf, int(max_len))
+    B, nnz, LD, seq = _seq_args(rows, row0, D, offsets, ids, qrow)
+    return B, nnz, LD, Hf, seq + [ctypes.byref(ps), int(heads), Hf, int(max_len)]
 
 
 def bst_fwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, out, workspace):
@@ -965,33 +981,21 @@ def bst_fwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, out, work
     first), the example's query row qrow [B] (absolute); params: {name: tensor} over BST_PARAM_NAMES (shapes:
     bst_param_shapes).  -> out [B, LD]: the mean of the encoder block's T = n + 1 output rows in columns 0..D-1, zeros
     behind.  Nothing is saved for the backward; inference is the same call.  ids.shape[0] must equal offsets[-1]."""
-    B, nnz, Hf, (rp, LD, D), csr, ps = _bst_args(rows, D, offsets, ids, qrow, params, max_len)
-    need = bst_workspace(D, heads, Hf, max_len, B, False)
-    if need:
-        _need_workspace("bst_fwd", workspace, need)
-    _lib.call("rm_bst_fwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(heads), Hf, int(max_len),
-              _chk(out, "out", F32, (B, LD)), _chk(workspace, "workspace", F32), _stream())
+    B, nnz, LD, Hf, args = _bst_args(rows, row0, D, offsets, ids, qrow, params, heads, max_len)
+    ws = _seq_workspace("bst_fwd", workspace, bst_workspace(D, heads, Hf, max_len, B, False))
+    _lib.call("rm_bst_fwd", *args, _chk(out, "out", F32, (B, LD)), ws, _stream())
 
 
 def bst_bwd(rows, row0, D, offsets, ids, qrow, params, heads, max_len, d_out, d_keys, d_query, grads, workspace):
     """rm_bst_bwd: d_out [B, D] view (row stride may be larger) = the pooled rows' gradient -> d_keys [nnz, D]
     overwritten; the candidate's gradient ADDED onto d_query [B, D] (a view, row stride may be larger; it may be other
     columns of d_out's buffer); grads: {name: tensor} over BST_PARAM_NAMES, all overwritten.  Deterministic."""
-    B, nnz, Hf, (rp, LD, D), csr, ps = _bst_args(rows, D, offsets, ids, qrow, params, max_len)
-    gs = _bst_struct(grads, "grads", D, Hf, int(max_len))
-    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
-        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
-            raise ValueError(f"bst_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
-    need = bst_workspace(D, heads, Hf, max_len, B, True)
-    if need:
-        _need_workspace("bst_bwd", workspace, need)
-    if workspace.data_ptr() % 16:
-        raise ValueError("bst_bwd: workspace must be 16-byte aligned")
-    _lib.call("rm_bst_bwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(heads), Hf, int(max_len),
-              d_out.data_ptr(), d_out.stride(0) if B > 1 else max(D, d_out.stride(0)),
-              _chk(d_keys, "d_keys", F32, (nnz, D)), d_query.data_ptr(),
-              d_query.stride(0) if B > 1 else max(D, d_query.stride(0)), ctypes.byref(gs),
-              _chk(workspace, "workspace", F32), _stream())
+    B, nnz, _, Hf, args = _bst_args(rows, row0, D, offsets, ids, qrow, params, heads, max_len)
+    gs = _bst_struct(grads, "grads", int(D), Hf, int(max_len))
+    do, do_ld, dq, dq_ld = _seq_grad_views("bst_bwd", B, D, d_out, d_query)
+    ws = _seq_workspace("bst_bwd", workspace, bst_workspace(D, heads, Hf, max_len, B, True), aligned=True)
+    _lib.call("rm_bst_bwd", *args, do, do_ld, _chk(d_keys, "d_keys", F32, (nnz, D)), dq, dq_ld, ctypes.byref(gs), ws,
+              _stream())
 
 
 DIEN_PARAM_NAMES = _lib.DIEN_PARAM_NAMES
@@ -1017,21 +1021,14 @@ def dien_param_shapes(D):
 
 
 def _dien_struct(params, what, D):
-    shapes = dien_param_shapes(D)
-    if set(params) != set(shapes):
-        raise ValueError(f"dien: {what} must hold exactly {DIEN_PARAM_NAMES}, got {sorted(params)}")
-    return _lib.DienParams(*[_chk(params[n], f"{what}[{n!r}]", F32, shapes[n]) for n in DIEN_PARAM_NAMES])
+    return _param_struct(_lib.DienParams, DIEN_PARAM_NAMES, dien_param_shapes(int(D)), params, what, "dien")
 
 
-def _dien_args(rows, D, offsets, ids, qrow, params):
-    if set(params) != set(DIEN_PARAM_NAMES):
-        raise ValueError(f"dien: params must hold exactly {DIEN_PARAM_NAMES}, got {sorted(params)}")
-    B, nnz, (rp, op, ip, qp) = _asp_csr(rows, offsets, ids, qrow)
-    if rows.dim() != 2:
-        raise ValueError(f"rows: expected [R, LD], got {tuple(rows.shape)}")
-    D = int(D)
+def _dien_args(rows, row0, D, offsets, ids, qrow, params, max_len):
+    """-> (B, nnz, LD, the call's arguments up to max_len)."""
     ps = _dien_struct(params, "params", D)
-    return B, nnz, (rp, int(rows.shape[1]), D), (op, ip, qp, B, nnz), ps
+    B, nnz, LD, seq = _seq_args(rows, row0, D, offsets, ids, qrow)
+    return B, nnz, LD, seq + [ctypes.byref(ps), int(max_len)]
 
 
 def dien_fwd(rows, row0, D, offsets, ids, qrow, params, max_len, save, out, workspace):
@@ -1040,12 +1037,9 @@ def dien_fwd(rows, row0, D, offsets, ids, qrow, params, max_len, save, out, work
     (shapes: dien_param_shapes).  -> out [B, LD]: the AUGRU's last state in columns 0..D-1, zeros behind (no history:
     a zero row).  save: keep what dien_bwd needs in the workspace (dien_workspace(.., backward=save) floats); `out` has
     the same bits either way.  ids.shape[0] must equal offsets[-1]."""
-    B, nnz, (rp, LD, D), csr, ps = _dien_args(rows, D, offsets, ids, qrow, params)
-    need = dien_workspace(D, max_len, B, nnz, bool(save))
-    if need:
-        _need_workspace("dien_fwd", workspace, need)
-    _lib.call("rm_dien_fwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(max_len), 1 if save else 0,
-              _chk(out, "out", F32, (B, LD)), _chk(workspace, "workspace", F32), _stream())
+    B, nnz, LD, args = _dien_args(rows, row0, D, offsets, ids, qrow, params, max_len)
+    ws = _seq_workspace("dien_fwd", workspace, dien_workspace(D, max_len, B, nnz, bool(save)))
+    _lib.call("rm_dien_fwd", *args, 1 if save else 0, _chk(out, "out", F32, (B, LD)), ws, _stream())
 
 
 def dien_bwd(rows, row0, D, offsets, ids, qrow, params, max_len, d_out, d_keys, d_query, grads, workspace):
@@ -1053,21 +1047,12 @@ def dien_bwd(rows, row0, D, offsets, ids, qrow, params, max_len, d_out, d_keys, 
     larger) = the pooled rows' gradient -> d_keys [nnz, D] overwritten; the query gradient ADDED onto d_query [B, D]
     (a view, row stride may be larger; it may be other columns of d_out's buffer); grads: {name: tensor} over
     DIEN_PARAM_NAMES, all overwritten.  Deterministic."""
-    B, nnz, (rp, LD, D), csr, ps = _dien_args(rows, D, offsets, ids, qrow, params)
+    B, nnz, _, args = _dien_args(rows, row0, D, offsets, ids, qrow, params, max_len)
     gs = _dien_struct(grads, "grads", D)
-    for t, name in ((d_out, "d_out"), (d_query, "d_query")):
-        if not t.is_cuda or t.dtype != F32 or tuple(t.shape) != (B, D) or (D > 1 and t.stride(1) != 1):
-            raise ValueError(f"dien_bwd: {name} must be a float32 [B, D] GPU view with unit stride along D")
-    need = dien_workspace(D, max_len, B, nnz, True)
-    if need:
-        _need_workspace("dien_bwd", workspace, need)
-    if workspace.data_ptr() % 16:
-        raise ValueError("dien_bwd: workspace must be 16-byte aligned")
-    _lib.call("rm_dien_bwd", rp, LD, D, int(row0), *csr, ctypes.byref(ps), int(max_len),
-              d_out.data_ptr(), d_out.stride(0) if B > 1 else max(D, d_out.stride(0)),
-              _chk(d_keys, "d_keys", F32, (nnz, D)), d_query.data_ptr(),
-              d_query.stride(0) if B > 1 else max(D, d_query.stride(0)), ctypes.byref(gs),
-              _chk(workspace, "workspace", F32), _stream())
+    do, do_ld, dq, dq_ld = _seq_grad_views("dien_bwd", B, D, d_out, d_query)
+    ws = _seq_workspace("dien_bwd", workspace, dien_workspace(D, max_len, B, nnz, True), aligned=True)
+    _lib.call("rm_dien_bwd", *args, do, do_ld, _chk(d_keys, "d_keys", F32, (nnz, D)), dq, dq_ld, ctypes.byref(gs), ws,
+              _stream())
 
 
 def gather_rows(table, rows, out):
