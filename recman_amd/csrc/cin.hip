@@ -216,6 +216,7 @@ __global__ __launch_bounds__(512 / MT) void cin_fwd_kernel(
   const int nchunks = Kp / 32;
   const bool aligned = !sym && (He & 31) == 0;  // block-uniform
   int i_cur = 0, j_cur = 0;  // (i, even j) of the running k' pair: wave-uniform
+  const int m_sym = sym ? m : 0;  // the fields whose row of the ordering starts at j = (i & ~1), not at 0
   static_assert(PF <= 2, "the filter prefetch below is written out for at most 2 float4 per thread");
   const int pfi0 = tid < NT * 256 ? tid : NT * 256 - 1;                     // clamped: loads are
   const int pfi1 = tid + NTHR < NT * 256 ? tid + NTHR : NT * 256 - 1;       // always in bounds
@@ -261,7 +262,10 @@ __global__ __launch_bounds__(512 / MT) void cin_fwd_kernel(
         wv[0] = wp[0];
       }
       j_cur += 2;  // (i, j) of the NEXT read
-      if (j_cur >= He) { ++i_cur; j_cur = sym ? (i_cur & ~1) : 0; }
+      // (past the last pair - the k' that pad K' to a multiple of 32 - x0 is the zero row and j restarts at 0
+      // in BOTH orderings: (i_cur & ~1) would walk rows past the Xk tile, and 0 x stale LDS is NaN, not 0,
+      // where an earlier kernel left a non-finite value there)
+      if (j_cur >= He) { ++i_cur; j_cur = i_cur < m_sym ? (i_cur & ~1) : 0; }
     };
     static_assert(MT == 1, "the pipelined step loop is written for one M-tile per wave");
     if (aligned) {

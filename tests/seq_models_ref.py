@@ -1,0 +1,557 @@
+"""CPU PyTorch restatement (dtype-generic, autograd) of ANY model over ANY front: every engine of
+recman_amd.engine.ENGINES with sequence features (SequenceFeat) of any pooling kind (SEQ_UNITS: "din", "transformer",
+"dien") next to plain, multi-valued and value features.
+
+TEST INFRASTRUCTURE.  Nothing is restated here: the embedding front is put together from the three pooling units
+(tests/asp_ref.py, tests/bst_ref.py, tests/dien_ref.py) and oracle.th_layers.feat_embedding_layer, the models from the
+public pieces of their own restatements that take E [B, F, D].  A sequence feature owns no rows, no bias-table entry and
+no linear entry: the linear term, the bias tables and the embedding l2 see spec.tl and idx[:, spec.plain_cols], as in
+tests/asp_ref.py.  tests/test_seq_models_host.py pins this file without a GPU - bit for bit against the restatements
+that are already pinned; tests/test_gpu_seq_models.py compares the engines against it in float64.
+
+The model names are the keys of ENGINES; the variants of one engine are told apart by hp (cross_type, block_order).
+MODELS maps the ids of the GPU cases to their engine."""
+import torch
+
+from oracle import th_layers as TL
+from tests import (afm_ref, asp_ref, autoint_ref, bst_ref, crossmix_ref, dien_ref, dlrm_ref, fibinet_ref, fmfm_ref,
+                   masknet_ref, pnn_ref)
+from tests.asp_ref import SeqSpec, _rnd, grad_measure, make_lengths  # noqa: F401
+from tests.cases import make_case as base_case
+
+KINK = 1e-6   # a ReLU unit whose float64 pre-activation is this close to 0 may flip in fp32; no example is left out
+TOL = 2e-5    # the project's gradient measure (tests/test_gpu_parity.py:_close_grad)
+KINDS = ("din", "transformer", "dien")
+UNIT_TAG = {"din": "asp", "transformer": "bst", "dien": "dien"}
+# the models whose restatement is the DeepFM composition without FM term and bias tables (tests/asp_ref.py)
+SEQ_MODELS = ("din", "bst", "dien")
+# id of a GPU case -> engine (key of ENGINES)
+MODELS = {"deepfm": "deepfm", "xdeepfm": "xdeepfm", "afm": "afm", "dcn": "dcn", "dcn_matrix": "dcn", "dcn_mix": "dcn",
+          "autoint": "autoint", "dlrm": "dlrm", "fibinet": "fibinet", "fmfm": "fmfm", "pnn": "pnn",
+          "masknet_parallel": "masknet", "masknet_serial": "masknet"}
+WRONG = ("no_query_grad", "no_key_grad", "row_grad_of_next_field", "query_grad_overwrites")
+
+
+class Spec(SeqSpec):
+    """SeqSpec with multi-valued and value features: spec.tl carries them, so that oracle.th_layers pools them and
+    orders linear_w as the reference does (sparse, value, multi-valued, dense)."""
+
+    def __init__(self, sparse_names, feat_sizes, dense_names, seq_query, seq_max_len=None, multi_names=(),
+                 value_names=()):
+        super().__init__(sparse_names, feat_sizes, dense_names, seq_query, seq_max_len)
+        self.multi_names, self.value_names = list(multi_names), list(value_names)
+        self.tl = TL.Spec(self.tl.sparse_names, self.tl.feat_sizes, self.dense_names, self.multi_names,
+                          self.value_names)
+
+
+def _kind(hp):
+    return str(hp.get("seq_pooling", "din")).lower()
+
+
+def unit_row(kind, p, name, Q, K, offsets, hp, k_probe=None):
+    """One sequence feature's pooled rows [B, D] by the unit's own restatement."""
+    if kind == "din":
+        m = len(hp.get("att_hidden_units", (80, 40)))
+        return asp_ref.asp_layer(Q, K, offsets, *asp_ref.asp_vars(p, f"{name}_", m),
+                                 hp.get("att_activation", "sigmoid"), hp.get("att_weight_normalization", False))
+    if kind == "transformer":
+        return bst_ref.bst_layer(Q, K, offsets, bst_ref.bst_vars(p, f"{name}_"), hp.get("att_head_num", 2), k_probe)
+    if kind == "dien":
+        return dien_ref.dien_layer(Q, K, offsets, dien_ref.dien_vars(p, f"{name}_"))
+    raise ValueError(kind)
+
+
+def embeddings(p, spec, idx, mv, hp, wrong=None, k_probe=None):
+    """E [B, F, D], field by field: a plain feature's table row, a multi-valued / value feature's row of
+    oracle.th_layers.feat_embedding_layer, a sequence feature's pooled history (the query feature's table; the kind is
+    hp["seq_pooling"]).  k_probe {sequence name: [B, max_len + 1, D] zeros}: added to the projected keys of the
+    transformer unit (tests/bst_ref.py:bst_block).  wrong: one of WRONG."""
+    kind, tl = _kind(hp), spec.tl
+    special = set(tl.multi_names) | set(tl.value_names)
+    pooled = TL.feat_embedding_layer(p, tl, idx[:, spec.plain_cols], use_bias=False, mv=mv)[0] if special else None
+    cols, seq_fields = [], []
+    for f, n in enumerate(spec.sparse_names):
+        if n in spec.seq_query:
+            qn = spec.seq_query[n]
+            T = p[f"{qn}_feat_embed"]
+            offsets, ids = mv[n]
+            Q, K = T[idx[:, spec.sparse_names.index(qn)]], T[ids]
+            if wrong == "no_query_grad":
+                Q = Q.detach()
+            if wrong == "no_key_grad":
+                K = K.detach()
+            cols.append(unit_row(kind, p, n, Q, K, offsets, hp, (k_probe or {}).get(n)))
+            seq_fields.append((f, spec.sparse_names.index(qn)))
+        elif n in special:
+            cols.append(pooled[:, tl.sparse_names.index(n)])
+        else:
+            cols.append(p[f"{n}_feat_embed"][idx[:, f]])
+    E = torch.stack(cols, dim=1)
+    if wrong in ("row_grad_of_next_field", "query_grad_overwrites") and E.requires_grad:
+        F = E.shape[1]
+
+        def hook(g):
+            g2 = g.clone()
+            for f, fq in seq_fields:
+                if wrong == "row_grad_of_next_field":
+                    g2[:, f] = g[:, (f + 1) % F]   # the pooled row's gradient read from the wrong column of d_rows
+                else:
+                    g2[:, fq] = 0                  # the unit's query gradient stored over the field's own, not added
+            return g2
+
+        E.register_hook(hook)
+    return E
+
+
+def _keep(hp, n, training):
+    keep = hp.get("deep_dropout") or [1] * (n + 1)
+    return list(keep) if training else [1] * (n + 1)
+
+
+def _dnn(p, x, hp, training, masks, default="relu"):
+    n = len(hp["deep_hidden_units"])
+    return TL.dnn(p, x, n, hp.get("deep_activation", default), _keep(hp, n, training), (masks or {}).get("dnn"))
+
+
+def _dnn_pres(p, x, hp, out):
+    act = TL.act_fn(hp.get("deep_activation", "relu"))
+    for i in range(len(hp.get("deep_hidden_units") or ())):
+        out.append(x @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
+        x = act(out[-1])
+
+
+def logit(model, p, spec, idx, dense, hp, mv=None, training=True, masks=None, wrong=None, k_probe=None, pres=None):
+    """The model's logit [B, 1] over embeddings(): each branch is the public piece of the model's own restatement, and
+    the branches are added in that restatement's order (so that a spec without a sequence feature gives the bits of the
+    model's own *_logit).  pres: a list that receives every pre-activation with a kink (ReLU / leaky ReLU units)."""
+    masks = masks or {}
+    E = embeddings(p, spec, idx, mv, hp, wrong, k_probe)
+    tl, pidx = spec.tl, idx[:, spec.plain_cols]
+    lin = lambda: TL.linear_layer(p, tl, pidx, dense, None, mv)  # noqa: E731
+    xe = TL.dnn_input(E, dense)
+    n = len(hp.get("deep_hidden_units") or ())
+    collect = pres is not None
+    if model in SEQ_MODELS or model == "deepfm":
+        out = lin()
+        if model == "deepfm" and hp.get("use_fm", True):
+            bias = TL.feat_embedding_layer(p, tl, pidx, use_bias=True, mv=mv)[1]
+            keep = hp.get("fm_dropout", (1, 1)) if training else (1, 1)
+            out = out + TL.fm_layer(E, bias, keep, masks.get("fm", (None, None)))
+        if hp.get("use_deep", True):
+            out = out + _dnn(p, xe, hp, training, masks)
+            if collect:
+                _dnn_pres(p, xe, hp, pres)
+        return out
+    if model == "xdeepfm":
+        nc = len(hp["cin_cross_layer_units"])
+        keep = hp.get("cin_dropout", [1] * (nc + 1)) if training else [1] * (nc + 1)
+        out = lin() + TL.cin(p, E, nc, hp.get("cin_activation", "leaky_relu"), keep, masks.get("cin"))
+        if collect:
+            # a leaky ReLU unit's output is its pre-activation or 0.2 of it: no closer to 0 than KINK means the same
+            # of the pre-activation
+            pres += TL.cin(p, E, nc, hp.get("cin_activation", "leaky_relu"), return_maps=True)[2]
+            _dnn_pres(p, xe, dict(hp, deep_activation=hp.get("deep_activation", "leaky_relu")), pres)
+        return out + _dnn(p, xe, hp, training, masks, "leaky_relu")
+    if model == "dcn":
+        dnn = _dnn(p, xe, hp, training, masks)
+        if collect:
+            _dnn_pres(p, xe, hp, pres)
+        cross = crossmix_ref.cross_mix_net(p, xe) if hp.get("cross_type", "vector") == "mix" else TL.cross_net(p, xe)
+        out = dnn + cross
+        if hp.get("strict_reference", False):
+            out = out + dnn
+        return out + lin() if hp.get("use_linear", True) else out
+    if model == "afm":
+        mask = masks.get("afm") if (training and hp.get("att_dropout", 1) < 1) else None
+        W, b = p["afm_attention_w"], p["afm_attention_b"]
+        if collect:
+            pres.append(afm_ref.afm_hidden(E, W, b)[1])
+        return lin() + afm_ref.afm_layer(E, W, b, p["afm_attention_h"], p["afm_projection_p"], mask).reshape(-1, 1)
+    if model == "autoint":
+        out = lin() + autoint_ref.autoint_stack(p, E, hp).reshape(-1, 1)
+        if collect:
+            pres += autoint_ref.autoint_stack(p, E, hp, return_pre=True)[1]
+            _dnn_pres(p, xe, hp, pres)
+        return out + _dnn(p, xe, hp, training, masks) if n else out
+    if model == "dlrm":
+        out = dlrm_ref.logit_from_embeddings(p, E, dense, hp, training, masks)
+        if collect:
+            pres += dlrm_ref.logit_from_embeddings(p, E, dense, hp, training, masks, return_pre=True)[1]
+        return out + lin() if hp.get("use_linear", False) else out
+    if model == "fmfm":
+        out = fmfm_ref.pair_logit(E, p["field_pair_w"], hp.get("field_interaction", "matrix")).reshape(-1, 1)
+        if hp.get("use_linear", True):
+            out = out + lin()
+        if collect:
+            _dnn_pres(p, xe, hp, pres)
+        return out + _dnn(p, xe, hp, training, masks) if n else out
+    # the models whose DNN reads the interaction's output
+    if model == "fibinet":
+        X = fibinet_ref.fibinet_x(p, E, hp)
+        x = torch.cat([X, dense], dim=1) if dense is not None and dense.shape[1] else X
+        if collect:
+            _, hs, s, ha, _ = fibinet_ref.gate(E, p["senet_w1"], p["senet_w2"])
+            pres += [hs, ha[s.abs().amax(dim=1) > 0]]  # (a gate whose first layer is all zero is exactly zero)
+        default = True
+    elif model == "pnn":
+        products = ((pnn_ref.INNER if hp.get("use_inner", True) else 0)
+                    | (pnn_ref.OUTER if hp.get("use_outer", False) else 0))
+        X = pnn_ref.product_layer(E, p.get("product_kernel"), products, hp.get("kernel_type", "mat"))
+        x = TL.dnn_input(X, dense)
+        default = False
+    elif model == "masknet":
+        x = TL.dnn_input(masknet_ref.blocks(p, E, dense, hp, pres if collect else None), dense)
+        default = True
+    else:
+        raise ValueError(model)
+    out = _dnn(p, x, hp, training, masks)
+    if collect:
+        _dnn_pres(p, x, hp, pres)
+    return out + lin() if hp.get("use_linear", default) else out
+
+
+_L2 = {"deepfm": TL.deepfm_l2, "xdeepfm": TL.xdeepfm_l2, "afm": afm_ref.afm_l2, "autoint": autoint_ref.autoint_l2,
+       "dlrm": dlrm_ref.dlrm_l2, "fibinet": fibinet_ref.fibinet_l2, "fmfm": fmfm_ref.fmfm_l2, "pnn": pnn_ref.pnn_l2,
+       "masknet": masknet_ref.masknet_l2}
+
+
+def l2(model, p, spec, hp):
+    """The model's own *_l2 on spec.tl.  DIN / BST / DIEN and DCN with the vector or the matrix cross take
+    tests/asp_ref.py:model_l2, the function the sequence models' restatements already call (the same terms as
+    oracle.th_layers.dcn_l2, summed in another order: the loss must keep its bits)."""
+    if model in SEQ_MODELS:
+        return asp_ref.model_l2("din", p, spec, hp)
+    if model == "dcn":
+        if hp.get("cross_type", "vector") == "mix":
+            return crossmix_ref.dcn_mix_l2(p, spec.tl, hp)
+        return asp_ref.model_l2("dcn", p, spec, hp)
+    return _L2[model](p, spec.tl, hp)
+
+
+def fwd_bwd(model, p, spec, idx, dense, y, hp, mv=None, task="classification", masks=None, wrong=None):
+    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
+    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
+    out = logit(model, leaves, spec, idx, dense, hp, mv, True, masks, wrong)
+    pred = TL.prediction(out, task)
+    loss = TL.create_loss(y, pred, task) + l2(model, leaves, spec, hp)
+    loss.backward()
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
+    return loss.detach(), out.detach().reshape(-1), pred.detach(), grads
+
+
+def min_abs_pre(model, p, spec, idx, dense, hp, mv=None):
+    """The distance of the case's closest kinked unit to its kink in float64: the DNN, the model's own ReLU units, the
+    din unit's hidden layers under att_activation "relu", the transformer unit's FFN over the real tokens (inf when
+    the model has no such unit)."""
+    pres = []
+    with torch.no_grad():
+        logit(model, p, spec, idx, dense, hp, mv, pres=pres)
+        out = [float(t.abs().min()) for t in pres if t.numel()]
+        kind = _kind(hp)
+        for n, qn in spec.seq_query.items():
+            T = p[f"{qn}_feat_embed"]
+            offsets, ids = mv[n]
+            Q, K = T[idx[:, spec.sparse_names.index(qn)]], T[ids]
+            if kind == "din" and hp.get("att_activation", "sigmoid") == "relu":
+                m = len(hp.get("att_hidden_units", (80, 40)))
+                out += [float(z.abs().min()) for z in
+                        asp_ref.asp_hidden(Q, K, offsets, *asp_ref.asp_vars(p, f"{n}_", m)[:2], "relu") if z.numel()]
+            if kind == "transformer":
+                out.append(float(bst_ref.ffn_kink_distance(Q, K, offsets, bst_ref.bst_vars(p, f"{n}_"),
+                                                           hp.get("att_head_num", 2)).min()))
+    return min(out + [float("inf")])
+
+
+def key_grad_abs_sums(model, k, task="classification"):
+    """{sequence name: sum over the tokens of |dLoss/dK_token| per column [D]} of a case under the transformer unit in
+    float64: the scale the analytically zero gradient of {name}_bst_bk is judged against
+    (tests/bst_ref.py:model_key_grad_abs_sum)."""
+    spec, B, D = k["spec"], k["idx"].shape[0], k["hp"]["embedding_size"]
+    probes = {n: torch.zeros(B, spec.seq_max_len[n] + 1, D, dtype=torch.float64, requires_grad=True)
+              for n in spec.seq_query}
+    out = logit(model, k["p"], spec, k["idx"], k["dense"], k["hp"], k["mv"], k_probe=probes)
+    TL.create_loss(k["y"], TL.prediction(out, task), task).backward()
+    return {n: t.grad.abs().sum(dim=(0, 1)) for n, t in probes.items()}
+
+
+# ------------------------------------------------------------------------------------------------- the comparison
+def is_loose(n, spec):
+    """The variables judged by max(TOL, 4 x the float32 CPU restatement's measure): a pooling unit's (batch sums that
+    are what is left of a cancellation, tests/test_gpu_din_model.py) and AutoInt's attention matrices
+    (tests/test_gpu_autoint_model.py).  Every other variable keeps the plain TOL."""
+    return n.startswith("autoint_") or any(n.startswith(f"{s}_{u}_") for s in spec.seq_query for u in UNIT_TAG.values())
+
+
+def zero_rule(n, spec, hp):
+    """"w0" / "bk" for the two analytically zero gradients ({name}_asp_w0 under the softmax, {name}_bst_bk), else
+    None."""
+    for s in spec.seq_query:
+        if n == f"{s}_asp_w0" and hp.get("att_weight_normalization", False):
+            return "w0"
+        if n == f"{s}_bst_bk":
+            return "bk"
+    return None
+
+
+def shared_rows(k):
+    """{query feature: sorted ids that are the candidate of one example and a history item of EVERY sequence feature
+    on that query feature}."""
+    spec, out = k["spec"], {}
+    for n, qn in spec.seq_query.items():
+        ids = set(k["mv"][n][1].tolist())
+        have = out.get(qn, set(k["idx"][:, spec.sparse_names.index(qn)].tolist()))
+        out[qn] = have & ids
+    return {qn: sorted(v) for qn, v in out.items()}
+
+
+def check_grads(k, grads, want, g32, bk_scales=None, what="", show=print):
+    """Compares a gradient set {reference name: tensor} with the float64 gradients `want` of case k; g32 = the float32
+    CPU restatement's gradients (the yardstick of the loose variables, never the kernel), bk_scales =
+    key_grad_abs_sums (transformer unit only).  Every figure goes to `show`; an AssertionError names everything that
+    missed.  -> [(name, measure, float32 CPU measure, bound)]."""
+    spec, hp = k["spec"], k["hp"]
+    assert set(grads) == set(want), sorted(set(grads) ^ set(want))
+    rows, bad = [], []
+    for n in sorted(want):
+        rule = zero_rule(n, spec, hp)
+        if rule == "w0":
+            # analytically zero under the softmax: float64 returns a 1e-18 residue, the relative measure means nothing
+            m, m32, bound = float(grads[n].detach().abs().max()), float(g32[n].abs().max()), 1e-6
+        elif rule == "bk":
+            # analytically zero: judged against the terms that cancel (tests/test_gpu_bst_model.py)
+            scale = bk_scales[n[: -len("_bst_bk")]]
+            m = float((grads[n].detach().cpu().double().abs() / scale).max())
+            m32 = float((g32[n].double().abs() / scale).max())
+            bound = max(TOL, 4 * m32)
+        else:
+            m, m32 = grad_measure(grads[n], want[n]), grad_measure(g32[n], want[n])
+            bound = max(TOL, 4 * m32) if is_loose(n, spec) else TOL
+        rows.append((n, m, m32, bound))
+        show(f"{what}{n}: {'|g|' if rule else 'measure'} {m:.2e}, float32 CPU {m32:.2e}, bound {bound:.2e}")
+        if not m <= bound:
+            bad.append(f"grad {n}: {m:.3e} > {bound:.3e} (float32 CPU {m32:.3e})")
+    # rows that are candidate and history item at once, on their own: both gradients arrived
+    for qn, both in shared_rows(k).items():
+        n = f"{qn}_feat_embed"
+        assert both and float(want[n][both].abs().max()) > 0, f"{what}no row of {qn} is candidate and history item"
+        m = grad_measure(grads[n][both], want[n][both])
+        show(f"{what}{n}[candidate-and-history rows]: measure {m:.2e}")
+        if not m <= TOL:
+            bad.append(f"grad {n}, candidate-and-history rows {both}: {m:.3e} > {TOL:.3e}")
+    assert not bad, what + "; ".join(bad)
+    return rows
+
+
+# --------------------------------------------------------------------------------------------------------- cases
+B, DN, MAX_LEN = 37, 2, 6
+_UNIT_CASE = {"din": (asp_ref.make_model_case, "din"), "transformer": (bst_ref.make_model_case, "bst"),
+              "dien": (dien_ref.make_model_case, "dien")}
+_CASES, _REFS = {}, {}
+
+
+def _f32(t):
+    return t.float().double()
+
+
+OWN_LOGIT = {"deepfm": TL.deepfm_logit, "xdeepfm": TL.xdeepfm_logit, "dcn": TL.dcn_logit, "dcn_matrix": TL.dcn_logit,
+             "dcn_mix": crossmix_ref.dcn_mix_logit, "afm": afm_ref.afm_logit, "autoint": autoint_ref.autoint_logit,
+             "dlrm": dlrm_ref.dlrm_logit, "fibinet": fibinet_ref.fibinet_logit, "fmfm": fmfm_ref.fmfm_logit,
+             "pnn": pnn_ref.pnn_logit, "masknet_parallel": masknet_ref.masknet_logit,
+             "masknet_serial": masknet_ref.masknet_logit}
+
+
+def own_case(model_id, D, F=4, Dn=DN):
+    """The model's own make_case at F plain fields and its smallest supported shape, in float64 (every value a float32
+    number): dict(spec (oracle.th_layers.Spec), p, idx, dense, y, hp).  OWN_LOGIT[model_id] is its own *_logit."""
+    model = MODELS[model_id]
+    d = F * D + Dn
+    hidden = (16, 8)
+    if model_id in ("deepfm", "xdeepfm", "dcn", "dcn_matrix"):
+        kw = {"deepfm": {}, "xdeepfm": dict(cin_units=(8, 4), scale=0.2)}.get(model_id,
+                                                                              dict(cross_layers=2, scale=0.15))
+        tl, p, idx, dense, y, hp = base_case(model, B=B, F=F, D=D, Dn=Dn, hidden=hidden, **kw)
+        p = {n: v.double() for n, v in p.items()}
+        if model_id == "dcn_matrix":  # drawn as tests/test_gpu_parity.py's matrix-cross test draws it
+            g = torch.Generator().manual_seed(21)
+            p["cross_w"] = _f32(torch.randn(2, d, d, generator=g) * (0.5 / d ** 0.5))
+            p["cross_b"] = _f32(torch.randn(2, d, generator=g) * 0.1)
+            hp = dict(hp, cross_type="matrix")
+        return dict(spec=tl, p=p, idx=idx, dense=dense.double(), y=y, hp=hp)
+    if model_id == "dcn_mix":
+        c = crossmix_ref.make_case(B, F, D, Dn, 2, 2, 8, hidden=hidden)
+    elif model_id == "afm":
+        c = afm_ref.make_afm_case(B, F, D, Dn, 4)
+    elif model_id == "autoint":
+        c = autoint_ref.make_case(B, F, D, Dn, 1, 2, 4)
+    elif model_id == "dlrm":
+        c = dlrm_ref.make_case(B, F, D, Dn, bottom=(16,), hidden=hidden, use_linear=True)
+    elif model_id == "fibinet":
+        c = fibinet_ref.make_case(B, F, D, Dn, 2, "each", hidden=hidden)
+    elif model_id == "fmfm":
+        c = fmfm_ref.make_case("matrix", (16,), B, F, D, Dn)
+    elif model_id == "pnn":
+        c = pnn_ref.make_case(pnn_ref.INNER | pnn_ref.OUTER, "mat", True, hidden, B, F, D, Dn)
+    elif model_id in ("masknet_parallel", "masknet_serial"):
+        # two blocks of the engine's default 64 units, not the smallest 8: the float32 CPU twin of a LayerNorm over
+        # 8 units misses half the GPU bound on its own (2.2e-5 on ln_emb_beta, serial blocks under the dien unit;
+        # at most 6.6e-6 at 64 - tests/test_seq_models_host.py asserts 1e-5)
+        c = masknet_ref.make_case(model_id.split("_")[1], 2, 64, 0.25, (16,), B, F, D, Dn)
+    else:
+        raise ValueError(model_id)
+    return dict(spec=c["spec"], p={n: v.double() for n, v in c["p"].items()}, idx=c["idx"], dense=c["dense"].double(),
+                y=c["y"], hp=dict(c["hp"]))
+
+
+def model_variables(model_id, D, F=4, Dn=DN):
+    """(variables, hyper-parameters) of the model alone, out of own_case: every variable but the embedding tables and
+    the linear term (DeepFM's bias tables stay), every l2 coefficient greater than 0."""
+    c = own_case(model_id, D, F, Dn)
+    keep_bias = model_id == "deepfm"
+    p = {n: v for n, v in c["p"].items() if not n.endswith("_feat_embed") and n not in ("linear_w", "linear_w0")
+         and (keep_bias or not n.endswith("_feat_bias"))}
+    return p, c["hp"]
+
+
+_KEEP_UNIT_HP = ("embedding_size", "seq_pooling", "att_hidden_units", "att_activation", "att_weight_normalization",
+                 "att_head_num", "att_ffn_units")
+
+
+def make_case(model_id, kind, D=8, seed=0, **unit_kw):
+    """A seeded case of model `model_id` (a key of MODELS) over the spec of tests/asp_ref.py:make_model_case - C0 (7),
+    item (11), hist -> item (max_len 6), C2 (5); B = 37, two dense features; example 0 has no history, example 1 one
+    item, example 2 six; item ids from the small range, so rows are candidate and history item at once.  Embedding,
+    linear and unit variables, ids, dense values and labels are the unit's own make_model_case's (unit_kw goes to
+    it), the model's variables are model_variables'.  The first stream in which every kinked unit is at least KINK
+    from its kink is taken (`attempt`, `min_abs_pre`).  Returns model (the engine), spec, p, idx, dense, y, hp, mv."""
+    key = (model_id, kind, D, seed, tuple(sorted(unit_kw.items())))
+    if key in _CASES:
+        return _CASES[key]
+    model = MODELS[model_id]
+    pm, hpm = model_variables(model_id, D)
+    make, unit_model = _UNIT_CASE[kind]
+    for attempt in range(64):
+        u = make(unit_model, B=B, D=D, Dn=DN, seed=64 * seed + attempt, max_len=MAX_LEN, **unit_kw)
+        spec = u["spec"]
+        p = {n: v for n, v in u["p"].items() if not n.startswith("dnn_")}
+        p.update(pm)
+        if model == "deepfm":  # the bias tables of the plain features, by position (the sizes are the same)
+            plain = [n for n in spec.sparse_names if n not in spec.seq_query]
+            for j, n in enumerate(plain):
+                p[f"{n}_feat_bias"] = p.pop(f"C{j}_feat_bias") if n != f"C{j}" else p[f"C{j}_feat_bias"]
+            for n in [n for n in p if n.endswith("_feat_bias") and n[: -len("_feat_bias")] not in plain]:
+                del p[n]
+        hp = {n: v for n, v in u["hp"].items() if n in _KEEP_UNIT_HP}
+        hp.update(embedding_l2_reg=1e-3, linear_l2_reg=1e-3, seq_pooling=kind)
+        hp.update({n: v for n, v in hpm.items() if n not in ("embedding_size",)})
+        if "use_linear" in hp or model in ("dlrm", "pnn"):
+            hp["use_linear"] = True
+        closest = min_abs_pre(model, p, spec, u["idx"], u["dense"], hp, u["mv"])
+        if closest >= KINK:
+            break
+    else:
+        raise AssertionError("no stream met the case conditions")
+    out = dict(model=model, spec=spec, p=p, idx=u["idx"], dense=u["dense"], y=u["y"], hp=hp, mv=u["mv"],
+               min_abs_pre=closest, attempt=attempt)
+    _CASES[key] = out
+    return out
+
+
+def make_mixed_case(kind, D=16, model="deepfm", seed=0):
+    """A seeded case over a mixed front: hist2 -> item (max_len 3, AHEAD of its query), C0 (7), item (11), hist -> item
+    (max_len 6), tags (9, multi-valued), val (6, a value feature); B = 37, three dense features.  Example 0 has both
+    histories empty, example 1 one item in each, example 2 both full; example 0 and example 3 have no tag; the value of
+    example 0 is 0.  model: "deepfm" (FM term and bias tables on) or "dcn" (vector cross, two layers).  mv follows
+    oracle.th_layers: (offsets, ids) per history and for tags, (ids, vals) for val.  The din unit runs with relu and
+    the softmax here (att_hidden_units (16, 8)), the transformer with 2 heads and 2 D FFN units.  The first stream in
+    which every kinked unit (DNN, the din unit's layers, the transformer's FFN) is at least KINK from its kink is
+    taken."""
+    key = (kind, D, model, seed)
+    if key in _CASES:
+        return _CASES[key]
+    names, sizes = ["hist2", "C0", "item", "hist", "tags", "val"], [0, 7, 11, 0, 9, 6]
+    max_len = {"hist2": 3, "hist": 6}
+    Dn, hidden = 3, (16, 8)
+    spec = Spec(names, sizes, [f"I{j}" for j in range(Dn)], {"hist2": "item", "hist": "item"}, max_len, ["tags"],
+                ["val"])
+    hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, deep_hidden_units=hidden, deep_l2_reg=1e-3,
+              deep_activation="relu", seq_pooling=kind)
+    if kind == "din":
+        # (the softmax and relu: {name}_asp_w0 is analytically zero, the unit's hidden layers have kinks)
+        hp.update(att_hidden_units=(16, 8), att_activation="relu", att_weight_normalization=True)
+    if kind == "transformer":
+        hp.update(att_head_num=2, att_ffn_units=2 * D)
+    if model == "dcn":
+        hp.update(cross_layer_num=2, cross_layer_l2_reg=1e-3, use_linear=True)
+    for attempt in range(64):
+        g = torch.Generator().manual_seed(23000 + 64 * seed + attempt)
+        rnd = _rnd(g)
+        p = {}
+        for n, V in zip(names, sizes):
+            if V:
+                p[f"{n}_feat_embed"] = rnd(V, D, std=0.3)
+                if model == "deepfm":
+                    p[f"{n}_feat_bias"] = rnd(V, 1, std=0.1)
+        p["linear_w"] = rnd(spec.tl.lin_layout[2], 1, std=0.1)
+        p["linear_w0"] = rnd(1, std=0.1)
+        d_in = len(names) * D + Dn
+        dims = [d_in] + list(hidden)
+        for i in range(len(hidden)):
+            p[f"dnn_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
+            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
+        p["dnn_w"] = rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5)
+        p["dnn_w0"] = rnd(1, std=0.1)
+        if model == "dcn":
+            p["cross_w"], p["cross_b"] = rnd(2, d_in, std=0.15), rnd(2, d_in, std=0.15)
+            p["cross_w_out"] = rnd(d_in, 1, std=0.15)
+        for n in spec.seq_query:
+            if kind == "din":
+                p.update(asp_ref.make_asp_params(D, hp["att_hidden_units"], g, prefix=f"{n}_"))
+            elif kind == "transformer":
+                p.update({f"{n}_bst_{v}": t for v, t in
+                          bst_ref.make_bst_params(D, 2, hp["att_ffn_units"], max_len[n], g).items()})
+            else:
+                p.update({f"{n}_dien_{v}": t for v, t in dien_ref.make_dien_params(D, g).items()})
+        idx = torch.stack([torch.randint(0, v, (B,), generator=g) if v else torch.zeros(B, dtype=torch.int64)
+                           for v in sizes], 1)
+        mv = {}
+        for n in spec.seq_query:
+            ln = make_lengths(B, max_len[n], g)
+            mv[n] = (torch.cat([torch.zeros(1, dtype=torch.int64), ln.cumsum(0)]),
+                     torch.randint(0, sizes[2], (int(ln.sum()),), generator=g))
+        nt = torch.randint(0, 4, (B,), generator=g)
+        nt[0], nt[3], nt[1] = 0, 0, 3
+        mv["tags"] = (torch.cat([torch.zeros(1, dtype=torch.int64), nt.cumsum(0)]),
+                      torch.randint(0, sizes[4], (int(nt.sum()),), generator=g))
+        vals = rnd(B)
+        vals[0] = 0.0
+        mv["val"] = (torch.randint(0, sizes[5], (B,), generator=g), vals)
+        dense = rnd(B, Dn)
+        y = (torch.rand(B, generator=g) < 0.3).long()
+        closest = min_abs_pre(model, p, spec, idx, dense, hp, mv)
+        if closest >= KINK:
+            break
+    else:
+        raise AssertionError("no stream met the case conditions")
+    out = dict(model=model, spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, mv=mv, min_abs_pre=closest,
+               attempt=attempt)
+    _CASES[key] = out
+    return out
+
+
+def to_f32(k):
+    """(p, dense, mv) of a case in float32: the float32 CPU twin's inputs."""
+    c = lambda t: t.float() if t.is_floating_point() else t  # noqa: E731
+    return ({n: c(v) for n, v in k["p"].items()}, c(k["dense"]),
+            {n: tuple(c(t) for t in e) for n, e in k["mv"].items()})
+
+
+def reference(k):
+    """(float64 fwd_bwd, the float32 CPU twin's gradients, key_grad_abs_sums or None) of a case: computed once, shared
+    by the tests that need it, never changed."""
+    if id(k) not in _REFS:
+        a = (k["model"], k["p"], k["spec"], k["idx"], k["dense"], k["y"], k["hp"], k["mv"])
+        p32, dense32, mv32 = to_f32(k)
+        g32 = fwd_bwd(k["model"], p32, k["spec"], k["idx"], dense32, k["y"], k["hp"], mv32)[3]
+        scales = key_grad_abs_sums(k["model"], k) if _kind(k["hp"]) == "transformer" else None
+        _REFS[id(k)] = (fwd_bwd(*a), g32, scales, k)  # (k is kept: its id stays taken)
+    return _REFS[id(k)][:3]
