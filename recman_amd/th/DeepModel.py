@@ -20,6 +20,7 @@ each global mini-batch is split over the ranks, every rank runs fwd+bwd on its p
 their shard rows, the dense parameters follow the all-reduced gradient.  predict() / evaluate() run
 every rank over all rows in step (the lookups are an exchange) and return the full result everywhere.
 """
+import contextlib
 import logging
 from time import time
 
@@ -303,6 +304,10 @@ class DeepModel(BaseEstimator, TransformerMixin):
                 st.capacity_factor = None
                 e._B = None
                 redone = True
+                if e.spec.scratch_names:
+                    # with exact split sizes the tags of multi-valued / value features travel as an expanded list
+                    # of varying length: no micro-batch pipeline there (make_sharded_engine refuses the pair)
+                    e.micro_batches = 1
                 loss = e.fwd_bwd(idx, dense, yt, masks=masks, weight=self._w, mv=mv)
         finally:
             e.micro_batches = M
@@ -396,10 +401,29 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                 masks=masks, manual_weights=mw, mv=self._mv_batch(mv_host, s, t))
             yield s, t, pred
 
+    @contextlib.contextmanager
+    def _exact_splits(self):
+        """predict() / evaluate() on a row-sharded table with fixed-capacity buckets look their rows up with EXACT
+        split sizes: a forward pass has nobody to redo a batch whose buckets overflowed (the clamped occurrences would
+        read another row - a wrong prediction, silently - and leave the sticky flag to the next training step).  The
+        engine's buffers are sized for the layout: re-made on entry and for the next fixed-capacity batch."""
+        e = self._build()
+        st = getattr(e, "st", None)
+        fixed = st.capacity_factor if (self._shard is not None and st is not None) else None
+        if not fixed:
+            yield
+            return
+        st.capacity_factor, e._B = None, None
+        try:
+            yield
+        finally:
+            st.capacity_factor, e._B = fixed, None
+
     def _predict_encoded(self, idx, dense, training, mv_host=None):
         out = np.empty((idx.shape[0],), dtype=np.float32)
-        for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
-            out[s:t] = pred.cpu().numpy()
+        with self._exact_splits():
+            for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
+                out[s:t] = pred.cpu().numpy()
         return out
 
     def _predict_device(self, idx, dense, training, mv_host=None):
@@ -407,8 +431,9 @@ class DeepModel(BaseEstimator, TransformerMixin):
         device fp32 buffer, with no host copy per batch."""
         e = self._build()
         out = torch.empty((idx.shape[0],), dtype=torch.float32, device=e.device)
-        for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
-            out[s:t].copy_(pred)
+        with self._exact_splits():
+            for s, t, pred in self._predict_batches(idx, dense, training, mv_host):
+                out[s:t].copy_(pred)
         return out
 
     def _metrics_on_device(self):

@@ -484,7 +484,13 @@ def test_model_fit_predict_save_restore_with_a_row_sharded_table_on_two_ranks(hi
     """The model classes under a two-rank torch.distributed job: the table row-sharded, fit() data parallel
     (ragged last batch, micro-batches, dense l2; "deepfm_genres": with ml-100k's multi-valued `genres`, whose tags
     travel through the exchange), predict() on every rank, save() / restore() with one shard file per rank.  Both ranks end with identical predictions and identical dense parameters, the loss
-    went down, a restored model predicts the same."""
+    went down, a restored model predicts the same.
+    What this test cannot see - both ranks wrong in the same way - is held by tests/test_gpu_shard_fit.py, against a
+    one-GPU twin with the row-wise optimizer and a float64 restatement of the sharded loop: fit() on two ranks over
+    1001 rows (the 41-row batch split 21 + 20; xDeepFM with fixed capacity 1.5 and two micro-batches, DeepFM with
+    `genres` and exact split sizes), a fit_on_batch step that overflows on ONE rank and is redone on both (plain, and
+    with `genres` + two micro-batches), and at world size 1 DeepFM / DCN / xDeepFM / DeepFM + `genres` with exact
+    split sizes, fixed capacity + micro-batches, the lazy table l2, and an epoch whose full batches all overflow."""
     world = 2
     out = str(tmp_path / "f")
     port = 29990 + ["deepfm", "xdeepfm", "deepfm_genres", "xdeepfm_defaults", "xdeepfm_ragged_fixed",
