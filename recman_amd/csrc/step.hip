@@ -61,7 +61,10 @@ constexpr int kPubDh = 0, kPubDT = 2048, kPubGS = kPubDT + 16 * kLDT * 4, kPubG 
 constexpr int oX = 0;                                 // [kRing][26][1024] rows of the embedding fields
 constexpr int oDense = oX + kRing * kXBufB;           // [4][1024] the dense pseudo-field (written by the head)
 constexpr int oJunk = oDense + 4 * kSlotB;            // sink of the DMAs of empty slots (every worker issues 4 per tile)
-constexpr int oPart = oJunk + kSlotB;                 // [2][7][kPartB]
+// the image an EMPTY slot reads (all zeros; every worker writes it in its prologue and reads its own writes).  An empty
+// slot must not read a ring buffer: the rows there are another worker's DMA, which only that worker's counted wait covers
+constexpr int oZero = oJunk + kSlotB;
+constexpr int oPart = oZero + kSlotB;                 // [2][7][kPartB]
 constexpr int oPub = oPart + 2 * kWorkers * kPartB;   // [2][kPubB]
 constexpr int kRowB = 28 * 64;                        // row numbers of a tile: [28 field slots][16] u32 (the head writes 7 per lane)
 constexpr int oRow = oPub + 2 * kPubB;                // [2][kRowB]
@@ -153,8 +156,9 @@ __device__ __forceinline__ void dma16(const char *src, char *lds_dst) {
 // LDS-DMAs, loads and stores are pending together), which drains the rows just requested.  So the load is an asm
 // statement, and entry_wait - the counted wait, naming the register "+v" - stands in front of its only consumer.
 // Between the two hipcc believes the register already holds the value: it must not read, copy or spill it there.
-// The worker keeps the four registers dead between use and reload (see the D phase); check the emitted code of a
-// new compiler for a v_mov or a scratch access of them between the load and the wait.
+// The worker keeps the four registers dead between use and reload (see the D phase); tests/test_step_waits_host.py
+// checks the emitted code of all six instantiations for an instruction that names them between the load and the
+// wait, for scratch accesses, and for the order and the counts derived below.
 template <class T>
 __device__ __forceinline__ void entry_load(T &dst, const void *src) {
   static_assert(sizeof(T) == 4, "one dword");
@@ -182,9 +186,11 @@ __device__ __forceinline__ void wait_vm(int younger) {
 // Invariant that makes the LDS-only wait sufficient: everything that crosses waves at this barrier is written with
 // ds_write by the wave that owns it - worker -> head: the partial sums (oPart); head -> workers: the published dh0 / g
 // / g*S (oPub), the row numbers (oRow), the dense ring (oDense), the labels (oY, head only).  x never crosses waves:
-// a DMA's rows are read by the wave that issued it alone, behind that wave's own counted wait_vm(); the global stores
-// (d_rows, logit, pred, dlogit) are read by nobody in this kernel.  The clobbers keep hipcc from moving LDS accesses
-// across either instruction.
+// a DMA's rows are read by the wave that issued it alone, behind that wave's own counted wait_vm() (nothing else
+// orders a ds_read behind an LDS-DMA; another wave's read would need that wait AND a barrier behind it, which the
+// tile loop no longer has - so a slot without a field reads the zero image oZero, never another worker's rows); the
+// global stores (d_rows, logit, pred, dlogit) are read by nobody in this kernel.  The clobbers keep hipcc from moving
+// LDS accesses across either instruction.
 __device__ __forceinline__ void tile_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -259,8 +265,10 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
   const int lo_row = n * F * 64 + 16 * q;  // d_rows: example n, slice q (the field adds 64 f)
   auto slot_base = [&](int j, int tile) {  // LDS byte offset of slot j's image of `tile` (wave-uniform)
     const int ring = oX + ((tile + 6) % 3) * kXBufB + fld[j] * kSlotB, dn = oDense + (tile & 3) * kSlotB;
-    return __builtin_amdgcn_readfirstlane((sx[j] || !sv[j]) ? ring : dn);
+    return __builtin_amdgcn_readfirstlane(sx[j] ? ring : (sv[j] ? dn : oZero));
   };
+  // the zero image of the empty slots: written here by every worker (the same zeros), read by the worker itself only
+  *reinterpret_cast<f32x4 *>(smem + oZero + lane * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
   // this lane's piece of a row: DMA lane (example lane >> 2, position lane & 3); the bias / linear entry it sums
   // (floats 16 / 17 of the row: lanes with (lane & 1) == 0 take the bias entry, the others the linear weight)
   const int piece = 16 * ((lane & 3) ^ swz(lane >> 2));
@@ -314,7 +322,9 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
     // Phases WITHOUT per-slot branches (one basic block each, so that hipcc interleaves the slots' MFMA chains and
     // keeps their LDS reads in flight together): R read everything the backward needs of the 4 slots, D issue the
     // DMAs / entry loads of tile s + 1 into the slots just read, M 64 MFMAs, S FM term + stores.  Empty slots run on
-    // field 0's data with zero weights (their dW0 accumulators are never stored, their d_rows store is dropped).
+    // the zero image (oZero) with zero weights (their dW0 accumulators are never stored, their d_rows store is
+    // dropped).  (They used to run on field 0's ring buffer - worker 0's DMA, which no wait of THIS wave covers: zero
+    // weights times the NaN bit patterns of a buffer not yet written are NaN.)
     {
       const int tb = s - 2, td = s + 1;
       const char *pub = smem + oPub + (tb & 1) * kPubB;
