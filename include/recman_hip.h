@@ -1193,6 +1193,55 @@ int rm_group_auc(const float *scores, const int64_t *labels, const int64_t *grou
                  void *workspace, int64_t *group_ids, int64_t *group_n, int64_t *group_pos, uint64_t *group_2u,
                  rm_group_auc_result *out, rm_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Multi-task learning: the gate-softmax + expert mixture of MMoE (Multi-gate Mixture-of-Experts, Ma et al., KDD
+ * 2018) for all tasks in one pass, and the loss head for several labels (csrc/mmoe.hip).  Nothing in the reference
+ * implements them: it knows one label per example (DeepModel.py:31-34).  Per example, E experts of width H, T tasks:
+ *     p_t = softmax_e(A_t), max-subtracted;   M_t = sum_e p_te Z_e
+ *   Z [B, ldz] (E H columns used, expert e at columns e H ..), A [B, lda] (T E columns, task t at t E ..),
+ *   M [B, ldm] (T H columns written, task t at t H ..), P [B, ldp] or NULL (T E columns written: the gate weights,
+ *   for inspection at inference).  Every operand is a pointer and a row stride in floats: a column range of a wider
+ *   buffer works; pointers 16-byte aligned, strides multiples of 4 floats and >= the width; columns past the width
+ *   are never read or written.
+ * rm_mmoe_mix_fwd replaces what a composition of softmax, T E scaled adds and T stores of p would move: Z and A are
+ *   read once, M is written once, p reaches HBM only when P is given (M has the same bits either way).
+ * rm_mmoe_mix_bwd, given dM = dLoss/dM, recomputes p and writes dZ [B, lddz] and dA [B, ldda] once (own columns only):
+ *     dZ_e = sum_t p_te dM_t;   c_te = <dM_t, Z_e>;   dA_te = p_te (c_te - sum_e' p_te' c_te')    (exactly 0 at E = 1)
+ *   No parameters, so no partial sums; no atomics, no workspace: two runs are bit-equal.
+ * Supported (rm_mmoe_mix_supported): 1 <= E <= 16, 1 <= T <= 8, H a multiple of 4 in 4..512; anything else, a NULL
+ *   or unaligned pointer, or a stride that is below its width or no multiple of 4 is RM_EINVAL before any launch,
+ *   the limits named in the message.  B = 0 is RM_OK.
+ * rm_mmoe_mix_tile: RM_MMOE_TILE the examples a block owns per tile (backward != 0: of rm_mmoe_mix_bwd),
+ *   RM_MMOE_CAP the cap of both grids: a block walks the batch again from B > cap * tile on.  -1 when unsupported.
+ */
+#define RM_MMOE_TILE 0
+#define RM_MMOE_CAP 1
+int rm_mmoe_mix_supported(int E, int T, int H);
+int rm_mmoe_mix_tile(int E, int T, int H, int backward, int which);
+int rm_mmoe_mix_fwd(const float *Z, int64_t ldz, const float *A, int64_t lda, int64_t B, int E, int T, int H,
+                    float *M, int64_t ldm, float *P, int64_t ldp, rm_stream_t stream);
+int rm_mmoe_mix_bwd(const float *Z, int64_t ldz, const float *A, int64_t lda, const float *dM, int64_t lddm,
+                    int64_t B, int E, int T, int H, float *dZ, int64_t lddz, float *dA, int64_t ldda,
+                    rm_stream_t stream);
+
+/* The loss head for T labels per example: rm_logit_loss's arithmetic per task (PredictionLayer + create_loss,
+ * layers.py:796-808, utils.py:192-198: Keras binary_crossentropy on clipped probabilities, or MSE), over the
+ * examples whose label is OBSERVED - NaN in Y means unobserved (CVR is defined on clicks only).
+ *   logit [T, B];  Y [B, T] fp32, NaN = unobserved;  task_type [T] HOST ints (0 classification, 1 regression);
+ *   task_weight [T] HOST floats;  1 <= T <= 8, B >= 1
+ *   pred   [T, B]  sigmoid(logit) or logit; written for unobserved labels too
+ *   dlogit [T, B]  w_t dl_t/dlogit / n_t * grad_scale where the label is observed, +0.0 elsewhere
+ *   n_t    [T] int64, the observed labels per task;  loss_t [T] the mean of l_t over them (0 when n_t = 0)
+ *   loss   [1]  sum_t w_t loss_t
+ * A task with no observed label contributes loss 0 and a zero gradient.  Counts and sums are two-stage reductions
+ * in double in a fixed order, no float atomics: two runs are bit-equal.  With Y, dlogit, n_t, loss_t and loss all
+ * NULL only pred is written (inference).  workspace: rm_multitask_loss_workspace(B, T) floats, 16-byte aligned
+ * (-1: unsupported T). */
+int64_t rm_multitask_loss_workspace(int64_t B, int T);
+int rm_multitask_loss(const float *logit, const float *Y, const int *task_type, const float *task_weight,
+                      float grad_scale, int64_t B, int T, float *pred, float *dlogit, int64_t *n_t, float *loss_t,
+                      float *loss, float *workspace, rm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SIGNATURES = {
     "rm_roc_auc": [P, P, I64, P, P, P],
     "rm_log_loss": [P, P, I64, c_float, P, P, P],
     "rm_group_auc": [P, P, P, I64, c_int, P, P, P, P, P, P, P],
+    "rm_mmoe_mix_supported": [c_int, c_int, c_int],
+    "rm_mmoe_mix_tile": [c_int, c_int, c_int, c_int, c_int],
+    "rm_mmoe_mix_fwd": [P, I64, P, I64, I64, c_int, c_int, c_int, P, I64, P, I64, P],
+    "rm_mmoe_mix_bwd": [P, I64, P, I64, P, I64, I64, c_int, c_int, c_int, P, I64, P, I64, P],
+    "rm_multitask_loss": [P, P, P, P, c_float, I64, c_int, P, P, P, P, P, P, P],
 }
 
 
@@ -196,6 +201,7 @@ SIGNATURES_I64 = {
     "rm_sparse_optimizer_workspace": [I64],
     "rm_metric_workspace": [I64],
     "rm_group_auc_workspace": [I64],
+    "rm_multitask_loss_workspace": [I64, c_int],
 }
 
 

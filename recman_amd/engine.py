@@ -2842,6 +2842,224 @@ class MaskNetEngine(Engine):
         ] + Engine.roofline_probes(self, idx, dense, y)
 
 
+def mmoe_limits(hp):
+    """MMoE's limits in one place (th.MMoE checks them at construction, MMoEEngine when it is built): a ValueError
+    naming the limit, or (task_names, task_types, task_weights, num_experts, expert_hidden_units, tower_hidden_units)."""
+    names = tuple(hp.get("task_names") or ("ctr", "cvr"))
+    types = tuple(hp.get("task_types") or ("classification",) * len(names))
+    weights = hp.get("task_weights")
+    weights = (1.0,) * len(names) if weights is None else tuple(float(w) for w in weights)
+    limits = ("1..8 tasks with one name, type and weight each, num_experts 1..16, expert_hidden_units multiples of 4 "
+              "with the last in 4..512, a non-empty tower_hidden_units")
+    if not 1 <= len(names) <= 8:
+        raise ValueError(f"MMoE: {len(names)} tasks ({limits})")
+    if len(types) != len(names) or len(weights) != len(names):
+        raise ValueError(f"MMoE: task_names, task_types and task_weights differ in length: {len(names)}, {len(types)}, "
+                         f"{len(weights)} ({limits})")
+    if len(set(names)) != len(names) or not all(isinstance(n, str) and n for n in names):
+        raise ValueError(f"MMoE: task_names {names!r} must be distinct non-empty strings")
+    for t in types:
+        if t not in ops.TASK_TYPES:
+            raise ValueError(f"MMoE: task type {t!r} is neither 'classification' nor 'regression'")
+    E = hp.get("num_experts", 8)
+    if not isinstance(E, int) or not 1 <= E <= 16:
+        raise ValueError(f"MMoE: num_experts={E!r} ({limits})")
+    experts = tuple(int(h) for h in (hp.get("expert_hidden_units", (256, 128)) or ()))
+    towers = tuple(int(h) for h in (hp.get("tower_hidden_units", (64,)) or ()))
+    if not experts or any(h < 4 or h % 4 for h in experts) or not ops.MMOE_H_MIN <= experts[-1] <= ops.MMOE_H_MAX:
+        raise ValueError(f"MMoE: expert_hidden_units={experts!r} ({limits})")
+    if not towers or any(h < 1 for h in towers):
+        raise ValueError(f"MMoE: tower_hidden_units={towers!r}: every task tower needs at least one hidden layer "
+                         f"({limits})")
+    return names, types, weights, E, experts, towers
+
+
+class MMoEEngine(Engine):
+    """Multi-gate Mixture-of-Experts (MMoE, Ma et al., KDD 2018): T tasks over one set of embedding tables.  Nothing in
+    the reference implements it (it knows one label per example).  x = [E | dense] [B, K0], never concatenated:
+        experts e < E:  h_e^0 = x;  h_e^{l+1} = act(h_e^l W_e^l + b_e^l) over expert_hidden_units;  Z_e = h_e^L [B, H]
+        gates t < T:    A_t = x G_t [B, E] (no bias, no hidden layer);  p_t = softmax(A_t)
+        mixture:        M_t = sum_e p_te Z_e                                              (csrc/mmoe.hip)
+        towers:         logit_t = DNN_t(M_t), tower_hidden_units + the output projection
+        loss = sum_t w_t * mean over the examples whose label t is observed (not NaN) of l_t  + the l2 terms
+    num_experts = 1 is the shared-bottom model.  Layout: the experts are STACKED - layer l of all experts is one
+    [B, E H_l] buffer, expert e at columns e H_l ..; layer 0 is one GEMM over x, deeper layers run per expert on the
+    column ranges; all gates are one GEMM x -> [B, T E]; M is one [B, T H] buffer whose column range t the tower of
+    task t reads in place (a tower narrow enough for the fused skinny-MLP kernels, which take contiguous rows, gets a
+    copy).  The gate weights p never reach HBM in training.
+    Variables (names chosen here): expert_layer_0_weights [K0, E H_1] / _bias [E H_1]; expert_layer_{l}_weights
+    [E, H_l, H_{l+1}] / _bias [E, H_{l+1}] for l >= 1; gate_weights [K0, T E] (task t at columns t E ..); per task the
+    tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".  Every matrix is glorot with the
+    fans of ONE expert or gate and under deep_l2_reg; biases start at zero.  No bias tables, no linear term, no
+    dropout, one GPU.  logit / pred / dlogit are [T, B]."""
+
+    model = "mmoe"
+    use_bias_tables = False
+    shardable = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = False
+        (self.task_names, self.task_types, self.task_weights, self.NE, self.expert_units,
+         self.tower_units) = mmoe_limits(hp)
+        if hp.get("strict_reference"):
+            raise NotImplementedError("MMoE: strict_reference reproduces quirks of the reference, which has no "
+                                      "multi-task model")
+        for key in ("deep_dropout", "expert_dropout", "tower_dropout"):
+            keep = hp.get(key)
+            if keep is not None and any(float(k) != 1.0 for k in keep):
+                raise NotImplementedError(f"MMoE: {key}={keep!r}: the experts and towers run without dropout")
+        self.T, self.H = len(self.task_names), self.expert_units[-1]
+        if not ops.mmoe_mix_supported(self.NE, self.T, self.H):
+            raise ValueError(f"MMoE: {self.NE} experts, {self.T} tasks, expert width {self.H} are not supported by "
+                             f"rm_mmoe_mix_fwd ({ops.MMOE_LIMITS})")
+        self.act = act_name(hp.get("deep_activation", "relu"))
+        self.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        K0, NE, T = self.FD + self.Dn, self.NE, self.T
+        self.K0 = K0
+        units = self.expert_units
+        self._var("expert_layer_0_weights", (K0, NE * units[0]), ("glorot", K0, units[0]), "deep_l2_reg")
+        self._var("expert_layer_0_bias", (NE * units[0],))
+        for l in range(1, len(units)):
+            self._var(f"expert_layer_{l}_weights", (NE, units[l - 1], units[l]), ("glorot", units[l - 1], units[l]),
+                      "deep_l2_reg")
+            self._var(f"expert_layer_{l}_bias", (NE, units[l]))
+        self._var("gate_weights", (K0, T * NE), ("glorot", K0, NE), "deep_l2_reg")
+        self.towers = [self._dnn(self.H, 0, self.tower_units, "relu", prefix=f"{n}_", stream_d_rows=False)
+                       for n in self.task_names]
+        # the GEMM shapes (K, N) of the experts and gates: their workspaces are sized for the largest
+        self._gemms = ([(K0, NE * units[0]), (K0, T * NE)]
+                       + [(units[l - 1], units[l]) for l in range(1, len(units))])
+
+    def _alloc_model(self, B):
+        dev, NE, T, H = self.device, self.NE, self.T, self.H
+        buf = lambda *shape: torch.empty(*shape, dtype=F32, device=dev)  # noqa: E731
+        self.ha = [buf(B, NE * h) for h in self.expert_units]    # the stacked expert activations, Z = ha[-1]
+        self.dha = [buf(B, NE * h) for h in self.expert_units]   # dLoss/d(pre-activation) of the same
+        lda = (T * NE + 3) // 4 * 4                              # (the mixture kernels take rows of whole float4s)
+        self.A, self.dA = buf(B, lda)[:, : T * NE], buf(B, lda)[:, : T * NE]
+        self.M, self.dM = buf(B, T * H), buf(B, T * H)
+        self.P = None                                            # gate weights [B, T E]: made by gate_weights()
+        self.dx = buf(B, self.FD)
+        self.logit, self.pred, self.dlogit = buf(T, B), buf(T, B), buf(T, B)
+        self.n_t = torch.zeros(T, dtype=I64, device=dev)
+        self.loss_t = torch.zeros(T, dtype=F32, device=dev)
+        self.loss_ws = buf(ops.multitask_loss_workspace(B, T))
+        # a tower on the fused skinny-MLP kernels reads and writes contiguous rows: its own copy of M_t / dM_t
+        copies = T > 1
+        self.Mc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
+        self.dMc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
+        for t, tw in enumerate(self.towers):
+            tw._alloc(B, dev)
+            tw.out = self.logit[t].view(B, 1)  # the tower's logit lands in its row of the [T, B] buffer
+        dims = [d for kn in self._gemms for d in kn]
+        side = max(dims)
+        self._fws = buf(max(ops.dense_filter_workspace(max(k, n), max(k, n)) for k, n in self._gemms))
+        self._wws = buf(max(1, max(ops.dense_wgrad_workspace(k, n, B) for k, n in self._gemms)))
+        self._fws6 = self._wws6 = None
+        if self.dense_gemm == "bf16x6":
+            self._fws6 = buf(ops.dense6_workspace(side, side, B))
+            self._wws6 = buf(max(ops.dense_wgrad6_workspace(k, n, B) for k, n in self._gemms))
+
+    def _cols(self, buf, l, e):
+        h = self.expert_units[l]
+        return buf[:, e * h: (e + 1) * h]
+
+    def _tower_in(self, t):
+        M_t = self.M[:, t * self.H: (t + 1) * self.H]
+        if self.Mc[t] is None:
+            return M_t
+        self.Mc[t].copy_(M_t)
+        return self.Mc[t]
+
+    def _model_fwd(self, idx, dense, want_p=False):
+        """Embedding lookup, experts, gates, mixture and towers: self.logit [T, B]."""
+        if self.spec.Dn and dense is None:
+            raise ValueError("MMoE: the dense features are missing")
+        self._embed(idx, dense, False, {}, None)
+        p, NE, T = self.params, self.NE, self.T
+        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
+        ops.dense_fwd(xe, xd, p["expert_layer_0_weights"], self.ha[0], self._fws, bias=p["expert_layer_0_bias"],
+                      act=self.act, ws6=self._fws6)
+        for l in range(1, len(self.expert_units)):
+            W, b = p[f"expert_layer_{l}_weights"], p[f"expert_layer_{l}_bias"]
+            for e in range(NE):
+                ops.dense_fwd(self._cols(self.ha[l - 1], l - 1, e), None, W[e], self._cols(self.ha[l], l, e),
+                              self._fws, bias=b[e], act=self.act, ws6=self._fws6)
+        ops.dense_fwd(xe, xd, p["gate_weights"], self.A, self._fws, act="identity", ws6=self._fws6)
+        if want_p and self.P is None:
+            self.P = torch.empty(idx.shape[0], (T * NE + 3) // 4 * 4, dtype=F32, device=self.device)[:, : T * NE]
+        ops.mmoe_mix_fwd(self.ha[-1], self.A, NE, T, self.M, P=self.P if want_p else None)
+        for t, tw in enumerate(self.towers):
+            tw.forward(self._tower_in(t), None)
+
+    def forward(self, idx, dense=None, training=False, masks=None, manual_weights=None, mv=None, gate_weights=False):
+        """-> (logit [T, B], pred [T, B]); pred_t = sigmoid(logit_t) for a classification task, logit_t for a
+        regression task.  gate_weights=True also leaves the gate weights in self.P [B, T E]."""
+        if manual_weights is not None:
+            raise NotImplementedError("MMoE has no linear term: manual feature weights do not apply")
+        self._alloc(idx.shape[0])
+        self._mv = mv
+        self._seq_save = bool(training)
+        self._model_fwd(idx, dense, want_p=gate_weights)
+        ops.multitask_loss(self.logit, self.task_types, self.pred)
+        return self.logit, self.pred
+
+    def fwd_bwd(self, idx, dense, y, masks=None, mv=None):
+        """One training step's forward + backward on labels y [B, T] (float32, NaN = unobserved).  Returns the loss
+        tensor [1] (the weighted task losses + the l2 terms); self.loss_t [T] and self.n_t [T] hold the tasks' mean
+        losses and observed counts.  Gradients: self.grads, self.d_rows [B,F,D] + idx."""
+        B = idx.shape[0]
+        self._alloc(B)
+        self._mv = mv
+        self._seq_save = True
+        if y.dtype != F32 or tuple(y.shape) != (B, self.T):
+            raise ValueError(f"MMoE: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
+                             f"{tuple(y.shape)}")
+        self._model_fwd(idx, dense)
+        ops.multitask_loss(self.logit, self.task_types, self.pred, Y=y, task_weights=self.task_weights,
+                           grad_scale=self.grad_scale, dlogit=self.dlogit, n_t=self.n_t, loss_t=self.loss_t,
+                           loss=self.loss, workspace=self.loss_ws)
+        p, g, NE, T, H = self.params, self.grads, self.NE, self.T, self.H
+        ident = self.act == "identity"
+        for t, tw in enumerate(self.towers):
+            dM_t = self.dM[:, t * H: (t + 1) * H]
+            if self.dMc[t] is None:
+                tw.backward(self.dlogit[t], dM_t)
+            else:
+                tw.backward(self.dlogit[t], self.dMc[t])
+                dM_t.copy_(self.dMc[t])
+        ops.mmoe_mix_bwd(self.ha[-1], self.A, NE, T, self.dM, self.dha[-1], self.dA)
+        if not ident:
+            ops.act_bwd_(self.dha[-1], self.ha[-1], self.act)
+        for l in range(len(self.expert_units) - 1, 0, -1):
+            W = p[f"expert_layer_{l}_weights"]
+            gW, gb = g[f"expert_layer_{l}_weights"], g[f"expert_layer_{l}_bias"]
+            for e in range(NE):
+                prev, da = self._cols(self.ha[l - 1], l - 1, e), self._cols(self.dha[l], l, e)
+                ops.dense_wgrad(prev, None, da, gW[e], self._wws, db=gb[e], ws6=self._wws6)
+                ops.dense_fwd(da, None, W[e], self._cols(self.dha[l - 1], l - 1, e), self._fws, transposed=True,
+                              epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD, act=self.act,
+                              aux1=None if ident else prev, ws6=self._fws6)
+        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
+        ops.dense_wgrad(xe, xd, self.dha[0], g["expert_layer_0_weights"], self._wws, db=g["expert_layer_0_bias"],
+                        ws6=self._wws6)
+        ops.dense_wgrad(xe, xd, self.dA, g["gate_weights"], self._wws, ws6=self._wws6)
+        # dLoss/dx of the gates and of the experts, summed into d_rows (the dense inputs need no gradient)
+        ops.dense_fwd(self.dA, None, p["gate_weights"][: self.FD], self.dx, self._fws, transposed=True,
+                      epilogue=ops.DENSE_ADD, ws6=self._fws6)
+        ops.dense_fwd(self.dha[0], None, p["expert_layer_0_weights"][: self.FD], self.d_rows.view(-1, self.FD),
+                      self._fws, transposed=True, epilogue=ops.DENSE_ADD, aux1=self.dx, ws6=self._fws6)
+        self._add_l2_grads()
+        self._seq_bwd()
+        return self._add_l2(self.loss)
+
+    def gate_weights(self, idx, dense=None, mv=None):
+        """The gate weights p [B, T, E] of a batch (an inference forward with rm_mmoe_mix_fwd's optional output)."""
+        self.forward(idx, dense, mv=mv, gate_weights=True)
+        return self.P.reshape(idx.shape[0], self.T, self.NE)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine, "pnn": PNNEngine,
-           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine}
+           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine, "mmoe": MMoEEngine}

@@ -1809,3 +1809,92 @@ def read_group_auc(out):
     """(value, groups, scored_groups, weight, P, flags) of a grouped-AUC record: one device-to-host copy."""
     r = out.cpu().numpy()
     return (float(r[:1].view("float64")[0]),) + tuple(int(v) for v in r[1:6])
+
+
+# ---- multi-task learning: MMoE's gate mixture and the loss head for several labels (csrc/mmoe.hip) ---------------
+MMOE_TILE = {"tile": 0, "cap": 1}  # RM_MMOE_TILE / RM_MMOE_CAP
+MMOE_LIMITS = "1 <= E <= 16 experts, 1 <= T <= 8 tasks, H a multiple of 4 in 4..512, row strides multiples of 4 floats"
+MMOE_H_MIN, MMOE_H_MAX = 4, 512
+TASK_TYPES = {"classification": 0, "regression": 1}
+
+
+def mmoe_mix_supported(E, T, H):
+    """rm_mmoe_mix_supported: 1 <= E <= 16, 1 <= T <= 8, H a multiple of 4 in 4..512."""
+    return bool(_lib.lib().rm_mmoe_mix_supported(int(E), int(T), int(H)))
+
+
+def mmoe_mix_tile(E, T, H, which="tile", backward=False):
+    """rm_mmoe_mix_tile: "tile" = the examples a block of the mixture kernels owns per tile, "cap" = the cap of their
+    grids (a block walks the batch again from B > cap * tile on)."""
+    n = int(_lib.lib().rm_mmoe_mix_tile(int(E), int(T), int(H), int(bool(backward)), MMOE_TILE[which]))
+    if n < 0:
+        raise ValueError(f"mmoe_mix: E={E}, T={T}, H={H} unsupported ({MMOE_LIMITS})")
+    return n
+
+
+def _mmoe_dims(Z, A, E, T):
+    E, T = int(E), int(T)
+    if Z.dim() != 2 or A.dim() != 2 or E < 1 or T < 1 or Z.shape[1] % E or A.shape[1] != T * E:
+        raise ValueError(f"mmoe_mix: Z {tuple(Z.shape)} must be [B, E H] and A {tuple(A.shape)} [B, T E] "
+                         f"(E={E}, T={T})")
+    return int(Z.shape[0]), E, T, int(Z.shape[1]) // E
+
+
+def mmoe_mix_fwd(Z, A, E, T, M, P=None):
+    """rm_mmoe_mix_fwd: Z [B, E H] expert outputs, A [B, T E] gate logits -> M [B, T H], M_t = softmax(A_t) Z, and -
+    when given - P [B, T E], the gate weights.  Every operand may be a column range of a wider buffer (16-byte aligned,
+    row stride a multiple of 4 floats); only the own columns are written.  The limits are checked by the library."""
+    B, E, T, H = _mmoe_dims(Z, A, E, T)
+    pz, ldz = _strided_rows(Z, "Z", B, E * H, True)
+    pa, lda = _strided_rows(A, "A", B, T * E, True)
+    pm, ldm = _strided_rows(M, "M", B, T * H, True)
+    pp, ldp = (None, 0) if P is None else _strided_rows(P, "P", B, T * E, True)
+    _lib.call("rm_mmoe_mix_fwd", pz, ldz, pa, lda, B, E, T, H, pm, ldm, pp, ldp, _stream())
+
+
+def mmoe_mix_bwd(Z, A, E, T, dM, dZ, dA):
+    """rm_mmoe_mix_bwd: dM [B, T H] = dLoss/dM -> dZ [B, E H] and dA [B, T E] (column ranges as in mmoe_mix_fwd; only
+    their own columns are written).  The gate weights are recomputed.  No workspace; deterministic."""
+    B, E, T, H = _mmoe_dims(Z, A, E, T)
+    pz, ldz = _strided_rows(Z, "Z", B, E * H, True)
+    pa, lda = _strided_rows(A, "A", B, T * E, True)
+    pdm, lddm = _strided_rows(dM, "dM", B, T * H, True)
+    pdz, lddz = _strided_rows(dZ, "dZ", B, E * H, True)
+    pda, ldda = _strided_rows(dA, "dA", B, T * E, True)
+    _lib.call("rm_mmoe_mix_bwd", pz, ldz, pa, lda, pdm, lddm, B, E, T, H, pdz, lddz, pda, ldda, _stream())
+
+
+def multitask_loss_workspace(B, T):
+    """Floats of workspace for multitask_loss (rm_multitask_loss_workspace)."""
+    n = int(_lib.lib().rm_multitask_loss_workspace(int(B), int(T)))
+    if n < 0:
+        raise ValueError(f"multitask_loss: B={B}, T={T} unsupported (B >= 1, 1 <= T <= 8 tasks)")
+    return n
+
+
+def multitask_loss(logit, task_types, pred, *, Y=None, task_weights=None, grad_scale=1.0, dlogit=None, n_t=None,
+                   loss_t=None, loss=None, workspace=None):
+    """rm_multitask_loss: logit [T, B], task_types T names ("classification" / "regression") -> pred [T, B]; with
+    labels Y [B, T] (float32, NaN = unobserved) and task_weights (T floats) also dlogit [T, B] = w_t dl/dlogit / n_t *
+    grad_scale (0 where unobserved), n_t [T] int64, loss_t [T] and loss [1] = sum_t w_t loss_t."""
+    if logit.dim() != 2:
+        raise ValueError(f"logit: expected [T, B], got {tuple(logit.shape)}")
+    T, B = int(logit.shape[0]), int(logit.shape[1])
+    if len(task_types) != T:
+        raise ValueError(f"multitask_loss: {len(task_types)} task types for {T} rows of logits")
+    types = _int_array([TASK_TYPES[t] for t in task_types])
+    train = any(t is not None for t in (dlogit, n_t, loss_t, loss))
+    weights = None
+    if train:
+        if Y is None or workspace is None:
+            raise ValueError("multitask_loss: the loss and its gradient need labels Y and a workspace")
+        w = [1.0] * T if task_weights is None else [float(v) for v in task_weights]
+        if len(w) != T:
+            raise ValueError(f"multitask_loss: {len(w)} task weights for {T} tasks")
+        weights = (ctypes.c_float * T)(*w)
+        _need_workspace("multitask_loss", workspace, multitask_loss_workspace(B, T))
+    _lib.call("rm_multitask_loss", _chk(logit, "logit", F32), _chk(Y, "Y", F32, (B, T), allow_none=not train),
+              types, weights, float(grad_scale), B, T, _chk(pred, "pred", F32, (T, B)),
+              _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
+              _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
+              _chk(workspace, "workspace", F32, allow_none=True), _stream())

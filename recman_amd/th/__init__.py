@@ -11,6 +11,7 @@ from .DeepFM import DeepFM
 from .FiBiNET import FiBiNET
 from .FmFM import FmFM, FwFM
 from .MaskNet import MaskNet
+from .MMoE import MMoE
 from .PNN import PNN
 from .BST import BST
 from .DIEN import DIEN
@@ -22,6 +23,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "PNN", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "MMoE", "PNN", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]
