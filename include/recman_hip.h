@@ -241,7 +241,7 @@ int rm_mlp_bwd(const float *xe, const float *xd, int FD, int Dn, int NL, const i
  * FMLayer :457-478, DNN :576-609, PredictionLayer :796-808, create_loss utils.py:192-198) - what rm_embed_mlp_fwd
  * followed by rm_mlp_bwd compute, without E, S, h_l or dh_l ever reaching HBM (every DeepFM gradient except the
  * parameter reductions is local to the example).  Shapes: fused-row table [R, table_ld] (rows [16 embedding | bias
- * entry | linear weight | ...], table_ld a multiple of 4, >= 20), D = 16, F <= 26, Dn <= 16, NL = 2 hidden layers
+ * entry | linear weight | ...], table_ld a multiple of 4, >= 20, < 2^30), D = 16, F <= 26, Dn <= 16, NL = 2 hidden layers
  * of width <= 32 (rm_deepfm_step_supported); FM, bias tables, linear term and DNN all on, no dropout masks - the
  * callers use the separate entry points for anything else.
  * In: idx [B,F] int64, field_off [F], dense [B,Dn] (NULL when Dn = 0), labels y (int64) or y_f (float),
@@ -269,6 +269,10 @@ int rm_deepfm_step(const int64_t *idx, const float *table, int64_t table_ld, con
                    float *const *dW, float *const *db, float *d_w_out, float *d_w0_out, float *d_lin_w_dense,
                    float *d_lin_w0, float *workspace, int64_t packed_rows, const float *lin_field_mask, int flags,
                    rm_stream_t stream);
+/* Test aid, not a product path: fills the LDS of every CU with one 32-bit pattern - workgroups of rm_deepfm_step's
+ * shape (512 threads, its full dynamic LDS size), twice the CU count of them, every word written with ds_write -
+ * so that what the step kernel finds in LDS before it has written it is known (tests/test_gpu_step_stale_lds.py). */
+int rm_debug_lds_fill(unsigned pattern, rm_stream_t stream);
 
 /* Epilogues of the library-GEMM DNN path (wide hidden layers, layers.py:593-601):
  * rm_bias_act: x[b,j] = act(x[b,j] + bias[j]) in place (bias may be NULL = a bias of +0.0: the add is still made,

@@ -30,13 +30,18 @@
 //    entry loads and the head's prefetch loads are asm statements behind hand-counted s_waitcnt vmcnt(N) (entry_load),
 //    and every wave issues the same vector-memory operations in every segment so that each count is one constant
 //    (derived where it is used).  The tile loops hold no s_waitcnt vmcnt(0).
+//  * LDS is waited for by count too where it matters: the reads of a worker's backward are issued up front in one
+//    fixed order (published dh0 / g / g*S, row numbers, slot 0 .. 3) and each row DMA D_j, which overwrites the image
+//    slot j has just read, stands behind s_waitcnt lgkmcnt(3 (3 - j)) - slot j's reads back, the later slots' still
+//    in flight under the MFMA groups in front of them (lds_load / slot_wait; the only lgkmcnt(0) in front of the
+//    matrix work is the tile barrier's).
 //  * one workgroup barrier per tile.  Segment s (between barriers s-1 and s): workers run backward(s-2) + the DMAs
 //    of tile s+1, then forward(s); the head runs epilogue(s-1) meanwhile.  forward(s) -> [barrier] -> epilogue(s) ->
 //    [barrier] -> backward(s): the head's serial chain (32 dependent MFMAs + the loss) always overlaps the workers'
 //    matrix work of the neighbouring tiles.
 //  * per-block partial sums (dW0 slab, small gradients, loss) go to the same finishing launch as rm_mlp_bwd's
 //    (mlp_finish_kernel): fixed order, deterministic.
-// Measured history and the per-wave phase times: profiles/r03_deepfm_step.md.
+// Measured history and the per-wave phase times: profiles/r03_deepfm_step.md, r04_deepfm_step.md, r05_deepfm_step.md.
 #include "mlp_internal.h"
 #include "rm_common.h"
 
@@ -97,7 +102,7 @@ __device__ unsigned long long rm_step_stamp_buf[256 * 8 * 8];
 struct StepArgs {
   const int64_t *idx, *field_off;
   const char *table;
-  int64_t row_bytes;
+  unsigned row_bytes;  // (< 2^32, rm_deepfm_step checks: row number x row size is ONE 32 x 32 -> 64 bit multiply)
   const float *dense;
   const int64_t *y;
   const float *y_f;
@@ -141,7 +146,7 @@ __device__ __forceinline__ f32x4 mfma16w(float a, float b, f32x4 c) {  // the wo
 // groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32): with lane = (example n = lane & 15, slice q = lane >> 4) a
 // group holds every example once, examples 4..11 with the other slice parity - swz = 3 for examples 8..15 gives the
 // four rows that share a bank window (n mod 4 equal) four different positions in either group.
-__device__ __forceinline__ int swz(int r) { return ((r >> 3) & 1) * 3; }
+__device__ __forceinline__ constexpr int swz(int r) { return ((r >> 3) & 1) * 3; }
 
 // One LDS-DMA piece: lane l's 16 bytes at src land at LDS address lds_dst + 16 l (lds_dst wave-uniform).  Through the
 // builtin (hipcc sets M0); hipcc does NOT order LDS reads behind it - that is wait_vm's job.
@@ -168,6 +173,67 @@ template <int YOUNGER>
 __device__ __forceinline__ void entry_wait(float &v) {
   asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "n"(YOUNGER) : "memory");
 }
+
+// The workers' backward reads LDS through asm statements that hipcc does NOT count (as entry_load), behind hand-counted
+// s_waitcnt lgkmcnt(N).  Why not plain loads: (1) hipcc books an LDS-DMA (global_load_lds) as a pending LDS access
+// that may return out of order, so behind the first D_j of a segment its wait for ANY LDS read still in flight is
+// s_waitcnt lgkmcnt(0) - the drain these waits replace; (2) it pairs and splits reads as it likes, and a count is a
+// number of INSTRUCTIONS.  Here the instructions are written out, so the R phase is exactly (in issue order, per
+// segment, every segment - a segment without a backward reads whatever the images hold and uses none of it):
+//     P:    dhB x 2 (ds_read_b128), dT x 8 (ds_read_b32), gS (b128), g (b32)                                  12
+//     rid:  rid[0..3] (ds_read_b32); PACKED: rid[j] rp[0][j] alternating                                   4 (8)
+//     slot j = 0, 1, 2, 3:  columns of examples q, 4 + q and 8 + q, 12 + q (2 x ds_read2st64_b32), e4 (b128)   3 each
+// Between the loop top and D_3 the worker issues NO other LDS operation and no scalar memory read (those share the
+// counter and return out of order), and a wave's LDS operations return in issue order.  So "at most N outstanding" =
+// everything but the youngest N has returned, and in front of D_j, which overwrites the ring image that slot j's
+// backward reads (tile s + 1 replaces tile s - 2), stands
+//     s_waitcnt lgkmcnt(3 (3 - j)) = 9, 6, 3, 0     behind slot j's last read: the 3 reads of each slot j + 1 .. 3
+// i.e. of the R = 28 (PACKED 32) reads of the segment the first R_j = R - 3 (3 - j) have returned at D_j: P, rid and
+// slot 0 before the first MFMA group, each later slot under the matrix work of the slots before it.  D_3's count is 0
+// because slot 3 is read last - three MFMA groups stand in front of it.
+// Invariant: a ring image is overwritten by D_j only after THIS wave's reads of it have returned, and no other wave
+// reads it (tile_barrier).
+// Between a read and the wait that covers it hipcc believes the register already holds the value: every wait names
+// "+v" the registers it covers (their consumers cannot move in front of it), and tests/test_step_lds_waits_host.py
+// checks the emitted code of all six instantiations - the counter replayed over the loop, no instruction naming a
+// destination register between its read and its wait, no scratch access.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int OFF, class T>
+__device__ __forceinline__ void lds_load(T &dst, unsigned addr) {  // one ds_read of sizeof(T) bytes at addr + OFF
+  static_assert(sizeof(T) == 4 || sizeof(T) == 16, "b32 or b128");
+  if (sizeof(T) == 4) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+  else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void lds_load_pair(f32x2 &dst, unsigned addr) {  // the dwords at addr and addr + 256
+  asm volatile("ds_read2st64_b32 %0, %1 offset1:1" : "=v"(dst) : "v"(addr) : "memory");
+}
+struct SlotRegs {  // what the backward reads of a slot: x[example 4 es + q][k = n] as col[es >> 1][es & 1], slice q of example n
+  f32x2 col[2];
+  f32x4 e4;
+};
+#define RM_SLOT_REGS(r) "+v"((r).col[0]), "+v"((r).col[1]), "+v"((r).e4)
+// in front of D_0: P, rid and slot 0
+template <bool PACKED>
+__device__ __forceinline__ void slot_wait0(f32x4 (&dhB)[2], float (&dT)[2][4], f32x4 &gS, float &g, unsigned (&rid)[4],
+                                           unsigned (&rp0)[4], SlotRegs &r) {
+  if (PACKED)
+    asm volatile("s_waitcnt lgkmcnt(9)"
+                 : "+v"(dhB[0]), "+v"(dhB[1]), "+v"(dT[0][0]), "+v"(dT[0][1]), "+v"(dT[0][2]), "+v"(dT[0][3]),
+                   "+v"(dT[1][0]), "+v"(dT[1][1]), "+v"(dT[1][2]), "+v"(dT[1][3]), "+v"(gS), "+v"(g), "+v"(rid[0]),
+                   "+v"(rid[1]), "+v"(rid[2]), "+v"(rid[3]), "+v"(rp0[0]), "+v"(rp0[1]), "+v"(rp0[2]), "+v"(rp0[3]),
+                   RM_SLOT_REGS(r)::"memory");
+  else
+    asm volatile("s_waitcnt lgkmcnt(9)"
+                 : "+v"(dhB[0]), "+v"(dhB[1]), "+v"(dT[0][0]), "+v"(dT[0][1]), "+v"(dT[0][2]), "+v"(dT[0][3]),
+                   "+v"(dT[1][0]), "+v"(dT[1][1]), "+v"(dT[1][2]), "+v"(dT[1][3]), "+v"(gS), "+v"(g), "+v"(rid[0]),
+                   "+v"(rid[1]), "+v"(rid[2]), "+v"(rid[3]), RM_SLOT_REGS(r)::"memory");
+}
+__device__ __forceinline__ void slot_wait(int j, SlotRegs &r) {  // in front of D_j, j = 1, 2, 3 (constant after unrolling)
+  if (j == 1) asm volatile("s_waitcnt lgkmcnt(6)" : RM_SLOT_REGS(r)::"memory");
+  else if (j == 2) asm volatile("s_waitcnt lgkmcnt(3)" : RM_SLOT_REGS(r)::"memory");
+  else asm volatile("s_waitcnt lgkmcnt(0)" : RM_SLOT_REGS(r)::"memory");
+}
+static_assert(kSlots == 4, "slot_wait's counts");
 
 // waits until at most `younger` (0..24) of this wave's vector-memory operations are outstanding
 __device__ __forceinline__ void wait_vm(int younger) {
@@ -259,9 +325,11 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
   // 4 es + q.  A slot's base is wave-uniform (field, ring buffer): base + lane offset is ONE add per access (a
   // `slot is a field ? ring : dense ring` select on the per-lane pointer was two v_cndmask per access)
   const int lo_slice = n * 64 + 16 * (q ^ swz(n));
-  int lo_col[4];
+  int lo_col[2];  // examples q (and 4 + q, 256 bytes on) and 8 + q (and 12 + q)
 #pragma unroll
-  for (int es = 0; es < 4; ++es) lo_col[es] = (4 * es + q) * 64 + 16 * ((n >> 2) ^ swz(4 * es + q)) + 4 * (n & 3);
+  for (int h = 0; h < 2; ++h) lo_col[h] = (8 * h + q) * 64 + 16 * ((n >> 2) ^ swz(8 * h + q)) + 4 * (n & 3);
+  static_assert(swz(0) == swz(4) && swz(3) == swz(7) && swz(8) == swz(12) && swz(11) == swz(15), "a pair of column reads shares its swizzle");
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem;  // LDS byte address of smem
   const int lo_row = n * F * 64 + 16 * q;  // d_rows: example n, slice q (the field adds 64 f)
   auto slot_base = [&](int j, int tile) {  // LDS byte offset of slot j's image of `tile` (wave-uniform)
     const int ring = oX + ((tile + 6) % 3) * kXBufB + fld[j] * kSlotB, dn = oDense + (tile & 3) * kSlotB;
@@ -307,6 +375,9 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
   constexpr int kSP = PACKED ? 2 : 1;
   constexpr int kYoungerE = 7 + 4 * kSP, kYounger = 8 + 6 * kSP;
   static_assert(kYounger <= 24, "wait_vm's range");
+  // (a kernel argument first used inside the loop is waited for THERE, by an s_waitcnt lgkmcnt(0) per use: a drain of
+  // the LDS reads in flight - the row size is used here once, and the scalar load's wait stands in front of the loop)
+  asm volatile("" ::"s"(a.row_bytes) : "memory");
   ST_DECL;
   ST_ADD(0);  // prologue
 
@@ -319,45 +390,39 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
     // hipcc's own wait in front of each use is a counted one (same order of the four additions as before)
     float side_sum = 0.f;
     // ------------------------------------------------------------ backward of tile s - 2, rows of tile s + 1
-    // Phases WITHOUT per-slot branches (one basic block each, so that hipcc interleaves the slots' MFMA chains and
-    // keeps their LDS reads in flight together): R read everything the backward needs of the 4 slots, D issue the
-    // DMAs / entry loads of tile s + 1 into the slots just read, M 64 MFMAs, S FM term + stores.  Empty slots run on
+    // Phases WITHOUT per-slot branches: R issue every LDS read the backward needs of the 4 slots, then per slot: wait
+    // for that slot's reads (counted), D issue the DMA / entry load of tile s + 1 into the slot just read, M its 16
+    // MFMAs, S FM term + store of the slot before.  Empty slots run on
     // the zero image (oZero) with zero weights (their dW0 accumulators are never stored, their d_rows store is
     // dropped).  (They used to run on field 0's ring buffer - worker 0's DMA, which no wait of THIS wave covers: zero
     // weights times the NaN bit patterns of a buffer not yet written are NaN.)
     {
       const int tb = s - 2, td = s + 1;
-      const char *pub = smem + oPub + (tb & 1) * kPubB;
       char *xd = smem + oX + ((td + 3) % 3) * kXBufB;  // (the same buffer: tile s + 1 replaces tile s - 2)
-      // (without a backward the S phase still runs and stores - into a buffer resource of zero records: zeros here)
-      f32x4 dhB[2], gS = f32x4{0.f, 0.f, 0.f, 0.f}, e4[kSlots];
-      float dT[2][4], g = 0.f, col[kSlots][4];
-#pragma unroll
-      for (int j = 0; j < kSlots; ++j) e4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (hasB) {  // ---- R
-#pragma unroll
-        for (int j = 0; j < kSlots; ++j) {
-          const char *xs = smem + slot_base(j, tb);
-#pragma unroll
-          for (int es = 0; es < 4; ++es)  // x[example 4 es + q][k = n]: slice n >> 2 of that row
-            col[j][es] = *reinterpret_cast<const float *>(xs + lo_col[es]);
-          e4[j] = *reinterpret_cast<const f32x4 *>(xs + lo_slice);
-        }
+      // ---- R: every LDS read of the backward, as asm statements in the ONE order lds_load's comment derives the
+      // counts for - P | rid | slot 0 | slot 1 | slot 2 | slot 3 - and never drained: what the first MFMA group needs
+      // comes back first, the later slots' reads run under the matrix work.  Unconditional: a segment without a
+      // backward reads whatever the images hold (its MFMAs are skipped, its stores go to a buffer resource of zero
+      // records), so that every segment issues the same LDS operations and each count is one constant
+      f32x4 dhB[2], gS;
+      float dT[2][4], g;
+      SlotRegs sr[kSlots];
+      unsigned rid[kSlots];
+      {
+        const unsigned pub = lds0 + oPub + (tb & 1) * kPubB;
+        lds_load<kPubDh>(dhB[0], pub + lane * 16);
+        lds_load<kPubDh + 1024>(dhB[1], pub + lane * 16);
+        const unsigned pt = pub + (q * kLDT + n) * 4;  // dh0[example 4 es + q][unit 16 uh + n]
 #pragma unroll
         for (int uh = 0; uh < 2; ++uh) {
-          dhB[uh] = *reinterpret_cast<const f32x4 *>(pub + kPubDh + (uh * 64 + lane) * 16);
-#pragma unroll
-          for (int es = 0; es < 4; ++es)
-            dT[uh][es] = *reinterpret_cast<const float *>(pub + kPubDT + ((4 * es + q) * kLDT + 16 * uh + n) * 4);
+          lds_load<kPubDT + (0 * 4 * kLDT) * 4>(dT[uh][0], pt + 64 * uh);
+          lds_load<kPubDT + (1 * 4 * kLDT) * 4>(dT[uh][1], pt + 64 * uh);
+          lds_load<kPubDT + (2 * 4 * kLDT) * 4>(dT[uh][2], pt + 64 * uh);
+          lds_load<kPubDT + (3 * 4 * kLDT) * 4>(dT[uh][3], pt + 64 * uh);
         }
-        gS = *reinterpret_cast<const f32x4 *>(pub + kPubGS + lane * 16);
-        g = *reinterpret_cast<const float *>(pub + kPubG + lane * 4);
+        lds_load<kPubGS>(gS, pub + lane * 16);
+        lds_load<kPubG>(g, pub + lane * 4);
       }
-      ST_ADD(1);  // R
-      // ---- D, M, S interleaved: a vector-memory instruction waits for a slot of the CU's memory pipeline (the
-      // younger waves of a SIMD pair sat up to 6,000 cycles per tile in a burst of 8 of them, tools/probe/
-      // step_stamps.py) - issued one at a time between groups of 16 MFMAs, the wait runs under the matrix work
-      unsigned rid[kSlots];
       if (PACKED) {  // after this: rp[g] = tile s + 1 - g; rp[3] = tile s - 2, whose gradients are stored below
 #pragma unroll
         for (int j = 0; j < kSlots; ++j) {
@@ -367,15 +432,26 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
         }
       }
       {  // (without a tile s + 1: whatever the buffer holds - such row numbers are never used)
-        const unsigned *rowid = reinterpret_cast<const unsigned *>(smem + oRow + (td & 1) * kRowB);
+        const unsigned rowid = lds0 + oRow + (td & 1) * kRowB;
 #pragma unroll
         for (int j = 0; j < kSlots; ++j) {
-          rid[j] = rowid[fld[j] * 16 + (lane >> 2)];
-          if (PACKED) rp[0][j] = rowid[fld[j] * 16 + n];
+          lds_load<0>(rid[j], rowid + (fld[j] * 16 + (lane >> 2)) * 4);
+          if (PACKED) lds_load<0>(rp[0][j], rowid + (fld[j] * 16 + n) * 4);
         }
       }
-      // the old rows have been READ (their values are in registers) before the new ones are requested
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < kSlots; ++j) {
+        const unsigned xs = lds0 + slot_base(j, tb);
+        // x[example 4 es + q][k = n], slice n >> 2 of that row: one read for es = 0, 1 and one for es = 2, 3 (the
+        // examples 4 es + q and 4 es + 4 + q lie four rows = 256 bytes apart in the same half of the tile: one swizzle)
+        lds_load_pair(sr[j].col[0], xs + lo_col[0]);
+        lds_load_pair(sr[j].col[1], xs + lo_col[1]);
+        lds_load<0>(sr[j].e4, xs + lo_slice);
+      }
+      ST_ADD(1);  // R
+      // ---- D, M, S interleaved: a vector-memory instruction waits for a slot of the CU's memory pipeline (the
+      // younger waves of a SIMD pair sat up to 6,000 cycles per tile in a burst of 8 of them, tools/probe/
+      // step_stamps.py) - issued one at a time between groups of 16 MFMAs, the wait runs under the matrix work
       const int64_t ex0 = ((int64_t)blockIdx.x + tb * tstride) * 16;
       const int64_t left = a.B - ex0;
       const int rows_t = left < 16 ? (int)left : 16;
@@ -409,6 +485,11 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           // empty slots, and every slot of a segment without a tile s + 1, fetch row 0 into the sink: every worker
           // issues the SAME vector-memory operations in EVERY segment, so the hand-counted wait of the forward is one
           // constant, and hipcc's own counted waits (for sdv) see one path through the loop
+          // D_j overwrites the image that slot j's backward reads (tile s + 1 replaces tile s - 2): slot j's reads
+          // have returned first - and only they, the later slots' stay in flight under this slot's MFMAs.  (The
+          // first wait also covers rid: it stands in front of the row address.)
+          if (j == 0) slot_wait0<PACKED>(dhB, dT, gS, g, rid, rp[0], sr[0]);
+          else slot_wait(j, sr[j]);
           const bool live = sx[j] && hasD;
           const char *row = a.table + ((RM_STEP_ABL & 4) || !live ? 0 : (int64_t)rid[j] * a.row_bytes);
           if (!(RM_STEP_ABL & 1)) entry_load(sdv[j], row + side_off);
@@ -419,10 +500,16 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
         if (hasB) {
 #pragma unroll
           for (int es = 0; es < 4; ++es) {
-            dw[j][0] = mfma16w(col[j][es], dT[0][es], dw[j][0]);
-            dw[j][1] = mfma16w(col[j][es], dT[1][es], dw[j][1]);
+            // no MFMA directly behind the one that writes its accumulator (a dependent 16x16x4 issues after 40 cycles,
+            // an independent one after 32); sched_barrier(0): hipcc's own order put the acc chain back to back
             acc[j] = mfma16w(w0x[j][0][es], dhB[0][es], acc[j]);
+            __builtin_amdgcn_sched_barrier(0);
+            dw[j][0] = mfma16w(sr[j].col[es >> 1][es & 1], dT[0][es], dw[j][0]);
+            __builtin_amdgcn_sched_barrier(0);
             acc[j] = mfma16w(w0x[j][1][es], dhB[1][es], acc[j]);
+            __builtin_amdgcn_sched_barrier(0);
+            dw[j][1] = mfma16w(sr[j].col[es >> 1][es & 1], dT[1][es], dw[j][1]);
+            __builtin_amdgcn_sched_barrier(0);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -431,20 +518,20 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           // slots without an embedding field: out of range, the store is dropped - every tile issues 4 of them
           const int i = j - 1;
           f32x4 o;
-          o.x = acc[i].x + (gS.x - g * e4[i].x);
-          o.y = acc[i].y + (gS.y - g * e4[i].y);
-          o.z = acc[i].z + (gS.z - g * e4[i].z);
-          o.w = acc[i].w + (gS.w - g * e4[i].w);
+          o.x = acc[i].x + (gS.x - g * sr[i].e4.x);
+          o.y = acc[i].y + (gS.y - g * sr[i].e4.y);
+          o.z = acc[i].z + (gS.z - g * sr[i].e4.z);
+          o.w = acc[i].w + (gS.w - g * sr[i].e4.w);
           store_row(i, o);
         }
       }
       {
         const int i = kSlots - 1;
         f32x4 o;
-        o.x = acc[i].x + (gS.x - g * e4[i].x);
-        o.y = acc[i].y + (gS.y - g * e4[i].y);
-        o.z = acc[i].z + (gS.z - g * e4[i].z);
-        o.w = acc[i].w + (gS.w - g * e4[i].w);
+        o.x = acc[i].x + (gS.x - g * sr[i].e4.x);
+        o.y = acc[i].y + (gS.y - g * sr[i].e4.y);
+        o.z = acc[i].z + (gS.z - g * sr[i].e4.z);
+        o.w = acc[i].w + (gS.w - g * sr[i].e4.w);
         store_row(i, o);
       }
     }
@@ -829,7 +916,31 @@ __global__ __launch_bounds__(512) void deepfm_step_kernel(StepArgs a) {
   }
 }
 
+// test aid (rm_debug_lds_fill): every byte of a CU's LDS that the step can allocate, set to one bit pattern
+__global__ __launch_bounds__(512) void lds_fill_kernel(unsigned pattern) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  volatile unsigned *p = reinterpret_cast<volatile unsigned *>(smem);
+  for (int i = threadIdx.x; i < kLdsBytes / 4; i += 512) p[i] = pattern;
+}
+
 }  // namespace
+
+// What the step kernel finds in LDS is whatever the last workgroup on that CU left there.  This makes it ONE known
+// pattern: workgroups of the step's shape and full dynamic LDS size (one fits a CU), twice as many as the device has
+// CUs, every word of the allocation written with ds_write.  A read of LDS that nothing of the step has written yet -
+// the kernel's one known race showed as such a read - then gives the same bits in every run (a quiet NaN, or zero),
+// not a flicker.  A test aid: no product path calls it.
+extern "C" int rm_debug_lds_fill(unsigned pattern, rm_stream_t stream) {
+  int dev = 0, cus = 0;
+  RM_REQUIRE(hipGetDevice(&dev) == hipSuccess &&
+                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0,
+             "rm_debug_lds_fill: no device");
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lds_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            kLdsBytes);
+  hipLaunchKernelGGL(lds_fill_kernel, dim3(2 * cus), dim3(512), kLdsBytes, (hipStream_t)stream, pattern);
+  RM_CHECK_LAUNCH("rm_debug_lds_fill");
+  return RM_OK;
+}
 
 #ifdef RM_STEP_STAMP
 extern "C" int rm_debug_step_stamps(unsigned long long *host, int n) {
@@ -868,6 +979,7 @@ extern "C" int rm_deepfm_step(const int64_t *idx, const float *table, int64_t ta
   RM_REQUIRE((y != nullptr) != (y_f != nullptr), "rm_deepfm_step: exactly one of y / y_f");
   RM_REQUIRE(task == 0 || task == 1, "rm_deepfm_step: task must be 0 or 1");
   RM_REQUIRE(rm_aligned16(table) && rm_aligned16(d_rows), "rm_deepfm_step: table / d_rows must be 16-byte aligned");
+  RM_REQUIRE(table_ld < (1ll << 30), "rm_deepfm_step: table_ld out of range");
   RM_REQUIRE(packed_rows >= 0 && packed_rows * 80 < (1ll << 31), "rm_deepfm_step: packed_rows out of range");
   const int K = 16 * F + Dn, Kp = ((K + 63) / 64) * 64;
   const int64_t ntiles = (B + 15) / 16;

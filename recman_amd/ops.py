@@ -1294,6 +1294,12 @@ def deepfm_step_workspace(F, Dn):
     return int(_lib.lib().rm_deepfm_step_workspace(int(F), int(Dn)))
 
 
+def debug_lds_fill(pattern):
+    """Test aid (rm_debug_lds_fill): every CU's LDS, as far as deepfm_step allocates it, filled with one 32-bit
+    pattern on the current stream - what the step then finds in LDS before it has written it is known."""
+    _lib.call("rm_debug_lds_fill", int(pattern) & 0xFFFFFFFF, _stream())
+
+
 def deepfm_step(idx, rows, field_off, D, table_ld, dense, y, Ws, bs, w_out, w0_out, lin_w_dense, lin_w0, act, task,
                 d_rows, logit, pred, dlogit, loss, dW, db, d_w_out, d_w0_out, d_lin_w_dense, d_lin_w0, workspace,
                 grad_scale=1.0, stream_rows=False, stream_d_rows=False, skip_finish=False, packed_rows=0,
