@@ -1246,6 +1246,56 @@ int rm_multitask_loss(const float *logit, const float *Y, const int *task_type, 
                       float grad_scale, int64_t B, int T, float *pred, float *dlogit, int64_t *n_t, float *loss_t,
                       float *loss, float *workspace, rm_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Two-tower retrieval: the in-batch softmax loss over the scores of every user row against every item row of the
+ * batch (DSSM / YouTube-DNN; the logQ correction of Yi et al., RecSys 2019), forward and backward, and the row
+ * normalisation of the tower outputs (csrc/inbatch.hip).  Nothing in the reference implements them: every model of
+ * it scores one (user, item) row.  U and V are [B, H] float32, each a pointer and a row stride in floats: a column
+ * range of a wider buffer works; pointers 16-byte aligned, strides multiples of 4 floats and >= H; columns outside
+ * the range are never read or written.
+ *     S_ij    = scale <U_i, V_j> - logq_j                  (logq NULL: 0; applied to the diagonal too)
+ *     allowed = (j == i) or item_id NULL or item_id_j != item_id_i       (accidental hits are masked out)
+ *     lse_i   = log sum_{j allowed} exp(S_ij)              (max-subtracted, online over the column tiles)
+ *     l_i     = lse_i - S_ii = row_loss_i
+ *     W       = sum_i w_i (w NULL: all 1; w_i >= 0);   loss = sum_i w_i l_i / W   (W == 0: loss 0)
+ *     rank_i  = #{ j allowed, j != i : S_ij > S_ii }       (int32, on the kernel's own float32 S; may be NULL)
+ *   backward: P_ij = exp(S_ij - lse_i) for allowed j, else 0;  G_ij = grad_scale w_i / W (P_ij - [i == j])
+ *     dU_i = scale sum_j G_ij V_j;   dV_j = scale sum_i G_ij U_i          (W == 0: both exactly 0)
+ * S, P and G [B, B] never reach HBM: the products run on the exact-f32 MFMA from tiles in LDS, the backward
+ *   recomputes S from U, V and the saved lse.  dU is owned by row tiles, dV by column tiles.  No float atomics; loss
+ *   and W are fixed-order two-stage sums in double.
+ * col_splits: 0 = the library's choice, 1..RM_IBS_MAX_SPLITS forces it: that many blocks share a row tile's columns
+ *   (a small batch has few row tiles).  The splits' partial (max, sum, rank) triples, and the backward's partial
+ *   sums, are combined in split order: two runs with the same col_splits are bit-equal.  A split count above the
+ *   number of column tiles is valid (the extra splits are empty).
+ * rm_inbatch_softmax_tile: RM_IBS_ROWS the rows a block owns, RM_IBS_COLS the rows of a streamed tile,
+ *   RM_IBS_MAX_SPLITS; -1 when H is unsupported.  workspace: rm_inbatch_softmax_workspace(B, H) floats, 16-byte
+ *   aligned; it covers the largest split count (-1: unsupported).
+ * Supported (rm_inbatch_softmax_supported): H a multiple of 4 in 4..256.  An unsupported H, a NULL or unaligned
+ *   pointer, a stride below H or no multiple of 4, a split count out of range: RM_EINVAL before any launch, the
+ *   limit named in the message.  B = 0 is RM_OK.
+ * rm_rownorm_fwd: Y = X / max(|X|_2, eps), inv_norm [B] = 1 / max(|X|_2, eps).  rm_rownorm_bwd: dX = inv_norm
+ *   (dY - Y <Y, dY>); dX may alias dY.  Operands and limits as above.
+ */
+#define RM_IBS_ROWS 0
+#define RM_IBS_COLS 1
+#define RM_IBS_MAX_SPLITS 2
+int rm_inbatch_softmax_supported(int H);
+int rm_inbatch_softmax_tile(int H, int which);
+int64_t rm_inbatch_softmax_workspace(int64_t B, int H);
+int rm_inbatch_softmax_fwd(const float *U, int64_t ldu, const float *V, int64_t ldv, const int64_t *item_id,
+                           const float *logq, const float *w, float scale, int64_t B, int H, int col_splits,
+                           float *lse, float *row_loss, int32_t *rank, float *loss, float *workspace,
+                           rm_stream_t stream);
+int rm_inbatch_softmax_bwd(const float *U, int64_t ldu, const float *V, int64_t ldv, const int64_t *item_id,
+                           const float *logq, const float *w, float scale, float grad_scale, int64_t B, int H,
+                           int col_splits, const float *lse, float *dU, int64_t lddu, float *dV, int64_t lddv,
+                           float *workspace, rm_stream_t stream);
+int rm_rownorm_fwd(const float *X, int64_t ldx, int64_t B, int H, float eps, float *Y, int64_t ldy, float *inv_norm,
+                   rm_stream_t stream);
+int rm_rownorm_bwd(const float *Y, int64_t ldy, const float *inv_norm, const float *dY, int64_t lddy, int64_t B,
+                   int H, float *dX, int64_t lddx, rm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

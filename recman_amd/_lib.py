@@ -170,6 +170,12 @@ SIGNATURES = {
     "rm_mmoe_mix_fwd": [P, I64, P, I64, I64, c_int, c_int, c_int, P, I64, P, I64, P],
     "rm_mmoe_mix_bwd": [P, I64, P, I64, P, I64, I64, c_int, c_int, c_int, P, I64, P, I64, P],
     "rm_multitask_loss": [P, P, P, P, c_float, I64, c_int, P, P, P, P, P, P, P],
+    "rm_inbatch_softmax_supported": [c_int],
+    "rm_inbatch_softmax_tile": [c_int, c_int],
+    "rm_inbatch_softmax_fwd": [P, I64, P, I64, P, P, P, c_float, I64, c_int, c_int, P, P, P, P, P, P],
+    "rm_inbatch_softmax_bwd": [P, I64, P, I64, P, P, P, c_float, c_float, I64, c_int, c_int, P, P, I64, P, I64, P, P],
+    "rm_rownorm_fwd": [P, I64, I64, c_int, c_float, P, I64, P, P],
+    "rm_rownorm_bwd": [P, I64, P, P, I64, I64, c_int, P, I64, P],
 }
 
 
@@ -203,6 +209,7 @@ SIGNATURES_I64 = {
     "rm_metric_workspace": [I64],
     "rm_group_auc_workspace": [I64],
     "rm_multitask_loss_workspace": [I64, c_int],
+    "rm_inbatch_softmax_workspace": [I64, c_int],
 }
 
 

@@ -2180,17 +2180,19 @@ class AutoIntEngine(DeepFMEngine):
 
 
 class Tower:
-    """A plain MLP tower in front of an interaction layer (DLRM's bottom MLP): a_0 = x [B,K0],
-    a_{l+1} = act(a_l W_l + b_l) for every layer, the last one included; no dropout, no output projection.
+    """A plain MLP tower in front of an interaction layer (DLRM's bottom MLP, the two towers of TwoTower): a_0 = x
+    [B,K0], a_{l+1} = act(a_l W_l + b_l) for every layer, the last one included; no dropout, no output projection.
+    linear_last: the last layer is a_L W_L + b_L without the activation (an embedding head).
     Variables {prefix}dnn_layer_{l}_weights / _bias.  Layer by layer on the wide dense kernels (csrc/gemm.hip,
     csrc/gemm6.hip): bias and activation in the epilogue, the bf16x6 path where `dense_gemm` allows it and the
     kernel takes the call - the choice MLP's wide path makes."""
 
-    def __init__(self, params, grads, K0, widths, activation, device, prefix, dense_gemm="bf16x6"):
+    def __init__(self, params, grads, K0, widths, activation, device, prefix, dense_gemm="bf16x6", linear_last=False):
         self.K0, self.widths = int(K0), [int(w) for w in widths]
         self.act = act_name(activation)
         if self.act not in ("relu", "leaky_relu", "identity"):
             raise ValueError(self.act)
+        self.linear_last = bool(linear_last)
         self.p, self.g, self.prefix = params, grads, prefix
         self.dims = [self.K0] + self.widths
         self.decl = {}
@@ -2206,35 +2208,41 @@ class Tower:
         self.da = [torch.empty(B, h, dtype=F32, device=device) for h in self.widths[:-1]]
         self._fws, self._wws, self._fws6, self._wws6 = _dense_workspaces(self.dims, B, device, self.dense_gemm)
 
-    def forward(self, x):
-        """x [B,K0] -> a_last [B, widths[-1]] (an internal buffer)."""
+    def forward(self, x, x2=None):
+        """[x | x2] [B,K0] -> a_last [B, widths[-1]] (an internal buffer); x and x2 (optional) may be column ranges
+        of wider buffers."""
         self._alloc(x.shape[0], x.device)
-        self.x = x
+        self.x, self.x2 = x, x2
         p, pre = self.p, self.prefix
-        prev = x
+        prev, last = x, len(self.widths) - 1
         for i in range(len(self.widths)):
-            ops.dense_fwd(prev, None, p[f"{pre}dnn_layer_{i}_weights"], self.a[i], self._fws,
-                          bias=p[f"{pre}dnn_layer_{i}_bias"], act=self.act, ws6=self._fws6)
+            ops.dense_fwd(prev, x2 if i == 0 else None, p[f"{pre}dnn_layer_{i}_weights"], self.a[i], self._fws,
+                          bias=p[f"{pre}dnn_layer_{i}_bias"],
+                          act="identity" if (self.linear_last and i == last) else self.act, ws6=self._fws6)
             prev = self.a[i]
         return prev
 
-    def backward(self, dz):
+    def backward(self, dz, dx=None):
         """dz [B, widths[-1]] = dLoss/da_last (turned into the last pre-activation's gradient in place); writes
-        the parameter gradients.  No gradient is formed for x."""
+        the parameter gradients.  dx [B, K] (K <= K0; a column range of a wider buffer works), when given, receives
+        dLoss/d(the first K columns of the input); without it no gradient is formed for the input."""
         p, gr, pre = self.p, self.g, self.prefix
         ident = self.act == "identity"
         da = dz
-        if not ident:
+        if not ident and not self.linear_last:
             ops.act_bwd_(da, self.a[-1], self.act)
         for i in range(len(self.widths) - 1, -1, -1):
             prev = self.a[i - 1] if i else self.x
-            ops.dense_wgrad(prev, None, da, gr[f"{pre}dnn_layer_{i}_weights"], self._wws,
+            ops.dense_wgrad(prev, None if i else self.x2, da, gr[f"{pre}dnn_layer_{i}_weights"], self._wws,
                             db=gr[f"{pre}dnn_layer_{i}_bias"], ws6=self._wws6)
             if i:
                 ops.dense_fwd(da, None, p[f"{pre}dnn_layer_{i}_weights"], self.da[i - 1], self._fws, transposed=True,
                               epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD, act=self.act,
                               aux1=None if ident else prev, ws6=self._fws6)
                 da = self.da[i - 1]
+            elif dx is not None:
+                ops.dense_fwd(da, None, p[f"{pre}dnn_layer_0_weights"][: dx.shape[1]], dx, self._fws, transposed=True,
+                              epilogue=ops.DENSE_ADD, ws6=self._fws6)
 
 
 class DLRMEngine(Engine):
@@ -3060,6 +3068,229 @@ class MMoEEngine(Engine):
         return self.P.reshape(idx.shape[0], self.T, self.NE)
 
 
+def _one_run(positions, what, side):
+    """positions (sorted) must be one contiguous run -> (first, last + 1); (0, 0) when empty."""
+    if not positions:
+        return 0, 0
+    if positions[-1] - positions[0] + 1 != len(positions):
+        raise ValueError(f"TwoTower: the {what} features of the {side} tower are not one contiguous run of the "
+                         f"FeatureDictionary's {what} features (positions {positions}): each tower reads its columns "
+                         "of the batch in place, so order the dictionary with every user feature before every item "
+                         "feature (or the other way round)")
+    return positions[0], positions[-1] + 1
+
+
+def twotower_limits(hp, spec=None):
+    """TwoTower's limits in one place (th.TwoTower checks them at construction, before any GPU work, TwoTowerEngine
+    when it is built): a ValueError naming the limit (NotImplementedError for a sequence feature), or a dict with H,
+    user_units, item_units, scale and - with spec, a FeatureSpec - `user` / `item` = (a, b, c, d): the tower reads the
+    embedding features [a, b) and the dense columns [c, d); id_col the column of idx of item_id_feature (or None)."""
+    user = tuple(hp.get("user_features") or ())
+    item = tuple(hp.get("item_features") or ())
+    uu = tuple(int(h) for h in (hp.get("user_hidden_units", (256, 128)) or ()))
+    iu = tuple(int(h) for h in (hp.get("item_hidden_units", (256, 128)) or ()))
+    limits = (f"the last units of both towers equal, a multiple of 4 in {ops.IBS_H_MIN}..{ops.IBS_H_MAX}; "
+              "temperature > 0; user_features and item_features partition the FeatureDictionary")
+    if not uu or not iu or any(h < 1 for h in uu + iu):
+        raise ValueError(f"TwoTower: user_hidden_units={uu!r}, item_hidden_units={iu!r}: every tower needs at least "
+                         f"its output layer ({limits})")
+    H = uu[-1]
+    if iu[-1] != H:
+        raise ValueError(f"TwoTower: the towers end in {uu[-1]} and {iu[-1]} units: both embeddings must have the same "
+                         f"width ({limits})")
+    if H % 4 or not ops.IBS_H_MIN <= H <= ops.IBS_H_MAX:
+        raise ValueError(f"TwoTower: embedding width {H} ({limits})")
+    temp = hp.get("temperature", 0.05)
+    if not isinstance(temp, (int, float)) or not temp > 0 or temp != temp or temp == float("inf"):
+        raise ValueError(f"TwoTower: temperature={temp!r} must be a positive finite number ({limits})")
+    if not user or not item:
+        raise ValueError(f"TwoTower: user_features={user!r}, item_features={item!r}: both towers need features "
+                         f"({limits})")
+    both = sorted(set(user) & set(item))
+    if both or len(set(user)) != len(user) or len(set(item)) != len(item):
+        raise ValueError(f"TwoTower: features {both or list(user + item)} are named twice ({limits})")
+    idf = hp.get("item_id_feature")
+    masking, logq = bool(hp.get("mask_accidental_hits", True)), bool(hp.get("logq_correction", False))
+    if idf is None and (masking or logq):
+        raise ValueError("TwoTower: mask_accidental_hits / logq_correction need item_id_feature, the SparseFeat of the "
+                         "item tower that identifies the item")
+    if idf is not None and idf not in item:
+        raise ValueError(f"TwoTower: item_id_feature={idf!r} is not one of item_features {item!r}")
+    out = dict(H=H, user_units=uu, item_units=iu, scale=1.0 / float(temp), id_col=None)
+    if spec is None:
+        return out
+    if spec.seq_names:
+        raise NotImplementedError(f"TwoTower: sequence features {spec.seq_names} are not supported: a history's "
+                                  "query would cross the towers")
+    known = list(spec.sparse_names) + list(spec.dense_names)
+    named = set(user) | set(item)
+    missing, unknown = [n for n in known if n not in named], sorted(named - set(known))
+    if missing or unknown:
+        raise ValueError(f"TwoTower: user_features and item_features must partition the FeatureDictionary: "
+                         f"{missing} are in neither list, {unknown} are not in the dictionary")
+    for side, names in (("user", user), ("item", item)):
+        a, b = _one_run([j for j, n in enumerate(spec.sparse_names) if n in names], "embedding", side)
+        c, d = _one_run([j for j, n in enumerate(spec.dense_names) if n in names], "dense", side)
+        if b == a:
+            raise ValueError(f"TwoTower: the {side} tower has no embedding feature (it needs at least one)")
+        out[side] = (a, b, c, d)
+    if idf is not None:
+        if idf not in spec.sparse_names or idf in spec.scratch_names:
+            raise ValueError(f"TwoTower: item_id_feature={idf!r} must be a plain SparseFeat (not a dense, multi-valued "
+                             "or value feature)")
+        out["id_col"] = spec.sparse_names.index(idf)
+    return out
+
+
+class TwoTowerEngine(Engine):
+    """Two-tower retrieval (DSSM / YouTube-DNN; the logQ correction of Yi et al., RecSys 2019).  Nothing in the
+    reference implements it: every model of it scores one (user, item) row.  x = [E | dense] [B, K0], never
+    concatenated; the user tower reads its columns (E.view(B, FD)[:, a D : b D], dense[:, c : d]) in place, the item
+    tower its own:
+        u = tower_user(x_user), v = tower_item(x_item): hidden layers with deep_activation, a final linear layer to H
+        normalize: u <- u / max(|u|, 1e-12), the same for v                                (rm_rownorm_fwd)
+        S_ij = <u_i, v_j> / temperature - logq[item_j];  accidental hits (item_j == item_i, j != i) masked out
+        loss = sum_i w_i (logsumexp_j S_ij - S_ii) / sum_i w_i  + the l2 terms             (rm_inbatch_softmax_fwd)
+    Labels y [B] (0/1), when given, are the row weights w: a row with 0 has no loss term of its own, its item still
+    serves as a negative.  The [B, B] scores never reach HBM (csrc/inbatch.hip).  Variables: user_dnn_layer_{l}_weights
+    / _bias, item_dnn_layer_{l}_weights / _bias (glorot / zeros, deep_l2_reg on every matrix) and item_logq [V of
+    item_id_feature], the log sampling probabilities - a table set from data (set_logq), not trained, kept by
+    state_dict() / load_params().  hp["col_splits"] (default 0: the library's choice) is handed to the kernels.  No
+    bias tables, no linear term, no dropout, one GPU (no row sharding, no cross-device negatives), a fixed temperature,
+    no sequence features."""
+
+    model = "twotower"
+    use_bias_tables = False
+    shardable = False
+    EPS = 1e-12
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = False
+        if hp.get("strict_reference"):
+            raise NotImplementedError("TwoTower: strict_reference reproduces quirks of the reference, which has no "
+                                      "retrieval model")
+        lim = twotower_limits(hp, spec)
+        self.H, self.scale, self.id_col = lim["H"], lim["scale"], lim["id_col"]
+        if not ops.inbatch_softmax_supported(self.H):
+            raise ValueError(f"TwoTower: embedding width {self.H} is not supported by rm_inbatch_softmax_fwd "
+                             f"({ops.IBS_LIMITS})")
+        self.normalize = bool(hp.get("normalize", True))
+        self.masking = bool(hp.get("mask_accidental_hits", True))
+        self.logq_on = bool(hp.get("logq_correction", False))
+        self.col_splits = int(hp.get("col_splits", 0))
+        self.cols = {s: lim[s] for s in ("user", "item")}
+        self.towers = {}
+        for side in ("user", "item"):
+            a, b, c, d = self.cols[side]
+            self.towers[side] = self._adopt(Tower(self.params, self.grads, (b - a) * self.D + (d - c),
+                                                  lim[f"{side}_units"], hp.get("deep_activation", "relu"), self.device,
+                                                  f"{side}_", dense_gemm=hp.get("dense_gemm", "bf16x6"),
+                                                  linear_last=True))
+        if self.id_col is not None:
+            self._view("item_logq", torch.zeros(spec.feat_sizes[self.id_col], dtype=F32, device=self.device))
+
+    def set_logq(self, logq):
+        """The log sampling probability of every encoded id of item_id_feature ([V] floats)."""
+        self.params["item_logq"].copy_(torch.as_tensor(logq).to(self.device, F32).reshape(-1))
+
+    def _alloc_model(self, B):
+        dev, H = self.device, self.H
+        buf = lambda *shape: torch.empty(*shape, dtype=F32, device=dev)  # noqa: E731
+        self.emb = {s: buf(B, H) for s in self.towers}      # the normalised embeddings (normalize)
+        self.inv = {s: buf(B) for s in self.towers}
+        self.d_emb = {s: buf(B, H) for s in self.towers}
+        self.lse, self.row_loss = buf(B), buf(B)
+        self.rank = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.loss_ws = buf(ops.inbatch_softmax_workspace(B, H))
+        for tw in self.towers.values():
+            tw._alloc(B, dev)
+
+    def _tower_fwd(self, side, dense):
+        """The tower of one side over the gathered batch -> its embeddings [B, H]."""
+        a, b, c, d = self.cols[side]
+        D = self.D
+        if d > c and dense is None:
+            raise ValueError("TwoTower: the dense features are missing")
+        out = self.towers[side].forward(self.E.view(-1, self.FD)[:, a * D: b * D], dense[:, c:d] if d > c else None)
+        if not self.normalize:
+            return out
+        ops.rownorm_fwd(out, self.emb[side], self.inv[side], self.EPS)
+        return self.emb[side]
+
+    def embeddings(self, side, idx, dense=None, mv=None):
+        """The embeddings [B, H] of one tower ("user" or "item"): only that tower runs (the other side's columns of idx
+        and dense are gathered and ignored)."""
+        self._alloc(idx.shape[0])
+        self._mv = mv
+        self._seq_save = False
+        self._embed(idx, dense, False, {}, None)
+        return self._tower_fwd(side, dense)
+
+    def _side_inputs(self, idx):
+        """(item ids or None, logq of the batch's items or None)."""
+        col = idx[:, self.id_col].contiguous() if self.id_col is not None else None
+        ids = col if self.masking else None
+        logq = self.params["item_logq"][col].contiguous() if self.logq_on else None
+        return ids, logq
+
+    def _weights(self, y, B):
+        if y is None:
+            return None
+        if y.dtype != F32 or tuple(y.shape) != (B,):
+            raise ValueError(f"TwoTower: labels must be float32 [B] (the row weights), got {y.dtype} {tuple(y.shape)}")
+        return y
+
+    def forward(self, idx, dense=None, training=False, masks=None, manual_weights=None, mv=None):
+        """-> (score [B], score [B]): score_i = <u_i, v_i> / temperature of the row's own pair (no logQ, no
+        sigmoid; a row-wise product of the two embedding buffers, summed in double and rounded once)."""
+        if manual_weights is not None:
+            raise NotImplementedError("TwoTower has no linear term: manual feature weights do not apply")
+        u = self.embeddings("user", idx, dense, mv)
+        v = self._tower_fwd("item", dense)
+        self.pred.copy_(torch.linalg.vecdot(u.double(), v.double()) * self.scale)
+        return self.pred, self.pred
+
+    def evaluate_batch(self, idx, dense=None, y=None, mv=None):
+        """The forward kernel's outputs for one batch: (loss [1], row_loss [B], rank [B] int32) - engine buffers,
+        valid until the next call.  No l2 terms."""
+        B = idx.shape[0]
+        u = self.embeddings("user", idx, dense, mv)
+        v = self._tower_fwd("item", dense)
+        ids, logq = self._side_inputs(idx)
+        ops.inbatch_softmax_fwd(u, v, self.scale, self.lse, self.row_loss, self.loss, self.loss_ws, item_id=ids,
+                                logq=logq, w=self._weights(y, B), rank=self.rank, col_splits=self.col_splits)
+        return self.loss, self.row_loss, self.rank
+
+    def fwd_bwd(self, idx, dense, y, masks=None, mv=None):
+        """One training step's forward + backward; y [B] float32 row weights or None.  Returns the loss tensor [1]
+        (the in-batch softmax loss + the l2 terms).  Gradients: self.grads, self.d_rows [B,F,D] + idx."""
+        B = idx.shape[0]
+        self._alloc(B)
+        self._mv = mv
+        self._seq_save = True
+        w = self._weights(y, B)
+        self._embed(idx, dense, False, {}, None)
+        u, v = self._tower_fwd("user", dense), self._tower_fwd("item", dense)
+        ids, logq = self._side_inputs(idx)
+        kw = dict(item_id=ids, logq=logq, w=w, col_splits=self.col_splits)
+        ops.inbatch_softmax_fwd(u, v, self.scale, self.lse, self.row_loss, self.loss, self.loss_ws, rank=self.rank,
+                                **kw)
+        ops.inbatch_softmax_bwd(u, v, self.scale, self.lse, self.d_emb["user"], self.d_emb["item"], self.loss_ws,
+                                grad_scale=self.grad_scale, **kw)
+        D = self.D
+        for side, tw in self.towers.items():
+            g = self.d_emb[side]
+            if self.normalize:
+                ops.rownorm_bwd(self.emb[side], self.inv[side], g, g)
+            a, b, _, _ = self.cols[side]
+            tw.backward(g, self.d_rows.view(-1, self.FD)[:, a * D: b * D])
+        self._add_l2_grads()
+        self._seq_bwd()
+        return self._add_l2(self.loss)
+
+
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine, "pnn": PNNEngine,
-           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine, "mmoe": MMoEEngine}
+           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine, "mmoe": MMoEEngine,
+           "twotower": TwoTowerEngine}

@@ -1904,3 +1904,89 @@ def multitask_loss(logit, task_types, pred, *, Y=None, task_weights=None, grad_s
               _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
               _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
               _chk(workspace, "workspace", F32, allow_none=True), _stream())
+
+
+# ---- two-tower retrieval: the in-batch softmax loss and the row normalisation (csrc/inbatch.hip) -------------------
+IBS_TILE = {"rows": 0, "cols": 1, "max_splits": 2}  # RM_IBS_ROWS / RM_IBS_COLS / RM_IBS_MAX_SPLITS
+IBS_LIMITS = "H a multiple of 4 in 4..256, row strides multiples of 4 floats, col_splits 0..8"
+IBS_H_MIN, IBS_H_MAX = 4, 256
+
+
+def inbatch_softmax_supported(H):
+    """rm_inbatch_softmax_supported: H a multiple of 4 in 4..256."""
+    return bool(_lib.lib().rm_inbatch_softmax_supported(int(H)))
+
+
+def inbatch_softmax_tile(H, which="rows"):
+    """rm_inbatch_softmax_tile: "rows" = the rows a block of the score kernels owns, "cols" = the rows of a streamed
+    tile, "max_splits" = the largest col_splits."""
+    n = int(_lib.lib().rm_inbatch_softmax_tile(int(H), IBS_TILE[which]))
+    if n < 0:
+        raise ValueError(f"inbatch_softmax: H={H} unsupported ({IBS_LIMITS})")
+    return n
+
+
+def inbatch_softmax_workspace(B, H):
+    """Floats of workspace for inbatch_softmax_fwd / _bwd (rm_inbatch_softmax_workspace; any col_splits)."""
+    n = int(_lib.lib().rm_inbatch_softmax_workspace(int(B), int(H)))
+    if n < 0:
+        raise ValueError(f"inbatch_softmax: B={B}, H={H} unsupported ({IBS_LIMITS})")
+    return n
+
+
+def _ibs_operands(U, V, item_id, logq, w, workspace, fn):
+    if U.dim() != 2 or V.dim() != 2 or tuple(U.shape) != tuple(V.shape):
+        raise ValueError(f"{fn}: U {tuple(U.shape)} and V {tuple(V.shape)} must both be [B, H]")
+    B, H = int(U.shape[0]), int(U.shape[1])
+    pu, ldu = _strided_rows(U, "U", B, H, True)
+    pv, ldv = _strided_rows(V, "V", B, H, True)
+    _need_workspace(fn, workspace, inbatch_softmax_workspace(B, H))
+    return (B, H, pu, ldu, pv, ldv, _chk(item_id, "item_id", I64, (B,), allow_none=True),
+            _chk(logq, "logq", F32, (B,), allow_none=True), _chk(w, "w", F32, (B,), allow_none=True))
+
+
+def inbatch_softmax_fwd(U, V, scale, lse, row_loss, loss, workspace, *, item_id=None, logq=None, w=None, rank=None,
+                        col_splits=0):
+    """rm_inbatch_softmax_fwd: U, V [B, H] (column ranges of wider buffers work), S = scale U V^T - logq with the
+    accidental hits of item_id masked out -> lse [B], row_loss [B] = lse_i - S_ii, rank [B] int32 (optional: the
+    number of allowed j != i with S_ij > S_ii) and loss [1] = sum_i w_i row_loss_i / sum_i w_i.  col_splits: 0 = the
+    library's choice.  The limits are checked by the library."""
+    B, H, pu, ldu, pv, ldv, pid, pq, pw = _ibs_operands(U, V, item_id, logq, w, workspace, "inbatch_softmax_fwd")
+    _lib.call("rm_inbatch_softmax_fwd", pu, ldu, pv, ldv, pid, pq, pw, float(scale), B, H, int(col_splits),
+              _chk(lse, "lse", F32, (B,)), _chk(row_loss, "row_loss", F32, (B,)),
+              _chk(rank, "rank", torch.int32, (B,), allow_none=True), _chk(loss, "loss", F32, (1,)),
+              _chk(workspace, "workspace", F32), _stream())
+
+
+def inbatch_softmax_bwd(U, V, scale, lse, dU, dV, workspace, *, item_id=None, logq=None, w=None, grad_scale=1.0,
+                        col_splits=0):
+    """rm_inbatch_softmax_bwd: the gradient of grad_scale * loss with the scores recomputed from U, V and the
+    forward's lse -> dU, dV [B, H] (column ranges work; only their own columns are written).  Deterministic."""
+    B, H, pu, ldu, pv, ldv, pid, pq, pw = _ibs_operands(U, V, item_id, logq, w, workspace, "inbatch_softmax_bwd")
+    pdu, lddu = _strided_rows(dU, "dU", B, H, True)
+    pdv, lddv = _strided_rows(dV, "dV", B, H, True)
+    _lib.call("rm_inbatch_softmax_bwd", pu, ldu, pv, ldv, pid, pq, pw, float(scale), float(grad_scale), B, H,
+              int(col_splits), _chk(lse, "lse", F32, (B,)), pdu, lddu, pdv, lddv, _chk(workspace, "workspace", F32),
+              _stream())
+
+
+def rownorm_fwd(X, Y, inv_norm, eps=1e-12):
+    """rm_rownorm_fwd: Y = X / max(|X|_2, eps) row by row, inv_norm [B] = 1 / max(|X|_2, eps); X, Y [B, H] (column
+    ranges work)."""
+    if X.dim() != 2:
+        raise ValueError(f"X: expected [B, H], got {tuple(X.shape)}")
+    B, H = int(X.shape[0]), int(X.shape[1])
+    px, ldx = _strided_rows(X, "X", B, H, True)
+    py, ldy = _strided_rows(Y, "Y", B, H, True)
+    _lib.call("rm_rownorm_fwd", px, ldx, B, H, float(eps), py, ldy, _chk(inv_norm, "inv_norm", F32, (B,)), _stream())
+
+
+def rownorm_bwd(Y, inv_norm, dY, dX):
+    """rm_rownorm_bwd: dX = inv_norm (dY - Y <Y, dY>) row by row; dX may be dY itself."""
+    if Y.dim() != 2:
+        raise ValueError(f"Y: expected [B, H], got {tuple(Y.shape)}")
+    B, H = int(Y.shape[0]), int(Y.shape[1])
+    py, ldy = _strided_rows(Y, "Y", B, H, True)
+    pdy, lddy = _strided_rows(dY, "dY", B, H, True)
+    pdx, lddx = _strided_rows(dX, "dX", B, H, True)
+    _lib.call("rm_rownorm_bwd", py, ldy, _chk(inv_norm, "inv_norm", F32, (B,)), pdy, lddy, B, H, pdx, lddx, _stream())

@@ -13,6 +13,7 @@ from .FmFM import FmFM, FwFM
 from .MaskNet import MaskNet
 from .MMoE import MMoE
 from .PNN import PNN
+from .TwoTower import TwoTower
 from .BST import BST
 from .DIEN import DIEN
 from .DIN import DIN
@@ -23,6 +24,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "MMoE", "PNN", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "MMoE", "PNN", "TwoTower", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]
