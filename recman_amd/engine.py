@@ -868,6 +868,13 @@ class Engine:
             # caches for the MLP / CIN kernels; "cache": heavy id reuse (Zipf-like), plain loads
             stream_rows=self.hp.get("table_row_reuse", "stream") == "stream")
 
+    def _embed_plain(self, idx, dense, training, masks, lin_w):
+        """The opening of a _branches_fwd without an FM term: the masks of this call (none outside training), then
+        the plain embed (E and the linear logit); returns the masks."""
+        m = (masks or {}) if training else {}
+        self._embed(idx, dense, False, m, lin_w)
+        return m
+
     def _mv_entry(self, f):
         """(offsets, ids, vals) of scratch-row field f from the mv dict: a multi-valued feature
         gives (offsets, ids); a value feature (offsets, ids, vals) with one id per example."""
@@ -1029,6 +1036,12 @@ class Engine:
         return [dict(name="embed_fwd_fused_kernel (rm_embed_fwd: gather + FM + linear)",
                      symbol="embed_fwd_fused_kernel", fn=lambda: self._embed(idx, dense, fm, None),
                      work=self._embed_fwd_bytes(idx.shape[0], fm), bound="hbm")]
+
+    def _probes(self, idx, dense, y, *own):
+        """A model's probe list: its own kernels as (name, symbol, fn, work, bound), the dominant one first (by habit
+        the backward kernel, then the forward kernel), followed by the base's gather probe."""
+        return ([dict(zip(("name", "symbol", "fn", "work", "bound"), p)) for p in own]
+                + Engine.roofline_probes(self, idx, dense, y))
 
     def _probe_fill(self, idx, dense, y):
         """One fwd_bwd per batch size, so that the kernels a probe launches on their own find their inputs."""
@@ -1648,8 +1661,7 @@ class DCNEngine(Engine):
         torch.add(self.cdx0[:, : self.FD], self.dxe_dnn, out=self.d_rows.view(-1, self.FD))
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
         self.dnn_logit = self.mlp.forward(xe, xd, self._dnn_keep(training), m.get("dnn"))
         p = self.params
@@ -1838,8 +1850,7 @@ class XDeepFMEngine(Engine):
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
         hp = self.hp
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
         ck = list(hp.get("cin_dropout") or []) if training else []
         self._cin_fwd(ck if ck and any(k < 1 for k in ck) else None, m.get("cin"))
         self.dnn_logit = self._mlp_last(self.mlp, self.E.view(-1, self.FD), dense if self.Dn else None,
@@ -1966,8 +1977,7 @@ class AFMEngine(Engine):
         return m if (m is not None and self.hp.get("att_dropout", 1) < 1) else None
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        self._embed_plain(idx, dense, training, masks, lin_w)
         self._mask = self._afm_mask(masks, training)
         ops.afm_fwd(self.E, *self._afm_params(), self.afm_logit, mask=self._mask,
                     stats=self.afm_stats if training else None)
@@ -1995,20 +2005,19 @@ class AFMEngine(Engine):
         self._probe_fill(idx, dense, y)  # E, stats, dlogit
         fwd, bwd = self.afm_flops(B, self.F, self.D, self.T)
         gr = self.grads
-        return [
-            dict(name=f"afm_bwd_kernel (rm_afm_bwd: F={self.F} D={self.D} T={self.T}; recompute + dE + dW, db, dh, "
-                      "dp; flops = forward + W dz, P dz^T, dP * E)", symbol="afm_bwd_kernel",
-                 fn=lambda: ops.afm_bwd(self.E, *self._afm_params(), self.dlogit, self.afm_logit, self.afm_stats,
-                                        self.d_rows, gr["afm_attention_w"], gr["afm_attention_b"],
-                                        gr["afm_attention_h"].view(-1), gr["afm_projection_p"].view(-1),
-                                        self.afm_ws),
-                 work=float(bwd), bound="mfma"),
-            dict(name=f"afm_fwd_kernel (rm_afm_fwd: F={self.F} D={self.D} T={self.T}; flops = P (D + 2 D T + 2 T "
-                      "+ 2 D) per example, on the vector ALU - priced against the fp32 peak both pipes share)",
-                 symbol="afm_fwd_kernel",
-                 fn=lambda: ops.afm_fwd(self.E, *self._afm_params(), self.afm_logit, stats=self.afm_stats),
-                 work=float(fwd), bound="mfma"),
-        ] + super().roofline_probes(idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"afm_bwd_kernel (rm_afm_bwd: F={self.F} D={self.D} T={self.T}; recompute + dE + dW, db, dh, "
+             "dp; flops = forward + W dz, P dz^T, dP * E)", "afm_bwd_kernel",
+             lambda: ops.afm_bwd(self.E, *self._afm_params(), self.dlogit, self.afm_logit, self.afm_stats,
+                                 self.d_rows, gr["afm_attention_w"], gr["afm_attention_b"],
+                                 gr["afm_attention_h"].view(-1), gr["afm_projection_p"].view(-1), self.afm_ws),
+             float(bwd), "mfma"),
+            (f"afm_fwd_kernel (rm_afm_fwd: F={self.F} D={self.D} T={self.T}; flops = P (D + 2 D T + 2 T "
+             "+ 2 D) per example, on the vector ALU - priced against the fp32 peak both pipes share)",
+             "afm_fwd_kernel",
+             lambda: ops.afm_fwd(self.E, *self._afm_params(), self.afm_logit, stats=self.afm_stats),
+             float(fwd), "mfma"))
 
 
 class DINEngine(DeepFMEngine):
@@ -2135,8 +2144,7 @@ class AutoIntEngine(DeepFMEngine):
             dy, spare = dx, dy
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
         self._att_fwd(training)
         branches = [(self.lin_logit, 1.0), (self.att_logit, 1.0)]
         if self.use_deep:
@@ -2164,19 +2172,18 @@ class AutoIntEngine(DeepFMEngine):
         dy = torch.randn(B, self.F, self.HD, dtype=F32, device=self.device)
         dx = torch.empty_like(self.E)
         shape = f"F={self.F} Din={self.D} H={self.H} dk={self.dk}"
-        return [
-            dict(name=f"autoint_bwd_kernel (rm_autoint_layer_bwd, layer 0: {shape}; recompute + dX + dWq, dWk, dWv, "
-                      "dWr; flops = 3 x forward)", symbol="autoint_bwd_kernel",
-                 fn=lambda: ops.autoint_layer_bwd(self.E, *self._att_weights(0, p), self.att_Y[0], self.att_stats[0],
-                                                  dy, self.H, self.scale, dx, *self._att_weights(0, gr), self.att_ws),
-                 work=float(bwd), bound="mfma"),
-            dict(name=f"autoint_fwd_kernel (rm_autoint_layer_fwd, layer 0: {shape}; flops = 8 F Din HD + 4 F^2 HD per "
-                      "example, on the vector ALU - priced against the fp32 peak both pipes share)",
-                 symbol="autoint_fwd_kernel",
-                 fn=lambda: ops.autoint_layer_fwd(self.E, *self._att_weights(0, p), self.H, self.scale, self.att_Y[0],
-                                                  stats=self.att_stats[0]),
-                 work=float(fwd), bound="mfma"),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"autoint_bwd_kernel (rm_autoint_layer_bwd, layer 0: {shape}; recompute + dX + dWq, dWk, dWv, "
+             "dWr; flops = 3 x forward)", "autoint_bwd_kernel",
+             lambda: ops.autoint_layer_bwd(self.E, *self._att_weights(0, p), self.att_Y[0], self.att_stats[0],
+                                           dy, self.H, self.scale, dx, *self._att_weights(0, gr), self.att_ws),
+             float(bwd), "mfma"),
+            (f"autoint_fwd_kernel (rm_autoint_layer_fwd, layer 0: {shape}; flops = 8 F Din HD + 4 F^2 HD per "
+             "example, on the vector ALU - priced against the fp32 peak both pipes share)", "autoint_fwd_kernel",
+             lambda: ops.autoint_layer_fwd(self.E, *self._att_weights(0, p), self.H, self.scale, self.att_Y[0],
+                                           stats=self.att_stats[0]),
+             float(fwd), "mfma"))
 
 
 class Tower:
@@ -2245,7 +2252,61 @@ class Tower:
                               epilogue=ops.DENSE_ADD, ws6=self._fws6)
 
 
-class DLRMEngine(Engine):
+class InteractionEngine(Engine):
+    """The flow DLRM, FiBiNET and PNN share: E -> one fused interaction kernel -> X [B, ldx] -> DNN([X | dense]);
+    final = DNN logit (+ linear if use_linear).  The DNN's dX is no table-row gradient: d_rows comes from the
+    interaction's backward, and since no other branch reads E it IS dLoss/dE.  X and dX are [B, ldx] buffers, ldx = W
+    rounded up to what the kernels' row loads need; the kernels and the DNN see the [:, :W] views, and the pad columns
+    are written once, as +0.0, when the buffers are made - never again.
+    A model plugs in with
+        _interaction(hp)          its limit checks and variable declarations -> (W, ldx)
+        _alloc_interaction(B)     its further per-batch-size buffers (optional)
+        _interact_fwd(dense, X)   E (and whatever it makes of dense) -> X
+        _interact_bwd(dX)         dX -> d_rows and its own variables' gradients
+    and the class attributes below."""
+
+    title = None               # the model's name in its error messages
+    linear_default = True      # hp["use_linear"] when it is absent
+    dnn_reads_dense = True     # DNN([X | dense]); False: DNN(X)
+    dnn_prefix = ""            # in front of the DNN's variable names
+    dnn_noun = "DNN"           # what the error message calls it
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = bool(hp.get("use_linear", self.linear_default))
+        self.W, self.ldx = self._interaction(hp)
+        hidden = tuple(hp.get("deep_hidden_units") or ())
+        if not hidden:
+            raise ValueError(f"{self.title}: deep_hidden_units must name at least one layer of the {self.dnn_noun}")
+        # (the DNN reads the interaction's output, not [E | dense]; its dX is no table-row gradient)
+        self.mlp = self._dnn(self.W, self.Dn if self.dnn_reads_dense else 0, hidden, "relu", prefix=self.dnn_prefix,
+                             stream_d_rows=False)
+
+    def _alloc_model(self, B):
+        self.X = torch.zeros(B, self.ldx, dtype=F32, device=self.device)
+        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=self.device)
+        self._alloc_interaction(B)
+
+    def _alloc_interaction(self, B):
+        pass
+
+    def _branches_fwd(self, idx, dense, training, masks, lin_w):
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
+        X = self.X[:, : self.W]
+        self._interact_fwd(dense, X)
+        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
+        self.dnn_logit = self._mlp_last(self.mlp, X, dense if self.mlp.Dn else None, self._dnn_keep(training),
+                                        m.get("dnn"), list(branches))
+        branches.append((self.dnn_logit, 1.0))
+        return branches
+
+    def _branches_bwd(self, idx, dense, g, masks):
+        dX = self.dX[:, : self.W]
+        self.mlp.backward(g, dX)
+        self._interact_bwd(dX)
+
+
+class DLRMEngine(InteractionEngine):
     """DLRM (arXiv 1906.00091, the MLPerf recommendation model): the dense features go through a bottom tower to
     one embedding-wide vector z; the interaction takes every pairwise dot product among z and the F rows of E;
     [z | dots] feeds the top MLP.  final = top logit (+ linear if use_linear).  Nothing in the reference implements it.
@@ -2257,50 +2318,32 @@ class DLRMEngine(Engine):
     matrix of both and top_dnn_w.  No bias tables.  X and dX live in buffers whose rows are padded to a multiple
     of 4 floats; the top MLP sees the [B, D + P] view."""
 
-    model = "dlrm"
+    model, title = "dlrm", "DLRM"
     use_bias_tables = False
+    linear_default = False
+    dnn_reads_dense, dnn_prefix, dnn_noun = False, "top_", "top tower"
 
-    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
-        super().__init__(spec, embedding_size, hp, task, device)
-        self.use_linear = bool(hp.get("use_linear", False))
+    def _interaction(self, hp):
         limits = "at least one dense feature, 1..40 embedding features, embedding_size 8/16/32/64"
         if self.Dn < 1:
             raise ValueError(f"DLRM: the bottom tower needs a dense feature, there is none ({limits})")
         if not ops.dot_interact_supported(self.F, self.D):
             raise ValueError(f"DLRM: {self.F} embedding features of embedding_size={self.D} are not supported by "
                              f"rm_dot_interact_fwd ({limits})")
-        hidden = tuple(hp.get("deep_hidden_units") or ())
-        if not hidden:
-            raise ValueError("DLRM: deep_hidden_units must name at least one layer of the top tower")
-        self.W, self.ldx = ops.dot_interact_width(self.F, self.D)
         self.bot = self._adopt(Tower(self.params, self.grads, self.Dn,
                                      tuple(hp.get("bottom_hidden_units", (64, 32))) + (self.D,),
                                      hp.get("deep_activation", "relu"), self.device, "bot_",
                                      dense_gemm=hp.get("dense_gemm", "bf16x6")))
-        # (the top tower reads the interaction's output, not [E | dense]; its dX is no table-row gradient)
-        self.mlp = self._dnn(self.W, 0, hidden, "relu", prefix="top_", stream_d_rows=False)
+        return ops.dot_interact_width(self.F, self.D)
 
-    def _alloc_model(self, B):
-        dev = self.device
-        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
-        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
-        self.dz = torch.empty(B, self.D, dtype=F32, device=dev)
+    def _alloc_interaction(self, B):
+        self.dz = torch.empty(B, self.D, dtype=F32, device=self.device)
 
-    def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+    def _interact_fwd(self, dense, X):
         self.z = self.bot.forward(dense)
-        X = self.X[:, : self.W]
         ops.dot_interact_fwd(self.E, self.z, X)
-        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
-        self.dnn_logit = self._mlp_last(self.mlp, X, None, self._dnn_keep(training), m.get("dnn"), list(branches))
-        branches.append((self.dnn_logit, 1.0))
-        return branches
 
-    def _branches_bwd(self, idx, dense, g, masks):
-        dX = self.dX[:, : self.W]
-        self.mlp.backward(g, dX)
-        # no other branch reads E: d_rows IS dLoss/dE
+    def _interact_bwd(self, dX):
         ops.dot_interact_bwd(self.E, self.z, dX, self.d_rows, self.dz)
         self.bot.backward(self.dz)
 
@@ -2310,17 +2353,16 @@ class DLRMEngine(Engine):
         X, dX = self.X[:, : self.W], self.dX[:, : self.W]
         d_rows, dz = torch.empty_like(self.d_rows), torch.empty_like(self.dz)
         shape = f"F={F} D={D} ldx={ldx}"
-        return [
-            dict(name=f"dot_bwd_kernel (rm_dot_interact_bwd, {shape}: E, z, dX read once, d_rows and dz written once)",
-                 symbol="dot_bwd_kernel", fn=lambda: ops.dot_interact_bwd(self.E, self.z, dX, d_rows, dz),
-                 work=B * 4 * (2 * F * D + 2 * D + ldx), bound="hbm"),
-            dict(name=f"dot_fwd_kernel (rm_dot_interact_fwd, {shape}: E and z read once, X written once)",
-                 symbol="dot_fwd_kernel", fn=lambda: ops.dot_interact_fwd(self.E, self.z, X),
-                 work=B * 4 * (F * D + D + ldx), bound="hbm"),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"dot_bwd_kernel (rm_dot_interact_bwd, {shape}: E, z, dX read once, d_rows and dz written once)",
+             "dot_bwd_kernel", lambda: ops.dot_interact_bwd(self.E, self.z, dX, d_rows, dz),
+             B * 4 * (2 * F * D + 2 * D + ldx), "hbm"),
+            (f"dot_fwd_kernel (rm_dot_interact_fwd, {shape}: E and z read once, X written once)",
+             "dot_fwd_kernel", lambda: ops.dot_interact_fwd(self.E, self.z, X), B * 4 * (F * D + D + ldx), "hbm"))
 
 
-class FiBiNETEngine(Engine):
+class FiBiNETEngine(InteractionEngine):
     """FiBiNET (arXiv 1905.09433): a squeeze-excitation gate re-weights the F rows of E, a bilinear interaction runs
     over every field pair of the raw and of the re-weighted rows, and the DNN reads both.  final = DNN([X | dense])
     (+ linear if use_linear, the default).  Nothing in the reference implements it.
@@ -2331,12 +2373,10 @@ class FiBiNETEngine(Engine):
     senet_bilinear_w [1 | F-1, D, D] - glorot, l2 key interaction_l2_reg.  No bias tables.  X and dX are [B, 2PD]
     buffers: 2PD = F(F-1)D is a multiple of 8, so their rows need no pad."""
 
-    model = "fibinet"
+    model, title = "fibinet", "FiBiNET"
     use_bias_tables = False
 
-    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
-        super().__init__(spec, embedding_size, hp, task, device)
-        self.use_linear = bool(hp.get("use_linear", True))
+    def _interaction(self, hp):
         limits = "2..40 embedding features, embedding_size 8/16/32, bilinear_type 'all' or 'each'"
         self.btype = hp.get("bilinear_type", "each")
         if self.btype == "interaction":
@@ -2352,44 +2392,25 @@ class FiBiNETEngine(Engine):
         if not ops.fibinet_supported(F, D, R, self.btype):
             raise ValueError(f"FiBiNET: {F} embedding features of embedding_size={D} are not supported by "
                              f"rm_fibinet_fwd ({limits})")
-        hidden = tuple(hp.get("deep_hidden_units") or ())
-        if not hidden:
-            raise ValueError("FiBiNET: deep_hidden_units must name at least one layer of the DNN")
         nW = F - 1 if self.btype == "each" else 1
         l2 = "interaction_l2_reg"
         self._var("senet_w1", (F, R), ("glorot", F, R), l2)
         self._var("senet_w2", (R, F), ("glorot", R, F), l2)
         self._var("bilinear_w", (nW, D, D), ("glorot", D, D), l2)
         self._var("senet_bilinear_w", (nW, D, D), ("glorot", D, D), l2)
-        self.W, self.ldx = ops.fibinet_width(F, D)
-        # (the DNN reads the interaction's output, not [E | dense]; its dX is no table-row gradient)
-        self.mlp = self._dnn(self.W, self.Dn, hidden, "relu", stream_d_rows=False)
+        return ops.fibinet_width(F, D)
 
-    def _alloc_model(self, B):
-        dev = self.device
-        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
-        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+    def _alloc_interaction(self, B):
         self.fib_ws = torch.empty(max(4, ops.fibinet_bwd_workspace(B, self.F, self.D, self.R, self.btype)),
-                                  dtype=F32, device=dev)
+                                  dtype=F32, device=self.device)
 
     def _fib_vars(self, d):
         return d["senet_w1"], d["senet_w2"], d["bilinear_w"], d["senet_bilinear_w"]
 
-    def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
-        X = self.X[:, : self.W]
+    def _interact_fwd(self, dense, X):
         ops.fibinet_fwd(self.E, *self._fib_vars(self.params), self.btype, X)
-        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
-        self.dnn_logit = self._mlp_last(self.mlp, X, dense if self.Dn else None, self._dnn_keep(training),
-                                        m.get("dnn"), list(branches))
-        branches.append((self.dnn_logit, 1.0))
-        return branches
 
-    def _branches_bwd(self, idx, dense, g, masks):
-        dX = self.dX[:, : self.W]
-        self.mlp.backward(g, dX)
-        # no other branch reads E: d_rows IS dLoss/dE
+    def _interact_bwd(self, dX):
         ops.fibinet_bwd(self.E, *self._fib_vars(self.params), self.btype, dX, self.d_rows,
                         *self._fib_vars(self.grads), self.fib_ws)
 
@@ -2400,17 +2421,15 @@ class FiBiNETEngine(Engine):
         d_rows = torch.empty_like(self.d_rows)
         dws = [torch.empty_like(t) for t in self._fib_vars(self.grads)]
         shape = f"F={F} D={D} R={self.R} {self.btype} ldx={ldx}"
-        return [
-            dict(name=f"fibinet_bwd_kernel (rm_fibinet_bwd, {shape}: E and dX read once from HBM, d_rows written once)",
-                 symbol="fibinet_bwd_kernel",
-                 fn=lambda: ops.fibinet_bwd(self.E, *self._fib_vars(self.params), self.btype, dX, d_rows, *dws,
-                                            self.fib_ws),
-                 work=B * 4 * (2 * F * D + ldx), bound="hbm"),
-            dict(name=f"fibinet_fwd_kernel (rm_fibinet_fwd, {shape}: E read once, X written once)",
-                 symbol="fibinet_fwd_kernel",
-                 fn=lambda: ops.fibinet_fwd(self.E, *self._fib_vars(self.params), self.btype, X),
-                 work=B * 4 * (F * D + ldx), bound="hbm"),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"fibinet_bwd_kernel (rm_fibinet_bwd, {shape}: E and dX read once from HBM, d_rows written once)",
+             "fibinet_bwd_kernel",
+             lambda: ops.fibinet_bwd(self.E, *self._fib_vars(self.params), self.btype, dX, d_rows, *dws, self.fib_ws),
+             B * 4 * (2 * F * D + ldx), "hbm"),
+            (f"fibinet_fwd_kernel (rm_fibinet_fwd, {shape}: E read once, X written once)", "fibinet_fwd_kernel",
+             lambda: ops.fibinet_fwd(self.E, *self._fib_vars(self.params), self.btype, X),
+             B * 4 * (F * D + ldx), "hbm"))
 
 
 class FmFMEngine(DeepFMEngine):
@@ -2456,8 +2475,7 @@ class FmFMEngine(DeepFMEngine):
                                    device=dev)
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
         ops.fmfm_fwd(self.E, self.params["field_pair_w"], self.ftype, self.pair_logit)
         branches = ([(self.lin_logit, 1.0)] if self.use_linear else []) + [(self.pair_logit, 1.0)]
         if self.use_deep:
@@ -2486,16 +2504,15 @@ class FmFMEngine(DeepFMEngine):
             fwd, bwd, bound = 4.0 * (B * F * D + B + w.numel()), 4.0 * (2 * B * F * D + B + 2 * w.numel()), "hbm"
             names = ("fmfm_vs_de_kernel", "fmfm_vs_fwd_kernel")
             what = "algorithmic bytes: E (+ g) in, logit / d_rows out, the weights and their gradient"
-        return [
-            dict(name=f"{names[0]} + dW kernels (rm_fmfm_bwd, {shape}; {what})", symbol=names[0],
-                 fn=lambda: ops.fmfm_bwd(self.E, w, self.ftype, self.dlogit, d_rows, dw, self.pair_ws),
-                 work=bwd, bound=bound),
-            dict(name=f"{names[1]} (rm_fmfm_fwd, {shape}; {what})", symbol=names[1],
-                 fn=lambda: ops.fmfm_fwd(self.E, w, self.ftype, self.pair_logit), work=fwd, bound=bound),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"{names[0]} + dW kernels (rm_fmfm_bwd, {shape}; {what})", names[0],
+             lambda: ops.fmfm_bwd(self.E, w, self.ftype, self.dlogit, d_rows, dw, self.pair_ws), bwd, bound),
+            (f"{names[1]} (rm_fmfm_fwd, {shape}; {what})", names[1],
+             lambda: ops.fmfm_fwd(self.E, w, self.ftype, self.pair_logit), fwd, bound))
 
 
-class PNNEngine(Engine):
+class PNNEngine(InteractionEngine):
     """Product-based Neural Network (PNN, arXiv 1611.00144) with the kernel-form product layer of the widely used
     open-source PNN (use_inner, use_outter, kernel_type mat / vec / num) - NOT the paper's sum-pooled outer-product
     shortcut.  final = DNN([X | dense]) (+ linear if use_linear; off by default).  Nothing in the reference implements
@@ -2508,13 +2525,12 @@ class PNNEngine(Engine):
     columns stay +0.0.  The DNN's dX is no table-row gradient: d_rows comes from rm_pnn_bwd, which adds the row part
     of dX to the products' gradient and writes it once."""
 
-    model = "pnn"
+    model, title = "pnn", "PNN"
     use_bias_tables = False
     shardable = False
+    linear_default = False
 
-    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
-        super().__init__(spec, embedding_size, hp, task, device)
-        self.use_linear = bool(hp.get("use_linear", False))
+    def _interaction(self, hp):
         limits = ("2..40 embedding features, embedding_size 8/16/32, use_inner or use_outer, kernel_type 'mat', 'vec' "
                   "or 'num'")
         self.ktype = hp.get("kernel_type", "mat")
@@ -2527,39 +2543,20 @@ class PNNEngine(Engine):
         if not ops.pnn_supported(F, D, self.products, self.ktype):
             raise ValueError(f"PNN: {F} embedding features of embedding_size={D} are not supported by rm_pnn_fwd "
                              f"({limits})")
-        hidden = tuple(hp.get("deep_hidden_units") or ())
-        if not hidden:
-            raise ValueError("PNN: deep_hidden_units must name at least one layer of the DNN")
         self.P = F * (F - 1) // 2
         self.outer = bool(self.products & ops.PNN_OUTER)
         if self.outer:
             self._var("product_kernel", ops.pnn_weight_shape(F, D, self.ktype), ("glorot", D, D), "interaction_l2_reg")
-        self.W, self.ldx = ops.pnn_width(F, D, self.products)
-        # (the DNN reads the product layer's output, not [E | dense]; its dX is no table-row gradient)
-        self.mlp = self._dnn(self.W, self.Dn, hidden, "relu", stream_d_rows=False)
+        return ops.pnn_width(F, D, self.products)
 
-    def _alloc_model(self, B):
-        dev = self.device
-        self.X = torch.zeros(B, self.ldx, dtype=F32, device=dev)
-        self.dX = torch.zeros(B, self.ldx, dtype=F32, device=dev)
+    def _alloc_interaction(self, B):
         self.pnn_ws = (torch.empty(max(4, ops.pnn_bwd_workspace(B, self.F, self.D, self.products, self.ktype)),
-                                   dtype=F32, device=dev) if self.outer else None)
+                                   dtype=F32, device=self.device) if self.outer else None)
 
-    def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
-        X = self.X[:, : self.W]
+    def _interact_fwd(self, dense, X):
         ops.pnn_fwd(self.E, self.params.get("product_kernel"), self.products, self.ktype, X)
-        branches = [(self.lin_logit, 1.0)] if self.use_linear else []
-        self.dnn_logit = self._mlp_last(self.mlp, X, dense if self.Dn else None, self._dnn_keep(training),
-                                        m.get("dnn"), list(branches))
-        branches.append((self.dnn_logit, 1.0))
-        return branches
 
-    def _branches_bwd(self, idx, dense, g, masks):
-        dX = self.dX[:, : self.W]
-        self.mlp.backward(g, dX)
-        # no other branch reads E: d_rows IS dLoss/dE
+    def _interact_bwd(self, dX):
         ops.pnn_bwd(self.E, self.params.get("product_kernel"), self.products, self.ktype, dX, self.d_rows,
                     self.grads.get("product_kernel"), self.pnn_ws)
 
@@ -2581,13 +2578,12 @@ class PNNEngine(Engine):
             fwd, bwd, bound = 4.0 * (B * F * D + B * ldx + nk), 4.0 * (2 * B * F * D + B * ldx + 2 * nk), "hbm"
             names = ("pnn_de_valu_kernel", "pnn_fwd_kernel")
             what = "algorithmic bytes: E (+ dX) in, X / d_rows out, the kernel and its gradient"
-        return [
-            dict(name=f"{names[0]} + dK kernels (rm_pnn_bwd, {shape}; {what})", symbol=names[0],
-                 fn=lambda: ops.pnn_bwd(self.E, k, self.products, self.ktype, dX, d_rows, dk, self.pnn_ws),
-                 work=bwd, bound=bound),
-            dict(name=f"{names[1]} (rm_pnn_fwd, {shape}; {what})", symbol=names[1],
-                 fn=lambda: ops.pnn_fwd(self.E, k, self.products, self.ktype, X), work=fwd, bound=bound),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"{names[0]} + dK kernels (rm_pnn_bwd, {shape}; {what})", names[0],
+             lambda: ops.pnn_bwd(self.E, k, self.products, self.ktype, dX, d_rows, dk, self.pnn_ws), bwd, bound),
+            (f"{names[1]} (rm_pnn_fwd, {shape}; {what})", names[1],
+             lambda: ops.pnn_fwd(self.E, k, self.products, self.ktype, X), fwd, bound))
 
 
 def masknet_limits(hp, F, D):
@@ -2740,8 +2736,7 @@ class MaskNetEngine(Engine):
             self._hidden_fwd(n, outs[n - 1])
 
     def _branches_fwd(self, idx, dense, training, masks, lin_w):
-        m = (masks or {}) if training else {}
-        self._embed(idx, dense, False, m, lin_w)
+        m = self._embed_plain(idx, dense, training, masks, lin_w)
         self._blocks_fwd(dense)
         branches = [(self.lin_logit, 1.0)] if self.use_linear else []
         self.dnn_logit = self._mlp_last(self.mlp, self.X, dense if self.Dn else None, self._dnn_keep(training),
@@ -2830,24 +2825,22 @@ class MaskNetEngine(Engine):
         h, dZ = torch.empty_like(self.Z[0]), torch.empty_like(self.Z[0])
         dh = self.dX[:, :H]
         shape = f"F={F} D={D} N={n}"
-        return [
-            dict(name=f"masknet_group_bwd_kernel (rm_masknet_group_bwd, {shape}: E, M_n, dY_n in, dM_n, d_rows out)",
-                 symbol="masknet_group_bwd_kernel",
-                 fn=lambda: ops.masknet_group_bwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, dY, dY, d_rows, dg, db,
-                                                  self.group_ws),
-                 work=4.0 * (B * FD * (2 + 3 * n) + 4 * FD), bound="hbm"),
-            dict(name=f"masknet_group_fwd_kernel (rm_masknet_group_fwd, {shape}: E and M_n in, Y_n out)",
-                 symbol="masknet_group_fwd_kernel",
-                 fn=lambda: ops.masknet_group_fwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, Y),
-                 work=4.0 * (B * FD * (1 + 2 * n) + 2 * FD), bound="hbm"),
-            dict(name=f"masknet_row_bwd_kernel (rm_masknet_row_bwd, H={H}: Z and dh in, dZ out)",
-                 symbol="masknet_row_bwd_kernel",
-                 fn=lambda: ops.masknet_row_bwd(self.Z[0], g1, b1, dh, dZ, dg1, db1, self.row_ws),
-                 work=4.0 * (3 * B * H + 4 * H), bound="hbm"),
-            dict(name=f"masknet_row_fwd_kernel (rm_masknet_row_fwd, H={H}: Z in, h out)",
-                 symbol="masknet_row_fwd_kernel", fn=lambda: ops.masknet_row_fwd(self.Z[0], g1, b1, h),
-                 work=4.0 * (2 * B * H + 2 * H), bound="hbm"),
-        ] + Engine.roofline_probes(self, idx, dense, y)
+        return self._probes(
+            idx, dense, y,
+            (f"masknet_group_bwd_kernel (rm_masknet_group_bwd, {shape}: E, M_n, dY_n in, dM_n, d_rows out)",
+             "masknet_group_bwd_kernel",
+             lambda: ops.masknet_group_bwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, dY, dY, d_rows, dg, db,
+                                           self.group_ws),
+             4.0 * (B * FD * (2 + 3 * n) + 4 * FD), "hbm"),
+            (f"masknet_group_fwd_kernel (rm_masknet_group_fwd, {shape}: E and M_n in, Y_n out)",
+             "masknet_group_fwd_kernel",
+             lambda: ops.masknet_group_fwd(self.E, p["ln_emb_gamma"], p["ln_emb_beta"], M, Y),
+             4.0 * (B * FD * (1 + 2 * n) + 2 * FD), "hbm"),
+            (f"masknet_row_bwd_kernel (rm_masknet_row_bwd, H={H}: Z and dh in, dZ out)", "masknet_row_bwd_kernel",
+             lambda: ops.masknet_row_bwd(self.Z[0], g1, b1, dh, dZ, dg1, db1, self.row_ws),
+             4.0 * (3 * B * H + 4 * H), "hbm"),
+            (f"masknet_row_fwd_kernel (rm_masknet_row_fwd, H={H}: Z in, h out)", "masknet_row_fwd_kernel",
+             lambda: ops.masknet_row_fwd(self.Z[0], g1, b1, h), 4.0 * (2 * B * H + 2 * H), "hbm"))
 
 
 def mmoe_limits(hp):

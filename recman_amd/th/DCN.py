@@ -20,7 +20,6 @@ class DCN(DeepModel):
                  loss_type="logloss", eval_metric=(roc_auc_score, log_loss), what_means_greater=None,
                  use_interactive_session=False, log_dir="./logs", strict_reference=False,
                  device="cuda", cross_type="vector", cross_experts=4, cross_low_rank=32):
-        assert loss_type in ["logloss", "mse"]
         hp = dict(embedding_size=embedding_size, embedding_l2_reg=embedding_l2_reg,
                   linear_l2_reg=linear_l2_reg, deep_hidden_units=tuple(deep_hidden_units),
                   deep_dropout=tuple(deep_dropout), deep_activation=deep_activation,
@@ -28,12 +27,5 @@ class DCN(DeepModel):
                   cross_layer_l2_reg=cross_layer_l2_reg, use_linear=use_linear,
                   learning_rate=learning_rate, optimizer=optimizer, cross_type=cross_type,
                   cross_experts=cross_experts, cross_low_rank=cross_low_rank)
-        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
-                           random_seed=random_seed,
-                           task="classification" if loss_type == "logloss" else "regression",
-                           strict_reference=strict_reference, device=device)
-        self.what_means_greater, self.use_interactive_session, self.log_dir = (
-            what_means_greater, use_interactive_session, log_dir)
-        self.loss_type, self.eval_metric = loss_type, eval_metric
-        for k, v in hp.items():
-            setattr(self, k, v)
+        self._init_front(feat_dict, hp, {}, loss_type, eval_metric, epoch, batch_size, random_seed,
+                         what_means_greater, use_interactive_session, log_dir, strict_reference, device)

@@ -26,8 +26,6 @@ class DIN(DeepModel):
                  learning_rate=0.001, optimizer="adam", random_seed=2019, loss_type="logloss",
                  eval_metric=(roc_auc_score, log_loss), l2_reg=0.1, what_means_greater=None,
                  use_interactive_session=True, log_dir="./logs", strict_reference=False, device="cuda"):
-        assert loss_type in ["logloss", "mse"], (
-            "loss_type can be either 'logloss' for classification task or 'mse' for regression task")
         if isinstance(att_activation, str) and att_activation.lower() == "dice":
             raise NotImplementedError("att_activation='dice': the reference's Dice (activation.py) uses undefined names "
                                       "and has no arithmetic to follow; use 'sigmoid' or 'relu'")
@@ -40,14 +38,7 @@ class DIN(DeepModel):
                   att_weight_normalization=att_weight_normalization, deep_hidden_units=tuple(deep_hidden_units),
                   deep_dropout=tuple(deep_dropout), deep_l2_reg=deep_l2_reg, deep_activation=deep_activation,
                   learning_rate=learning_rate, optimizer=optimizer)
-        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
-                           random_seed=random_seed,
-                           task="classification" if loss_type == "logloss" else "regression",
-                           strict_reference=strict_reference, device=device)
-        # TF-only knobs and the unused argument are accepted and ignored
-        self.what_means_greater, self.use_interactive_session, self.log_dir = (
-            what_means_greater, use_interactive_session, log_dir)
-        self.l2_reg = l2_reg
-        self.loss_type, self.eval_metric = loss_type, eval_metric
-        for k, v in hp.items():  # sklearn get_params()/clone() need the ctor arguments back
-            setattr(self, k, v)
+        # (as given: clone() compares the attributes with the arguments)
+        given = dict(l2_reg=l2_reg)
+        self._init_front(feat_dict, hp, given, loss_type, eval_metric, epoch, batch_size, random_seed,
+                         what_means_greater, use_interactive_session, log_dir, strict_reference, device)

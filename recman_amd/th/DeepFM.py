@@ -18,20 +18,10 @@ class DeepFM(DeepModel):
                  use_interactive_session=False, log_dir="./logs", strict_reference=False,
                  device="cuda"):
         assert use_fm or use_deep  # DeepFM.py:54
-        assert loss_type in ["logloss", "mse"], (
-            "loss_type can be either 'logloss' for classification task or 'mse' for regression task")
         hp = dict(embedding_size=embedding_size, embedding_l2_reg=embedding_l2_reg,
                   linear_l2_reg=linear_l2_reg, fm_dropout=tuple(fm_dropout),
                   deep_hidden_units=tuple(deep_hidden_units), deep_dropout=tuple(deep_dropout),
                   deep_l2_reg=deep_l2_reg, deep_activation=deep_activation, use_fm=use_fm,
                   use_deep=use_deep, learning_rate=learning_rate, optimizer=optimizer)
-        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
-                           random_seed=random_seed,
-                           task="classification" if loss_type == "logloss" else "regression",
-                           strict_reference=strict_reference, device=device)
-        # TF-only knobs are accepted and ignored
-        self.what_means_greater, self.use_interactive_session, self.log_dir = (
-            what_means_greater, use_interactive_session, log_dir)
-        self.loss_type, self.eval_metric = loss_type, eval_metric
-        for k, v in hp.items():  # sklearn get_params()/clone() need the ctor arguments back
-            setattr(self, k, v)
+        self._init_front(feat_dict, hp, {}, loss_type, eval_metric, epoch, batch_size, random_seed,
+                         what_means_greater, use_interactive_session, log_dir, strict_reference, device)

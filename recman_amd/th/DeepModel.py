@@ -58,6 +58,36 @@ class DeepModel(BaseEstimator, TransformerMixin):
         self._opt = None
         self._shard, self._w = None, None  # (rank, world) of a row-sharded table; this rank's batch share
 
+    # ------------------------------------------------- what the front ends' constructors share
+    @staticmethod
+    def _keep_probabilities(deep_dropout, hidden):
+        """deep_dropout as the DNN's KEEP probabilities (layers.py:461): one for its input and one per hidden layer;
+        None = no dropout."""
+        keep = tuple(deep_dropout) if deep_dropout is not None else (1,) * (len(hidden) + 1)
+        if len(keep) != len(hidden) + 1:
+            raise ValueError(f"deep_dropout needs {len(hidden) + 1} keep probabilities (input + every hidden layer), "
+                             f"got {deep_dropout!r}")
+        return keep
+
+    def _init_front(self, feat_dict, hp, as_given, loss_type, eval_metric, epoch, batch_size, random_seed,
+                    what_means_greater, use_interactive_session, log_dir, strict_reference, device):
+        """The tail of a front end's constructor (the pattern of recman/tf/core/AFM.py:27-48): loss_type picks the
+        task, hp becomes hparams, and every constructor argument becomes an attribute - sklearn's get_params() /
+        clone() need them back.  as_given: the arguments hp holds in a normalised form, or not at all, under their
+        names - stored as given, because clone() compares the attributes with the arguments.  The TF-only knobs
+        (what_means_greater, use_interactive_session, log_dir) are accepted and ignored."""
+        assert loss_type in ["logloss", "mse"], (
+            "loss_type can be either 'logloss' for classification task or 'mse' for regression task")
+        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
+                           random_seed=random_seed,
+                           task="classification" if loss_type == "logloss" else "regression",
+                           strict_reference=strict_reference, device=device)
+        self.what_means_greater, self.use_interactive_session, self.log_dir = (
+            what_means_greater, use_interactive_session, log_dir)
+        self.loss_type, self.eval_metric = loss_type, eval_metric
+        for k, v in {**hp, **as_given}.items():
+            setattr(self, k, v)
+
     # ------------------------------------------------------------------ engine
     def _build(self):
         if self._engine is not None:

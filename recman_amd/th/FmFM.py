@@ -26,32 +26,19 @@ class FmFM(DeepModel):
                  optimizer="adam", random_seed=2019, loss_type="logloss", eval_metric=(roc_auc_score, log_loss),
                  what_means_greater=None, use_interactive_session=True, log_dir="./logs", strict_reference=False,
                  device="cuda"):
-        assert loss_type in ["logloss", "mse"], (
-            "loss_type can be either 'logloss' for classification task or 'mse' for regression task")
         if field_interaction not in FIELD_INTERACTIONS:
             raise ValueError(f"{type(self).__name__}: field_interaction {field_interaction!r} is not one of 'matrix', "
                              "'vector', 'scalar'")
         hidden = tuple(deep_hidden_units or ())
-        keep = tuple(deep_dropout) if deep_dropout is not None else (1,) * (len(hidden) + 1)
-        if len(keep) != len(hidden) + 1:
-            raise ValueError(f"deep_dropout needs {len(hidden) + 1} keep probabilities (input + every hidden layer), "
-                             f"got {deep_dropout!r}")
+        keep = self._keep_probabilities(deep_dropout, hidden)
         hp = dict(embedding_size=embedding_size, field_interaction=field_interaction, deep_hidden_units=hidden,
                   deep_dropout=keep, deep_l2_reg=deep_l2_reg, interaction_l2_reg=interaction_l2_reg,
                   deep_activation=deep_activation, use_linear=use_linear, embedding_l2_reg=embedding_l2_reg,
                   linear_l2_reg=linear_l2_reg, learning_rate=learning_rate, optimizer=optimizer)
-        DeepModel.__init__(self, feat_dict, hp, metrics=eval_metric, epoch=epoch, batch_size=batch_size,
-                           random_seed=random_seed,
-                           task="classification" if loss_type == "logloss" else "regression",
-                           strict_reference=strict_reference, device=device)
-        # TF-only knobs are accepted and ignored
-        self.what_means_greater, self.use_interactive_session, self.log_dir = (
-            what_means_greater, use_interactive_session, log_dir)
-        self.loss_type, self.eval_metric = loss_type, eval_metric
-        for k, v in hp.items():  # sklearn get_params()/clone() need the ctor arguments back
-            setattr(self, k, v)
         # (as given: clone() compares the attributes with the arguments)
-        self.deep_dropout, self.deep_hidden_units = deep_dropout, deep_hidden_units
+        given = dict(deep_dropout=deep_dropout, deep_hidden_units=deep_hidden_units)
+        self._init_front(feat_dict, hp, given, loss_type, eval_metric, epoch, batch_size, random_seed,
+                         what_means_greater, use_interactive_session, log_dir, strict_reference, device)
 
 
 class FwFM(FmFM):

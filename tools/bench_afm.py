@@ -5,7 +5,6 @@ the [B, P, D] pair tensor), whole-batch and in pieces of 4096 examples - alterna
 Flops per kernel: AFMEngine.afm_flops (per pair D + 2 D T + 2 T + 2 D forward; the backward recomputes that and adds
 2 (2 D T) + 4 D), priced against the 157.3 TFLOP/s fp32 peak.  Also an AFMEngine.fwd_bwd step beside a DeepFM step at
 the same shape.  python tools/bench_afm.py [--json out.json]"""
-import json
 import os
 import sys
 
@@ -15,29 +14,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import afm_ref as R
-
-PEAK = 157.3e12
-
-
-def med(ts):
-    return sorted(ts)[len(ts) // 2]
-
-
-def alternate(fns, n=20, warm=3):
-    """Median ms per contender, the contenders taking turns."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [med(t) for t in ts]
+from tools._bench import PEAK_MFMA as PEAK, criteo_like, emit, medians
 
 
 def kernels(B, F, D, T, comparator=True):
@@ -65,7 +42,7 @@ def kernels(B, F, D, T, comparator=True):
             y.backward(g)
 
         fns += [composed, lambda: composed(4096)]
-    ms = alternate(fns)
+    ms = medians(fns, 20, 3)
     f_fwd, f_bwd = eng.AFMEngine.afm_flops(B, F, D, T)
     rec = {"shape": dict(B=B, F=F, D=D, T=T), "afm_fwd_ms": round(ms[0], 4), "afm_fwd_inference_ms": round(ms[1], 4),
            "afm_bwd_ms": round(ms[2], 4), "fwd_tflops": round(f_fwd / ms[0] / 1e9, 2),
@@ -82,25 +59,15 @@ def kernels(B, F, D, T, comparator=True):
 def steps(B=65536, F=26, D=16, Dn=13):
     """An AFMEngine.fwd_bwd step beside a DeepFM step at the same shape (hashed ids over 26 x 40000 rows)."""
     out = {}
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     for name, hp in (("afm", dict(att_factor=8)), ("deepfm", dict(deep_hidden_units=(32, 32)))):
         e = eng.ENGINES[name](spec, D, hp)
         eng.init_reference(e)
-        out[name + "_fwd_bwd_ms"] = round(alternate([lambda: e.fwd_bwd(idx, dense, y)])[0], 4)
+        out[name + "_fwd_bwd_ms"] = round(medians([lambda: e.fwd_bwd(idx, dense, y)], 20, 3)[0], 4)
         del e
     return out
 
 
 if __name__ == "__main__":
-    res = {"kernels": [kernels(65536, 26, 16, 8), kernels(65536, 26, 16, 32),
-                       kernels(8192, 40, 64, 64, comparator=False)], "steps": steps()}
-    for k in res["kernels"]:
-        print(json.dumps(k))
-    print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    emit({"kernels": [kernels(65536, 26, 16, 8), kernels(65536, 26, 16, 32),
+                      kernels(8192, 40, 64, 64, comparator=False)], "steps": steps()})

@@ -6,7 +6,6 @@ process.  Shape: B = 65536, D = 16, hidden (80, 40), history lengths uniform 1..
 run with Zipf-distributed ids.  Flops per position: 2 (4D H1 + H1 H2) + 2 H_last forward; the backward recomputes that
 and adds four products of the two GEMMs' sizes (dz1, dx, dW1, dW0); priced against the 157.3 TFLOP/s fp32 peak.  Also
 a DIN engine step with and without the sequence feature.  python tools/bench_asp.py [--json out.json]"""
-import json
 import os
 import sys
 
@@ -16,7 +15,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import asp_ref as R
-from tools.bench_afm import alternate
+from tools._bench import emit, medians
 
 PEAK = 157.3e12
 
@@ -73,7 +72,7 @@ def kernels(B=65536, D=16, hidden=(80, 40), max_len=50, rows=1_000_000, act="sig
             t.grad = None
         R.asp_layer(Q, K, offsets, leaves[:m], leaves[m:2 * m], leaves[-2], leaves[-1], act, norm).backward(g_out)
 
-    ms = alternate([fwd, bwd, composed])
+    ms = medians([fwd, bwd, composed], 20, 3)
     f_fwd, f_bwd = asp_flops(nnz, D, hidden)
     fused = ms[0] + ms[1]
     # the contenders compute the same thing (gradients: tests/test_gpu_asp.py, against float64)
@@ -109,16 +108,10 @@ def steps(B=65536, F=26, D=16, Dn=13, max_len=50, rows=1_000_000):
             spec, ix, mv = eng.FeatureSpec(names, sizes, [f"I{j}" for j in range(Dn)]), idx.cuda(), None
         e = eng.DINEngine(spec, D, hp)
         eng.init_reference(e)
-        out[f"din_fwd_bwd_{tag}_ms"] = round(alternate([lambda: e.fwd_bwd(ix, dense, y, mv=mv)])[0], 4)
+        out[f"din_fwd_bwd_{tag}_ms"] = round(medians([lambda: e.fwd_bwd(ix, dense, y, mv=mv)], 20, 3)[0], 4)
         del e
     return out
 
 
 if __name__ == "__main__":
-    res = {"kernels": [kernels(), kernels(zipf=True), kernels(norm=True, act="relu")], "steps": steps()}
-    for k in res["kernels"]:
-        print(json.dumps(k))
-    print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    emit({"kernels": [kernels(), kernels(zipf=True), kernels(norm=True, act="relu")], "steps": steps()})

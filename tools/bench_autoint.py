@@ -7,7 +7,6 @@ for the four projections + 4 F^2 HD for scores and weighted sums per example; th
 forwards), against the 157.3 TFLOP/s f32 matrix peak.  Also the three-layer default model's AutoIntEngine.fwd_bwd step.
     python tools/bench_autoint.py [--json out.json] [--kernels-only]
 `--kernels-only` launches nothing but the fused kernels (the run to put under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -17,30 +16,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import autoint_ref as R
-
-PEAK = 157.3e12
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
+from tools._bench import PEAK_MFMA as PEAK, alternate, criteo_like, hbm_fields, main
 
 
 def kernels(B, F, Din, H, dk, comparator=True):
@@ -72,9 +48,7 @@ def kernels(B, F, Din, H, dk, comparator=True):
            "fwd_tflops": round(f_fwd / ms[0]["median"] / 1e9, 2), "bwd_tflops": round(f_bwd / ms[1]["median"] / 1e9, 2),
            "fwd_peak_share": round(f_fwd / (ms[0]["median"] * 1e-3) / PEAK, 4),
            "bwd_peak_share": round(f_bwd / (ms[1]["median"] * 1e-3) / PEAK, 4),
-           "fwd_hbm_gb": round(hbm_fwd / 1e9, 4), "bwd_hbm_gb": round(hbm_bwd / 1e9, 4),
-           "fwd_hbm_tb_s": round(hbm_fwd / (ms[0]["median"] * 1e-3) / 1e12, 3),
-           "bwd_hbm_tb_s": round(hbm_bwd / (ms[1]["median"] * 1e-3) / 1e12, 3)}
+           **hbm_fields(hbm_fwd, hbm_bwd, ms[0], ms[1], peak_share=False)}
     if comparator:
         fused = ms[0]["median"] + ms[1]["median"]
         rec.update(composed_fwd_bwd_ms=ms[2], ratio_composed_over_fused=round(ms[2]["median"] / fused, 2))
@@ -84,26 +58,18 @@ def kernels(B, F, Din, H, dk, comparator=True):
 def step(B=65536, F=26, D=16, Dn=13, hidden=()):
     """AutoIntEngine.fwd_bwd, the default model (three layers, two heads of 8, residual), hashed ids over 26 x 40000
     rows; with `hidden` the AutoInt+ variant."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     e = eng.AutoIntEngine(spec, D, dict(deep_hidden_units=tuple(hidden)))
     eng.init_reference(e)
     return alternate([lambda: e.fwd_bwd(idx, dense, y)])[0]
 
 
+def all_kernels(comparator):
+    out = [kernels(65536, 26, 16, 2, 8, comparator=comparator)]
+    if comparator:
+        out += [kernels(65536, 26, 16, 2, 16), kernels(8192, 40, 64, 8, 8, comparator=False)]
+    return out
+
+
 if __name__ == "__main__":
-    only = "--kernels-only" in sys.argv
-    res = {"kernels": [kernels(65536, 26, 16, 2, 8, comparator=not only)]}
-    if not only:
-        res["kernels"] += [kernels(65536, 26, 16, 2, 16), kernels(8192, 40, 64, 8, 8, comparator=False)]
-        res["steps"] = {"autoint_fwd_bwd_ms": step(), "autoint_plus_32x32_fwd_bwd_ms": step(hidden=(32, 32))}
-    for k in res["kernels"]:
-        print(json.dumps(k))
-    if "steps" in res:
-        print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(all_kernels, lambda: {"autoint_fwd_bwd_ms": step(), "autoint_plus_32x32_fwd_bwd_ms": step(hidden=(32, 32))})

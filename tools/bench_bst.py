@@ -8,7 +8,6 @@ recomputes that and adds two products per forward product (the input's and the w
 157.3 TFLOP/s fp32 peak.  Bytes: one D-float row read per token and direction, the pooled rows, and in the backward the
 key gradients, the pooled rows' gradient and the query gradient's read-modify-write; priced against 8 TB/s.  Also a
 BST engine step with and without the sequence feature.  python tools/bench_bst.py [--json out.json]"""
-import json
 import os
 import sys
 
@@ -18,7 +17,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import bst_ref as R
-from tools.bench_afm import alternate
+from tools._bench import emit, medians
 from tools.bench_asp import history
 
 PEAK = 157.3e12
@@ -69,8 +68,8 @@ def kernels(B=65536, D=16, heads=2, Hf=64, max_len=20, rows=1_000_000, zipf=Fals
             t.grad = None
         R.bst_layer(Q, K, offsets, leaves, heads).backward(g_out)
 
-    ms = alternate([fwd, bwd, composed])
-    alone = alternate([fwd, bwd])  # without the comparator's 50 ms of other traffic between the launches
+    ms = medians([fwd, bwd, composed], 20, 3)
+    alone = medians([fwd, bwd], 20, 3)  # without the comparator's 50 ms of other traffic between the launches
     f_fwd, f_bwd, b_fwd, b_bwd = bst_work(offsets, D, Hf, LD)
     fused = ms[0] + ms[1]
     # the contenders compute the same thing (gradients: tests/test_gpu_bst.py, against float64)
@@ -108,16 +107,10 @@ def steps(B=65536, F=26, D=16, Dn=13, max_len=20, rows=1_000_000):
     ix = idx.cuda()
     ix_seq = torch.cat([idx, torch.zeros(B, 1, dtype=torch.int64)], 1).cuda()
     mv = {"hist": (offsets, ids)}
-    ms = alternate([lambda: plain.fwd_bwd(ix, dense, y), lambda: seq.fwd_bwd(ix_seq, dense, y, mv=mv)])
+    ms = medians([lambda: plain.fwd_bwd(ix, dense, y), lambda: seq.fwd_bwd(ix_seq, dense, y, mv=mv)], 20, 3)
     return {"bst_fwd_bwd_without_sequence_ms": round(ms[0], 4), "bst_fwd_bwd_with_sequence_ms": round(ms[1], 4),
             "nnz": int(ids.shape[0])}
 
 
 if __name__ == "__main__":
-    res = {"kernels": [kernels(), kernels(zipf=True)], "steps": steps()}
-    for k in res["kernels"]:
-        print(json.dumps(k))
-    print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    emit({"kernels": [kernels(), kernels(zipf=True)], "steps": steps()})

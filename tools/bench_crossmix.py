@@ -8,7 +8,6 @@ matrix and mix with deep_hidden_units (400, 400) in the same process.
     python tools/bench_crossmix.py [--json out.json] [--kernels-only | --step-only]
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's steps (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -18,30 +17,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import crossmix_ref as R
-
-PEAK = 8.0e12
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
+from tools._bench import PEAK_HBM as PEAK, alternate, criteo_like, main
 
 
 def kernels(B, E, r, comparator=True):
@@ -88,11 +64,7 @@ def kernels(B, E, r, comparator=True):
 
 def steps(B=65536, F=26, D=16, Dn=13, L=3, E=4, r=32, hidden=(400, 400)):
     """DCNEngine.fwd_bwd for the three cross types taking turns, hashed ids over 26 x 40000 rows."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     engines = {}
     for ct in ("vector", "matrix", "mix"):
         e = eng.DCNEngine(spec, D, dict(deep_hidden_units=tuple(hidden), cross_layer_num=L, cross_type=ct,
@@ -103,20 +75,13 @@ def steps(B=65536, F=26, D=16, Dn=13, L=3, E=4, r=32, hidden=(400, 400)):
     return {f"dcn_{ct}_fwd_bwd_ms": m for ct, m in zip(engines, ms)}
 
 
+def all_kernels(comparator):
+    out = [kernels(65536, 4, 32, comparator=comparator)]
+    if comparator:
+        out += [kernels(65536, 8, 32, comparator=False), kernels(65536, 4, 64, comparator=False),
+                kernels(65536, 3, 8, comparator=False)]
+    return out
+
+
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = [kernels(65536, 4, 32, comparator=not only)]
-        if not only:
-            res["kernels"] += [kernels(65536, 8, 32, comparator=False), kernels(65536, 4, 64, comparator=False),
-                               kernels(65536, 3, 8, comparator=False)]
-    if not only:
-        res["steps"] = steps()
-    for k in res.get("kernels", ()):
-        print(json.dumps(k))
-    if "steps" in res:
-        print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(all_kernels, steps)

@@ -10,7 +10,6 @@ the 157.3 TFLOP/s fp32 peak.  Bytes: per position one D-float row read, h_t writ
 (forward); the rows, h_t, g_t, a_t read, two [4, D] sets of pre-activation gradients written and read, the key gradient
 written (backward); priced against 8 TB/s.  Also a DIEN engine step with and without the sequence feature.
 python tools/bench_dien.py [--json out.json]"""
-import json
 import os
 import sys
 
@@ -20,7 +19,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import dien_ref as R
-from tools.bench_afm import alternate
+from tools._bench import emit, medians
 from tools.bench_asp import history
 
 PEAK = 157.3e12
@@ -65,8 +64,8 @@ def kernels(B=65536, D=16, max_len=20, rows=1_000_000, zipf=False):
             t.grad = None
         R.dien_layer(Q, K, offsets, leaves).backward(g_out)
 
-    ms = alternate([fwd, bwd, composed])
-    alone = alternate([fwd, bwd])  # without the comparator's other traffic between the launches
+    ms = medians([fwd, bwd, composed], 20, 3)
+    alone = medians([fwd, bwd], 20, 3)  # without the comparator's other traffic between the launches
     f_fwd, f_bwd, b_fwd, b_bwd = dien_work(offsets, D, LD)
     fused = ms[0] + ms[1]
     # the contenders compute the same thing (gradients: tests/test_gpu_dien.py, against float64)
@@ -104,16 +103,10 @@ def steps(B=65536, F=26, D=16, Dn=13, max_len=20, rows=1_000_000):
     ix = idx.cuda()
     ix_seq = torch.cat([idx, torch.zeros(B, 1, dtype=torch.int64)], 1).cuda()
     mv = {"hist": (offsets, ids)}
-    ms = alternate([lambda: plain.fwd_bwd(ix, dense, y), lambda: seq.fwd_bwd(ix_seq, dense, y, mv=mv)])
+    ms = medians([lambda: plain.fwd_bwd(ix, dense, y), lambda: seq.fwd_bwd(ix_seq, dense, y, mv=mv)], 20, 3)
     return {"dien_fwd_bwd_without_sequence_ms": round(ms[0], 4), "dien_fwd_bwd_with_sequence_ms": round(ms[1], 4),
             "nnz": int(ids.shape[0])}
 
 
 if __name__ == "__main__":
-    res = {"kernels": [kernels(), kernels(zipf=True)], "steps": steps()}
-    for k in res["kernels"]:
-        print(json.dumps(k))
-    print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    emit({"kernels": [kernels(), kernels(zipf=True)], "steps": steps()})

@@ -8,7 +8,6 @@ bottom_hidden_units=(512, 256) and deep_hidden_units=(512, 256).
     python tools/bench_dlrm.py [--json out.json] [--kernels-only | --step-only]
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's step (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -18,30 +17,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import dlrm_ref as R
-
-PEAK = 8.0e12
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
+from tools._bench import alternate, criteo_like, hbm_fields, main
 
 
 def kernels(B, F, D, comparator=True):
@@ -69,11 +45,7 @@ def kernels(B, F, D, comparator=True):
     ms = alternate(fns)
     hbm_fwd, hbm_bwd = 4 * B * (F * D + D + ldx), 4 * B * (2 * F * D + 2 * D + ldx)
     rec = {"shape": dict(B=B, F=F, D=D, ldx=ldx), "fwd_ms": ms[0], "bwd_ms": ms[1],
-           "fwd_hbm_gb": round(hbm_fwd / 1e9, 4), "bwd_hbm_gb": round(hbm_bwd / 1e9, 4),
-           "fwd_hbm_tb_s": round(hbm_fwd / (ms[0]["median"] * 1e-3) / 1e12, 3),
-           "bwd_hbm_tb_s": round(hbm_bwd / (ms[1]["median"] * 1e-3) / 1e12, 3),
-           "fwd_peak_share": round(hbm_fwd / (ms[0]["median"] * 1e-3) / PEAK, 4),
-           "bwd_peak_share": round(hbm_bwd / (ms[1]["median"] * 1e-3) / PEAK, 4)}
+           **hbm_fields(hbm_fwd, hbm_bwd, ms[0], ms[1])}
     if comparator:
         fused = ms[0]["median"] + ms[1]["median"]
         rec.update(composed_fwd_bwd_ms=ms[2], ratio_composed_over_fused=round(ms[2]["median"] / fused, 2))
@@ -87,29 +59,18 @@ def kernels(B, F, D, comparator=True):
 
 def step(B=65536, F=26, D=16, Dn=13, bottom=(512, 256), hidden=(512, 256)):
     """DLRMEngine.fwd_bwd, hashed ids over 26 x 40000 rows."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     e = eng.DLRMEngine(spec, D, dict(bottom_hidden_units=tuple(bottom), deep_hidden_units=tuple(hidden)))
     eng.init_reference(e)
     return alternate([lambda: e.fwd_bwd(idx, dense, y)])[0]
 
 
+def all_kernels(comparator):
+    out = [kernels(65536, 26, 16, comparator=comparator)]
+    if comparator:
+        out += [kernels(65536, 40, 64, comparator=False), kernels(65536, 7, 16, comparator=False)]
+    return out
+
+
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = [kernels(65536, 26, 16, comparator=not only)]
-        if not only:
-            res["kernels"] += [kernels(65536, 40, 64, comparator=False), kernels(65536, 7, 16, comparator=False)]
-    if not only:
-        res["steps"] = {"dlrm_512x256_512x256_fwd_bwd_ms": step()}
-    for k in res.get("kernels", ()):
-        print(json.dumps(k))
-    if "steps" in res:
-        print(json.dumps(res["steps"]))
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(all_kernels, lambda: {"dlrm_512x256_512x256_fwd_bwd_ms": step()})

@@ -9,7 +9,6 @@ d_rows out) against the 8 TB/s HBM spec.  Also FmFMEngine.fwd_bwd without a DNN 
     python tools/bench_fmfm.py [--json out.json] [--kernels-only | --step-only]
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's step (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -19,30 +18,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import fmfm_ref as R
-
-PEAK_HBM, PEAK_MFMA = 8.0e12, 157.3e12
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
+from tools._bench import PEAK_MFMA, alternate, criteo_like, hbm_gb_s_fields, main
 
 
 def composed_logit(E, W, ftype, li, lj):
@@ -92,11 +68,7 @@ def kernels(B, F, D, ftype, comparator=True):
                    bwd_peak_share=round(rec["bwd_tflop_s"] * 1e12 / PEAK_MFMA, 4))
     else:
         hbm_fwd, hbm_bwd = 4.0 * (B * F * D + B + W.numel()), 4.0 * (2 * B * F * D + B + 2 * W.numel())
-        rec.update(fwd_hbm_gb=round(hbm_fwd / 1e9, 4), bwd_hbm_gb=round(hbm_bwd / 1e9, 4),
-                   fwd_gb_s=round(hbm_fwd / (ms[0]["median"] * 1e-3) / 1e9, 1),
-                   bwd_gb_s=round(hbm_bwd / (ms[1]["median"] * 1e-3) / 1e9, 1))
-        rec.update(fwd_peak_share=round(rec["fwd_gb_s"] * 1e9 / PEAK_HBM, 4),
-                   bwd_peak_share=round(rec["bwd_gb_s"] * 1e9 / PEAK_HBM, 4))
+        rec.update(hbm_gb_s_fields(hbm_fwd, hbm_bwd, ms[0], ms[1], "peak_share"))
     if comparator:
         fused = ms[0]["median"] + ms[1]["median"]
         rec.update(composed_fwd_bwd_ms=ms[2], ratio_composed_over_fused=round(ms[2]["median"] / fused, 2))
@@ -110,28 +82,13 @@ def kernels(B, F, D, ftype, comparator=True):
 
 def step(ftype, hidden, B=65536, F=26, D=16, Dn=13):
     """FmFMEngine.fwd_bwd, hashed ids over 26 x 40000 rows."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     e = eng.FmFMEngine(spec, D, dict(deep_hidden_units=tuple(hidden), field_interaction=ftype))
     eng.init_reference(e)
     return alternate([lambda: e.fwd_bwd(idx, dense, y)], n=20, warm=3)[0]
 
 
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = [kernels(65536, 26, 16, t, comparator=not only) for t in R.TYPES]
-    if not only:
-        res["steps"] = {f"fmfm_{t}_{'x'.join(map(str, h)) or 'no_dnn'}_fwd_bwd_ms": step(t, h)
-                        for t in R.TYPES for h in ((), (400, 400))}
-    for k in res.get("kernels", ()):
-        print(json.dumps(k), flush=True)
-    if "steps" in res:
-        print(json.dumps(res["steps"]), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(lambda comparator: [kernels(65536, 26, 16, t, comparator=comparator) for t in R.TYPES],
+         lambda: {f"fmfm_{t}_{'x'.join(map(str, h)) or 'no_dnn'}_fwd_bwd_ms": step(t, h)
+                  for t in R.TYPES for h in ((), (400, 400))})

@@ -9,7 +9,6 @@ HBM spec: group forward 4 B F D (1 + 2 N), group backward 4 B F D (2 + 3 N), row
     python tools/bench_masknet.py [--json out.json] [--kernels-only | --step-only]
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's step (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import subprocess
 import sys
@@ -20,32 +19,9 @@ import torch.nn.functional as Fn
 
 from recman_amd import engine as eng
 from recman_amd import ops
+from tools._bench import PEAK_HBM, alternate, criteo_like, emit, selected
 
-PEAK_HBM = 8.0e12
 ROTATE_BYTES = 512 << 20
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches);
-    fn(i) works on buffer set i."""
-    for i in range(warm):
-        for fn in fns:
-            fn(i)
-    ts = [[] for _ in fns]
-    for i in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn(i)
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
 
 
 def clock():
@@ -89,7 +65,7 @@ def group(B, F, D, N, comparator=True):
             gl.grad = bl.grad = None
 
         fns.append(composed)
-    ms = alternate(fns)
+    ms = alternate(fns, indexed=True)  # fn(i) works on buffer set i
     fb, bb = 4.0 * (B * W * (1 + 2 * N) + 2 * W), 4.0 * (B * W * (2 + 3 * N) + 4 * W)
     rec = {"kernel": "group", "shape": dict(B=B, F=F, D=D, N=N, buffer_sets=S,
                                             tile=ops.masknet_group_tile(F, D, "tile"),
@@ -124,7 +100,7 @@ def row(B, H, comparator=True):
             gl.grad = bl.grad = None
 
         fns.append(composed)
-    ms = alternate(fns)
+    ms = alternate(fns, indexed=True)  # fn(i) works on buffer set i
     fb, bb = 4.0 * (2 * B * H + 2 * H), 4.0 * (3 * B * H + 4 * H)
     rec = {"kernel": "row", "shape": dict(B=B, H=H, buffer_sets=S, tile=ops.masknet_row_tile(H, "tile"),
                                           cap=ops.masknet_row_tile(H, "cap")),
@@ -141,30 +117,16 @@ def row(B, H, comparator=True):
 
 def step(order, B=65536, F=26, D=16, Dn=13, N=3, H=256, ratio=2.0, hidden=(128, 128)):
     """MaskNetEngine.fwd_bwd, hashed ids over 26 x 40000 rows."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     e = eng.MaskNetEngine(spec, D, dict(block_order=order, num_blocks=N, block_hidden_units=H, reduction_ratio=ratio,
                                         deep_hidden_units=tuple(hidden)))
     eng.init_reference(e)
-    return alternate([lambda i: e.fwd_bwd(idx, dense, y)], n=20, warm=3)[0]
+    return alternate([lambda: e.fwd_bwd(idx, dense, y)], n=20, warm=3)[0]
 
 
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = [group(65536, 26, 16, 3, comparator=not only), row(65536, 256, comparator=not only)]
-    if not only:
-        res["steps"] = {f"masknet_{o}_fwd_bwd_ms": step(o) for o in ("parallel", "serial")}
+    res = selected(lambda comparator: [group(65536, 26, 16, 3, comparator=comparator),
+                                       row(65536, 256, comparator=comparator)],
+                   lambda: {f"masknet_{o}_fwd_bwd_ms": step(o) for o in ("parallel", "serial")})
     res["clock"] = clock()
-    for k in res.get("kernels", ()):
-        print(json.dumps(k), flush=True)
-    if "steps" in res:
-        print(json.dumps(res["steps"]), flush=True)
-    print(json.dumps({"clock": res["clock"]}), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res)

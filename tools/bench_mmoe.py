@@ -8,7 +8,6 @@ T H) forward and twice that backward (dM in, dZ and dA out on top), against the 
 The shape: B = 65536, F = 26, D = 16, 13 dense features, 8 experts of (256, 128), 2 tasks, towers of (64,).
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's step (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -17,31 +16,9 @@ import torch
 
 from recman_amd import engine as eng
 from recman_amd import ops
+from tools._bench import alternate, hashed_batch, hbm_gb_s_fields, main
 
-PEAK_HBM = 8.0e12
 SHAPE = dict(B=65536, F=26, D=16, Dn=13, E=8, experts=(256, 128), T=2, towers=(64,))
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
 
 
 def composed_mix(Z, A, E, T):
@@ -75,13 +52,9 @@ def kernels(B, E, T, H, comparator=True):
     ms = dict(zip(names, alternate(fns)))
     rec = {"shape": dict(B=B, E=E, T=T, H=H, tile=ops.mmoe_mix_tile(E, T, H), cap=ops.mmoe_mix_tile(E, T, H, "cap"))}
     rec.update(ms)
-    f_ms, b_ms = ms["fwd_ms"]["median"] * 1e-3, ms["bwd_ms"]["median"] * 1e-3
     hbm_fwd = 4.0 * B * (E * H + T * E + T * H)
     hbm_bwd = 2 * hbm_fwd
-    rec.update(fwd_hbm_gb=round(hbm_fwd / 1e9, 4), bwd_hbm_gb=round(hbm_bwd / 1e9, 4),
-               fwd_gb_s=round(hbm_fwd / f_ms / 1e9, 1), bwd_gb_s=round(hbm_bwd / b_ms / 1e9, 1))
-    rec.update(fwd_hbm_share=round(rec["fwd_gb_s"] * 1e9 / PEAK_HBM, 4),
-               bwd_hbm_share=round(rec["bwd_gb_s"] * 1e9 / PEAK_HBM, 4))
+    rec.update(hbm_gb_s_fields(hbm_fwd, hbm_bwd, ms["fwd_ms"], ms["bwd_ms"], "hbm_share"))
     if comparator:
         fused = ms["fwd_ms"]["median"] + ms["bwd_ms"]["median"]
         rec["ratio_composed_fwd_over_fused_fwd"] = round(ms["composed_fwd_ms"]["median"] / ms["fwd_ms"]["median"], 2)
@@ -95,14 +68,10 @@ def kernels(B, E, T, H, comparator=True):
 
 def step(B, F, D, Dn, E, experts, T, towers):
     """MMoEEngine.fwd_bwd, hashed ids over 26 x 40000 rows, about 30 % of the second task's labels observed."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense = torch.randn(B, Dn, generator=g).cuda()
+    spec, idx, dense, g = hashed_batch(B, F, Dn)
     Y = (torch.rand(B, T, generator=g) < 0.3).float()
     Y[Y[:, 0] == 0, 1:] = float("nan")
     Y = Y.cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
     names = ("ctr", "cvr", "like", "dwell", "t4", "t5", "t6", "t7")[:T]
     e = eng.MMoEEngine(spec, D, dict(task_names=names, task_types=("classification",) * T, num_experts=E,
                                      expert_hidden_units=tuple(experts), tower_hidden_units=tuple(towers)))
@@ -111,17 +80,6 @@ def step(B, F, D, Dn, E, experts, T, towers):
 
 
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
     s = SHAPE
-    res = {}
-    if not step_only:
-        res["kernels"] = [kernels(s["B"], s["E"], s["T"], s["experts"][-1], comparator=not only)]
-    if not only:
-        res["steps"] = {"mmoe_8x256x128_2x64_fwd_bwd_ms": step(**s)}
-    for k in res.get("kernels", ()):
-        print(json.dumps(k), flush=True)
-    if "steps" in res:
-        print(json.dumps(res["steps"]), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(lambda comparator: [kernels(s["B"], s["E"], s["T"], s["experts"][-1], comparator=comparator)],
+         lambda: {"mmoe_8x256x128_2x64_fwd_bwd_ms": step(**s)})

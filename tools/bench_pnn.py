@@ -12,7 +12,6 @@ in, d_rows out) against the 8 TB/s HBM spec.  Also PNNEngine.fwd_bwd with deep_h
     python tools/bench_pnn.py [--json out.json] [--kernels-only | --step-only]
 `--kernels-only` launches nothing but the fused kernels, `--step-only` nothing but the engine's step (the runs to put
 under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -22,30 +21,7 @@ import torch
 from recman_amd import engine as eng
 from recman_amd import ops
 from tests import pnn_ref as R
-
-PEAK_HBM, PEAK_MFMA = 8.0e12, 157.3e12
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
+from tools._bench import PEAK_MFMA, alternate, criteo_like, hbm_gb_s_fields, main
 
 
 def composed_layer(E, K, products, kt, li, lj):
@@ -112,10 +88,7 @@ def kernels(B, F, D, products, kt, comparator=True):
     f_ms, b_ms = ms["fwd_ms"]["median"] * 1e-3, ms["bwd_ms"]["median"] * 1e-3
     nk = K.numel() if outer else 0
     hbm_fwd, hbm_bwd = 4.0 * (B * F * D + B * ldx + nk), 4.0 * (2 * B * F * D + B * ldx + 2 * nk)
-    rec.update(fwd_hbm_gb=round(hbm_fwd / 1e9, 4), bwd_hbm_gb=round(hbm_bwd / 1e9, 4),
-               fwd_gb_s=round(hbm_fwd / f_ms / 1e9, 1), bwd_gb_s=round(hbm_bwd / b_ms / 1e9, 1))
-    rec.update(fwd_hbm_share=round(rec["fwd_gb_s"] * 1e9 / PEAK_HBM, 4),
-               bwd_hbm_share=round(rec["bwd_gb_s"] * 1e9 / PEAK_HBM, 4))
+    rec.update(hbm_gb_s_fields(hbm_fwd, hbm_bwd, ms["fwd_ms"], ms["bwd_ms"], "hbm_share"))
     if mat:
         flops = 2.0 * B * P * D * D
         rec.update(fwd_gflop=round(flops / 1e9, 3), bwd_gflop=round(3 * flops / 1e9, 3),
@@ -137,11 +110,7 @@ def kernels(B, F, D, products, kt, comparator=True):
 
 def step(products, kt, hidden=(400, 400), B=65536, F=26, D=16, Dn=13):
     """PNNEngine.fwd_bwd, hashed ids over 26 x 40000 rows."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense, y = torch.randn(B, Dn, generator=g).cuda(), (torch.rand(B, generator=g) < 0.3).long().cuda()
-    spec = eng.FeatureSpec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, idx, dense, y = criteo_like(B, F, Dn)
     e = eng.PNNEngine(spec, D, dict(deep_hidden_units=tuple(hidden), use_inner=bool(products & R.INNER),
                                     use_outer=bool(products & R.OUTER), kernel_type=kt))
     eng.init_reference(e)
@@ -153,16 +122,5 @@ def tag(products, kt):
 
 
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = [kernels(65536, 26, 16, pr, kt, comparator=not only) for pr, kt in R.COMBOS]
-    if not only:
-        res["steps"] = {f"pnn_{tag(pr, kt)}_400x400_fwd_bwd_ms": step(pr, kt) for pr, kt in R.COMBOS}
-    for k in res.get("kernels", ()):
-        print(json.dumps(k), flush=True)
-    if "steps" in res:
-        print(json.dumps(res["steps"]), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(lambda comparator: [kernels(65536, 26, 16, pr, kt, comparator=comparator) for pr, kt in R.COMBOS],
+         lambda: {f"pnn_{tag(pr, kt)}_400x400_fwd_bwd_ms": step(pr, kt) for pr, kt in R.COMBOS})

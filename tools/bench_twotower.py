@@ -9,7 +9,6 @@ recomputations of the scores and two products), against the 157.3 TFLOP/s f32-MF
 Shapes: H = 64 and 128 at B = 4096, 8192 and 32768; the step with the default towers (256, 128) at F = 26 (13 user and
 13 item features), D = 16, 13 dense features, B = 8192.  `--kernels-only` launches nothing but the fused kernels,
 `--step-only` nothing but the engine's step (the runs to put under rocprofv3 --kernel-trace --stats)."""
-import json
 import os
 import sys
 
@@ -18,34 +17,12 @@ import torch
 
 from recman_amd import engine as eng
 from recman_amd import ops
+from tools._bench import PEAK_MFMA as PEAK_F32_MFMA, alternate, hashed_batch, main
 
-PEAK_F32_MFMA = 157.3e12
 SHAPES = [(B, H) for H in (64, 128) for B in (4096, 8192, 32768)]
 COMPOSED_MAX_B = 32768  # beyond it each of the composition's [B, B] matrices (4 B^2 bytes) passes 17 GB
 STEP = dict(B=8192, F=26, D=16, Dn=13, towers=(256, 128))
 SCALE = 20.0
-
-
-def stats(ts):
-    ts = sorted(ts)
-    return dict(min=round(ts[0], 4), median=round(ts[len(ts) // 2], 4), mean=round(sum(ts) / len(ts), 4))
-
-
-def alternate(fns, n=50, warm=5):
-    """min / median / mean ms per contender, the contenders taking turns (warm-up rounds first: clocks and caches)."""
-    for _ in range(warm):
-        for fn in fns:
-            fn()
-    ts = [[] for _ in fns]
-    for _ in range(n):
-        for fn, acc in zip(fns, ts):
-            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            z.record()
-            z.synchronize()
-            acc.append(a.elapsed_time(z))
-    return [stats(t) for t in ts]
 
 
 def composed_loss(U, V, ids, logq, w):
@@ -109,12 +86,8 @@ def kernels(B, H, comparator=True):
 
 def step(B, F, D, Dn, towers):
     """TwoTowerEngine.fwd_bwd: hashed ids over 26 x 40000 rows, the first half of the features the user's."""
-    g = torch.Generator().manual_seed(0)
-    sizes = [40000] * F
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1).cuda()
-    dense = torch.randn(B, Dn, generator=g).cuda()
-    names, dn = [f"C{i}" for i in range(F)], [f"I{j}" for j in range(Dn)]
-    spec = eng.FeatureSpec(names, sizes, dn)
+    spec, idx, dense, _ = hashed_batch(B, F, Dn)
+    names, dn = spec.sparse_names, spec.dense_names
     hp = dict(user_features=tuple(names[: F // 2] + dn[: Dn // 2]), item_features=tuple(names[F // 2:] + dn[Dn // 2:]),
               item_id_feature=names[F // 2], user_hidden_units=tuple(towers), item_hidden_units=tuple(towers),
               temperature=0.05)
@@ -124,17 +97,5 @@ def step(B, F, D, Dn, towers):
 
 
 if __name__ == "__main__":
-    only, step_only = "--kernels-only" in sys.argv, "--step-only" in sys.argv
-    res = {}
-    if not step_only:
-        res["kernels"] = []
-        for B, H in SHAPES:
-            res["kernels"].append(kernels(B, H, comparator=not only))
-            print(json.dumps(res["kernels"][-1]), flush=True)
-    if not only:
-        s = STEP
-        res["steps"] = {f"twotower_B{s['B']}_2x256x128_fwd_bwd_ms": step(**s)}
-        print(json.dumps(res["steps"]), flush=True)
-    if "--json" in sys.argv:
-        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
-            json.dump(res, f, indent=1)
+    main(lambda comparator: [kernels(B, H, comparator=comparator) for B, H in SHAPES],
+         lambda: {f"twotower_B{STEP['B']}_2x256x128_fwd_bwd_ms": step(**STEP)})
