@@ -269,10 +269,15 @@ int rm_deepfm_step(const int64_t *idx, const float *table, int64_t table_ld, con
                    float *const *dW, float *const *db, float *d_w_out, float *d_w0_out, float *d_lin_w_dense,
                    float *d_lin_w0, float *workspace, int64_t packed_rows, const float *lin_field_mask, int flags,
                    rm_stream_t stream);
-/* Test aid, not a product path: fills the LDS of every CU with one 32-bit pattern - workgroups of rm_deepfm_step's
- * shape (512 threads, its full dynamic LDS size), twice the CU count of them, every word written with ds_write -
- * so that what the step kernel finds in LDS before it has written it is known (tests/test_gpu_step_stale_lds.py). */
+/* Test aids, not product paths.  rm_debug_lds_fill fills the LDS of every CU with one 32-bit pattern: workgroups of
+ * 512 threads that allocate a CU's whole LDS (163,840 bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, so one fits a
+ * CU), four times the CU count of them, every word written with ds_write - what the kernel behind it on the stream
+ * finds in LDS before it has written it is then known (tests/stale_state.py, tests/test_gpu_stale_lds.py,
+ * tests/test_gpu_step_stale_lds.py).  rm_debug_lds_probe is the fill's own check: nblocks workgroups that allocate the
+ * whole LDS, write none of it and count the words that differ from pattern; mismatches [nblocks] (device) gets one
+ * count per block. */
 int rm_debug_lds_fill(unsigned pattern, rm_stream_t stream);
+int rm_debug_lds_probe(unsigned pattern, unsigned *mismatches, int nblocks, rm_stream_t stream);
 
 /* Epilogues of the library-GEMM DNN path (wide hidden layers, layers.py:593-601):
  * rm_bias_act: x[b,j] = act(x[b,j] + bias[j]) in place (bias may be NULL = a bias of +0.0: the add is still made,
@@ -916,7 +921,14 @@ int rm_cin_layer_bwd(const float *X0, const float *Xk, int64_t xk_bstride, int x
  * rm_dense_wgrad: dW[K1+K2, N] (+)= [A1 | A2]^T . G[M,N]  (reduction over the batch, split
  *   into slabs + a deterministic second-stage sum); db [N] (NULL ok) = the column sums of G, i.e. the
  *   bias gradient of the same layer, from the G tiles the kernel stages anyway;
- *   workspace: rm_dense_wgrad_workspace floats. */
+ *   workspace: rm_dense_wgrad_workspace floats.
+ * Padding (these four entry points): a row stride may exceed the row's width (lda1 > K1, ldc > N, ld_aux1 > N,
+ *   ldg > N, lddw > N ...).  The columns between the width and the stride are NEVER read and never written - they
+ *   may hold NaN or another tensor's data.  Loads that reach past a row's end (a float4 over a ragged K1, a tile
+ *   over a ragged N) select, they do not multiply by zero.  rm_dense_fwd6's last slab of a ragged K re-reads
+ *   columns [K - 32, K) of A1 itself, inside the row, against zeroed weights: no pad column either.  Workspaces are
+ *   written before they are read and never beyond the size their *_workspace() function reports
+ *   (tests/test_gpu_dense.py runs with NaN pads, NaN-filled workspaces and guard bands). */
 enum { RM_DENSE_BIAS_ACT = 0, RM_DENSE_MUL_ACTGRAD = 1, RM_DENSE_ADD = 2, RM_DENSE_CROSS = 3 };
 int64_t rm_dense_filter_workspace(int K, int N);
 int rm_dense_fwd(const float *A1, int64_t lda1, int K1, const float *A2, int64_t lda2, int K2,

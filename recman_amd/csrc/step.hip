@@ -916,29 +916,67 @@ __global__ __launch_bounds__(512) void deepfm_step_kernel(StepArgs a) {
   }
 }
 
-// test aid (rm_debug_lds_fill): every byte of a CU's LDS that the step can allocate, set to one bit pattern
+// test aids (rm_debug_lds_fill, rm_debug_lds_probe): all of a CU's LDS - more than the step's own kLdsBytes, so that a
+// kernel with a smaller allocation, wherever the CU places it, lies inside the fill
+constexpr int kCuLdsBytes = 160 * 1024;
+static_assert(kLdsBytes <= kCuLdsBytes, "the fill must cover the step's allocation");
+
 __global__ __launch_bounds__(512) void lds_fill_kernel(unsigned pattern) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   volatile unsigned *p = reinterpret_cast<volatile unsigned *>(smem);
-  for (int i = threadIdx.x; i < kLdsBytes / 4; i += 512) p[i] = pattern;
+  // two passes: a block lives about twice as long as the dispatcher needs to hand one block to every CU, so the
+  // first wave of blocks covers the device before any CU is free for a second one
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = threadIdx.x; i < kCuLdsBytes / 4; i += 512) p[i] = pattern;
+    __syncthreads();
+  }
+}
+
+// one wave per block, the whole LDS allocated and nothing of it written: counts the words that differ from pattern
+__global__ __launch_bounds__(64) void lds_probe_kernel(unsigned pattern, unsigned *mismatches) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const volatile unsigned *p = reinterpret_cast<const volatile unsigned *>(smem);
+  unsigned n = 0;
+  for (int i = threadIdx.x; i < kCuLdsBytes / 4; i += 64) n += p[i] != pattern;
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);  // a cross-lane permute: no LDS storage
+  if (threadIdx.x == 0) mismatches[blockIdx.x] = n;
 }
 
 }  // namespace
 
-// What the step kernel finds in LDS is whatever the last workgroup on that CU left there.  This makes it ONE known
-// pattern: workgroups of the step's shape and full dynamic LDS size (one fits a CU), twice as many as the device has
-// CUs, every word of the allocation written with ds_write.  A read of LDS that nothing of the step has written yet -
-// the kernel's one known race showed as such a read - then gives the same bits in every run (a quiet NaN, or zero),
+// What a kernel finds in LDS is whatever the last workgroup on that CU left there.  This makes it ONE known pattern:
+// workgroups that allocate a CU's whole LDS (so exactly one fits a CU), four times as many as the device has CUs,
+// every word written with ds_write.  A read of LDS that the kernel behind it has not written yet - the step's one
+// known race showed as such a read, cin.hip's 0 x stale padding as another - then gives the same bits in every run,
 // not a flicker.  A test aid: no product path calls it.
-extern "C" int rm_debug_lds_fill(unsigned pattern, rm_stream_t stream) {
-  int dev = 0, cus = 0;
+static int lds_aid_cus(const void *kernel, const char *who, int *cus) {
+  int dev = 0, lds = 0;
   RM_REQUIRE(hipGetDevice(&dev) == hipSuccess &&
-                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0,
-             "rm_debug_lds_fill: no device");
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lds_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kLdsBytes);
-  hipLaunchKernelGGL(lds_fill_kernel, dim3(2 * cus), dim3(512), kLdsBytes, (hipStream_t)stream, pattern);
+                 hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && *cus > 0 &&
+                 hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess,
+             "%s: no device", who);
+  RM_REQUIRE(lds == kCuLdsBytes, "%s: the device reports %d bytes of LDS per block, built for %d", who, lds,
+             kCuLdsBytes);
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kCuLdsBytes);
+  return RM_OK;
+}
+
+extern "C" int rm_debug_lds_fill(unsigned pattern, rm_stream_t stream) {
+  int cus = 0;
+  if (int rc = lds_aid_cus(reinterpret_cast<const void *>(lds_fill_kernel), "rm_debug_lds_fill", &cus)) return rc;
+  hipLaunchKernelGGL(lds_fill_kernel, dim3(4 * cus), dim3(512), kCuLdsBytes, (hipStream_t)stream, pattern);
   RM_CHECK_LAUNCH("rm_debug_lds_fill");
+  return RM_OK;
+}
+
+// The fill's own check: nblocks workgroups that each hold a CU's whole LDS, write none of it and count the words that
+// are not pattern; mismatches[block] (device, nblocks unsigned) gets the block's count.
+extern "C" int rm_debug_lds_probe(unsigned pattern, unsigned *mismatches, int nblocks, rm_stream_t stream) {
+  RM_REQUIRE(mismatches && nblocks > 0, "rm_debug_lds_probe: mismatches is NULL or nblocks = %d", nblocks);
+  int cus = 0;
+  if (int rc = lds_aid_cus(reinterpret_cast<const void *>(lds_probe_kernel), "rm_debug_lds_probe", &cus)) return rc;
+  hipLaunchKernelGGL(lds_probe_kernel, dim3(nblocks), dim3(64), kCuLdsBytes, (hipStream_t)stream, pattern, mismatches);
+  RM_CHECK_LAUNCH("rm_debug_lds_probe");
   return RM_OK;
 }
 

@@ -1295,9 +1295,17 @@ def deepfm_step_workspace(F, Dn):
 
 
 def debug_lds_fill(pattern):
-    """Test aid (rm_debug_lds_fill): every CU's LDS, as far as deepfm_step allocates it, filled with one 32-bit
-    pattern on the current stream - what the step then finds in LDS before it has written it is known."""
+    """Test aid (rm_debug_lds_fill): all of every CU's LDS filled with one 32-bit pattern on the current stream - what
+    the next kernel finds in LDS before it has written it is known."""
     _lib.call("rm_debug_lds_fill", int(pattern) & 0xFFFFFFFF, _stream())
+
+
+def debug_lds_probe(pattern, nblocks):
+    """Test aid (rm_debug_lds_probe): nblocks workgroups that hold a CU's whole LDS and write none of it; returns
+    their counts of words that differ from `pattern` (int32 [nblocks], device)."""
+    out = torch.full((int(nblocks),), -1, dtype=torch.int32, device="cuda")
+    _lib.call("rm_debug_lds_probe", int(pattern) & 0xFFFFFFFF, out.data_ptr(), int(nblocks), _stream())
+    return out
 
 
 def deepfm_step(idx, rows, field_off, D, table_ld, dense, y, Ws, bs, w_out, w0_out, lin_w_dense, lin_w0, act, task,

@@ -5,11 +5,17 @@ the class is absent from the reference, DCN.py:7,134-137) and torch autograd of 
 The kernels work in closed form (x_l = c_l x0 + sum_{j<l} b_j: L+1 dot products + a scalar recurrence, the
 backward from the saved dot products alone), so these cases pin that algebra: every lane mapping the
 kernels template on (FD <= 256 / <= 512, no / <= 64 / > 64 dense columns), row counts around the
-rows-per-wave unroll, L = 1..8, and the gradient hand-off to the parameter-gradient GEMM."""
+rows-per-wave unroll, L = 1..8, and the gradient hand-off to the parameter-gradient GEMM.
+
+Every output a call overwrites starts as NaN (tests/stale_state.py).  The main test's body is a runner
+(`_fwd_bwd_case`) that tests/test_gpu_stale_lds.py runs again behind known LDS contents."""
+import functools
+
 import pytest
 import torch
 
 from oracle import th_layers as T
+from tests.stale_state import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -53,14 +59,24 @@ def _close(got, want, rtol, what):
     (4100, 416, 13, 6),    # more rows than one pass of the grid's waves
 ])
 def test_cross_fwd_bwd_match_autograd(hip_lib, B, FD, Dn, L):
+    _fwd_bwd_case(B, FD, Dn, L)
+
+
+@functools.lru_cache(maxsize=None)
+def _case_and_oracle(B, FD, Dn, L):
+    case = _case(B, FD, Dn, L)
+    return case, _oracle(*case[:6])
+
+
+def _fwd_bwd_case(B, FD, Dn, L):
     from recman_amd import ops
 
-    xe, xd, w, b, wo, gl, dxin = _case(B, FD, Dn, L)
-    logit_o, dxe_o, dw_o, db_o, dwo_o = _oracle(xe, xd, w, b, wo, gl)
+    (xe, xd, w, b, wo, gl, dxin), (logit_o, dxe_o, dw_o, db_o, dwo_o) = _case_and_oracle(B, FD, Dn, L)
     dev = "cuda"
     c = lambda t: None if t is None else t.to(dev).contiguous()  # noqa: E731
     xe_, xd_, w_, b_, wo_, gl_, dxin_ = map(c, (xe, xd, w, b, wo, gl, dxin))
-    logit = torch.empty(B, device=dev)
+    logit = poisoned(B)
+    res = {}
     p = torch.full((B, ops.cross_p_ld(L)), float("nan"), device=dev)
     ops.cross_fwd(xe_, xd_, w_, b_, wo_, logit, p)
     _close(logit, logit_o, 2e-6, "logit")
@@ -68,9 +84,10 @@ def test_cross_fwd_bwd_match_autograd(hip_lib, B, FD, Dn, L):
     want_p = torch.cat([x0 @ w.double().t(), (x0 @ wo.double()).view(-1, 1)], 1)
     _close(p[:, : L + 1], want_p, 2e-6, "saved dot products")
     # inference form: no p row
-    logit2 = torch.empty(B, device=dev)
+    logit2 = poisoned(B)
     ops.cross_fwd(xe_, xd_, w_, b_, wo_, logit2, None)
     assert torch.equal(logit2, logit)
+    res.update(logit=logit, p=p[:, : L + 1])
 
     for dx in (dxin_, None):
         d_xe = torch.full((B, FD), float("nan"), device=dev)
@@ -80,16 +97,19 @@ def test_cross_fwd_bwd_match_autograd(hip_lib, B, FD, Dn, L):
         _close(d_xe, want, 5e-6, "d_xe")
         assert torch.isfinite(coef).all()
         _close(coef[:, 2 * L + 1], gl.double(), 0, "coef g column")
+        res["d_xe", dx is not None], res["coef", dx is not None] = d_xe, coef
     # parameter gradients: P = x0^T coef[:, :L+1], column sums of the rest (what the engine does with
     # rm_dense_wgrad / rm_linear_dense_bwd; plain torch here - the hand-off is what is under test)
     P = (x0.t() @ coef[:, : L + 1].double().cpu()).float().to(dev).contiguous()
     colsum = coef[:, L + 1:].double().sum(0).float().contiguous()
     d = FD + Dn
-    dw, db, dwo = (torch.empty(L, d, device=dev), torch.empty(L, d, device=dev), torch.empty(d, device=dev))
+    dw, db, dwo = poisoned(L, d), poisoned(L, d), poisoned(d)
     ops.cross_param_grads(P, colsum, w_, b_, wo_, dw, db, dwo)
     _close(dw, dw_o, 2e-5, "d cross_w")
     _close(db, db_o, 2e-5, "d cross_b")
     _close(dwo, dwo_o, 2e-5, "d cross_w_out")
+    res.update(dw=dw, db=db, dwo=dwo)
+    return res
 
 
 def test_cross_kernels_are_deterministic_and_reject_bad_shapes(hip_lib):
@@ -99,8 +119,8 @@ def test_cross_kernels_are_deterministic_and_reject_bad_shapes(hip_lib):
     xe, xd, w, b, wo, gl, dxin = (t.cuda() if t is not None else None for t in _case(B, FD, Dn, L, seed=3))
     outs = []
     for _ in range(2):
-        logit, p = torch.empty(B, device="cuda"), torch.zeros(B, ops.cross_p_ld(L), device="cuda")
-        d_xe, coef = torch.empty(B, FD, device="cuda"), torch.empty(B, 2 * L + 2, device="cuda")
+        logit, p = poisoned(B), torch.zeros(B, ops.cross_p_ld(L), device="cuda")
+        d_xe, coef = poisoned(B, FD), poisoned(B, 2 * L + 2)
         ops.cross_fwd(xe, xd, w, b, wo, logit, p)
         ops.cross_bwd(w, b, wo, gl, p, d_xe, coef, dx_in_e=dxin)
         outs.append((logit, p, d_xe, coef))

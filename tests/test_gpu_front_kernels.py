@@ -422,6 +422,10 @@ def test_linear_dense_bwd_three_paths_against_float64(hip_lib, B):
     float off 16-byte alignment), with Dn + 1 > 256 (Dn = 1023: four column rounds) and at Pp = 256 exactly (255);
     wide float4 kernel (64 aligned, 256, 400) with its workspace-derived block cap.  Either output NULL; two runs
     bit-equal (fixed-order two-stage reduction)."""
+    _linear_dense_bwd_case(B)
+
+
+def _linear_dense_bwd_case(B):
     _cite("embed.hip", "if (Dn >= 64 && Dn % 4 == 0 && rm_aligned16(dense)) {")
     _cite("embed.hip", "const int64_t cap = 256 * 1024 / (Dn + 1);")
     _cite("embed.hip", "nblk = rm_grid_cap((B + 63) / 64, (int)(cap < 2048 ? cap : 2048));")
@@ -438,6 +442,7 @@ def test_linear_dense_bwd_three_paths_against_float64(hip_lib, B):
     g = _gen(B)
     ws = torch.empty(262_144, device="cuda")
     gg = _randn(g, B)
+    outs = []
     for Dn, aligned in DENSE_BWD_DN:
         if Dn == 0:
             dense = None
@@ -463,6 +468,8 @@ def test_linear_dense_bwd_three_paths_against_float64(hip_lib, B):
         R.assert_bits(d_w02, d_w0, what + ": d_w0 with d_w_dense NULL, second run")
         if Dn:
             R.assert_bits(d_w2, d_w, what + ": d_w_dense with d_w0 NULL, second run")
+        outs.append((d_w, d_w0))
+    return outs
 
 
 # =================================================================================================================
@@ -491,6 +498,10 @@ def test_logit_loss_against_float64(hip_lib, B, coefs, task, ydt):
     On top of that, tighter: B * dlogit and the loss against the float64 function of the fp32 probability the kernel
     wrote - Keras takes the cross-entropy from its fp32 sigmoid output, whose 1 - p is quantised to 2^-24 (0.5 % at
     |z| = 12), and dlogit / B at B = 600 001 would pass the absolute tolerance with any value."""
+    _logit_loss_case(B, coefs, task, ydt)
+
+
+def _logit_loss_case(B, coefs, task, ydt):
     _cite("loss.hip", "constexpr int kMaxBlocks = 1024;")
     _cite("loss.hip", "const int nblk = rm_grid_cap((B + kBlock - 1) / kBlock, kMaxBlocks);")
     sweep = 1024 * KBLOCK
@@ -523,6 +534,7 @@ def test_logit_loss_against_float64(hip_lib, B, coefs, task, ydt):
         ops.logit_loss(br, task=task, workspace=ws if "loss" in part else None, **kw, **part)
         for k in part:
             R.assert_bits(part[k], out[k], f"{what}: {k} with {skip} = NULL (and run again)")
+    return out
 
 
 @pytest.mark.parametrize("ydt", [I64, F32], ids=["int64", "float"])
@@ -729,17 +741,32 @@ def test_shard_route_against_the_torch_router(hip_lib, world):
             cases += [(0.1, False), (1.0, False), (0.0, True)]
         for negative, constant in cases:
             idx, field_off = _route_inputs(n, g, negative, constant)
-            pos, send, counts = (torch.full((n,), -5, dtype=I64, device="cuda"), torch.full((n,), -5, dtype=I64, device="cuda"),
-                                 torch.full((world,), -5, dtype=I64, device="cuda"))
-            ops.shard_route(idx, field_off, world, pos, send, counts, ws)
-            pos_t, counts_t, send_t = route_torch(idx, field_off, world)
-            what = f"shard_route world={world} n={n} negative={negative} constant={constant}"
-            assert torch.equal(counts, counts_t), what + ": counts"
-            assert torch.equal(pos, pos_t), what + ": pos"
-            nv = send_t.numel()
-            assert nv == int((idx >= 0).sum()) and torch.equal(send[:nv], send_t), what + ": send_ids"
-            if constant:
-                assert int((counts > 0).sum()) == 1 and int(counts.sum()) == n   # every id owned by one rank
+            _shard_route_case(idx, field_off, world, ws, constant, f"n={n} negative={negative} constant={constant}")
+
+
+def _shard_route_case(idx, field_off, world, ws, constant, tag):
+    n = idx.numel()
+    pos, send, counts = (torch.full((n,), -5, dtype=I64, device="cuda"), torch.full((n,), -5, dtype=I64, device="cuda"),
+                         torch.full((world,), -5, dtype=I64, device="cuda"))
+    ops.shard_route(idx, field_off, world, pos, send, counts, ws)
+    pos_t, counts_t, send_t = route_torch(idx, field_off, world)
+    what = f"shard_route world={world} {tag}"
+    assert torch.equal(counts, counts_t), what + ": counts"
+    assert torch.equal(pos, pos_t), what + ": pos"
+    nv = send_t.numel()
+    assert nv == int((idx >= 0).sum()) and torch.equal(send[:nv], send_t), what + ": send_ids"
+    if constant:
+        assert int((counts > 0).sum()) == 1 and int(counts.sum()) == n   # every id owned by one rank
+    return pos, send[:nv], counts
+
+
+def _shard_route_padded_run(idx, field_off, world, c, over, ws):
+    n = idx.numel()
+    pos, send, counts = (torch.full((n,), -5, dtype=I64, device="cuda"),
+                         torch.full((world * c,), -5, dtype=I64, device="cuda"),
+                         torch.full((world,), -5, dtype=I64, device="cuda"))
+    ops.shard_route_padded(idx, field_off, world, c, pos, send, counts, over, ws)
+    return pos, send, counts
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 8, 16])
@@ -757,11 +784,7 @@ def test_shard_route_padded_capacity_and_sticky_overflow(hip_lib, world):
             over = torch.zeros(1, dtype=torch.int32, device="cuda")
 
             def run(c):
-                pos, send, counts = (torch.full((n,), -5, dtype=I64, device="cuda"),
-                                     torch.full((world * c,), -5, dtype=I64, device="cuda"),
-                                     torch.full((world,), -5, dtype=I64, device="cuda"))
-                ops.shard_route_padded(idx, field_off, world, c, pos, send, counts, over, ws)
-                return pos, send, counts
+                return _shard_route_padded_run(idx, field_off, world, c, over, ws)
 
             what = f"shard_route_padded world={world} n={n} negative={negative} constant={constant}"
             pos, send, counts = run(cap)

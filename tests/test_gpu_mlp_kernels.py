@@ -606,6 +606,10 @@ class Front:
 
 @pytest.mark.parametrize("F,Dn,ld,B,lin,hidden,act,want,tail", EMF_CASES, ids=lambda v: str(v).replace(" ", ""))
 def test_embed_mlp_fwd_against_float64(hip_lib, F, Dn, ld, B, lin, hidden, act, want, tail):
+    _embed_mlp_fwd_case(F, Dn, ld, B, lin, hidden, act, want, tail)
+
+
+def _embed_mlp_fwd_case(F, Dn, ld, B, lin, hidden, act, want, tail):
     _cite("mlp.hip", "const int nhc = Kp / 32;")
     _cite("mlp.hip", "const int nf = F - 2 * hc;")      # odd F: a half chunk with one live field
     _cite("mlp.hip", "const float *p = ef.table + rows[q] * ef.table_ld + sub * 4;")
@@ -682,6 +686,7 @@ def test_embed_mlp_fwd_against_float64(hip_lib, F, Dn, ld, B, lin, hidden, act, 
     o3, f3, _ = run(False, not tail)
     R.assert_bits(f3.logit.v, f.logit.v, f"{what}: logit with{'out' if tail else ''} a tail")
     R.assert_bits(o3["E"].v, o["E"].v, f"{what}: E with{'out' if tail else ''} a tail")
+    return dict({k: a.v for k, a in o.items()}, h=f.hv(), logit=f.logit.v)
 
 
 # ============================================================================================ 6. argument checks

@@ -13,6 +13,7 @@ import torch
 from oracle import th_layers as T
 from tests import test_gpu_dense as TD
 from tests.cases import make_case
+from tests.stale_state import assert_guards_intact, guarded, poisoned
 from tests.test_gpu_parity import _close, _close_grad, _engine
 
 pytestmark = pytest.mark.gpu
@@ -286,10 +287,10 @@ def test_cin_layer_bwd_dm_pass_looping(hip_lib, B, m, H, N, D, act, first, last,
 
     f = lambda t: t.detach().float().cuda().contiguous()
     dX0 = torch.full((B, m, D), 0.5, device="cuda")  # accumulate onto a known value
-    dXk = None if first else torch.empty(B, H, D, device="cuda")
-    dW = torch.empty(m * H, N, device="cuda")
-    dbias = torch.empty(N, device="cuda")
-    ws = torch.empty(ops.cin_bwd_workspace(B, m, H, N, D), device="cuda")
+    dXk = None if first else poisoned(B, H, D)
+    dW = poisoned(m * H, N)
+    dbias = poisoned(N)
+    ws, wsbuf = guarded(ops.cin_bwd_workspace(B, m, H, N, D))
     ops.cin_layer_bwd(f(X0), f(Xk), H, f(W), act, out_d, f(gvec), dX0, dW, dbias, ws,
                       xk_is_x0=first, d_hidden=f(dh) if pool_from else None, cin_w_direct=f(cw),
                       pool_from=pool_from, accumulate_dx0=True, dXk=dXk, split=bool(split), first6=split == "first6")
@@ -306,6 +307,7 @@ def test_cin_layer_bwd_dm_pass_looping(hip_lib, B, m, H, N, D, act, first, last,
         close(dXk, torch.cat(gxk), "dXk")
     close(dW, W.grad, "dW")
     close(dbias, bias.grad, "dbias")
+    assert_guards_intact(wsbuf, "rm_cin_bwd_workspace")
 
 
 @pytest.mark.parametrize("cin_gemm", ["bf16x6", "f32"])
