@@ -9,9 +9,13 @@ the arithmetic is the paper's (arXiv 1708.04617 eq. (4)-(6)) as the project's co
 The model (AFM.py:111-126) is composed from the public functions of oracle.th_layers, imported and not modified.
 tests/test_afm_host.py pins this file without a GPU; the GPU tests compare the HIP kernels against it in float64.
 """
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure  # noqa: F401  (part of this module's interface)
 
 # kernel-level GPU cases (B, F, D, T) of tests/test_gpu_afm.py; tests/test_afm_host.py asserts the kink guard's cap on
 # every one of them (each with h_scale 1; the two softmax-range cases again with 400)
@@ -22,7 +26,6 @@ GPU_CASES = [(37, 5, 8, 8), (64, 26, 16, 8), (130, 26, 16, 32), (9, 39, 64, 64),
 CASE_SEEDS = {(9, 39, 64, 64): 3}
 RANGE_CASES = [(64, 26, 16, 8), (130, 26, 16, 32)]
 RANGE_H_SCALE = 400.0
-KINK = 1e-6        # a hidden unit whose float64 pre-activation is this close to 0 may flip in fp32
 KINK_CAP = 0.20    # largest share of examples the guard may zero
 
 # model-level GPU cases of tests/test_gpu_afm_model.py: keyword arguments of make_afm_case.  Their g comes from
@@ -102,23 +105,13 @@ def afm_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_weights
 
 def afm_l2(p, spec, hp):
     """AFM.py:132-143: embeddings + linear + the attention layer's l2 (the attention matrix only, as in the paper)."""
-    return (TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0)) + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
-            + hp.get("att_l2_reg", 0.0) * 0.5 * p["afm_attention_w"].square().sum())
+    return C.base_l2(p, spec, hp, None, True) + hp.get("att_l2_reg", 0.0) * 0.5 * p["afm_attention_w"].square().sum()
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = afm_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + afm_l2(p, spec, hp), logit, pred
-
-
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, afm_logit, afm_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
 # -------------------------------------------------------------------------------------------------------- cases
@@ -129,26 +122,15 @@ def make_afm_case(B, F, D, Dn, T, seed=0, h_scale=1.0, dtype=torch.float64, att_
       layer level: E ~ 0.3 N(0,1), W, b, h, p_vec, mask (multiplier for keep 0.8), g, dE_up - g is ZERO for every
         example that has a hidden unit with |z| < KINK in float64 (`near` marks them, `zeroed` = their share);
       `model_min_abs_z`: the model-level case's hidden unit closest to its kink."""
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     g = torch.Generator().manual_seed(1000 + seed)
-
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-
-    p = {}
-    for name, V in zip(spec.sparse_names, sizes):
-        p[f"{name}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
-    p["afm_attention_w"] = rnd(D, T, std=(2.0 / (D + T)) ** 0.5)
+    rnd = C.rnd_stream(g)
+    p = C.draw_front(rnd, spec, D, std=0.3)
+    p["afm_attention_w"] = glorot(rnd, (D, T), D, T)
     p["afm_attention_b"] = rnd(T, std=0.1)
-    p["afm_attention_h"] = (rnd(T, 1, std=(2.0 / (T + 1)) ** 0.5) * h_scale).float().double()
-    p["afm_projection_p"] = rnd(D, 1, std=(2.0 / (D + 1)) ** 0.5)
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
+    p["afm_attention_h"] = (glorot(rnd, (T, 1), T, 1) * h_scale).float().double()
+    p["afm_projection_p"] = glorot(rnd, (D, 1), D, 1)
+    idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
     mask = (torch.rand(B, D, generator=g) < 0.8).to(torch.float64) / 0.8
     gl = rnd(B)
     dE_up = rnd(B, F, D, std=0.1)
@@ -181,13 +163,3 @@ def layer_reference(case, use_mask, use_up, dtype=torch.float64):
     (y * case["g"].to(dtype)).sum().backward()
     dE = E.grad + (case["dE_up"].to(dtype) if use_up else 0)
     return tuple(t.detach().double() for t in (y, dE, W.grad, b.grad, h.grad, p.grad))
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())

@@ -17,8 +17,10 @@ tests/test_asp_host.py pins this file without a GPU; the GPU tests compare the H
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK  # noqa: F401  (part of this module's interface)
+from tests.ref_common import grad_measure_or_empty as grad_measure  # noqa: F401  (a batch may hold no history item)
 
-KINK = 1e-6        # a ReLU unit whose float64 pre-activation is this close to 0 may flip in fp32
 KINK_CAP = 0.20    # largest share of examples the guard may zero
 
 # kernel-level GPU cases of tests/test_gpu_asp.py (keyword arguments of make_asp_case); tests/test_asp_host.py asserts
@@ -118,42 +120,15 @@ def score_grad_abs_sum(case):
     return float(s.grad.abs().sum())
 
 
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    if want.numel() == 0:
-        return 0.0
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())
-
-
 # ------------------------------------------------------------------------------------------------ layer-level cases
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-def make_lengths(B, max_len, g):
-    """History lengths in 0..max_len; the first examples are 0, 1 and max_len long."""
-    n = torch.randint(0, max_len + 1, (B,), generator=g)
-    forced = [0, 1, max_len][:B]
-    n[: len(forced)] = torch.tensor(forced)
-    return n
-
-
 def make_asp_params(D, hidden, g, prefix="", w_scale=1.0):
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     dims = [4 * D] + list(hidden)
     p = {}
     for i in range(len(hidden)):
-        p[f"{prefix}asp_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
+        p[f"{prefix}asp_layer_{i}_weights"] = C.glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
         p[f"{prefix}asp_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p[f"{prefix}asp_w"] = (rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5) * w_scale).float().double()
+    p[f"{prefix}asp_w"] = (C.glorot(rnd, (dims[-1], 1), dims[-1], 1) * w_scale).float().double()
     p[f"{prefix}asp_w0"] = rnd(1, std=0.1)
     return p
 
@@ -170,14 +145,8 @@ def make_asp_case(B, D, hidden, act, norm, max_len, V=23, seed=0, w_scale=1.0):
     ReLU unit with a pre-activation within KINK of 0 in float64 (`near`, `zeroed` = their share); dq_up [B, D] what the
     query-gradient buffer holds before the backward adds to it."""
     g = torch.Generator().manual_seed(7000 + seed)
-    rnd = _rnd(g)
-    table = rnd(V, 2 * D, std=0.3)
-    qidx = torch.randint(0, V, (B,), generator=g)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, V, (int(n.sum()),), generator=g)
-    if B >= 3 and max_len >= 2:
-        ids[int(offsets[2]) + 1] = ids[int(offsets[2])]  # a repeated id inside one history
+    rnd = C.rnd_stream(g)
+    table, qidx, offsets, ids = C.draw_lookup(g, rnd, B, D, max_len, V)
     p = make_asp_params(D, hidden, g, w_scale=w_scale)
     gl = rnd(B, D)
     dq_up = rnd(B, D, std=0.1)
@@ -246,18 +215,9 @@ def embeddings(p, spec, idx, mv, hp):
 
 def model_logit(model, p, spec, idx, dense, hp, mv, training=True, masks=None):
     """DIN: linear + DNN([E | dense]).  DCN (DCN.py:99-144): dnn + cross (+ linear)."""
-    masks = masks or {}
-    E = embeddings(p, spec, idx, mv, hp)
-    x = TL.dnn_input(E, dense)
-    n = len(hp["deep_hidden_units"])
-    keep = hp.get("deep_dropout", [1] * (n + 1)) if training else [1] * (n + 1)
-    dnn = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, masks.get("dnn"))
-    lin = TL.linear_layer(p, spec.tl, idx[:, spec.plain_cols], dense)
-    if model == "din":
-        return lin + dnn
-    assert model == "dcn"
-    logit = dnn + TL.cross_net(p, x)
-    return logit + lin if hp.get("use_linear", True) else logit
+    from tests import seq_models_ref as S  # (imports this module: what the three units' models share lives there)
+
+    return S.unit_model_logit("din", embeddings(p, spec, idx, mv, hp), model, p, spec, idx, dense, hp, training, masks)
 
 
 def model_l2(model, p, spec, hp):
@@ -272,58 +232,25 @@ def model_l2(model, p, spec, hp):
 
 def fwd_bwd(model, p, spec, idx, dense, y, hp, mv, task="classification", masks=None):
     """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    logit = model_logit(model, leaves, spec, idx, dense, hp, mv, True, masks)
-    pred = TL.prediction(logit, task)
-    loss = TL.create_loss(y, pred, task) + model_l2(model, leaves, spec, hp)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+    from tests import seq_models_ref as S
+
+    return S.unit_fwd_bwd(model_logit, "din", model, p, spec, idx, dense, y, hp, mv, task, masks)
 
 
 def make_model_case(model, B, D, Dn, seed=0, att_hidden_units=(80, 40), att_activation="sigmoid",
                     att_weight_normalization=False, max_len=6, dtype=torch.float64):
-    """A seeded model-level case: plain features C0 (7), item (11), C2 (5), the history `hist` of `item` between them
-    (so the pooled row is not the last field), Dn dense features.  Item ids come from a small range, so rows are
-    target in one example and history item in another.  Returns spec, p (reference variable names), idx (the
-    sequence's column is a placeholder 0), dense, y, hp, mv = {"hist": (offsets, ids)}, min_abs_z (the attention
-    unit's pre-activation closest to 0)."""
-    g = torch.Generator().manual_seed(9000 + seed)
-    rnd = _rnd(g)
-    names, sizes = ["C0", "item", "hist", "C2"], [7, 11, 0, 5]
-    spec = SeqSpec(names, sizes, [f"I{j}" for j in range(Dn)], {"hist": "item"}, {"hist": max_len})
-    p = {}
-    for n, V in zip(names, sizes):
-        if V:
-            p[f"{n}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.tl.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
-    hidden = (32, 32) if model == "din" else (24, 16)
-    d_in = len(names) * D + Dn
-    dims = [d_in] + list(hidden)
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p["dnn_w"] = rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5)
-    p["dnn_w0"] = rnd(1, std=0.1)
-    hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, deep_hidden_units=hidden,
-              deep_l2_reg=1e-3, deep_activation="relu", att_hidden_units=tuple(att_hidden_units),
-              att_activation=att_activation, att_weight_normalization=att_weight_normalization)
-    if model == "dcn":
-        L = 2
-        p["cross_w"], p["cross_b"] = rnd(L, d_in, std=0.15), rnd(L, d_in, std=0.15)
-        p["cross_w_out"] = rnd(d_in, 1, std=0.15)
-        hp.update(cross_layer_num=L, cross_layer_l2_reg=1e-3, use_linear=True)
-    p.update(make_asp_params(D, att_hidden_units, g, prefix="hist_"))
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) if v else torch.zeros(B, dtype=torch.int64)
-                       for v in sizes], 1)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, sizes[1], (int(n.sum()),), generator=g)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
-    T = p["item_feat_embed"]
-    pre = asp_hidden(T[idx[:, 1]], T[ids], offsets, *asp_vars(p, "hist_", len(att_hidden_units))[:2], att_activation)
-    c = lambda t: t.to(dtype) if t.is_floating_point() else t  # noqa: E731
-    return dict(model=model, spec=spec, p={k: c(v) for k, v in p.items()}, idx=idx, dense=c(dense), y=y, hp=hp,
-                mv={"hist": (offsets, ids)}, min_abs_z=min(float(z.abs().min()) for z in pre))
+    """A seeded model-level case (seq_models_ref.make_unit_model_case: its front and what it returns) of DIN or of DCN
+    over the din unit, with min_abs_z = the attention unit's pre-activation closest to 0.  Item ids come from a small
+    range, so rows are target in one example and history item in another."""
+    from tests import seq_models_ref as S
+
+    def probe(p, idx, offsets, ids):
+        T = p["item_feat_embed"]
+        Ws, bs = asp_vars(p, "hist_", len(att_hidden_units))[:2]
+        pre = asp_hidden(T[idx[:, 1]], T[ids], offsets, Ws, bs, att_activation)
+        return min(float(z.abs().min()) for z in pre)
+
+    unit_hp = dict(att_hidden_units=tuple(att_hidden_units), att_activation=att_activation,
+                   att_weight_normalization=att_weight_normalization)
+    return S.make_unit_model_case(9000, "din", model, B, D, Dn, seed, max_len, dtype, unit_hp,
+                                  lambda g: make_asp_params(D, att_hidden_units, g, prefix="hist_"), probe)

@@ -10,9 +10,14 @@ eq. (5)-(8)) as the project's contract states it.  One layer maps X [B,F,Din] to
 The model is composed from the public functions of oracle.th_layers, imported and not modified.
 tests/test_autoint_host.py pins this file without a GPU; the GPU tests compare the HIP kernels against it in float64.
 """
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, grad_measure  # noqa: F401  (part of this module's interface)
+from tests.ref_common import rnd_stream as _rnd  # noqa: F401  (tests/test_gpu_autoint_model.py draws with it)
 
 # kernel-level GPU cases (B, F, Din, H, dk) of tests/test_gpu_autoint.py; tests/test_autoint_host.py asserts the kink
 # guard's cap on every one of them (the two softmax-range cases again with Wq x 400)
@@ -21,7 +26,7 @@ GPU_CASES = [(37, 5, 8, 2, 4), (64, 26, 16, 2, 8), (130, 26, 16, 2, 16), (9, 39,
              (4100, 26, 16, 2, 8), (150, 1, 16, 2, 8)]
 RANGE_CASES = [(64, 26, 16, 2, 8), (130, 26, 16, 2, 16)]
 RANGE_Q_SCALE = 400.0
-KINK = 1e-6        # a unit whose float64 pre-activation O + X Wr is this close to 0 may flip in fp32
+# (KINK: here the pre-activation is O + X Wr)
 KINK_CAP = 0.20    # largest share of examples the guard may zero
 
 # model-level GPU cases of tests/test_gpu_autoint_model.py: keyword arguments of make_case.  Their upstream gradient
@@ -126,47 +131,30 @@ def autoint_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_wei
     logit = logit + autoint_stack(p, E, hp).reshape(-1, 1)
     n = len(hp.get("deep_hidden_units") or ())
     if n:
-        keep = hp.get("deep_dropout") or [1] * (n + 1)
-        keep = list(keep) if training else [1] * (n + 1)
-        logit = logit + TL.dnn(p, TL.dnn_input(E, dense), n, hp.get("deep_activation", "relu"), keep,
-                               (masks or {}).get("dnn"))
+        logit = logit + TL.dnn(p, TL.dnn_input(E, dense), n, hp.get("deep_activation", "relu"),
+                               C.dnn_keep(hp, n, training), (masks or {}).get("dnn"))
     return logit
 
 
 def autoint_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0)) + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
-    out = out + sum(hp.get("att_l2_reg", 0.0) * 0.5 * p[n].square().sum() for n in att_names(hp))
+    out = C.base_l2(p, spec, hp, None, True)  # (the DNN's term comes behind the attention's here)
+    out = out + C.param_l2(att_names(hp), p, hp.get("att_l2_reg", 0.0))
     n = len(hp.get("deep_hidden_units") or ())
     if n:
         out = out + TL.dnn_l2(p, n, hp.get("deep_l2_reg", 0.0))
     return out
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = autoint_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + autoint_l2(p, spec, hp), logit, pred
-
-
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, autoint_logit, autoint_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
 # -------------------------------------------------------------------------------------------------------- cases
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
 def glorot(rnd, fan_in, fan_out):
-    return rnd(fan_in, fan_out, std=(2.0 / (fan_in + fan_out)) ** 0.5)
+    """A [fan_in, fan_out] matrix."""
+    return C.glorot(rnd, (fan_in, fan_out), fan_in, fan_out)
 
 
 def make_layer_case(B, F, Din, H, dk, seed=0, q_scale=1.0):
@@ -175,7 +163,7 @@ def make_layer_case(B, F, Din, H, dk, seed=0, q_scale=1.0):
     O + X Wr (with the residual) or O (without) within KINK of 0 in float64, at either scale of the scores: `near`
     marks them, `zeroed` is their share."""
     g = torch.Generator().manual_seed(2000 + seed)
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     HD = H * dk
     X = rnd(B, F, Din, std=0.3)
     Wq = (glorot(rnd, Din, HD) * q_scale).float().double()
@@ -192,15 +180,10 @@ def make_layer_case(B, F, Din, H, dk, seed=0, q_scale=1.0):
                 zeroed=float(near.double().mean()))
 
 
-_LAYER_CASES = {}
-
-
+@C.memo
 def gpu_case(c, q_scale=1.0):
     """make_layer_case for a kernel-level (B, F, Din, H, dk) of GPU_CASES / RANGE_CASES (made once, never changed)."""
-    key = (tuple(c), q_scale)
-    if key not in _LAYER_CASES:
-        _LAYER_CASES[key] = make_layer_case(*c, seed=0, q_scale=q_scale)
-    return _LAYER_CASES[key]
+    return make_layer_case(*c, seed=0, q_scale=q_scale)
 
 
 def layer_reference(case, use_res, use_up, scaling, dtype=torch.float64):
@@ -226,31 +209,18 @@ def head_reference(case, Y, dtype=torch.float64):
 def make_case(B, F, D, Dn, L, H, dk, seed=0, att_res=True, att_scaling=False, hidden=(), dtype=torch.float64):
     """A seeded model-level case: spec, p (the variable names of the contract), idx, dense, y, hp; `model_min_abs_pre`
     is the distance of the closest unit of any layer (and, with a DNN, of any hidden unit) to its kink."""
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     g = torch.Generator().manual_seed(3000 + seed)
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     HD = H * dk
-    p = {}
-    for name, V in zip(spec.sparse_names, sizes):
-        p[f"{name}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
+    p = C.draw_front(rnd, spec, D, std=0.3)
     for l in range(L):
         for n in layer_names(l, att_res):
             p[n] = glorot(rnd, D if l == 0 else HD, HD)
     p["autoint_w"] = glorot(rnd, F * HD, 1)
     p["autoint_w0"] = rnd(1, std=0.1)
-    dims = [F * D + Dn] + list(hidden)
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = glorot(rnd, dims[i], dims[i + 1])
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    if hidden:
-        p["dnn_w"] = glorot(rnd, dims[-1], 1)
-        p["dnn_w0"] = rnd(1, std=0.1)
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
+    C.draw_dnn(rnd, p, [F * D + Dn] + list(hidden), head=bool(hidden))
+    idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
     hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, att_layer_num=L, att_embedding_size=dk,
               att_head_num=H, att_res=att_res, att_scaling=att_scaling, att_l2_reg=1e-3,
               deep_hidden_units=tuple(hidden), deep_dropout=(1,) * (len(hidden) + 1), deep_l2_reg=1e-3 if hidden else 0.0,
@@ -265,19 +235,4 @@ def min_abs_pre(p, spec, idx, dense, hp, mv=None):
     """The smallest |pre-activation| of the model on a batch: every unit of every interacting layer and DNN layer."""
     E, _ = TL.feat_embedding_layer(p, spec, idx, use_bias=False, mv=mv)
     pres = autoint_stack(p, E, hp, return_pre=True)[1]
-    x = TL.dnn_input(E, dense)
-    for i in range(len(hp.get("deep_hidden_units") or ())):
-        z = x @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"]
-        pres.append(z)
-        x = torch.relu(z)
-    return min(float(t.abs().min()) for t in pres)
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())
+    return C.min_abs(pres + C.dnn_pres(p, TL.dnn_input(E, dense), len(hp.get("deep_hidden_units") or ())))

@@ -20,8 +20,10 @@ oracle.th_layers, imported and not modified."""
 import torch
 
 from oracle import th_layers as TL
-from tests.asp_ref import (KINK, KINK_CAP, RANGE_SCALE, SeqSpec, _rnd, grad_measure, make_lengths,  # noqa: F401
-                           model_l2, segments)
+from tests import ref_common as C
+from tests.asp_ref import KINK_CAP, RANGE_SCALE, SeqSpec, segments  # noqa: F401  (the sequence front, its case limits)
+from tests.ref_common import KINK  # noqa: F401  (part of this module's interface; here the units are the FFN's)
+from tests.ref_common import grad_measure_or_empty as grad_measure  # noqa: F401  (a batch may hold no history item)
 
 NAMES = ("wq", "wk", "wv", "wo", "bq", "bk", "bv", "bo", "ffn_w1", "ffn_b1", "ffn_w2", "ffn_b2", "ln1_gamma", "ln1_beta",
          "ln2_gamma", "ln2_beta", "pos")
@@ -129,7 +131,7 @@ def key_grad_abs_sum(case):
 # ------------------------------------------------------------------------------------------------ layer-level cases
 def make_bst_params(D, heads, Hf, max_len, g, wq_scale=1.0):
     """Random and non-trivial in every member: glorot matrices, biases ~ 0.1 N, gains ~ 1 + 0.3 N, P ~ 0.3 N."""
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     p = {}
     for n in ("wq", "wk", "wv", "wo"):
         p[n] = rnd(D, D, std=(1.0 / D) ** 0.5)
@@ -152,14 +154,8 @@ def make_bst_case(B, D, heads, Hf, max_len, V=23, seed=0, wq_scale=1.0):
     unit whose pre-activation is within KINK of 0 in float64 (`near`, `zeroed` = their share); dq_up [B, D] what the
     query-gradient buffer holds before the backward adds to it.  Every value is a float32 number."""
     g = torch.Generator().manual_seed(11000 + seed)
-    rnd = _rnd(g)
-    table = rnd(V, 2 * D, std=0.3)
-    qidx = torch.randint(0, V, (B,), generator=g)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, V, (int(n.sum()),), generator=g)
-    if B >= 3 and max_len >= 2:
-        ids[int(offsets[2]) + 1] = ids[int(offsets[2])]  # a repeated id inside one history
+    rnd = C.rnd_stream(g)
+    table, qidx, offsets, ids = C.draw_lookup(g, rnd, B, D, max_len, V)
     p = make_bst_params(D, heads, Hf, max_len, g, wq_scale)
     gl = rnd(B, D)
     dq_up = rnd(B, D, std=0.1)
@@ -205,29 +201,17 @@ def embeddings(p, spec, idx, mv, hp, k_probe=None):
 
 def model_logit(model, p, spec, idx, dense, hp, mv, training=True, masks=None, k_probe=None):
     """BST: linear + DNN([E | dense]) (as DIN).  DCN (DCN.py:99-144): dnn + cross (+ linear)."""
-    masks = masks or {}
+    from tests import seq_models_ref as S  # (imports this module: what the three units' models share lives there)
+
     E = embeddings(p, spec, idx, mv, hp, k_probe)
-    x = TL.dnn_input(E, dense)
-    n = len(hp["deep_hidden_units"])
-    keep = hp.get("deep_dropout", [1] * (n + 1)) if training else [1] * (n + 1)
-    dnn = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, masks.get("dnn"))
-    lin = TL.linear_layer(p, spec.tl, idx[:, spec.plain_cols], dense)
-    if model == "bst":
-        return lin + dnn
-    assert model == "dcn"
-    logit = dnn + TL.cross_net(p, x)
-    return logit + lin if hp.get("use_linear", True) else logit
+    return S.unit_model_logit("bst", E, model, p, spec, idx, dense, hp, training, masks)
 
 
 def fwd_bwd(model, p, spec, idx, dense, y, hp, mv, task="classification", masks=None):
     """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    logit = model_logit(model, leaves, spec, idx, dense, hp, mv, True, masks)
-    pred = TL.prediction(logit, task)
-    loss = TL.create_loss(y, pred, task) + model_l2("din" if model == "bst" else model, leaves, spec, hp)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+    from tests import seq_models_ref as S
+
+    return S.unit_fwd_bwd(model_logit, "bst", model, p, spec, idx, dense, y, hp, mv, task, masks)
 
 
 def model_key_grad_abs_sum(k, task="classification"):
@@ -241,48 +225,19 @@ def model_key_grad_abs_sum(k, task="classification"):
 
 
 def make_model_case(model, B, D, Dn, seed=0, att_head_num=2, att_ffn_units=None, max_len=6, dtype=torch.float64):
-    """A seeded model-level case: plain features C0 (7), item (11), C2 (5), the history `hist` of `item` between them
-    (so the pooled row is not the last field), Dn dense features.  Item ids come from a small range, so rows are
-    candidate in one example and history item in another.  Returns spec, p (reference variable names), idx (the
-    sequence's column is a placeholder 0), dense, y, hp, mv = {"hist": (offsets, ids)}, min_abs_z (the FFN
-    pre-activation closest to 0 over the real tokens)."""
-    g = torch.Generator().manual_seed(13000 + seed)
-    rnd = _rnd(g)
+    """A seeded model-level case (seq_models_ref.make_unit_model_case: its front and what it returns) of BST or of DCN
+    over the transformer unit, with min_abs_z = the FFN pre-activation closest to 0 over the real tokens.  Item ids
+    come from a small range, so rows are candidate in one example and history item in another."""
+    from tests import seq_models_ref as S
+
     Hf = int(att_ffn_units or 4 * D)
-    names, sizes = ["C0", "item", "hist", "C2"], [7, 11, 0, 5]
-    spec = SeqSpec(names, sizes, [f"I{j}" for j in range(Dn)], {"hist": "item"}, {"hist": max_len})
-    p = {}
-    for n, V in zip(names, sizes):
-        if V:
-            p[f"{n}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.tl.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
-    hidden = (32, 32) if model == "bst" else (24, 16)
-    d_in = len(names) * D + Dn
-    dims = [d_in] + list(hidden)
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p["dnn_w"] = rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5)
-    p["dnn_w0"] = rnd(1, std=0.1)
-    hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, deep_hidden_units=hidden,
-              deep_l2_reg=1e-3, deep_activation="relu", seq_pooling="transformer", att_head_num=att_head_num,
-              att_ffn_units=Hf)
-    if model == "dcn":
-        L = 2
-        p["cross_w"], p["cross_b"] = rnd(L, d_in, std=0.15), rnd(L, d_in, std=0.15)
-        p["cross_w_out"] = rnd(d_in, 1, std=0.15)
-        hp.update(cross_layer_num=L, cross_layer_l2_reg=1e-3, use_linear=True)
-    p.update({f"hist_bst_{n}": v for n, v in make_bst_params(D, att_head_num, Hf, max_len, g).items()})
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) if v else torch.zeros(B, dtype=torch.int64)
-                       for v in sizes], 1)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, sizes[1], (int(n.sum()),), generator=g)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
-    T = p["item_feat_embed"]
-    dist = ffn_kink_distance(T[idx[:, 1]], T[ids], offsets, bst_vars(p, "hist_"), att_head_num)
-    c = lambda t: t.to(dtype) if t.is_floating_point() else t  # noqa: E731
-    return dict(model=model, spec=spec, p={k: c(v) for k, v in p.items()}, idx=idx, dense=c(dense), y=y, hp=hp,
-                mv={"hist": (offsets, ids)}, min_abs_z=float(dist.min()))
+
+    def draw_unit(g):
+        return {f"hist_bst_{n}": v for n, v in make_bst_params(D, att_head_num, Hf, max_len, g).items()}
+
+    def probe(p, idx, offsets, ids):
+        T = p["item_feat_embed"]
+        return float(ffn_kink_distance(T[idx[:, 1]], T[ids], offsets, bst_vars(p, "hist_"), att_head_num).min())
+
+    unit_hp = dict(seq_pooling="transformer", att_head_num=att_head_num, att_ffn_units=Hf)
+    return S.make_unit_model_case(13000, "bst", model, B, D, Dn, seed, max_len, dtype, unit_hp, draw_unit, probe)

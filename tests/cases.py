@@ -2,12 +2,13 @@
 import torch
 
 from oracle import th_layers as T
+from tests.ref_common import field_sizes
 
 
 def make_case(model, B=37, F=5, D=8, Dn=2, sizes=None, hidden=(16, 8), cin_units=(), cross_layers=0,
               seed=0, scale=0.3, hp_extra=None, dtype=torch.float32):
     if sizes is None:
-        sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
+        sizes = field_sizes(F)
     spec = T.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
     p = T.make_params(spec, model, D, hidden=hidden, cin_units=cin_units, cross_layers=cross_layers,
                       use_bias=(model == "deepfm"), seed=2019 + seed, dtype=dtype, scale=scale)

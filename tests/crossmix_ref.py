@@ -14,9 +14,13 @@ The gate is per layer.  Everything but the cross network is composed from the pu
 imported and not modified.  tests/test_crossmix_host.py pins this file without a GPU; the GPU tests compare the HIP
 kernels and the engine against it in float64.
 """
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, to_f32  # noqa: F401  (part of this module's interface)
 
 # kernel-level GPU cases (B, E, r) of tests/test_gpu_cross_mix.py (the grid-stride case is built there)
 GPU_CASES = [(5, 1, 8), (37, 1, 8), (33, 3, 8), (9, 5, 16), (64, 4, 32), (130, 4, 16), (65, 2, 64), (257, 8, 32)]
@@ -28,7 +32,6 @@ MODEL_CASES = {
     "no_dense_r64": (65, 7, 8, 0, 4, 2, 64),
 }
 TOL_M, TOL_GRAD = 1e-5, 2e-5  # the project's own: absolute on M and the logits, the gradient measure on gradients
-KINK = 1e-6  # a relu unit of the DNN whose float64 pre-activation is this close to 0 may flip in fp32
 
 
 def tanh_exp(x):
@@ -96,47 +99,33 @@ def core_loops(t, s, C):
     return torch.tensor(out, dtype=t.dtype).reshape(len(tl), E * r)
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
-
-
 SPECIAL_ROWS = {3: "t x 8", 4: "t = 0", 5: "s x 60", 6: "s = 0", 7: "dm = 0"}
-_KERNEL_CASES = {}
 
 
+@C.memo
 def kernel_case(B, E, r, seed=0):
     """A seeded kernel-level case in float64 (made once per shape, never changed): t ~ N(0,1), s ~ 2 N(0,1),
     C ~ 1.5 glorot(r, r), dm ~ N(0,1); with B > 8 the special rows 3: t x 8 (saturated tanh), 4: t = 0 (m exactly 0),
     5: s x 60 (needs the max-subtraction), 6: s = 0 (p = 1/E), 7: dm = 0 (dt, ds exactly 0).  With the float64 outputs
     m, dt, ds, dC."""
-    key = (B, E, r, seed)
-    if key not in _KERNEL_CASES:
-        for attempt in range(64):  # the first stream whose special rows are what they claim (see below)
-            rnd = _rnd(torch.Generator().manual_seed(9000 + 64 * seed + attempt))
-            t, s, dm = rnd(B, E * r), rnd(B, E, std=2.0), rnd(B, E * r)
-            C = (1.5 * glorot(rnd, (E, r, r), r, r)).float().double()
-            if B <= 8:
-                break
+    def build(g, rnd):
+        t, s, dm = rnd(B, E * r), rnd(B, E, std=2.0), rnd(B, E * r)
+        Cm = (1.5 * glorot(rnd, (E, r, r), r, r)).float().double()
+        if B > 8:
             t[3] *= 8.0
             t[4] = 0.0
             s[5] *= 60.0
             s[6] = 0.0
             dm[7] = 0.0
-            # row 3 holds a tanh that rounds to 1 in float32; row 5 has a score whose float32 exp overflows without the max-subtraction
-            if float(t[3].abs().max()) > 9.1 and (E == 1 or float(s[5].max()) > 100.0):
-                break
-        else:
-            raise AssertionError("no stream gave the special rows")
-        dt, ds, dC = core_bwd(t, s, C, dm)
-        _KERNEL_CASES[key] = dict(B=B, E=E, r=r, t=t, s=s, C=C, dm=dm, m=core_fwd(t, s, C), dt=dt, ds=ds, dC=dC)
-    return _KERNEL_CASES[key]
+        return t, s, dm, Cm
+
+    def ok(drawn):  # the special rows are what they claim: row 3 holds a tanh that rounds to 1 in float32; row 5 has a
+        t, s = drawn[:2]  # score whose float32 exp overflows without the max-subtraction
+        return B <= 8 or (float(t[3].abs().max()) > 9.1 and (E == 1 or float(s[5].max()) > 100.0))
+
+    t, s, dm, Cm = C.first_stream(9000 + 64 * seed, build, ok)[0]
+    dt, ds, dC = core_bwd(t, s, Cm, dm)
+    return dict(B=B, E=E, r=r, t=t, s=s, C=Cm, dm=dm, m=core_fwd(t, s, Cm), dt=dt, ds=ds, dC=dC)
 
 
 def f32_errors(case, tanh=torch.tanh):
@@ -167,8 +156,7 @@ def cross_mix_net(p, x0, tanh=torch.tanh):
 CROSS_L2_NAMES = ("cross_v", "cross_gate", "cross_c", "cross_u", "cross_w_out")
 
 
-def cross_mix_l2(p, l2_reg):
-    return sum(l2_reg * 0.5 * p[n].square().sum() for n in CROSS_L2_NAMES)
+cross_mix_l2 = partial(C.param_l2, CROSS_L2_NAMES)  # (p, l2_reg)
 
 
 def dcn_mix_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_weights=None, mv=None, tanh=torch.tanh,
@@ -186,36 +174,18 @@ def dcn_mix_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_wei
         logit = logit + dnn_logit
     if hp.get("use_linear", True):
         logit = logit + TL.linear_layer(p, spec, idx, dense, manual_weights, mv)
-    if return_pre:
-        pres, y = [], x
-        for i in range(n):
-            pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-            y = torch.relu(pres[-1])
-        return logit, pres
-    return logit
+    return (logit, C.dnn_pres(p, x, n)) if return_pre else logit  # (the pre-activations without dropout)
 
 
 def dcn_mix_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0))
-    if hp.get("use_linear", True):
-        out = out + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
-    out = out + TL.dnn_l2(p, len(hp["deep_hidden_units"]), hp.get("deep_l2_reg", 0.0))
-    return out + cross_mix_l2(p, hp.get("cross_layer_l2_reg", 0.0))
+    return C.base_l2(p, spec, hp, len(hp["deep_hidden_units"]), hp.get("use_linear", True)) + cross_mix_l2(
+        p, hp.get("cross_layer_l2_reg", 0.0))
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None, tanh=torch.tanh):
-    logit = dcn_mix_logit(p, spec, idx, dense, hp, True, masks, mv=mv, tanh=tanh)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + dcn_mix_l2(p, spec, hp), logit, pred
-
-
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None, tanh=torch.tanh):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv, tanh)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None, tanh=torch.tanh) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, dcn_mix_logit, dcn_mix_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
 def cross_params(rnd, d, L, E, r):
@@ -230,54 +200,21 @@ def cross_params(rnd, d, L, E, r):
     }
 
 
-_MODEL_CASES = {}
-
-
+@C.memo
 def make_case(B, F, D, Dn, L, E, r, seed=0, hidden=(32, 32), use_linear=True, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p (the variable names of the contract),
     idx, dense, y, hp.  Embeddings ~ N(0, 0.15^2), dense ~ N(0,1), cross_b ~ N(0, 0.1^2); `min_abs_pre` is the distance
     of the DNN's closest unit to its kink."""
-    key = (B, F, D, Dn, L, E, r, seed, tuple(hidden), use_linear, l2)
-    if key in _MODEL_CASES:
-        return _MODEL_CASES[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     g = torch.Generator().manual_seed(8000 + seed)
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     d = F * D + Dn
-    p = {}
-    for name, V in zip(spec.sparse_names, sizes):
-        p[f"{name}_feat_embed"] = rnd(V, D, std=0.15)
-    p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
-    dims = [d] + list(hidden)
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p["dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-    p["dnn_w0"] = rnd(1, std=0.1)
+    p = C.draw_front(rnd, spec, D, std=0.15)
+    C.draw_dnn(rnd, p, [d] + list(hidden))
     p.update(cross_params(rnd, d, L, E, r))
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
+    idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
     hp = dict(embedding_size=D, embedding_l2_reg=l2, linear_l2_reg=l2, deep_hidden_units=tuple(hidden),
               deep_dropout=(1,) * (len(hidden) + 1), deep_l2_reg=l2, cross_layer_l2_reg=l2, cross_layer_num=L,
               cross_type="mix", cross_experts=E, cross_low_rank=r, use_linear=use_linear)
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp)
-    out["min_abs_pre"] = min(float(t.abs().min()) for t in dcn_mix_logit(p, spec, idx, dense, hp, return_pre=True)[1])
-    _MODEL_CASES[key] = out
-    return out
-
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())
+    return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp,
+                min_abs_pre=C.min_abs(dcn_mix_logit(p, spec, idx, dense, hp, return_pre=True)[1]))

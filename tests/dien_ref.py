@@ -20,7 +20,9 @@ public functions of oracle.th_layers, imported and not modified."""
 import torch
 
 from oracle import th_layers as TL
-from tests.asp_ref import RANGE_SCALE, SeqSpec, _rnd, grad_measure, make_lengths, model_l2, segments  # noqa: F401
+from tests import ref_common as C
+from tests.asp_ref import RANGE_SCALE, SeqSpec, segments  # noqa: F401  (the sequence front and its case limits)
+from tests.ref_common import grad_measure_or_empty as grad_measure  # noqa: F401  (a batch may hold no history item)
 
 NAMES = ("gru_w", "gru_u", "gru_b", "att_w", "augru_w", "augru_u", "augru_b")
 BIG_BIAS = 100.0
@@ -110,7 +112,7 @@ def dien_layer(Q, K, offsets, p):
 def make_dien_params(D, g, att_scale=1.0, big_bias=False):
     """Glorot matrices, biases ~ 0.1 N.  att_scale multiplies att_w; big_bias sets every second bias entry of both
     GRUs to +-BIG_BIAS with alternating sign."""
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     p = {}
     for n in ("gru", "augru"):
         p[n + "_w"] = rnd(D, 3 * D, std=(2.0 / (4 * D)) ** 0.5)
@@ -129,14 +131,8 @@ def make_dien_case(B, D, max_len, V=23, seed=0, att_scale=1.0, big_bias=False):
     p: the 7 parameters; g [B, D] the pooled rows' gradient; dq_up [B, D] what the query-gradient buffer holds before
     the backward adds to it.  Every value is a float32 number."""
     g = torch.Generator().manual_seed(17000 + seed)
-    rnd = _rnd(g)
-    table = rnd(V, 2 * D, std=0.3)
-    qidx = torch.randint(0, V, (B,), generator=g)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, V, (int(n.sum()),), generator=g)
-    if B >= 3 and max_len >= 2:
-        ids[int(offsets[2]) + 1] = ids[int(offsets[2])]  # a repeated id inside one history
+    rnd = C.rnd_stream(g)
+    table, qidx, offsets, ids = C.draw_lookup(g, rnd, B, D, max_len, V)
     p = make_dien_params(D, g, att_scale, big_bias)
     return dict(B=B, D=D, max_len=max_len, table=table, qidx=qidx, offsets=offsets, ids=ids, p=p, g=rnd(B, D),
                 dq_up=rnd(B, D, std=0.1))
@@ -177,69 +173,26 @@ def embeddings(p, spec, idx, mv, hp):
 
 def model_logit(model, p, spec, idx, dense, hp, mv, training=True, masks=None):
     """DIEN: linear + DNN([E | dense]) (as DIN).  DCN (DCN.py:99-144): dnn + cross (+ linear)."""
-    masks = masks or {}
-    E = embeddings(p, spec, idx, mv, hp)
-    x = TL.dnn_input(E, dense)
-    n = len(hp["deep_hidden_units"])
-    keep = hp.get("deep_dropout", [1] * (n + 1)) if training else [1] * (n + 1)
-    dnn = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, masks.get("dnn"))
-    lin = TL.linear_layer(p, spec.tl, idx[:, spec.plain_cols], dense)
-    if model == "dien":
-        return lin + dnn
-    assert model == "dcn"
-    logit = dnn + TL.cross_net(p, x)
-    return logit + lin if hp.get("use_linear", True) else logit
+    from tests import seq_models_ref as S  # (imports this module: what the three units' models share lives there)
+
+    return S.unit_model_logit("dien", embeddings(p, spec, idx, mv, hp), model, p, spec, idx, dense, hp, training, masks)
 
 
 def fwd_bwd(model, p, spec, idx, dense, y, hp, mv, task="classification", masks=None):
     """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    logit = model_logit(model, leaves, spec, idx, dense, hp, mv, True, masks)
-    pred = TL.prediction(logit, task)
-    loss = TL.create_loss(y, pred, task) + model_l2("din" if model == "dien" else model, leaves, spec, hp)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+    from tests import seq_models_ref as S
+
+    return S.unit_fwd_bwd(model_logit, "dien", model, p, spec, idx, dense, y, hp, mv, task, masks)
 
 
 def make_model_case(model, B, D, Dn, seed=0, max_len=6, dtype=torch.float64):
-    """A seeded model-level case: plain features C0 (7), item (11), C2 (5), the history `hist` of `item` between them
-    (so the pooled row is not the last field), Dn dense features.  Item ids come from a small range, so rows are
-    candidate in one example and history item in another.  Returns spec, p (reference variable names), idx (the
-    sequence's column is a placeholder 0), dense, y, hp, mv = {"hist": (offsets, ids)}."""
-    g = torch.Generator().manual_seed(19000 + seed)
-    rnd = _rnd(g)
-    names, sizes = ["C0", "item", "hist", "C2"], [7, 11, 0, 5]
-    spec = SeqSpec(names, sizes, [f"I{j}" for j in range(Dn)], {"hist": "item"}, {"hist": max_len})
-    p = {}
-    for n, V in zip(names, sizes):
-        if V:
-            p[f"{n}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.tl.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
-    hidden = (32, 32) if model == "dien" else (24, 16)
-    d_in = len(names) * D + Dn
-    dims = [d_in] + list(hidden)
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p["dnn_w"] = rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5)
-    p["dnn_w0"] = rnd(1, std=0.1)
-    hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, deep_hidden_units=hidden,
-              deep_l2_reg=1e-3, deep_activation="relu", seq_pooling="dien")
-    if model == "dcn":
-        L = 2
-        p["cross_w"], p["cross_b"] = rnd(L, d_in, std=0.15), rnd(L, d_in, std=0.15)
-        p["cross_w_out"] = rnd(d_in, 1, std=0.15)
-        hp.update(cross_layer_num=L, cross_layer_l2_reg=1e-3, use_linear=True)
-    p.update({f"hist_dien_{n}": v for n, v in make_dien_params(D, g).items()})
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) if v else torch.zeros(B, dtype=torch.int64)
-                       for v in sizes], 1)
-    n = make_lengths(B, max_len, g)
-    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), n.cumsum(0)])
-    ids = torch.randint(0, sizes[1], (int(n.sum()),), generator=g)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
-    c = lambda t: t.to(dtype) if t.is_floating_point() else t  # noqa: E731
-    return dict(model=model, spec=spec, p={k: c(v) for k, v in p.items()}, idx=idx, dense=c(dense), y=y, hp=hp,
-                mv={"hist": (offsets, ids)})
+    """A seeded model-level case (seq_models_ref.make_unit_model_case: its front and what it returns) of DIEN or of
+    DCN over the dien unit; no unit of it has a kink, so there is no min_abs_z.  Item ids come from a small range, so
+    rows are candidate in one example and history item in another."""
+    from tests import seq_models_ref as S
+
+    def draw_unit(g):
+        return {f"hist_dien_{n}": v for n, v in make_dien_params(D, g).items()}
+
+    return S.make_unit_model_case(19000, "dien", model, B, D, Dn, seed, max_len, dtype, dict(seq_pooling="dien"),
+                                  draw_unit)

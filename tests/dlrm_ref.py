@@ -13,14 +13,18 @@ as the project's contract states it.  With v_0 = z [B,D] and v_f = E[:, f-1] (f 
 The model is composed from the public functions of oracle.th_layers, imported and not modified.
 tests/test_dlrm_host.py pins this file without a GPU; the GPU tests compare the HIP kernels against it in float64.
 """
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, grad_measure  # noqa: F401  (part of this module's interface)
+from tests.ref_common import rnd_stream as _rnd  # noqa: F401  (tests/test_gpu_dlrm_model.py draws with it)
 
 # kernel-level GPU cases (B, F, D) of tests/test_gpu_dot_interact.py
 GPU_CASES = [(3, 1, 8), (5, 2, 16), (6, 7, 16), (5, 5, 32), (9, 31, 16), (9, 32, 16), (4, 40, 64), (131, 26, 16),
              (70001, 3, 8)]
-KINK = 1e-6  # a unit whose float64 pre-activation is this close to 0 may flip in fp32
 EPS23 = 2.0 ** -23
 
 # model-level GPU cases of tests/test_gpu_dlrm_model.py: keyword arguments of make_case.  The label-driven upstream
@@ -109,33 +113,22 @@ def bwd_bound(E, z, dX):
     return (F + 2) * EPS23 * b
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
 def glorot(rnd, fan_in, fan_out):
-    return rnd(fan_in, fan_out, std=(2.0 / (fan_in + fan_out)) ** 0.5)
+    """A [fan_in, fan_out] matrix."""
+    return C.glorot(rnd, (fan_in, fan_out), fan_in, fan_out)
 
 
-_KERNEL_CASES = {}
-
-
+@C.memo
 def kernel_case(B, F, D, seed=0):
     """A seeded kernel-level case in float64 (made once per shape, never changed): E, z, dX ~ N(0,1); example 1 has all
     its E rows zero, example 2 has z = 0.  With the float64 outputs X, d_rows, dz and the bounds."""
-    key = (B, F, D, seed)
-    if key not in _KERNEL_CASES:
-        rnd = _rnd(torch.Generator().manual_seed(5000 + seed))
-        E, z, dX = rnd(B, F, D), rnd(B, D), rnd(B, D + pairs(F))
-        E[1 % B] = 0.0
-        z[2 % B] = 0.0
-        d_rows, dz = interact_bwd(E, z, dX)
-        _KERNEL_CASES[key] = dict(B=B, F=F, D=D, E=E, z=z, dX=dX, X=interact(E, z), d_rows=d_rows, dz=dz,
-                                  bx=fwd_bound(E, z), bdv=bwd_bound(E, z, dX))
-    return _KERNEL_CASES[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(5000 + seed))
+    E, z, dX = rnd(B, F, D), rnd(B, D), rnd(B, D + pairs(F))
+    E[1 % B] = 0.0
+    z[2 % B] = 0.0
+    d_rows, dz = interact_bwd(E, z, dX)
+    return dict(B=B, F=F, D=D, E=E, z=z, dX=dX, X=interact(E, z), d_rows=d_rows, dz=dz, bx=fwd_bound(E, z),
+                bdv=bwd_bound(E, z, dX))
 
 
 def _ratio(err, bound):
@@ -205,8 +198,7 @@ def top_tower(p, X, hp, keep=None, masks=None):
 def logit_from_embeddings(p, E, dense, hp, training=True, masks=None, return_pre=False):
     """The towers and the interaction on given embedding rows E [B,F,D]: the top logit [B,1]."""
     z, pres = bottom_tower(p, dense, hp)
-    n = len(hp["deep_hidden_units"])
-    keep = list(hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
+    keep = C.dnn_keep(hp, len(hp["deep_hidden_units"]), training)
     out, pres_top = top_tower(p, interact(E, z), hp, keep, (masks or {}).get("dnn"))
     return (out, pres + pres_top) if return_pre else out
 
@@ -227,7 +219,7 @@ def deep_l2_names(hp):
 
 
 def tower_l2(p, hp):
-    return sum(hp.get("deep_l2_reg", 0.0) * 0.5 * p[n].square().sum() for n in deep_l2_names(hp))
+    return C.param_l2(deep_l2_names(hp), p, hp.get("deep_l2_reg", 0.0))
 
 
 def dlrm_l2(p, spec, hp):
@@ -237,53 +229,29 @@ def dlrm_l2(p, spec, hp):
     return out
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = dlrm_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + dlrm_l2(p, spec, hp), logit, pred
-
-
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, dlrm_logit, dlrm_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
 def tower_params(rnd, D, F, Dn, bottom, hidden):
     """The variables of both towers: glorot weights, biases ~ 0.1 N(0,1)."""
     p = {}
-    dims = [Dn] + list(bottom) + [D]
-    for l in range(len(dims) - 1):
-        p[f"bot_dnn_layer_{l}_weights"] = glorot(rnd, dims[l], dims[l + 1])
-        p[f"bot_dnn_layer_{l}_bias"] = rnd(dims[l + 1], std=0.1)
-    dims = [D + pairs(F)] + list(hidden)
-    for l in range(len(hidden)):
-        p[f"top_dnn_layer_{l}_weights"] = glorot(rnd, dims[l], dims[l + 1])
-        p[f"top_dnn_layer_{l}_bias"] = rnd(dims[l + 1], std=0.1)
-    p["top_dnn_w"] = glorot(rnd, dims[-1], 1)
-    p["top_dnn_w0"] = rnd(1, std=0.1)
+    C.draw_dnn(rnd, p, [Dn] + list(bottom) + [D], head=False, prefix="bot_")
+    C.draw_dnn(rnd, p, [D + pairs(F)] + list(hidden), prefix="top_")
     return p
 
 
 def make_case(B, F, D, Dn, seed=0, bottom=(16,), hidden=(32, 32), use_linear=False, dtype=torch.float64):
     """A seeded model-level case: spec, p (the variable names of the contract), idx, dense, y, hp; `model_min_abs_pre`
     is the distance of the closest unit of either tower to its kink."""
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     g = torch.Generator().manual_seed(7000 + seed)
-    rnd = _rnd(g)
-    p = {}
-    for name, V in zip(spec.sparse_names, sizes):
-        p[f"{name}_feat_embed"] = rnd(V, D, std=0.3)
-    p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-    p["linear_w0"] = rnd(1, std=0.1)
+    rnd = C.rnd_stream(g)
+    p = C.draw_front(rnd, spec, D, std=0.3)
     p.update(tower_params(rnd, D, F, Dn, bottom, hidden))
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-    dense = rnd(B, Dn)
-    y = (torch.rand(B, generator=g) < 0.3).long()
+    idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
     hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, bottom_hidden_units=tuple(bottom),
               deep_hidden_units=tuple(hidden), deep_dropout=(1,) * (len(hidden) + 1), deep_l2_reg=1e-3,
               deep_activation="relu", use_linear=use_linear)
@@ -299,13 +267,3 @@ def min_abs_pre(p, spec, idx, dense, hp, mv=None, E=None, masks=None):
         E, _ = TL.feat_embedding_layer(p, spec, idx, use_bias=False, mv=mv)
     pres = logit_from_embeddings(p, E, dense, hp, True, masks, return_pre=True)[1]
     return min(float(t.detach().abs().min()) for t in pres)
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())

@@ -17,11 +17,14 @@ Everything but the interaction is composed from the public functions of oracle.t
 tests/test_fibinet_host.py pins this file without a GPU; the GPU tests compare the HIP kernels and the engine against it
 in float64.
 """
-import itertools
+from functools import partial
 
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, pair_fields, pairs, to_f32  # noqa: F401  (its interface)
+from tests.ref_common import rnd_stream as _rnd  # noqa: F401  (tests/test_gpu_fibinet_model.py draws with it)
 
 # kernel-level GPU cases (B, F, D, R, type) of tests/test_gpu_fibinet.py (the grid-stride case is built there)
 GPU_CASES = [(5, 2, 8, 1, "each"), (33, 3, 8, 1, "all"), (37, 5, 8, 2, "each"), (130, 26, 16, 8, "each"),
@@ -34,19 +37,8 @@ MODEL_CASES = {
     "criteo_like": (130, 26, 16, 13, 3, "each"),
 }
 TOL_X, TOL_GRAD = 1e-5, 2e-5  # |X - X64| <= TOL_X max(1, |X64|); the project's gradient measure on gradients
-KINK = 1e-6  # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 PARAMS = ("senet_w1", "senet_w2", "bilinear_w", "senet_bilinear_w")
 WRONG = ("sum_squeeze", "each_by_right", "no_second_relu", "branches_swapped", "v_uses_bilinear_w")
-
-
-def pairs(F):
-    return F * (F - 1) // 2
-
-
-def pair_fields(F):
-    """(left fields, right fields) of the P pairs in itertools.combinations order, as index tensors."""
-    li, lj = zip(*itertools.combinations(range(F), 2))
-    return torch.tensor(li), torch.tensor(lj)
 
 
 def reduction(F, ratio):
@@ -166,17 +158,6 @@ def interact_bwd(E, W1, W2, Wb, Wsb, btype, dX):
     return dE, dW1, dW2, dWb, dWsb
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
-
-
 def gate_conditions(E, W1, W2):
     """(the smallest |pre-activation| of the gate, the share of gates a > 0, the most negative pre-activation of a) in
     float64.  The z W1 entries of an example whose rows are all zero and the s W2 entries of an example whose s is
@@ -190,9 +171,9 @@ def gate_conditions(E, W1, W2):
 
 
 SPECIAL_ROWS = {3: "E = 0", 4: "dX = 0", 5: "E x 8"}
-_KERNEL_CASES = {}
 
 
+@C.memo
 def kernel_case(B, F, D, R, btype, seed=0):
     """A seeded kernel-level case in float64 (made once per shape, never changed): E ~ N(0,1), W1 and W2 ~ 2 glorot,
     the bilinear weights ~ N(0, 1/D), dX ~ N(0,1); with B > 8 the special rows 3: E = 0 (X and dE exactly 0),
@@ -200,40 +181,36 @@ def kernel_case(B, F, D, R, btype, seed=0):
     pre-activation at least KINK from 0, a gate open and a gate closed by the second relu (none closed at F = 2,
     R = 1), and with B >= 33 a share of open gates in [0.2, 0.8]; tests/test_fibinet_host.py asserts them.  With the
     float64 outputs X, dE and the four parameter gradients."""
-    key = (B, F, D, R, btype, seed)
-    if key not in _KERNEL_CASES:
-        nW, W = n_matrices(F, btype), 2 * pairs(F) * D
-        for attempt in range(64):
-            rnd = _rnd(torch.Generator().manual_seed(11000 + 64 * seed + attempt))
-            E, dX = rnd(B, F, D), rnd(B, W)
-            W1, W2 = 2.0 * glorot(rnd, (F, R), F, R), 2.0 * glorot(rnd, (R, F), R, F)
-            Wb, Wsb = rnd(nW, D, D, std=D ** -0.5), rnd(nW, D, D, std=D ** -0.5)
-            if B > 8:
-                E[3] = 0.0
-                dX[4] = 0.0
-                E[5] *= 8.0
-            dist, share, most_negative = gate_conditions(E, W1, W2)
-            # (some gate open and some closed by its relu, or the second relu would have nothing to do)
-            closed = most_negative >= 0 if one_pair_one_unit(F, R) else most_negative < 0
-            if dist >= KINK and share > 0 and closed and (B < 33 or 0.2 <= share <= 0.8):
-                break
-        else:
-            raise AssertionError("no stream met the case conditions")
-        dE, dW1, dW2, dWb, dWsb = interact_bwd(E, W1, W2, Wb, Wsb, btype, dX)
-        _KERNEL_CASES[key] = dict(B=B, F=F, D=D, R=R, btype=btype, E=E, dX=dX, senet_w1=W1, senet_w2=W2, bilinear_w=Wb,
-                                  senet_bilinear_w=Wsb, X=interact(E, W1, W2, Wb, Wsb, btype), dE=dE,
-                                  d_senet_w1=dW1, d_senet_w2=dW2, d_bilinear_w=dWb, d_senet_bilinear_w=dWsb)
-    return _KERNEL_CASES[key]
+    nW, W = n_matrices(F, btype), 2 * pairs(F) * D
+
+    def build(g, rnd):
+        E, dX = rnd(B, F, D), rnd(B, W)
+        W1, W2 = 2.0 * glorot(rnd, (F, R), F, R), 2.0 * glorot(rnd, (R, F), R, F)
+        Wb, Wsb = rnd(nW, D, D, std=D ** -0.5), rnd(nW, D, D, std=D ** -0.5)
+        if B > 8:
+            E[3] = 0.0
+            dX[4] = 0.0
+            E[5] *= 8.0
+        return E, dX, W1, W2, Wb, Wsb
+
+    def ok(drawn):
+        dist, share, most_negative = gate_conditions(drawn[0], drawn[2], drawn[3])
+        # (some gate open and some closed by its relu, or the second relu would have nothing to do)
+        closed = most_negative >= 0 if one_pair_one_unit(F, R) else most_negative < 0
+        return dist >= KINK and share > 0 and closed and (B < 33 or 0.2 <= share <= 0.8)
+
+    E, dX, W1, W2, Wb, Wsb = C.first_stream(11000 + 64 * seed, build, ok)[0]
+    dE, dW1, dW2, dWb, dWsb = interact_bwd(E, W1, W2, Wb, Wsb, btype, dX)
+    return dict(B=B, F=F, D=D, R=R, btype=btype, E=E, dX=dX, senet_w1=W1, senet_w2=W2, bilinear_w=Wb,
+                senet_bilinear_w=Wsb, X=interact(E, W1, W2, Wb, Wsb, btype), dE=dE,
+                d_senet_w1=dW1, d_senet_w2=dW2, d_bilinear_w=dWb, d_senet_bilinear_w=dWsb)
 
 
 def case_weights(case, dtype=torch.float64):
     return tuple(case[n].to(dtype) for n in PARAMS)
 
 
-def x_error(X, X64):
-    """max |X - X64| / max(1, |X64|): the forward's measure."""
-    X, X64 = X.detach().cpu().double(), X64.detach().cpu().double()
-    return float(((X - X64).abs() / X64.abs().clamp(min=1.0)).max()) if X.numel() else 0.0
+x_error = C.rel_error
 
 
 def f32_errors(case):
@@ -260,106 +237,51 @@ def fibinet_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_wei
     if dense is not None and dense.shape[1]:
         x = torch.cat([x, dense], dim=1)
     n = len(hp["deep_hidden_units"])
-    keep = list(hp.get("deep_dropout") or [1] * (n + 1)) if training else [1] * (n + 1)
+    keep = C.dnn_keep(hp, n, training)
     logit = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, masks.get("dnn"))
     if hp.get("use_linear", True):
         logit = logit + TL.linear_layer(p, spec, idx, dense, manual_weights, mv)
     if return_pre:
         z, hs, s, ha, a = gate(E, p["senet_w1"], p["senet_w2"])
-        dm = masks.get("dnn") or [None] * (n + 1)
-        pres, y = [hs, ha[s.abs().amax(dim=1) > 0]], TL.dropout(x, keep[0], dm[0])
-        for i in range(n):
-            pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-            y = TL.dropout(torch.relu(pres[-1]), keep[i + 1], dm[i + 1])
-        return logit, pres
+        return logit, [hs, ha[s.abs().amax(dim=1) > 0]] + C.dnn_pres(p, x, n, keep, masks.get("dnn"))
     return logit
 
 
-def interaction_l2(p, l2_reg):
-    return sum(l2_reg * 0.5 * p[n].square().sum() for n in PARAMS)
+interaction_l2 = partial(C.param_l2, PARAMS)  # (p, l2_reg)
 
 
 def fibinet_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0))
-    if hp.get("use_linear", True):
-        out = out + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
-    out = out + TL.dnn_l2(p, len(hp["deep_hidden_units"]), hp.get("deep_l2_reg", 0.0))
-    return out + interaction_l2(p, hp.get("interaction_l2_reg", 0.0))
+    return C.base_l2(p, spec, hp, len(hp["deep_hidden_units"]), hp.get("use_linear", True)) + interaction_l2(
+        p, hp.get("interaction_l2_reg", 0.0))
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = fibinet_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + fibinet_l2(p, spec, hp), logit, pred
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, fibinet_logit, fibinet_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
-
-
-_MODEL_CASES = {}
-
-
+@C.memo
 def make_case(B, F, D, Dn, ratio, btype, seed=0, hidden=(32, 32), use_linear=True, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p (the variable names of the contract),
     idx, dense, y, hp.  Embeddings ~ N(0, 0.15^2), dense ~ N(0,1), the gate's matrices ~ 2 glorot, the bilinear ones
     glorot (N(0, 1/D)); `min_abs_pre` is the distance of the closest unit - the gate's and the DNN's - to its kink.  The
     first stream whose min_abs_pre is at least KINK is taken."""
-    key = (B, F, D, Dn, ratio, btype, seed, tuple(hidden), use_linear, l2)
-    if key in _MODEL_CASES:
-        return _MODEL_CASES[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     R, nW = reduction(F, ratio), n_matrices(F, btype)
     hp = dict(embedding_size=D, embedding_l2_reg=l2, linear_l2_reg=l2, deep_hidden_units=tuple(hidden),
               deep_dropout=(1,) * (len(hidden) + 1), deep_l2_reg=l2, interaction_l2_reg=l2, bilinear_type=btype,
               reduction_ratio=ratio, use_linear=use_linear)
-    for attempt in range(64):
-        g = torch.Generator().manual_seed(12000 + 64 * seed + attempt)
-        rnd = _rnd(g)
-        p = {}
-        for name, V in zip(spec.sparse_names, sizes):
-            p[f"{name}_feat_embed"] = rnd(V, D, std=0.15)
-        p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-        p["linear_w0"] = rnd(1, std=0.1)
-        dims = [2 * pairs(F) * D + Dn] + list(hidden)
-        for i in range(len(hidden)):
-            p[f"dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        p["dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-        p["dnn_w0"] = rnd(1, std=0.1)
+
+    def build(g, rnd):
+        p = C.draw_front(rnd, spec, D, std=0.15)
+        C.draw_dnn(rnd, p, [2 * pairs(F) * D + Dn] + list(hidden))
         p["senet_w1"] = 2.0 * glorot(rnd, (F, R), F, R)
         p["senet_w2"] = 2.0 * glorot(rnd, (R, F), R, F)
         p["bilinear_w"] = glorot(rnd, (nW, D, D), D, D)
         p["senet_bilinear_w"] = glorot(rnd, (nW, D, D), D, D)
-        idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-        dense = rnd(B, Dn)
-        y = (torch.rand(B, generator=g) < 0.3).long()
-        pres = fibinet_logit(p, spec, idx, dense, hp, return_pre=True)[1]
-        min_abs_pre = min(float(t.abs().min()) for t in pres if t.numel())
-        if min_abs_pre >= KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
-    _MODEL_CASES[key] = out
-    return out
+        idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
+        min_abs_pre = C.min_abs(fibinet_logit(p, spec, idx, dense, hp, return_pre=True)[1])
+        return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
 
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())
+    return C.first_stream(12000 + 64 * seed, build, lambda k: k["min_abs_pre"] >= KINK)[0]

@@ -18,11 +18,13 @@ Everything but the pair term is composed from the public functions of oracle.th_
 tests/test_fmfm_host.py pins this file without a GPU; the GPU tests compare the HIP kernels and the engine against it in
 float64.
 """
-import itertools
+from functools import partial
 
 import torch
 
 from oracle import th_layers as TL
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, pair_fields, pairs, to_f32  # noqa: F401  (its interface)
 
 TYPES = ("matrix", "vector", "scalar")
 # kernel-level GPU cases (B, F, D) of tests/test_gpu_fmfm.py, each for the three types (the grid-stride case is built
@@ -36,18 +38,7 @@ MODEL_CASES = {
     "matrix_criteo_like": ("matrix", (32, 32), 130, 26, 16, 13),
 }
 TOL_LOGIT, TOL_GRAD = 1e-5, 2e-5  # |logit - logit64| <= TOL_LOGIT max(1, |logit64|); the project's gradient measure
-KINK = 1e-6  # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 WRONG = ("transposed", "with_diagonal", "both_orders", "matrix_by_left_field")
-
-
-def pairs(F):
-    return F * (F - 1) // 2
-
-
-def pair_fields(F):
-    """(left fields, right fields) of the P pairs in itertools.combinations order, as index tensors."""
-    li, lj = zip(*itertools.combinations(range(F), 2))
-    return torch.tensor(li), torch.tensor(lj)
 
 
 def weight_shape(F, D, ftype):
@@ -160,50 +151,32 @@ def init_weights(F, D, ftype, dtype=torch.float64):
     return torch.ones(weight_shape(F, D, ftype), dtype=dtype)
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
-
-
 SPECIAL_ROWS = {3: "E = 0", 4: "g = 0", 5: "E x 8"}
-_KERNEL_CASES = {}
 
 
+@C.memo
 def kernel_case(B, F, D, ftype, seed=0):
     """A seeded kernel-level case in float64 (made once per shape, never changed): E ~ N(0, s^2) with s^2 = (P D)^(-1/2)
     (the logit, a sum of about P D products of two entries, is then O(1)), matrix weights I + 0.25 N(0,1) (not
     symmetric: a transposed matrix shows), vector and scalar weights N(0,1), g ~ N(0,1), dE_up ~ 0.1 N(0,1); with
     B > 8 the special rows 3: E = 0 (logit and dE exactly 0), 4: g = 0 (dE exactly 0), 5: E x 8.  With the float64
     outputs logit, dE (without dE_up) and dW."""
-    key = (B, F, D, ftype, seed)
-    if key not in _KERNEL_CASES:
-        rnd = _rnd(torch.Generator().manual_seed(14000 + 16 * seed + TYPES.index(ftype)))
-        E = rnd(B, F, D, std=(pairs(F) * D) ** -0.25)
-        if ftype == "matrix":
-            W = (torch.eye(D, dtype=torch.float64) + 0.25 * rnd(pairs(F), D, D)).float().double()
-        else:
-            W = rnd(*weight_shape(F, D, ftype))
-        g, up = rnd(B), rnd(B, F, D, std=0.1)
-        if B > 8:
-            E[3] = 0.0
-            g[4] = 0.0
-            E[5] *= 8.0
-        dE, dW = pair_bwd(E, W, ftype, g)
-        _KERNEL_CASES[key] = dict(B=B, F=F, D=D, ftype=ftype, E=E, W=W, g=g, dE_up=up,
-                                  logit=pair_logit(E, W, ftype), dE=dE, dW=dW)
-    return _KERNEL_CASES[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(14000 + 16 * seed + TYPES.index(ftype)))
+    E = rnd(B, F, D, std=(pairs(F) * D) ** -0.25)
+    if ftype == "matrix":
+        W = (torch.eye(D, dtype=torch.float64) + 0.25 * rnd(pairs(F), D, D)).float().double()
+    else:
+        W = rnd(*weight_shape(F, D, ftype))
+    g, up = rnd(B), rnd(B, F, D, std=0.1)
+    if B > 8:
+        E[3] = 0.0
+        g[4] = 0.0
+        E[5] *= 8.0
+    dE, dW = pair_bwd(E, W, ftype, g)
+    return dict(B=B, F=F, D=D, ftype=ftype, E=E, W=W, g=g, dE_up=up, logit=pair_logit(E, W, ftype), dE=dE, dW=dW)
 
 
-def logit_error(got, want):
-    """max |got - want| / max(1, |want|): the forward's measure."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    return float(((got - want).abs() / want.abs().clamp(min=1.0)).max()) if got.numel() else 0.0
+logit_error = C.rel_error
 
 
 def f32_errors(case):
@@ -225,105 +198,47 @@ def fmfm_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_weight
     n = len(hp.get("deep_hidden_units") or ())
     pres = []
     if n:
-        keep = hp.get("deep_dropout") or [1] * (n + 1)
-        keep = list(keep) if training else [1] * (n + 1)
-        dm = (masks or {}).get("dnn")
+        keep, dm = C.dnn_keep(hp, n, training), (masks or {}).get("dnn")
         x = TL.dnn_input(E, dense)
         logit = logit + TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, dm)
         if return_pre:
-            dm = dm or [None] * (n + 1)
-            y = TL.dropout(x, keep[0], dm[0])
-            for i in range(n):
-                pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-                y = TL.dropout(torch.relu(pres[-1]), keep[i + 1], dm[i + 1])
+            pres = C.dnn_pres(p, x, n, keep, dm)
     return (logit, pres) if return_pre else logit
 
 
-def interaction_l2(p, l2_reg):
-    return l2_reg * 0.5 * p["field_pair_w"].square().sum()
+interaction_l2 = partial(C.param_l2, ("field_pair_w",))  # (p, l2_reg)
 
 
 def fmfm_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0))
-    if hp.get("use_linear", True):
-        out = out + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
     n = len(hp.get("deep_hidden_units") or ())
-    if n:
-        out = out + TL.dnn_l2(p, n, hp.get("deep_l2_reg", 0.0))
-    return out + interaction_l2(p, hp.get("interaction_l2_reg", 0.0))
+    return C.base_l2(p, spec, hp, n or None, hp.get("use_linear", True)) + interaction_l2(
+        p, hp.get("interaction_l2_reg", 0.0))
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = fmfm_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + fmfm_l2(p, spec, hp), logit, pred
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, fmfm_logit, fmfm_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
-
-
-_MODEL_CASES = {}
-
-
+@C.memo
 def make_case(ftype, hidden, B, F, D, Dn, seed=0, use_linear=True, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p (the variable names of the contract),
     idx, dense, y, hp.  Embeddings ~ N(0, 0.15^2), dense ~ N(0,1), field_pair_w its initial value + 0.25 N(0,1) (so that
     it is neither plain FM nor symmetric); `min_abs_pre` is the distance of the closest DNN unit to its kink (inf
     without a DNN).  The first stream whose min_abs_pre is at least KINK is taken."""
-    key = (ftype, tuple(hidden), B, F, D, Dn, seed, use_linear, l2)
-    if key in _MODEL_CASES:
-        return _MODEL_CASES[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     n = len(hidden)
     hp = dict(embedding_size=D, embedding_l2_reg=l2, linear_l2_reg=l2, deep_hidden_units=tuple(hidden),
               deep_dropout=(1,) * (n + 1), deep_l2_reg=l2 if n else 0.0, interaction_l2_reg=l2,
               field_interaction=ftype, use_linear=use_linear, deep_activation="relu")
-    for attempt in range(64):
-        g = torch.Generator().manual_seed(15000 + 64 * seed + attempt)
-        rnd = _rnd(g)
-        p = {}
-        for name, V in zip(spec.sparse_names, sizes):
-            p[f"{name}_feat_embed"] = rnd(V, D, std=0.15)
-        p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-        p["linear_w0"] = rnd(1, std=0.1)
-        dims = [F * D + Dn] + list(hidden)
-        for i in range(n):
-            p[f"dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        if n:
-            p["dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-            p["dnn_w0"] = rnd(1, std=0.1)
+
+    def build(g, rnd):
+        p = C.draw_front(rnd, spec, D, std=0.15)
+        C.draw_dnn(rnd, p, [F * D + Dn] + list(hidden), head=n > 0)
         p["field_pair_w"] = (init_weights(F, D, ftype) + 0.25 * rnd(*weight_shape(F, D, ftype))).float().double()
-        idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-        dense = rnd(B, Dn)
-        y = (torch.rand(B, generator=g) < 0.3).long()
-        pres = fmfm_logit(p, spec, idx, dense, hp, return_pre=True)[1]
-        min_abs_pre = min([float(t.abs().min()) for t in pres] + [float("inf")])
-        if min_abs_pre >= KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
-    _MODEL_CASES[key] = out
-    return out
+        idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
+        min_abs_pre = C.min_abs(fmfm_logit(p, spec, idx, dense, hp, return_pre=True)[1])
+        return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
 
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
-
-
-def grad_measure(got, want):
-    """The project's gradient measure (tests/test_gpu_parity.py:_close_grad) as a number: the largest
-    |got - want| / max(|want|, 0.1 max|want|); an all-zero `want` demands an all-zero `got` (inf otherwise)."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    scale = float(want.abs().max())
-    if scale == 0.0:
-        return 0.0 if float(got.abs().max()) == 0.0 else float("inf")
-    return float(((got - want).abs() / torch.clamp(want.abs(), min=0.1 * scale)).max())
+    return C.first_stream(15000 + 64 * seed, build, lambda k: k["min_abs_pre"] >= KINK)[0]

@@ -15,14 +15,18 @@ Everything but the blocks is composed from the public functions of oracle.th_lay
 tests/test_masknet_host.py pins this file without a GPU; the GPU tests compare the HIP kernels and the engine against it
 in float64.
 """
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
-from tests.fmfm_ref import _rnd, glorot, grad_measure, logit_error, to_f32  # noqa: F401  (shared measures)
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, to_f32  # noqa: F401  (part of this module's interface)
+from tests.ref_common import rel_error as logit_error
+from tests.ref_common import rnd_stream as _rnd  # noqa: F401  (tests/test_masknet_host.py draws with it)
 
 EPS = 1e-5
 TOL_Y, TOL_GRAD = 1e-5, 2e-5  # |Y - Y64| <= TOL_Y max(1, |Y64|); the project's gradient measure
-KINK = 1e-6  # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 # kernel-level row cases keep every pre-activation 2e-6 away from 0: v = gamma xhat + beta with xhat rounded once from
 # float64 (6e-8 relative) and |gamma xhat| < 8 is within 1e-6 of its float64 value
 ROW_KINK = 2e-6
@@ -118,9 +122,6 @@ def row_bwd(Z, gamma, beta, dh):
 
 
 # ------------------------------------------------------------------------------------------------ kernel cases
-_CASES = {}
-
-
 def _special(X, B, scale_small=1e-3):
     """The special examples of a case with B > 8, on X [B, rows, n]: an all-zero example, a row shifted by +50 with a
     spread of 0.05 (its mean far above its spread), a row scaled by 1e-3 (its spread near sqrt(eps))."""
@@ -130,60 +131,51 @@ def _special(X, B, scale_small=1e-3):
         X[EX_SMALL, -1] = (X[EX_SMALL, -1] * scale_small).float().double()
 
 
+@C.memo
 def kernel_case(B, F, D, N, seed=0):
     """A seeded group-kernel case in float64 (made once per shape, never changed): E ~ N(0,1), gains 1 + 0.5 N(0,1),
     biases 0.3 N(0,1), masks and upstream gradients N(0,1), dE_up 0.1 N(0,1); with B > 8 example 3 is all zero, example
     4 has zero upstream gradient, row 0 of example 5 is shifted by +50 (spread 0.05) and the last row of example 6 is
     scaled by 1e-3.  With the float64 outputs Y, dM, dE (without dE_up), dgamma, dbeta."""
-    key = ("group", B, F, D, N, seed)
-    if key not in _CASES:
-        rnd = _rnd(torch.Generator().manual_seed(16000 + seed))
-        E = rnd(B, F, D)
-        _special(E, B)
-        gamma, beta = (1.0 + rnd(F, D, std=0.5)).float().double(), rnd(F, D, std=0.3)
-        Ms, dYs = [rnd(B, F * D) for _ in range(N)], [rnd(B, F * D) for _ in range(N)]
-        if B > 8:
-            for dY in dYs:
-                dY[EX_NO_GRAD] = 0.0
-        dMs, dE, dg, db = group_bwd(E, gamma, beta, Ms, dYs)
-        _CASES[key] = dict(B=B, F=F, D=D, N=N, E=E, gamma=gamma, beta=beta, M=Ms, dY=dYs, dE_up=rnd(B, F, D, std=0.1),
-                           Y=group_fwd(E, gamma, beta, Ms), dM=dMs, dE=dE, dgamma=dg, dbeta=db)
-    return _CASES[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(16000 + seed))
+    E = rnd(B, F, D)
+    _special(E, B)
+    gamma, beta = (1.0 + rnd(F, D, std=0.5)).float().double(), rnd(F, D, std=0.3)
+    Ms, dYs = [rnd(B, F * D) for _ in range(N)], [rnd(B, F * D) for _ in range(N)]
+    if B > 8:
+        for dY in dYs:
+            dY[EX_NO_GRAD] = 0.0
+    dMs, dE, dg, db = group_bwd(E, gamma, beta, Ms, dYs)
+    return dict(B=B, F=F, D=D, N=N, E=E, gamma=gamma, beta=beta, M=Ms, dY=dYs, dE_up=rnd(B, F, D, std=0.1),
+                Y=group_fwd(E, gamma, beta, Ms), dM=dMs, dE=dE, dgamma=dg, dbeta=db)
 
 
+@C.memo
 def plain_case(B, H, seed=0):
     """normalize = 0: X = h_prev >= 0 like a block's output, one mask."""
-    key = ("plain", B, H, seed)
-    if key not in _CASES:
-        rnd = _rnd(torch.Generator().manual_seed(16500 + seed))
-        X, M, dY = torch.relu(rnd(B, H)), rnd(B, H), rnd(B, H)
-        dM, dX = plain_bwd(X, M, dY)
-        _CASES[key] = dict(B=B, H=H, X=X, M=M, dY=dY, dE_up=rnd(B, H, std=0.1), Y=plain_fwd(X, M), dM=dM, dX=dX)
-    return _CASES[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(16500 + seed))
+    X, M, dY = torch.relu(rnd(B, H)), rnd(B, H), rnd(B, H)
+    dM, dX = plain_bwd(X, M, dY)
+    return dict(B=B, H=H, X=X, M=M, dY=dY, dE_up=rnd(B, H, std=0.1), Y=plain_fwd(X, M), dM=dM, dX=dX)
 
 
+@C.memo
 def row_case(B, H, seed=0):
     """A seeded row-kernel case: Z ~ N(0,1) with the special examples of kernel_case (the whole row is the group),
     the first stream whose pre-activations all stay ROW_KINK away from 0."""
-    key = ("row", B, H, seed)
-    if key not in _CASES:
-        for attempt in range(64):
-            rnd = _rnd(torch.Generator().manual_seed(17000 + 64 * seed + attempt))
-            Z = rnd(B, 1, H)
-            _special(Z, B)
-            Z = Z.view(B, H)
-            gamma, beta, dh = (1.0 + rnd(H, std=0.5)).float().double(), rnd(H, std=0.3), rnd(B, H)
-            if B > 8:
-                dh[EX_NO_GRAD] = 0.0
-            h, pre = row_fwd(Z, gamma, beta, return_pre=True)
-            if float(pre.abs().min()) >= ROW_KINK:
-                break
-        else:
-            raise AssertionError("no stream met the case conditions")
-        dZ, dg, db = row_bwd(Z, gamma, beta, dh)
-        _CASES[key] = dict(B=B, H=H, attempt=attempt, Z=Z, gamma=gamma, beta=beta, dh=dh, h=h, pre=pre, dZ=dZ,
-                           dgamma=dg, dbeta=db)
-    return _CASES[key]
+    def build(g, rnd):
+        Z = rnd(B, 1, H)
+        _special(Z, B)
+        Z = Z.view(B, H)
+        gamma, beta, dh = (1.0 + rnd(H, std=0.5)).float().double(), rnd(H, std=0.3), rnd(B, H)
+        if B > 8:
+            dh[EX_NO_GRAD] = 0.0
+        return (Z, gamma, beta, dh) + row_fwd(Z, gamma, beta, return_pre=True)
+
+    (Z, gamma, beta, dh, h, pre), attempt = C.first_stream(17000 + 64 * seed, build,
+                                                           lambda k: float(k[5].abs().min()) >= ROW_KINK)
+    dZ, dg, db = row_bwd(Z, gamma, beta, dh)
+    return dict(B=B, H=H, attempt=attempt, Z=Z, gamma=gamma, beta=beta, dh=dh, h=h, pre=pre, dZ=dZ, dgamma=dg, dbeta=db)
 
 
 def group_errors(case, Y, dM, dE, dg, db):
@@ -261,46 +253,25 @@ def masknet_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_wei
     pres = []
     X = TL.dnn_input(blocks(p, E, dense, hp, pres, wrong), dense)
     n = len(hp["deep_hidden_units"])
-    keep = hp.get("deep_dropout") or [1] * (n + 1)
-    keep = list(keep) if training else [1] * (n + 1)
-    dm = (masks or {}).get("dnn")
+    keep, dm = C.dnn_keep(hp, n, training), (masks or {}).get("dnn")
     logit = TL.dnn(p, X, n, hp.get("deep_activation", "relu"), keep, dm)
     if hp.get("use_linear", True):
         logit = logit + TL.linear_layer(p, spec, idx, dense, manual_weights, mv)
-    if return_pre:
-        dm = dm or [None] * (n + 1)
-        y = TL.dropout(X, keep[0], dm[0])
-        for i in range(n):
-            pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-            y = TL.dropout(torch.relu(pres[-1]), keep[i + 1], dm[i + 1])
-        return logit, pres
-    return logit
+    return (logit, pres + C.dnn_pres(p, X, n, keep, dm)) if return_pre else logit
 
 
 def masknet_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0))
-    if hp.get("use_linear", True):
-        out = out + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
+    out = C.base_l2(p, spec, hp, len(hp["deep_hidden_units"]), hp.get("use_linear", True))
     reg = hp.get("deep_l2_reg", 0.0)
-    out = out + TL.dnn_l2(p, len(hp["deep_hidden_units"]), reg)
     for n in range(1, hp.get("num_blocks", 3) + 1):
         out = out + sum(reg * 0.5 * p[f"block{n}_{w}_weights"].square().sum() for w in ("agg", "proj", "hidden"))
     return out
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = masknet_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + masknet_l2(p, spec, hp), logit, pred
-
-
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, masknet_logit, masknet_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
 def min_abs_pre(p, spec, idx, dense, hp, masks=None, mv=None):
@@ -324,13 +295,8 @@ def block_params(rnd, hp, F, D, Dn):
         p[f"block{n}_hidden_weights"] = glorot(rnd, (wout, H), wout, H)
         p[f"block{n}_ln_gamma"] = (1.0 + rnd(H, std=0.3)).float().double()
         p[f"block{n}_ln_beta"] = rnd(H, std=0.2)
-    hidden = list(hp["deep_hidden_units"])
-    dims = [(len(widths) if hp["block_order"] == "parallel" else 1) * H + Dn] + hidden
-    for i in range(len(hidden)):
-        p[f"dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-        p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-    p["dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-    p["dnn_w0"] = rnd(1, std=0.1)
+    d_in = (len(widths) if hp["block_order"] == "parallel" else 1) * H + Dn
+    C.draw_dnn(rnd, p, [d_in] + list(hp["deep_hidden_units"]))
     return p
 
 
@@ -342,37 +308,22 @@ MODEL_CASES = {
     "serial1": ("serial", 1, 8, 1.3, (16,), 33, 3, 32, 2),
     "serial3_no_dense": ("serial", 3, 32, 1.0, (16, 16), 256, 4, 16, 0),
 }
-_MODEL_CASES = {}
 
 
+@C.memo
 def make_case(order, N, H, ratio, hidden, B, F, D, Dn, seed=0, use_linear=True, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p, idx, dense, y, hp.  Embeddings ~
     N(0, 0.15^2), dense ~ N(0,1).  The first stream in which every relu unit is at least MODEL_KINK from its kink."""
-    key = (order, N, H, ratio, tuple(hidden), B, F, D, Dn, seed, use_linear, l2)
-    if key in _MODEL_CASES:
-        return _MODEL_CASES[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     hp = dict(embedding_size=D, embedding_l2_reg=l2, linear_l2_reg=l2, deep_hidden_units=tuple(hidden),
               deep_dropout=(1,) * (len(hidden) + 1), deep_l2_reg=l2, block_order=order, num_blocks=N,
               block_hidden_units=H, reduction_ratio=ratio, use_linear=use_linear, deep_activation="relu")
-    for attempt in range(64):
-        g = torch.Generator().manual_seed(18000 + 64 * seed + attempt)
-        rnd = _rnd(g)
-        p = {}
-        for name, V in zip(spec.sparse_names, sizes):
-            p[f"{name}_feat_embed"] = rnd(V, D, std=0.15)
-        p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-        p["linear_w0"] = rnd(1, std=0.1)
+
+    def build(g, rnd):
+        p = C.draw_front(rnd, spec, D, std=0.15)
         p.update(block_params(rnd, hp, F, D, Dn))
-        idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-        dense = rnd(B, Dn)
-        y = (torch.rand(B, generator=g) < 0.3).long()
-        closest = min_abs_pre(p, spec, idx, dense, hp)
-        if closest >= MODEL_KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=closest, attempt=attempt)
-    _MODEL_CASES[key] = out
-    return out
+        idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
+        return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre(p, spec, idx, dense, hp))
+
+    k, attempt = C.first_stream(18000 + 64 * seed, build, lambda k: k["min_abs_pre"] >= MODEL_KINK)
+    return dict(k, attempt=attempt)

@@ -23,10 +23,10 @@ import torch
 
 from oracle import th_layers as TL
 from tests import asp_ref
-from tests.fmfm_ref import grad_measure  # noqa: F401  (re-exported: the project's gradient measure)
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, to_f32  # noqa: F401  (part of this module's interface)
 
 TOL_GRAD = 2e-5
-KINK = 1e-6  # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 NAN = float("nan")
 
 # kernel-level GPU cases (B, E, T, H): the default with B no multiple of any tile; every minimum (p = 1, dA exactly 0);
@@ -80,30 +80,18 @@ def mix_loops(Z, A, E, T):
     return torch.tensor(out, dtype=Z.dtype)
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-_MIX = {}
-
-
+@C.memo
 def mix_case(B, E, T, H, seed=0, logit_scale=1.0):
     """A seeded kernel-level case in float64 (made once per key, never changed): Z, dM ~ N(0,1), A ~ logit_scale
     N(0,1); with the float64 outputs M, P, dZ, dA and the float32 CPU restatement's own measures `f32` (M, dZ, dA)."""
-    key = (B, E, T, H, seed, logit_scale)
-    if key not in _MIX:
-        rnd = _rnd(torch.Generator().manual_seed(31000 + 97 * seed + B + 7 * E + 13 * T + H))
-        Z, A, dM = rnd(B, E * H), (rnd(B, T * E) * logit_scale).float().double(), rnd(B, T * H)
-        M, P = mix_fwd(Z, A, E, T)
-        dZ, dA = mix_bwd(Z, A, E, T, dM)
-        M32, _ = mix_fwd(Z.float(), A.float(), E, T)
-        dZ32, dA32 = mix_bwd(Z.float(), A.float(), E, T, dM.float())
-        f32 = dict(M=grad_measure(M32, M), dZ=grad_measure(dZ32, dZ), dA=grad_measure(dA32, dA))
-        _MIX[key] = dict(B=B, E=E, T=T, H=H, Z=Z, A=A, dM=dM, M=M, P=P, dZ=dZ, dA=dA, f32=f32)
-    return _MIX[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(31000 + 97 * seed + B + 7 * E + 13 * T + H))
+    Z, A, dM = rnd(B, E * H), (rnd(B, T * E) * logit_scale).float().double(), rnd(B, T * H)
+    M, P = mix_fwd(Z, A, E, T)
+    dZ, dA = mix_bwd(Z, A, E, T, dM)
+    M32, _ = mix_fwd(Z.float(), A.float(), E, T)
+    dZ32, dA32 = mix_bwd(Z.float(), A.float(), E, T, dM.float())
+    f32 = dict(M=grad_measure(M32, M), dZ=grad_measure(dZ32, dZ), dA=grad_measure(dA32, dA))
+    return dict(B=B, E=E, T=T, H=H, Z=Z, A=A, dM=dM, M=M, P=P, dZ=dZ, dA=dA, f32=f32)
 
 
 # ----------------------------------------------------------------------------------------------- the loss head
@@ -145,35 +133,30 @@ def loss_head_grad(logit, Y, types, weights=None, grad_scale=1.0):
     return loss.detach(), loss_t.detach(), n_t, pred.detach(), g * grad_scale
 
 
-_LOSS = {}
-
-
+@C.memo
 def loss_case(T, B, seed=0):
     """A seeded loss-head case in float64 (made once, never changed): logits ~ 2 N(0,1); tasks alternate classification
     and regression (task 0 classification); weights 0.5 + 0.25 t; with T > 1, about 70 % of task 1's labels are NaN and
     the LAST task (T > 2) has no observed label at all; grad_scale 0.5.  With the float64 outputs and the float32 CPU
     restatement's own measures `f32` (pred, dlogit, loss_t)."""
-    key = (T, B, seed)
-    if key not in _LOSS:
-        g = torch.Generator().manual_seed(32000 + 101 * seed + 17 * T + B)
-        rnd = _rnd(g)
-        types = ["classification" if t % 2 == 0 else "regression" for t in range(T)]
-        weights = [0.5 + 0.25 * t for t in range(T)]
-        logit = rnd(T, B, std=2.0)
-        Y = torch.empty(B, T, dtype=torch.float64)
-        for t, kind in enumerate(types):
-            Y[:, t] = (torch.rand(B, generator=g) < 0.3).double() if kind == "classification" else rnd(B)
-        if T > 1:
-            Y[torch.rand(B, generator=g) < 0.7, 1] = NAN
-        if T > 2:
-            Y[:, T - 1] = NAN
-        want = loss_head_grad(logit, Y, types, weights, 0.5)
-        got32 = loss_head_grad(logit.float(), Y.float(), types, weights, 0.5)
-        f32 = dict(pred=grad_measure(got32[3], want[3]), dlogit=grad_measure(got32[4], want[4]),
-                   loss_t=grad_measure(got32[1], want[1]))
-        _LOSS[key] = dict(T=T, B=B, types=types, weights=weights, grad_scale=0.5, logit=logit, Y=Y, loss=want[0],
-                          loss_t=want[1], n_t=want[2], pred=want[3], dlogit=want[4], f32=f32)
-    return _LOSS[key]
+    g = torch.Generator().manual_seed(32000 + 101 * seed + 17 * T + B)
+    rnd = C.rnd_stream(g)
+    types = ["classification" if t % 2 == 0 else "regression" for t in range(T)]
+    weights = [0.5 + 0.25 * t for t in range(T)]
+    logit = rnd(T, B, std=2.0)
+    Y = torch.empty(B, T, dtype=torch.float64)
+    for t, kind in enumerate(types):
+        Y[:, t] = (torch.rand(B, generator=g) < 0.3).double() if kind == "classification" else rnd(B)
+    if T > 1:
+        Y[torch.rand(B, generator=g) < 0.7, 1] = NAN
+    if T > 2:
+        Y[:, T - 1] = NAN
+    want = loss_head_grad(logit, Y, types, weights, 0.5)
+    got32 = loss_head_grad(logit.float(), Y.float(), types, weights, 0.5)
+    f32 = dict(pred=grad_measure(got32[3], want[3]), dlogit=grad_measure(got32[4], want[4]),
+               loss_t=grad_measure(got32[1], want[1]))
+    return dict(T=T, B=B, types=types, weights=weights, grad_scale=0.5, logit=logit, Y=Y, loss=want[0],
+                loss_t=want[1], n_t=want[2], pred=want[3], dlogit=want[4], f32=f32)
 
 
 # ---------------------------------------------------------------------------------------------------- the model
@@ -239,11 +222,8 @@ def model_loss(p, spec, idx, dense, Y, hp, mv=None, E_in=None):
 
 def fwd_bwd(p, spec, idx, dense, Y, hp, mv=None):
     """One forward+backward: (loss, logit [T, B], pred [T, B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, Y, hp, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach(), pred.detach(), grads
+    out, grads = C.backward(model_loss, p, spec, idx, dense, Y, hp, mv)
+    return out + (grads,)
 
 
 def d_rows(p, spec, idx, dense, Y, hp, mv=None):
@@ -253,10 +233,6 @@ def d_rows(p, spec, idx, dense, Y, hp, mv=None):
     logit, _ = mmoe_logits(p, spec, idx, dense, hp, mv, E_in=E)
     loss_head(logit, Y.to(logit.dtype), hp["task_types"], hp.get("task_weights"))[0].backward()
     return E.grad
-
-
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
 
 
 # model-level cases: (task_types, num_experts, expert_hidden_units, tower_hidden_units, B, F, D, Dn, nan_share, attempt)
@@ -273,7 +249,6 @@ MODEL_CASES = {
     "one_task": (("classification",), 3, (16,), (8,), 66, 4, 8, 2, 0.0, 0),
 }
 SEQ_CASE = (C2, 3, (16, 8), (40,), 0)  # over tests/asp_ref.py's front (B = 37, D = 8, two dense features): + attempt
-_MODEL = {}
 
 
 def task_names(T):
@@ -287,13 +262,8 @@ def _model_vars(rnd, p, K0, names, NE, units, towers):
         p[f"expert_layer_{l}_weights"] = glorot(rnd, (NE, units[l - 1], units[l]), units[l - 1], units[l])
         p[f"expert_layer_{l}_bias"] = rnd(NE, units[l], std=0.1)
     p["gate_weights"] = rnd(K0, len(names) * NE, std=0.3)  # (wide enough that the gates are not all near 1 / E)
-    dims = [units[-1]] + list(towers)
     for name in names:
-        for i in range(len(towers)):
-            p[f"{name}_dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-            p[f"{name}_dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        p[f"{name}_dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-        p[f"{name}_dnn_w0"] = rnd(1, std=0.1)
+        C.draw_dnn(rnd, p, [units[-1]] + list(towers), prefix=f"{name}_")
 
 
 def _labels(g, rnd, B, types, nan_share):
@@ -316,44 +286,35 @@ def min_abs_pre(p, spec, idx, dense, hp, mv=None):
     pres = []
     with torch.no_grad():
         mmoe_logits(p, spec, idx, dense, hp, mv, pres=pres)
-    return min(float(t.abs().min()) for t in pres)
+    return C.min_abs(pres)
 
 
+@C.memo
 def make_case(types, NE, units, towers, B, F, D, Dn, nan_share, attempt, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p (the contract's variable names, with
     the unused linear_w / linear_w0 of every state_dict), idx, dense, Y [B, T], hp.  Embeddings ~ N(0, 0.3^2), dense ~
     N(0,1); `min_abs_pre` is the distance of the closest expert or tower unit to its kink."""
-    key = (tuple(types), NE, tuple(units), tuple(towers), B, F, D, Dn, nan_share, attempt, l2)
-    if key in _MODEL:
-        return _MODEL[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     hp = _hp(types, NE, units, towers, D, l2)
     g = torch.Generator().manual_seed(33000 + attempt)
-    rnd = _rnd(g)
-    p = {}
-    for name, V in zip(spec.sparse_names, sizes):
-        p[f"{name}_feat_embed"] = rnd(V, D, std=0.3)
+    rnd = C.rnd_stream(g)
+    # (its own draw of the front: the linear term is unused, so linear_w and linear_w0 are zeros and draw nothing)
+    p = {f"{name}_feat_embed": rnd(V, D, std=0.3) for name, V in zip(spec.sparse_names, sizes)}
     p["linear_w"] = torch.zeros(spec.lin_layout[2], 1, dtype=torch.float64)
     p["linear_w0"] = torch.zeros(1, dtype=torch.float64)
     _model_vars(rnd, p, F * D + Dn, hp["task_names"], NE, units, towers)
-    idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-    dense = rnd(B, Dn)
+    idx, dense = C.draw_idx(g, sizes, B), rnd(B, Dn)
     Y = _labels(g, rnd, B, types, nan_share)
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, Y=Y, hp=hp, mv=None,
-               min_abs_pre=min_abs_pre(p, spec, idx, dense, hp))
-    _MODEL[key] = out
-    return out
+    return dict(spec=spec, p=p, idx=idx, dense=dense, Y=Y, hp=hp, mv=None,
+                min_abs_pre=min_abs_pre(p, spec, idx, dense, hp))
 
 
+@C.memo
 def make_seq_case(types=SEQ_CASE[0], NE=SEQ_CASE[1], units=SEQ_CASE[2], towers=SEQ_CASE[3], attempt=SEQ_CASE[4],
                   l2=1e-3):
     """MMoE over the front of tests/asp_ref.py:make_model_case - C0 (7), item (11), hist -> item (max_len 6, din
     pooling), C2 (5); B = 37, D = 8, two dense features: the embedding tables, the unit's variables, ids, histories and
     dense values are that case's, the MMoE variables and labels are drawn here."""
-    key = ("seq", tuple(types), NE, tuple(units), tuple(towers), attempt, l2)
-    if key in _MODEL:
-        return _MODEL[key]
     u = asp_ref.make_model_case("din", B=37, D=8, Dn=2, seed=attempt, max_len=6)
     spec = u["spec"]
     p = {n: v for n, v in u["p"].items() if not n.startswith("dnn_")}
@@ -361,14 +322,8 @@ def make_seq_case(types=SEQ_CASE[0], NE=SEQ_CASE[1], units=SEQ_CASE[2], towers=S
     hp.update({n: u["hp"][n] for n in ("att_hidden_units", "att_activation", "att_weight_normalization")},
               seq_pooling="din")
     g = torch.Generator().manual_seed(34000 + attempt)
-    rnd = _rnd(g)
+    rnd = C.rnd_stream(g)
     _model_vars(rnd, p, spec.F * 8 + 2, hp["task_names"], NE, units, towers)
     Y = _labels(g, rnd, 37, types, 0.3)
-    out = dict(model="mmoe", spec=spec, p=p, idx=u["idx"], dense=u["dense"], Y=Y, hp=hp, mv=u["mv"],
-               min_abs_pre=min_abs_pre(p, spec, u["idx"], u["dense"], hp, u["mv"]))
-    _MODEL[key] = out
-    return out
-
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
+    return dict(model="mmoe", spec=spec, p=p, idx=u["idx"], dense=u["dense"], Y=Y, hp=hp, mv=u["mv"],
+                min_abs_pre=min_abs_pre(p, spec, u["idx"], u["dense"], hp, u["mv"]))

@@ -29,7 +29,7 @@ import re
 import numpy as np
 import torch
 
-from tests.asp_ref import grad_measure
+from tests.ref_common import grad_measure_or_empty as grad_measure
 
 KINDS = ("adam", "adagrad", "sgd")
 ENTRIES = ("fields", "pairs", "rows")

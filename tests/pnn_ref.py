@@ -17,17 +17,20 @@ it - not the paper's sum-pooled outer-product shortcut.  Per example, E [F,D], P
       dE_i += G_in[p] E_j + G_out[p] K_(p) E_j    dE_j += G_in[p] E_i + G_out[p] K_(p)^T E_i
       d_rows = dX[:, 0:FD] + dE                   dK[p] = sum_b G_out[b,p] E_bi (x) E_bj (vec: its diagonal; num: trace)
 
-`products` is the bit set INNER = 1 | OUTER = 2.  The per-pair terms, the pair order and the gradient measure are those
-of tests/fmfm_ref.py (imported, not modified); everything but the product layer is composed from the public functions
+`products` is the bit set INNER = 1 | OUTER = 2.  The per-pair terms and the pair order are those of tests/fmfm_ref.py
+(imported, not modified); everything but the product layer is composed from the public functions
 of oracle.th_layers.  tests/test_pnn_host.py pins this file without a GPU; the GPU tests compare the HIP kernels and
 the engine against it in float64.
 """
 import itertools
+from functools import partial
 
 import torch
 
 from oracle import th_layers as TL
-from tests.fmfm_ref import grad_measure, pair_fields, pair_terms  # noqa: F401  (grad_measure: re-exported)
+from tests import ref_common as C
+from tests.fmfm_ref import pair_terms
+from tests.ref_common import KINK, glorot, grad_measure, pair_fields, pairs, to_f32  # noqa: F401  (its interface)
 
 INNER, OUTER = 1, 2
 KERNELS = ("mat", "vec", "num")
@@ -49,12 +52,7 @@ MODEL_CASES = {
     "inner_mat_criteo_like": (INNER | OUTER, "mat", False, (32, 32), 130, 26, 16, 13),
 }
 TOL_X, TOL_GRAD = 1e-5, 2e-5  # |X - X64| <= TOL_X max(1, |X64|) per element; the project's gradient measure
-KINK = 1e-6  # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 WRONG = ("transposed", "j_major", "blocks_swapped", "with_diagonal", "matrix_by_left_field")
-
-
-def pairs(F):
-    return F * (F - 1) // 2
 
 
 def n_products(products):
@@ -170,25 +168,13 @@ def product_bwd(E, K, products, kernel_type, dX):
     return d_rows, dk if kernel_type == "vec" else dk.sum(dim=1)
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
-
-
 SPECIAL_ROWS = {3: "E = 0", 4: "dX = 0", 5: "E x 8"}
 MAX_STREAMS = 128  # draws kernel_case may try for one case
-_KERNEL_CASES = {}
 
 
 def _draw_kernel_case(B, F, D, products, kernel_type, stream):
     gen = torch.Generator().manual_seed(16000 + 64 * stream + 8 * products + KERNELS.index(kernel_type))
-    rnd = _rnd(gen)
+    rnd = C.rnd_stream(gen)
     E = rnd(B, F, D, std=D ** -0.25)
     K = None
     if products & OUTER:
@@ -220,23 +206,22 @@ def kernel_case(B, F, D, products, kernel_type, ldx_pad=0, seed=0):
     (`stream` says which; 0 for all but a few).  It is the E x 8 row that makes this a matter of the draw at the widest
     shapes: a mat product of that row at D = 32 is a sum of 1024 terms of size 20, and the few of the row's P products
     that cancel to below 1 are held to 1e-5 absolute (tests/test_pnn_host.py lists the streams)."""
-    key = (B, F, D, products, kernel_type, seed)
-    if key not in _KERNEL_CASES:
-        for stream in range(MAX_STREAMS * seed, MAX_STREAMS * (seed + 1)):
-            case = _draw_kernel_case(B, F, D, products, kernel_type, stream)
-            case["f32"] = f32_errors(case)
-            if case["f32"][0] <= TOL_X and max(case["f32"][1:]) <= TOL_GRAD:
-                break
-        else:
-            raise AssertionError(f"no stream of {(B, F, D, products, kernel_type)} met the float32 condition")
-        _KERNEL_CASES[key] = case
-    return dict(_KERNEL_CASES[key], ldx=_KERNEL_CASES[key]["W"] + ldx_pad)
+    case = _kernel_case(B, F, D, products, kernel_type, seed)
+    return dict(case, ldx=case["W"] + ldx_pad)
 
 
-def x_error(got, want):
-    """max |got - want| / max(1, |want|) over the elements: the forward's measure."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    return float(((got - want).abs() / want.abs().clamp(min=1.0)).max()) if got.numel() else 0.0
+@C.memo
+def _kernel_case(B, F, D, products, kernel_type, seed):
+    # (its own loop: MAX_STREAMS streams from MAX_STREAMS * seed on, each seeded by _draw_kernel_case)
+    for stream in range(MAX_STREAMS * seed, MAX_STREAMS * (seed + 1)):
+        case = _draw_kernel_case(B, F, D, products, kernel_type, stream)
+        case["f32"] = f32_errors(case)
+        if case["f32"][0] <= TOL_X and max(case["f32"][1:]) <= TOL_GRAD:
+            return case
+    raise AssertionError(f"no stream of {(B, F, D, products, kernel_type)} met the float32 condition")
+
+
+x_error = C.rel_error
 
 
 def f32_errors(case):
@@ -255,99 +240,50 @@ def pnn_logit(p, spec, idx, dense, hp, training=True, masks=None, manual_weights
     products = (INNER if hp.get("use_inner", True) else 0) | (OUTER if hp.get("use_outer", False) else 0)
     X = product_layer(E, p.get("product_kernel"), products, hp.get("kernel_type", "mat"))
     n = len(hp["deep_hidden_units"])
-    keep = hp.get("deep_dropout") or [1] * (n + 1)
-    keep = list(keep) if training else [1] * (n + 1)
-    dm = (masks or {}).get("dnn")
+    keep, dm = C.dnn_keep(hp, n, training), (masks or {}).get("dnn")
     x = TL.dnn_input(X, dense)
     logit = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, dm)
     if hp.get("use_linear", False):
         logit = logit + TL.linear_layer(p, spec, idx, dense, manual_weights, mv)
-    pres = []
-    if return_pre:
-        dm = dm or [None] * (n + 1)
-        y = TL.dropout(x, keep[0], dm[0])
-        for i in range(n):
-            pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-            y = TL.dropout(torch.relu(pres[-1]), keep[i + 1], dm[i + 1])
-    return (logit, pres) if return_pre else logit
+    return (logit, C.dnn_pres(p, x, n, keep, dm)) if return_pre else logit
 
 
-def interaction_l2(p, l2_reg):
-    return l2_reg * 0.5 * p["product_kernel"].square().sum() if "product_kernel" in p else 0.0
+interaction_l2 = partial(C.param_l2, ("product_kernel",))  # (p, l2_reg); 0 without the outer product's kernel
 
 
 def pnn_l2(p, spec, hp):
-    out = TL.embedding_l2(p, spec, hp.get("embedding_l2_reg", 0.0))
-    if hp.get("use_linear", False):
-        out = out + TL.linear_l2(p, hp.get("linear_l2_reg", 0.0))
-    out = out + TL.dnn_l2(p, len(hp["deep_hidden_units"]), hp.get("deep_l2_reg", 0.0))
-    return out + interaction_l2(p, hp.get("interaction_l2_reg", 0.0))
+    return C.base_l2(p, spec, hp, len(hp["deep_hidden_units"]), hp.get("use_linear", False)) + interaction_l2(
+        p, hp.get("interaction_l2_reg", 0.0))
 
 
-def model_loss(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    logit = pnn_logit(p, spec, idx, dense, hp, True, masks, mv=mv)
-    pred = TL.prediction(logit, task)
-    return TL.create_loss(y, pred, task) + pnn_l2(p, spec, hp), logit, pred
+# (p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None) -> (loss, logit [B,1], pred)
+model_loss = partial(C.model_loss, pnn_logit, pnn_l2)
+# ... -> (loss, logit [B], pred [B], grads): one forward+backward, the twin of oracle.th_layers.fwd_bwd
+fwd_bwd = partial(C.fwd_bwd, model_loss)
 
 
-def fwd_bwd(p, spec, idx, dense, y, hp, task="classification", masks=None, mv=None):
-    """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, logit, pred = model_loss(leaves, spec, idx, dense, y, hp, task, masks, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), logit.detach().reshape(-1), pred.detach(), grads
-
-
-_MODEL_CASES = {}
-
-
+@C.memo
 def make_case(products, kernel_type, use_linear, hidden, B, F, D, Dn, seed=0, l2=1e-4):
     """A seeded model-level case in float64 (made once, never changed): spec, p (the variable names of the contract),
     idx, dense, y, hp.  Embeddings ~ N(0, 0.15^2), dense ~ N(0,1), product_kernel glorot (fan D / D) + for "mat" the
     identity (so that the outer products are neither tiny nor symmetric); `min_abs_pre` is the distance of the closest DNN unit to its kink.  The first stream whose min_abs_pre
     is at least KINK is taken."""
-    key = (products, kernel_type, use_linear, tuple(hidden), B, F, D, Dn, seed, l2)
-    if key in _MODEL_CASES:
-        return _MODEL_CASES[key]
-    sizes = [7, 11, 5, 13, 3, 17, 4, 9, 6, 8][:F] if F <= 10 else [5 + (i * 7) % 23 for i in range(F)]
-    spec = TL.Spec([f"C{i}" for i in range(F)], sizes, [f"I{j}" for j in range(Dn)])
+    spec, sizes = C.plain_spec(F, Dn)
     n = len(hidden)
     hp = dict(embedding_size=D, embedding_l2_reg=l2, linear_l2_reg=l2, deep_hidden_units=tuple(hidden),
               deep_dropout=(1,) * (n + 1), deep_l2_reg=l2, interaction_l2_reg=l2, use_inner=bool(products & INNER),
               use_outer=bool(products & OUTER), kernel_type=kernel_type, use_linear=use_linear, deep_activation="relu")
-    for attempt in range(64):
-        g = torch.Generator().manual_seed(17000 + 64 * seed + attempt)
-        rnd = _rnd(g)
-        p = {}
-        for name, V in zip(spec.sparse_names, sizes):
-            p[f"{name}_feat_embed"] = rnd(V, D, std=0.15)
-        p["linear_w"] = rnd(spec.lin_layout[2], 1, std=0.1)
-        p["linear_w0"] = rnd(1, std=0.1)
-        dims = [width(F, D, products) + Dn] + list(hidden)
-        for i in range(n):
-            p[f"dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        p["dnn_w"] = glorot(rnd, (dims[-1], 1), dims[-1], 1)
-        p["dnn_w0"] = rnd(1, std=0.1)
+
+    def build(g, rnd):
+        p = C.draw_front(rnd, spec, D, std=0.15)
+        C.draw_dnn(rnd, p, [width(F, D, products) + Dn] + list(hidden))
         if products & OUTER:
             K = glorot(rnd, weight_shape(F, D, kernel_type), D, D)
             if kernel_type == "mat":
                 K = (K + torch.eye(D, dtype=torch.float64)).float().double()
             p["product_kernel"] = K
-        idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in sizes], 1)
-        dense = rnd(B, Dn)
-        y = (torch.rand(B, generator=g) < 0.3).long()
-        pres = pnn_logit(p, spec, idx, dense, hp, return_pre=True)[1]
-        min_abs_pre = min(float(t.abs().min()) for t in pres)
-        if min_abs_pre >= KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
-    _MODEL_CASES[key] = out
-    return out
+        idx, dense, y = C.draw_batch(g, rnd, sizes, B, Dn)
+        min_abs_pre = C.min_abs(pnn_logit(p, spec, idx, dense, hp, return_pre=True)[1])
+        return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, min_abs_pre=min_abs_pre)
 
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
+    return C.first_stream(17000 + 64 * seed, build, lambda k: k["min_abs_pre"] >= KINK)[0]

@@ -10,16 +10,25 @@ tests/asp_ref.py.  tests/test_seq_models_host.py pins this file without a GPU - 
 that are already pinned; tests/test_gpu_seq_models.py compares the engines against it in float64.
 
 The model names are the keys of ENGINES; the variants of one engine are told apart by hp (cross_type, block_order).
-MODELS maps the ids of the GPU cases to their engine."""
+MODELS maps the ids of the GPU cases to their engine.
+
+What the three units' own model restatements (DIN, BST, DIEN: make_model_case, model_logit and fwd_bwd of
+tests/asp_ref.py, tests/bst_ref.py, tests/dien_ref.py) share is written once here too: make_unit_model_case,
+unit_model_logit, unit_fwd_bwd.  They stay apart from logit() and embeddings() below, which
+tests/test_seq_models_host.py pins to them."""
+from functools import partial
+
 import torch
 
 from oracle import th_layers as TL
 from tests import (afm_ref, asp_ref, autoint_ref, bst_ref, crossmix_ref, dien_ref, dlrm_ref, fibinet_ref, fmfm_ref,
                    masknet_ref, pnn_ref)
-from tests.asp_ref import SeqSpec, _rnd, grad_measure, make_lengths  # noqa: F401
+from tests import ref_common as C
+from tests.asp_ref import SeqSpec
 from tests.cases import make_case as base_case
+from tests.ref_common import KINK  # noqa: F401  (part of this module's interface; no example is left out here)
+from tests.ref_common import grad_measure_or_empty as grad_measure  # a batch may hold no history item
 
-KINK = 1e-6   # a ReLU unit whose float64 pre-activation is this close to 0 may flip in fp32; no example is left out
 TOL = 2e-5    # the project's gradient measure (tests/test_gpu_parity.py:_close_grad)
 KINDS = ("din", "transformer", "dien")
 UNIT_TAG = {"din": "asp", "transformer": "bst", "dien": "dien"}
@@ -44,6 +53,73 @@ class Spec(SeqSpec):
                           self.value_names)
 
 
+# -------------------------------------------------------------------------- the units' own model restatements
+def make_unit_model_case(seed_base, unit_model, model, B, D, Dn, seed, max_len, dtype, unit_hp, draw_unit, probe=None):
+    """A seeded model-level case of `model` = unit_model ("din" / "bst" / "dien") or "dcn" over that unit: plain
+    features C0 (7), item (11), C2 (5), the history `hist` of `item` between them (so the pooled row is not the last
+    field), Dn dense features.  unit_hp: the unit's hp entries; draw_unit(g) -> the unit's variables; probe(p, idx,
+    offsets, ids) -> min_abs_z, the distance of the unit's closest kinked pre-activation to 0 (None: it has none).
+    Returns model, spec, p (reference variable names), idx (the sequence's column is a placeholder 0), dense, y, hp,
+    mv = {"hist": (offsets, ids)} (, min_abs_z)."""
+    g = torch.Generator().manual_seed(seed_base + seed)
+    rnd = C.rnd_stream(g)
+    names, sizes = ["C0", "item", "hist", "C2"], [7, 11, 0, 5]
+    spec = SeqSpec(names, sizes, [f"I{j}" for j in range(Dn)], {"hist": "item"}, {"hist": max_len})
+    p = C.draw_front(rnd, spec, D, std=0.3)
+    hidden = (32, 32) if model == unit_model else (24, 16)
+    d_in = len(names) * D + Dn
+    C.draw_dnn(rnd, p, [d_in] + list(hidden))
+    hp = dict(embedding_size=D, embedding_l2_reg=1e-3, linear_l2_reg=1e-3, deep_hidden_units=hidden,
+              deep_l2_reg=1e-3, deep_activation="relu", **unit_hp)
+    if model == "dcn":
+        L = 2
+        p["cross_w"], p["cross_b"] = rnd(L, d_in, std=0.15), rnd(L, d_in, std=0.15)
+        p["cross_w_out"] = rnd(d_in, 1, std=0.15)
+        hp.update(cross_layer_num=L, cross_layer_l2_reg=1e-3, use_linear=True)
+    p.update(draw_unit(g))
+    idx = C.draw_idx(g, sizes, B)
+    offsets, ids = C.draw_history(g, B, max_len, sizes[1])
+    dense = rnd(B, Dn)
+    y = C.draw_labels(g, B)
+    c = lambda t: t.to(dtype) if t.is_floating_point() else t  # noqa: E731
+    out = dict(model=model, spec=spec, p={k: c(v) for k, v in p.items()}, idx=idx, dense=c(dense), y=y, hp=hp,
+               mv={"hist": (offsets, ids)})
+    if probe is not None:
+        out["min_abs_z"] = probe(p, idx, offsets, ids)
+    return out
+
+
+def unit_model_logit(unit_model, E, model, p, spec, idx, dense, hp, training=True, masks=None):
+    """On E = the unit's own embeddings(): `unit_model` is linear + DNN([E | dense]); "dcn" (DCN.py:99-144) is dnn +
+    cross (+ linear)."""
+    masks = masks or {}
+    x = TL.dnn_input(E, dense)
+    n = len(hp["deep_hidden_units"])
+    keep = hp.get("deep_dropout", [1] * (n + 1)) if training else [1] * (n + 1)
+    dnn = TL.dnn(p, x, n, hp.get("deep_activation", "relu"), keep, masks.get("dnn"))
+    lin = TL.linear_layer(p, spec.tl, idx[:, spec.plain_cols], dense)
+    if model == unit_model:
+        return lin + dnn
+    assert model == "dcn"
+    logit = dnn + TL.cross_net(p, x)
+    return logit + lin if hp.get("use_linear", True) else logit
+
+
+def _fwd_bwd(logit_fn, l2_fn, model, p, spec, idx, dense, y, hp, mv, task, masks, **kw):
+    """ref_common.fwd_bwd for a logit that takes (model, p, spec, idx, dense, hp, mv, training, masks, **kw)."""
+    def as_model_logit(p, spec, idx, dense, hp, training, masks, mv):
+        return logit_fn(model, p, spec, idx, dense, hp, mv, training, masks, **kw)
+
+    return C.fwd_bwd(partial(C.model_loss, as_model_logit, l2_fn), p, spec, idx, dense, y, hp, task, masks, mv)
+
+
+def unit_fwd_bwd(model_logit, unit_model, model, p, spec, idx, dense, y, hp, mv, task="classification", masks=None):
+    """fwd_bwd of a unit's own restatement: its model_logit with the l2 of tests/asp_ref.py (DIN's for every unit)."""
+    l2_fn = partial(asp_ref.model_l2, "din" if model == unit_model else model)
+    return _fwd_bwd(model_logit, l2_fn, model, p, spec, idx, dense, y, hp, mv, task, masks)
+
+
+# ------------------------------------------------------------------------------------------ any model, any front
 def _kind(hp):
     return str(hp.get("seq_pooling", "din")).lower()
 
@@ -230,13 +306,7 @@ def l2(model, p, spec, hp):
 
 def fwd_bwd(model, p, spec, idx, dense, y, hp, mv=None, task="classification", masks=None, wrong=None):
     """One forward+backward: (loss, logit [B], pred [B], grads) - the twin of oracle.th_layers.fwd_bwd."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    out = logit(model, leaves, spec, idx, dense, hp, mv, True, masks, wrong)
-    pred = TL.prediction(out, task)
-    loss = TL.create_loss(y, pred, task) + l2(model, leaves, spec, hp)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), out.detach().reshape(-1), pred.detach(), grads
+    return _fwd_bwd(logit, partial(l2, model), model, p, spec, idx, dense, y, hp, mv, task, masks, wrong=wrong)
 
 
 def min_abs_pre(model, p, spec, idx, dense, hp, mv=None):
@@ -346,7 +416,7 @@ def check_grads(k, grads, want, g32, bk_scales=None, what="", show=print):
 B, DN, MAX_LEN = 37, 2, 6
 _UNIT_CASE = {"din": (asp_ref.make_model_case, "din"), "transformer": (bst_ref.make_model_case, "bst"),
               "dien": (dien_ref.make_model_case, "dien")}
-_CASES, _REFS = {}, {}
+_REFS = {}
 
 
 def _f32(t):
@@ -416,6 +486,7 @@ _KEEP_UNIT_HP = ("embedding_size", "seq_pooling", "att_hidden_units", "att_activ
                  "att_head_num", "att_ffn_units")
 
 
+@C.memo
 def make_case(model_id, kind, D=8, seed=0, **unit_kw):
     """A seeded case of model `model_id` (a key of MODELS) over the spec of tests/asp_ref.py:make_model_case - C0 (7),
     item (11), hist -> item (max_len 6), C2 (5); B = 37, two dense features; example 0 has no history, example 1 one
@@ -423,13 +494,10 @@ def make_case(model_id, kind, D=8, seed=0, **unit_kw):
     linear and unit variables, ids, dense values and labels are the unit's own make_model_case's (unit_kw goes to
     it), the model's variables are model_variables'.  The first stream in which every kinked unit is at least KINK
     from its kink is taken (`attempt`, `min_abs_pre`).  Returns model (the engine), spec, p, idx, dense, y, hp, mv."""
-    key = (model_id, kind, D, seed, tuple(sorted(unit_kw.items())))
-    if key in _CASES:
-        return _CASES[key]
     model = MODELS[model_id]
     pm, hpm = model_variables(model_id, D)
     make, unit_model = _UNIT_CASE[kind]
-    for attempt in range(64):
+    for attempt in range(64):  # (its own loop: the streams are the unit's make_model_case's seeds, not generators)
         u = make(unit_model, B=B, D=D, Dn=DN, seed=64 * seed + attempt, max_len=MAX_LEN, **unit_kw)
         spec = u["spec"]
         p = {n: v for n, v in u["p"].items() if not n.startswith("dnn_")}
@@ -447,15 +515,12 @@ def make_case(model_id, kind, D=8, seed=0, **unit_kw):
             hp["use_linear"] = True
         closest = min_abs_pre(model, p, spec, u["idx"], u["dense"], hp, u["mv"])
         if closest >= KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(model=model, spec=spec, p=p, idx=u["idx"], dense=u["dense"], y=u["y"], hp=hp, mv=u["mv"],
-               min_abs_pre=closest, attempt=attempt)
-    _CASES[key] = out
-    return out
+            return dict(model=model, spec=spec, p=p, idx=u["idx"], dense=u["dense"], y=u["y"], hp=hp, mv=u["mv"],
+                        min_abs_pre=closest, attempt=attempt)
+    raise AssertionError(f"no stream of {(model_id, kind, D, seed)} met the case conditions of make_case")
 
 
+@C.memo
 def make_mixed_case(kind, D=16, model="deepfm", seed=0):
     """A seeded case over a mixed front: hist2 -> item (max_len 3, AHEAD of its query), C0 (7), item (11), hist -> item
     (max_len 6), tags (9, multi-valued), val (6, a value feature); B = 37, three dense features.  Example 0 has both
@@ -465,9 +530,6 @@ def make_mixed_case(kind, D=16, model="deepfm", seed=0):
     the softmax here (att_hidden_units (16, 8)), the transformer with 2 heads and 2 D FFN units.  The first stream in
     which every kinked unit (DNN, the din unit's layers, the transformer's FFN) is at least KINK from its kink is
     taken."""
-    key = (kind, D, model, seed)
-    if key in _CASES:
-        return _CASES[key]
     names, sizes = ["hist2", "C0", "item", "hist", "tags", "val"], [0, 7, 11, 0, 9, 6]
     max_len = {"hist2": 3, "hist": 6}
     Dn, hidden = 3, (16, 8)
@@ -482,9 +544,9 @@ def make_mixed_case(kind, D=16, model="deepfm", seed=0):
         hp.update(att_head_num=2, att_ffn_units=2 * D)
     if model == "dcn":
         hp.update(cross_layer_num=2, cross_layer_l2_reg=1e-3, use_linear=True)
-    for attempt in range(64):
-        g = torch.Generator().manual_seed(23000 + 64 * seed + attempt)
-        rnd = _rnd(g)
+
+    def build(g, rnd):
+        # (its own draw of the front: with DeepFM a table's bias column follows the table)
         p = {}
         for n, V in zip(names, sizes):
             if V:
@@ -494,12 +556,7 @@ def make_mixed_case(kind, D=16, model="deepfm", seed=0):
         p["linear_w"] = rnd(spec.tl.lin_layout[2], 1, std=0.1)
         p["linear_w0"] = rnd(1, std=0.1)
         d_in = len(names) * D + Dn
-        dims = [d_in] + list(hidden)
-        for i in range(len(hidden)):
-            p[f"dnn_layer_{i}_weights"] = rnd(dims[i], dims[i + 1], std=(2.0 / (dims[i] + dims[i + 1])) ** 0.5)
-            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        p["dnn_w"] = rnd(dims[-1], 1, std=(2.0 / (dims[-1] + 1)) ** 0.5)
-        p["dnn_w0"] = rnd(1, std=0.1)
+        C.draw_dnn(rnd, p, [d_in] + list(hidden))
         if model == "dcn":
             p["cross_w"], p["cross_b"] = rnd(2, d_in, std=0.15), rnd(2, d_in, std=0.15)
             p["cross_w_out"] = rnd(d_in, 1, std=0.15)
@@ -511,13 +568,8 @@ def make_mixed_case(kind, D=16, model="deepfm", seed=0):
                           bst_ref.make_bst_params(D, 2, hp["att_ffn_units"], max_len[n], g).items()})
             else:
                 p.update({f"{n}_dien_{v}": t for v, t in dien_ref.make_dien_params(D, g).items()})
-        idx = torch.stack([torch.randint(0, v, (B,), generator=g) if v else torch.zeros(B, dtype=torch.int64)
-                           for v in sizes], 1)
-        mv = {}
-        for n in spec.seq_query:
-            ln = make_lengths(B, max_len[n], g)
-            mv[n] = (torch.cat([torch.zeros(1, dtype=torch.int64), ln.cumsum(0)]),
-                     torch.randint(0, sizes[2], (int(ln.sum()),), generator=g))
+        idx = C.draw_idx(g, sizes, B)
+        mv = {n: C.draw_history(g, B, max_len[n], sizes[2]) for n in spec.seq_query}
         nt = torch.randint(0, 4, (B,), generator=g)
         nt[0], nt[3], nt[1] = 0, 0, 3
         mv["tags"] = (torch.cat([torch.zeros(1, dtype=torch.int64), nt.cumsum(0)]),
@@ -526,16 +578,12 @@ def make_mixed_case(kind, D=16, model="deepfm", seed=0):
         vals[0] = 0.0
         mv["val"] = (torch.randint(0, sizes[5], (B,), generator=g), vals)
         dense = rnd(B, Dn)
-        y = (torch.rand(B, generator=g) < 0.3).long()
-        closest = min_abs_pre(model, p, spec, idx, dense, hp, mv)
-        if closest >= KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
-    out = dict(model=model, spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, mv=mv, min_abs_pre=closest,
-               attempt=attempt)
-    _CASES[key] = out
-    return out
+        y = C.draw_labels(g, B)
+        return dict(model=model, spec=spec, p=p, idx=idx, dense=dense, y=y, hp=hp, mv=mv,
+                    min_abs_pre=min_abs_pre(model, p, spec, idx, dense, hp, mv))
+
+    k, attempt = C.first_stream(23000 + 64 * seed, build, lambda k: k["min_abs_pre"] >= KINK)
+    return dict(k, attempt=attempt)
 
 
 def to_f32(k):

@@ -11,6 +11,7 @@ from sklearn.metrics import log_loss
 
 from oracle import th_layers as TL
 from tests import fibinet_ref as R
+from tests import ref_common as C
 from tests.test_gpu_parity import _close, _close_grad
 
 pytestmark = pytest.mark.gpu
@@ -279,25 +280,17 @@ def _wide_case():
         return _WIDE
     B, FD, Dn, hidden, keep = 130, 10400, 13, (32, 32), (0.9, 0.8, 0.8)
     dims = [FD + Dn] + list(hidden)
-    for attempt in range(16):
-        g = torch.Generator().manual_seed(13000 + attempt)
-        rnd = R._rnd(g)
-        x = rnd(B, FD + Dn)
-        p = {}
-        for i in range(2):
-            p[f"dnn_layer_{i}_weights"] = R.glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-            p[f"dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
-        p["dnn_w"], p["dnn_w0"] = R.glorot(rnd, (32, 1), 32, 1), rnd(1, std=0.1)
+
+    def build(g, rnd):
+        x, p = rnd(B, FD + Dn), {}
+        C.draw_dnn(rnd, p, dims)
         masks = [(torch.rand(B, d, generator=g) < kp).double() for d, kp in zip(dims, keep)]
-        gl = rnd(B, std=1.0 / B)
-        y, pres = TL.dropout(x, keep[0], masks[0]), []
-        for i in range(2):
-            pres.append(y @ p[f"dnn_layer_{i}_weights"] + p[f"dnn_layer_{i}_bias"])
-            y = TL.dropout(torch.relu(pres[-1]), keep[i + 1], masks[i + 1])
-        if min(float(t.abs().min()) for t in pres) >= R.KINK:
-            break
-    else:
-        raise AssertionError("no stream met the case conditions")
+        return x, p, masks, rnd(B, std=1.0 / B)
+
+    def clear(k):
+        return C.min_abs(C.dnn_pres(k[1], k[0], 2, keep, k[2])) >= R.KINK
+
+    (x, p, masks, gl), _ = C.first_stream(13000, build, clear, attempts=16)
     leaves = {n: v.clone().requires_grad_(True) for n, v in p.items()}
     xl = x.clone().requires_grad_(True)
     logit = TL.dnn(leaves, xl, 2, "relu", list(keep), masks).reshape(-1)

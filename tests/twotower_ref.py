@@ -25,10 +25,10 @@ import math
 import torch
 
 from oracle import th_layers as TL
-from tests.fmfm_ref import grad_measure  # noqa: F401  (re-exported: the project's gradient measure)
+from tests import ref_common as C
+from tests.ref_common import KINK, glorot, grad_measure, to_f32  # noqa: F401  (part of this module's interface)
 
 TOL_GRAD = 2e-5
-KINK = 1e-6   # a relu unit whose float64 pre-activation is this close to 0 may flip in fp32
 EPS = 1e-12   # the row norm's floor (engine.TwoTowerEngine.EPS)
 TIE = 1e-4    # |S_ij - S_ii| <= TIE max(1, |S_ii|) in float64 is a near tie: the float32 rank may differ there
 TIE_SHARE = 0.25  # at most this share of a rank case's rows may have a near tie
@@ -139,63 +139,46 @@ def rownorm_bwd(Y, inv, dY):
     return inv.unsqueeze(1) * (dY - Y * (Y * dY).sum(dim=1, keepdim=True))
 
 
-def _rnd(g):
-    def rnd(*shape, std=1.0):
-        # (every value is a float32 number: the kernels, the float32 restatement and float64 see the same inputs)
-        return (torch.randn(*shape, generator=g, dtype=torch.float64) * std).float().double()
-    return rnd
-
-
-_IBS = {}
-
-
+@C.memo
 def ibs_case(B, H, ids=True, logq=True, w=True, scale=20.0, normalised=True, seed=0, same_ids=False, zero_w=False):
     """A seeded kernel-level case in float64 (made once per key, never changed): U, V ~ N(0,1), rows normalised (in
     float64, then rounded to float32 values) when `normalised`; item ids from about B/3 values (real duplicates), logq
     in [-6, 0], about a quarter of w zero; grad_scale 0.5.  With the float64 outputs lse, row_loss, loss, rank, dU, dV,
     the near-tie counts `ties` and the float32 CPU restatement's own measures `f32`."""
-    key = (B, H, ids, logq, w, scale, normalised, seed, same_ids, zero_w)
-    if key not in _IBS:
-        g = torch.Generator().manual_seed(41000 + 131 * seed + 7 * B + H)
-        rnd = _rnd(g)
-        U, V = rnd(B, H), rnd(B, H)
-        if normalised:
-            U, V = rownorm_fwd(U)[0].float().double(), rownorm_fwd(V)[0].float().double()
-        item = torch.randint(0, max(1, B // 3), (B,), generator=g) + 5 if ids else None
-        if same_ids:
-            item = torch.full((B,), 9, dtype=torch.int64)
-        lq = (-6.0 * torch.rand(B, generator=g, dtype=torch.float64)).float().double() if logq else None
-        wt = (torch.rand(B, generator=g) >= 0.25).double() if w else None
-        if zero_w:
-            wt = torch.zeros(B, dtype=torch.float64)
-        gs = 0.5
-        f = fwd(U, V, scale, item, lq, wt)
-        dU, dV = bwd(U, V, scale, item, lq, wt, gs)
-        c32 = lambda t: None if t is None else t.float()  # noqa: E731
-        f32r = fwd(U.float(), V.float(), scale, item, c32(lq), c32(wt))
-        dU32, dV32 = bwd(U.float(), V.float(), scale, item, c32(lq), c32(wt), gs)
-        f32 = dict(lse=grad_measure(f32r["lse"], f["lse"]), row_loss=grad_measure(f32r["row_loss"], f["row_loss"]),
-                   loss=grad_measure(f32r["loss"], f["loss"]), dU=grad_measure(dU32, dU), dV=grad_measure(dV32, dV))
-        _IBS[key] = dict(B=B, H=H, U=U, V=V, item=item, logq=lq, w=wt, scale=scale, grad_scale=gs, S=f["S"],
-                         lse=f["lse"], row_loss=f["row_loss"], loss=f["loss"], rank=f["rank"], dU=dU, dV=dV,
-                         ties=near_ties(f["S"], f["ok"]), f32=f32)
-    return _IBS[key]
+    g = torch.Generator().manual_seed(41000 + 131 * seed + 7 * B + H)
+    rnd = C.rnd_stream(g)
+    U, V = rnd(B, H), rnd(B, H)
+    if normalised:
+        U, V = rownorm_fwd(U)[0].float().double(), rownorm_fwd(V)[0].float().double()
+    item = torch.randint(0, max(1, B // 3), (B,), generator=g) + 5 if ids else None
+    if same_ids:
+        item = torch.full((B,), 9, dtype=torch.int64)
+    lq = (-6.0 * torch.rand(B, generator=g, dtype=torch.float64)).float().double() if logq else None
+    wt = (torch.rand(B, generator=g) >= 0.25).double() if w else None
+    if zero_w:
+        wt = torch.zeros(B, dtype=torch.float64)
+    gs = 0.5
+    f = fwd(U, V, scale, item, lq, wt)
+    dU, dV = bwd(U, V, scale, item, lq, wt, gs)
+    c32 = lambda t: None if t is None else t.float()  # noqa: E731
+    f32r = fwd(U.float(), V.float(), scale, item, c32(lq), c32(wt))
+    dU32, dV32 = bwd(U.float(), V.float(), scale, item, c32(lq), c32(wt), gs)
+    f32 = dict(lse=grad_measure(f32r["lse"], f["lse"]), row_loss=grad_measure(f32r["row_loss"], f["row_loss"]),
+               loss=grad_measure(f32r["loss"], f["loss"]), dU=grad_measure(dU32, dU), dV=grad_measure(dV32, dV))
+    return dict(B=B, H=H, U=U, V=V, item=item, logq=lq, w=wt, scale=scale, grad_scale=gs, S=f["S"],
+                lse=f["lse"], row_loss=f["row_loss"], loss=f["loss"], rank=f["rank"], dU=dU, dV=dV,
+                ties=near_ties(f["S"], f["ok"]), f32=f32)
 
 
-_RN = {}
-
-
+@C.memo
 def rownorm_case(B, H, seed=0):
-    key = (B, H, seed)
-    if key not in _RN:
-        rnd = _rnd(torch.Generator().manual_seed(42000 + 17 * seed + 3 * B + H))
-        X, dY = rnd(B, H, std=2.0), rnd(B, H)
-        Y, inv = rownorm_fwd(X)
-        dX = rownorm_bwd(Y, inv, dY)
-        Y32, inv32 = rownorm_fwd(X.float())
-        f32 = dict(Y=grad_measure(Y32, Y), dX=grad_measure(rownorm_bwd(Y32, inv32, dY.float()), dX))
-        _RN[key] = dict(B=B, H=H, X=X, dY=dY, Y=Y, inv=inv, dX=dX, f32=f32)
-    return _RN[key]
+    rnd = C.rnd_stream(torch.Generator().manual_seed(42000 + 17 * seed + 3 * B + H))
+    X, dY = rnd(B, H, std=2.0), rnd(B, H)
+    Y, inv = rownorm_fwd(X)
+    dX = rownorm_bwd(Y, inv, dY)
+    Y32, inv32 = rownorm_fwd(X.float())
+    f32 = dict(Y=grad_measure(Y32, Y), dX=grad_measure(rownorm_bwd(Y32, inv32, dY.float()), dX))
+    return dict(B=B, H=H, X=X, dY=dY, Y=Y, inv=inv, dX=dX, f32=f32)
 
 
 # ---------------------------------------------------------------------------------------------------- the model
@@ -255,11 +238,12 @@ def model_loss(p, spec, idx, dense, y, hp, mv=None, E_in=None):
 
 def fwd_bwd(p, spec, idx, dense, y, hp, mv=None):
     """One forward+backward: (loss, row_loss [B], rank [B], grads)."""
-    leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
-    loss, f = model_loss(leaves, spec, idx, dense, y, hp, mv)
-    loss.backward()
-    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-    return loss.detach(), f["row_loss"].detach(), f["rank"], grads
+    def loss_fn(leaves):
+        loss, f = model_loss(leaves, spec, idx, dense, y, hp, mv)
+        return loss, f["row_loss"], f["rank"]
+
+    out, grads = C.backward(loss_fn, p)
+    return out + (grads,)
 
 
 def d_rows(p, spec, idx, dense, y, hp, mv=None):
@@ -286,22 +270,18 @@ def sgd_steps(p, spec, idx, dense, y, hp, lr, steps, mv=None):
     return losses, p
 
 
-def glorot(rnd, shape, fan_in, fan_out):
-    return rnd(*shape, std=(2.0 / (fan_in + fan_out)) ** 0.5)
-
-
 USER, ITEM = ("U0", "U1", "Utags", "du"), ("item", "Icat", "di")
 SIZES = dict(U0=7, U1=11, Utags=5, item=13, Icat=6)
-_MODEL = {}
 
 
 def min_abs_pre(p, spec, idx, dense, hp, mv):
     pres = []
     with torch.no_grad():
         model_parts(p, spec, idx, dense, hp, mv, pres=pres)
-    return min(float(t.abs().min()) for t in pres)
+    return C.min_abs(pres)
 
 
+@C.memo
 def make_case(normalize=True, masking=True, logq=False, labels=False, B=37, D=8, units=((16, 8), (12, 8)), l2=1e-4,
               attempt=0):
     """A seeded model-level case in float64 (made once, never changed): three user embedding features (Utags
@@ -309,26 +289,23 @@ def make_case(normalize=True, masking=True, logq=False, labels=False, B=37, D=8,
     unused linear_w / linear_w0 of every state_dict), idx, dense, y (weights or None), mv, hp.  Embeddings ~ N(0,
     0.3^2), dense ~ N(0,1).  The first stream from `attempt` on whose every hidden ReLU pre-activation is at least
     KINK from 0 in float64 is taken (`attempt` in the result says which)."""
-    key = (normalize, masking, logq, labels, B, D, units, l2, attempt)
-    if key in _MODEL:
-        return _MODEL[key]
     names = [n for n in USER + ITEM if n in SIZES]
     spec = TL.Spec(names, [SIZES[n] for n in names], ["du", "di"], multi_names=["Utags"])
     hp = dict(embedding_size=D, embedding_l2_reg=l2, deep_l2_reg=l2, user_features=USER, item_features=ITEM,
               item_id_feature="item", user_hidden_units=tuple(units[0]), item_hidden_units=tuple(units[1]),
               temperature=0.05 if normalize else 1.0, normalize=normalize, mask_accidental_hits=masking,
               logq_correction=logq, deep_activation="relu")
+    # (its own loop and front: ten streams from `attempt` on, the last one kept whatever its gap; the linear term is
+    # unused, so linear_w and linear_w0 are zeros and draw nothing; Utags' ids come as a CSR)
     for a in range(attempt, attempt + 10):
         g = torch.Generator().manual_seed(43000 + a)
-        rnd = _rnd(g)
+        rnd = C.rnd_stream(g)
         p = {f"{n}_feat_embed": rnd(SIZES[n], D, std=0.3) for n in names}
         p["linear_w"] = torch.zeros(spec.lin_layout[2], 1, dtype=torch.float64)
         p["linear_w0"] = torch.zeros(1, dtype=torch.float64)
         for side, un, feats in (("user", units[0], USER), ("item", units[1], ITEM)):
-            dims = [sum(D for n in feats if n in SIZES) + sum(1 for n in feats if n not in SIZES)] + list(un)
-            for i in range(len(un)):
-                p[f"{side}_dnn_layer_{i}_weights"] = glorot(rnd, (dims[i], dims[i + 1]), dims[i], dims[i + 1])
-                p[f"{side}_dnn_layer_{i}_bias"] = rnd(dims[i + 1], std=0.1)
+            d_in = sum(D for n in feats if n in SIZES) + sum(1 for n in feats if n not in SIZES)
+            C.draw_dnn(rnd, p, [d_in] + list(un), head=False, prefix=f"{side}_")
         p["item_logq"] = (-6.0 * torch.rand(SIZES["item"], generator=g, dtype=torch.float64)).float().double()
         idx = torch.stack([torch.randint(0, SIZES[n], (B,), generator=g) for n in names], 1)
         idx[:, names.index("Utags")] = 0  # (a multi-valued feature's idx column is a placeholder)
@@ -340,10 +317,4 @@ def make_case(normalize=True, masking=True, logq=False, labels=False, B=37, D=8,
         gap = min_abs_pre(p, spec, idx, dense, hp, mv)
         if gap >= KINK:
             break
-    out = dict(spec=spec, p=p, idx=idx, dense=dense, y=y, mv=mv, hp=hp, min_abs_pre=gap, attempt=a)
-    _MODEL[key] = out
-    return out
-
-
-def to_f32(p):
-    return {n: v.float() for n, v in p.items()}
+    return dict(spec=spec, p=p, idx=idx, dense=dense, y=y, mv=mv, hp=hp, min_abs_pre=gap, attempt=a)
