@@ -1,4 +1,4 @@
-"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h).
+"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h and include/recman_hip_topk.h).
 
 There is NO fallback: if the library is missing or a symbol does not resolve the
 import raises, and every call that returns a non-zero code raises RecmanHipError
@@ -214,6 +214,15 @@ SIGNATURES_I64 = {
 }
 
 
+# name -> (restype, argtypes): the entry points of include/recman_hip_topk.h, in its order
+SIGNATURES_TOPK = {
+    "rm_topk_ip_supported": (c_int, [c_int, c_int]),
+    "rm_topk_ip_tile": (c_int, [c_int, c_int]),
+    "rm_topk_ip_workspace": (c_int64, [I64, I64, c_int, c_int]),
+    "rm_topk_ip": (c_int, [P, I64, P, I64, I64, I64, c_int, c_float, c_int, P, P, c_int, P, P, I64, P, P]),
+}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RecmanHipError(
@@ -234,6 +243,10 @@ def _load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = c_int
+    for name, (restype, argtypes) in SIGNATURES_TOPK.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = restype
     return lib
 
 

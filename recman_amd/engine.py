@@ -3282,6 +3282,36 @@ class TwoTowerEngine(Engine):
         self._seq_bwd()
         return self._add_l2(self.loss)
 
+    TOPK_WS_FLOATS = 1 << 26  # topk()'s workspace bound: 256 MB
+
+    def topk(self, u, items, k, exclude=None):
+        """Exact retrieval (rm_topk_ip): per row of u [n, H] the k rows of the catalogue items [N, H] with the highest
+        <u_i, items_j> / temperature (no logQ), sorted by score descending, then row ascending -> (rows int64 [n, k],
+        scores float32 [n, k]) device tensors; -1 / -inf past the available rows.  exclude: None or (offsets [n + 1],
+        rows) int64 device tensors, the catalogue rows each query must not get back.  The queries go in groups of
+        whole 64-row query tiles, as many as keep the workspace within TOPK_WS_FLOATS floats (one tile at the least,
+        whose workspace is at most 64 x 64 x 2048 x 2 floats = 64 MiB for k = 1024); the result does not depend on the
+        grouping."""
+        n, N, H = int(u.shape[0]), int(items.shape[0]), int(items.shape[1])
+        if not ops.topk_ip_supported(H, k):
+            raise ValueError(f"TwoTower.topk: k={k} with H={H} is not supported by rm_topk_ip ({ops.TOPK_LIMITS})")
+        rows = torch.empty(n, k, dtype=torch.int64, device=self.device)
+        scores = torch.empty(n, k, dtype=F32, device=self.device)
+        if n == 0:
+            return rows, scores
+        tile = ops.topk_ip_tile(H)
+        per_tile = max(1, ops.topk_ip_workspace(tile, N, H, k))
+        group = min(n, max(1, self.TOPK_WS_FLOATS // per_tile) * tile)
+        ws = torch.empty(ops.topk_ip_workspace(group, N, H, k), dtype=F32, device=self.device)
+        off = None if exclude is None else exclude[0].tolist()
+        for s in range(0, n, group):
+            t = min(s + group, n)
+            ex = None
+            if exclude is not None:
+                ex = ((exclude[0][s:t + 1] - off[s]).contiguous(), exclude[1][off[s]:off[t]].contiguous())
+            ops.topk_ip(u[s:t], items, k, self.scale, rows[s:t], scores[s:t], ws, exclude=ex)
+        return rows, scores
+
 
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine, "pnn": PNNEngine,

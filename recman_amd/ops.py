@@ -1998,3 +1998,81 @@ def rownorm_bwd(Y, inv_norm, dY, dX):
     pdy, lddy = _strided_rows(dY, "dY", B, H, True)
     pdx, lddx = _strided_rows(dX, "dX", B, H, True)
     _lib.call("rm_rownorm_bwd", py, ldy, _chk(inv_norm, "inv_norm", F32, (B,)), pdy, lddy, B, H, pdx, lddx, _stream())
+
+
+# ---- exact top-k retrieval by inner product over an item catalogue (csrc/topk.hip, include/recman_hip_topk.h) -----
+TOPK_TILE = {"rows": 0, "cols": 1, "max_splits": 2}  # RM_TOPK_ROWS / RM_TOPK_COLS / RM_TOPK_MAX_SPLITS
+TOPK_LIMITS = "H a multiple of 4 in 4..256, k in 1..1024, row strides multiples of 4 floats, item_splits 0..64"
+
+
+def topk_ip_supported(H, k):
+    """rm_topk_ip_supported: H a multiple of 4 in 4..256 and k in 1..1024."""
+    return bool(_lib.lib().rm_topk_ip_supported(int(H), int(k)))
+
+
+def topk_ip_tile(H, which="rows"):
+    """rm_topk_ip_tile: "rows" = the query rows a block owns, "cols" = the catalogue rows of a streamed tile,
+    "max_splits" = the largest item_splits."""
+    n = int(_lib.lib().rm_topk_ip_tile(int(H), TOPK_TILE[which]))
+    if n < 0:
+        raise ValueError(f"topk_ip: H={H} unsupported ({TOPK_LIMITS})")
+    return n
+
+
+def topk_ip_workspace(Nq, N, H, k):
+    """Floats of workspace for topk_ip over Nq queries and N catalogue rows (rm_topk_ip_workspace; any item_splits).
+    Linear in Nq: a caller with many queries bounds it by processing them in groups."""
+    n = int(_lib.lib().rm_topk_ip_workspace(int(Nq), int(N), int(H), int(k)))
+    if n < 0:
+        raise ValueError(f"topk_ip: Nq={Nq}, N={N}, H={H}, k={k} unsupported ({TOPK_LIMITS})")
+    return n
+
+
+def _sorted_exclusions(exclude, Nq):
+    """(offsets [Nq + 1], rows [nnz]) int64 device tensors -> the same CSR with every query's rows ascending, or
+    (None, None) when it holds no row."""
+    if exclude is None:
+        return None, None
+    offsets, rows = exclude
+    _chk(offsets, "exclude offsets", I64, (Nq + 1,))
+    _chk(rows, "exclude rows", I64)
+    if rows.dim() != 1 or rows.numel() == 0:
+        if rows.dim() != 1:
+            raise ValueError(f"exclude rows: expected a 1-D tensor, got {tuple(rows.shape)}")
+        return None, None
+    counts = offsets[1:] - offsets[:-1]
+    if bool((counts < 0).any()) or int(offsets[0]) != 0 or int(offsets[-1]) != rows.numel():
+        raise ValueError("exclude: offsets must rise from 0 to the number of rows")
+    seg = torch.repeat_interleave(torch.arange(Nq, device=rows.device), counts)
+    by_row = torch.sort(rows, stable=True).indices
+    by_seg = torch.sort(seg[by_row], stable=True).indices
+    return offsets, rows[by_row][by_seg].contiguous()
+
+
+def topk_ip(Q, C, k, scale, out_rows, out_scores, workspace, *, exclude=None, item_splits=0):
+    """rm_topk_ip: per query row i of Q [Nq, H] the best min(k, available) rows j of the catalogue C [N, H] by
+    s_ij = fl(scale <Q_i, C_j>) (fp32, the same value for a pair wherever it is computed), sorted by score descending,
+    then row ascending, NaN last -> out_rows int64 / out_scores float32 [Nq, >= k] with one row stride (columns past k
+    untouched; slots past the available rows hold -1 / -inf).  Q and C may be column ranges of wider buffers.
+    exclude: None or (offsets [Nq + 1], rows) int64 device tensors, the catalogue rows query i must not get back
+    (sorted here; rows outside [0, N) are ignored, duplicates allowed).  item_splits: 0 = the library's choice; the
+    result is the same bits for every split count.  The limits are checked by the library."""
+    if Q.dim() != 2 or C.dim() != 2 or Q.shape[1] != C.shape[1]:
+        raise ValueError(f"topk_ip: Q {tuple(Q.shape)} and C {tuple(C.shape)} must be [Nq, H] and [N, H]")
+    Nq, N, H = int(Q.shape[0]), int(C.shape[0]), int(Q.shape[1])
+    pq, ldq = _strided_rows(Q, "Q", Nq, H, True)
+    pc, ldc = _strided_rows(C, "C", N, H, True)
+    for t, name, dt in ((out_rows, "out_rows", I64), (out_scores, "out_scores", F32)):
+        if not t.is_cuda or t.dtype != dt or t.dim() != 2 or t.shape[0] != Nq or t.shape[1] < k or \
+                (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"topk_ip: {name} must be a {dt} device tensor [{Nq}, >= {k}] with unit column stride, "
+                             f"got {t.dtype} {tuple(t.shape)}")
+    ldo = out_rows.stride(0) if Nq > 1 else int(k)
+    if Nq > 1 and out_scores.stride(0) != ldo:
+        raise ValueError(f"topk_ip: out_rows and out_scores must share one row stride ({ldo} != "
+                         f"{out_scores.stride(0)})")
+    _need_workspace("topk_ip", workspace, topk_ip_workspace(Nq, N, H, k) if topk_ip_supported(H, k) else 0)
+    eo, er = _sorted_exclusions(exclude, Nq)
+    _lib.call("rm_topk_ip", pq, ldq, pc, ldc, Nq, N, H, float(scale), int(k),
+              None if eo is None else eo.data_ptr(), None if er is None else er.data_ptr(), int(item_splits),
+              out_rows.data_ptr(), out_scores.data_ptr(), int(ldo), _chk(workspace, "workspace", F32), _stream())

@@ -37,12 +37,16 @@ class TwoTower(DeepModel):
     item (item_id_feature) from its softmax; logq_correction subtracts log q(item) from the scores, with q estimated
     from the training frame by fit(): logq[id] = log((count[id] + 1) / (N + V)).
     predict(X) returns the [N] scores of the rows' own pairs (no logQ, no sigmoid); user_embeddings(X) /
-    item_embeddings(X) return [N, H] from a frame that holds only that tower's columns - feed them to whatever
-    nearest-neighbour index you use; evaluate(X, y=None) returns [in-batch loss, recall@k for k in recall_at] (named
-    in `metric_names`).
+    item_embeddings(X) return [N, H] from a frame that holds only that tower's columns; evaluate(X, y=None) returns
+    [in-batch loss, recall@k for k in recall_at] (named in `metric_names`).
+
+    Retrieval: index_items(X_items) keeps the item tower's embeddings of a catalogue on the GPU; retrieve(X_users, k)
+    returns the exact top-k catalogue rows and scores <u, v> / temperature of every user row (csrc/topk.hip);
+    evaluate_catalogue(X, y=None) returns recall@k against the whole catalogue (named in `catalogue_metric_names`),
+    which, unlike evaluate(), depends on neither batch_size nor row order.
 
     Out of scope: row sharding and multi-rank training, cross-device negatives, a learnable temperature, sampled or
-    hard negatives beyond the batch, approximate or brute-force top-k search over an item catalogue, a bf16x6
+    hard negatives beyond the batch, approximate top-k indexes (IVF, HNSW), quantised catalogues, a bf16x6
     split-operand form of the score products, dropout inside the towers, sequence features (SequenceFeat raises: its
     query would cross the towers), strict_reference, feeder="pinned".  The TF-only arguments are stored and used
     nowhere."""
@@ -73,6 +77,8 @@ class TwoTower(DeepModel):
         DeepModel.__init__(self, feat_dict, hp, metrics=[], epoch=epoch, batch_size=batch_size,
                            random_seed=random_seed, task="classification", strict_reference=False, device=device)
         self.metric_names = ["inbatch_loss"] + [f"recall@{k}" for k in self._recall_ks]
+        self.catalogue_metric_names = [f"catalogue_recall@{k}" for k in self._recall_ks]
+        self._index = None  # index_items(): the catalogue's embeddings [N, H] on the GPU and its item ids
         # TF-only knobs are accepted and ignored
         self.eval_metric, self.what_means_greater, self.use_interactive_session, self.log_dir = (
             eval_metric, what_means_greater, use_interactive_session, log_dir)
@@ -125,7 +131,8 @@ class TwoTower(DeepModel):
                 torch.from_numpy(np.ascontiguousarray(inp.dense)).to(dev), mv)
 
     # ----------------------------------------------------------------- predict
-    def _embeddings(self, X, side):
+    def _embeddings(self, X, side, on_device=False):
+        """[N, H] float32 of one tower: host numpy, or with on_device a device tensor."""
         e = self._build()
         own = set(self.hparams[f"{side}_features"])
         if all(f in X for f in self.feat_dict):
@@ -137,11 +144,15 @@ class TwoTower(DeepModel):
                 raise KeyError(f"TwoTower.{side}_embeddings: the frame lacks the {side} features {missing}")
             idx, dense, mv_host = self._encode_side(X, side)
         n = idx.shape[0]
-        out = np.empty((n, e.H), dtype=np.float32)
+        out = torch.empty((n, e.H), dtype=torch.float32, device=e.device) if on_device else \
+            np.empty((n, e.H), dtype=np.float32)
         for s in range(0, n, self.batch_size):
             t = min(s + self.batch_size, n)
             emb = e.embeddings(side, idx[s:t].contiguous(), dense[s:t].contiguous(), mv=self._mv_batch(mv_host, s, t))
-            out[s:t] = emb.cpu().numpy()
+            if on_device:
+                out[s:t].copy_(emb)
+            else:
+                out[s:t] = emb.cpu().numpy()
         return out
 
     def user_embeddings(self, X):
@@ -152,6 +163,89 @@ class TwoTower(DeepModel):
     def item_embeddings(self, X):
         """The item tower's embeddings [N, H] float32.  X needs the item features only; only the item tower runs."""
         return self._embeddings(X, "item")
+
+    # --------------------------------------------------------------- retrieval
+    def index_items(self, X_items):
+        """Runs the item tower over the catalogue X_items (a frame with the item features; the item_id_feature
+        column too when it is set) and keeps its embeddings [N, H] on the GPU, with the encoded item ids: the index
+        retrieve() and evaluate_catalogue() search.  Catalogue row j is row j of X_items.  fit(), fit_on_batch() and
+        restore() drop the index (its embeddings would be stale).  -> self."""
+        idf = self.hparams.get("item_id_feature")
+        ids = None
+        if idf:
+            if idf not in X_items:
+                raise KeyError(f"TwoTower.index_items: the frame lacks the item_id_feature column {idf!r}")
+            f = self.feat_dict[idf]
+            ids = np.asarray(f(X_items[f.name])).reshape(-1).astype(np.int64)
+        emb = self._embeddings(X_items, "item", on_device=True)
+        self._index = dict(emb=emb, item_id=ids)
+        return self
+
+    def _need_index(self, what):
+        if self._index is None:
+            raise RuntimeError(f"TwoTower.{what}: no item index - call index_items(X_items) first (after fit() or "
+                               "restore(), which drop it)")
+        return self._index
+
+    @staticmethod
+    def _exclusions(exclude, s, t, dev):
+        """Rows [s, t) of `exclude` (one iterable of catalogue rows per query row) as a device CSR."""
+        lists = [np.asarray(list(r), dtype=np.int64).reshape(-1) for r in exclude[s:t]]
+        offsets = np.concatenate([[0], np.cumsum([len(r) for r in lists])]).astype(np.int64)
+        rows = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        return torch.from_numpy(offsets).to(dev), torch.from_numpy(rows.astype(np.int64)).to(dev)
+
+    def _retrieve_rows(self, X_users, k, exclude, what):
+        """Host (rows, scores) [n, k] of retrieve(); the argument errors raise before any GPU work."""
+        index = self._need_index(what)
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError(f"TwoTower.{what}: k={k} must be in 1..1024")
+        if exclude is not None and len(exclude) != len(X_users):
+            raise ValueError(f"TwoTower.{what}: exclude holds {len(exclude)} lists for {len(X_users)} rows")
+        e = self._build()
+        u = self._embeddings(X_users, "user", on_device=True)
+        n = u.shape[0]
+        rows, scores = np.empty((n, k), np.int64), np.empty((n, k), np.float32)
+        for s in range(0, n, self.batch_size):
+            t = min(s + self.batch_size, n)
+            ex = None if exclude is None else self._exclusions(exclude, s, t, e.device)
+            r, sc = e.topk(u[s:t], index["emb"], k, exclude=ex)
+            rows[s:t], scores[s:t] = r.cpu().numpy(), sc.cpu().numpy()
+        return rows, scores
+
+    def retrieve(self, X_users, k, exclude=None):
+        """The exact top-k of the indexed catalogue for every row of X_users (a frame with the user features):
+        -> (rows int64 [n, k], scores float32 [n, k]), the catalogue rows sorted by score <u, v> / temperature (no
+        logQ) descending, then by row; row -1 and score -inf past the available rows.  exclude: None or one iterable
+        of catalogue rows per user row, rows that row must not get back.  Works in batches of batch_size; the
+        result does not depend on it."""
+        return self._retrieve_rows(X_users, k, exclude, "retrieve")
+
+    def evaluate_catalogue(self, X, y=None, exclude=None):
+        """[recall@k for k in recall_at] (`catalogue_metric_names`) against the whole indexed catalogue: row i of X
+        (user features and the item_id_feature column) is a hit at k when one of its top-k catalogue rows carries the
+        row's own item id; rows with y == 0 are not counted (0 when none is).  exclude as for retrieve().  Unlike
+        evaluate(), the value depends on neither batch_size nor row order."""
+        idf = self.hparams.get("item_id_feature")
+        if not idf:
+            raise ValueError("TwoTower.evaluate_catalogue: needs item_id_feature (a hit is a retrieved row with the "
+                             "row's own item id)")
+        index = self._need_index("evaluate_catalogue")
+        if idf not in X:
+            raise KeyError(f"TwoTower.evaluate_catalogue: the frame lacks the item_id_feature column {idf!r}")
+        n = len(X)
+        live = np.ones(n, dtype=bool) if y is None else self._weights(y, n) > 0
+        f = self.feat_dict[idf]
+        own = np.asarray(f(X[f.name])).reshape(-1).astype(np.int64)
+        kmax = max(self._recall_ks)
+        rows, _ = self._retrieve_rows(X, kmax, exclude, "evaluate_catalogue")
+        ids = np.where(rows >= 0, index["item_id"][np.clip(rows, 0, None)], -1)
+        hit = ids == own[:, None]
+        W = int(live.sum())
+        if W == 0:
+            return [0.0] * len(self._recall_ks)
+        return [float(hit[live, :k].any(axis=1).sum()) / W for k in self._recall_ks]
 
     def _evaluate_encoded(self, idx, dense, mv_host, w):
         """[in-batch loss, recall@k ..] over batches of batch_size in order; w: host float32 weights or None."""
@@ -226,3 +320,11 @@ class TwoTower(DeepModel):
     def fit_on_batch(self, X, y=None):
         idx, dense, yt = self._encode(X, y)
         return self._fit_encoded(idx, dense, yt, self._mv_batch(self._mv_host, 0, idx.shape[0]))
+
+    def _fit_encoded(self, idx, dense, yt, mv=None):
+        self._index = None  # the towers change: the catalogue's embeddings would be stale
+        return DeepModel._fit_encoded(self, idx, dense, yt, mv)
+
+    def restore(self, path="ckpt_model.pt"):
+        self._index = None
+        return DeepModel.restore(self, path)
