@@ -1,4 +1,5 @@
-"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h and include/recman_hip_topk.h).
+"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h, include/recman_hip_topk.h and
+include/recman_hip_multitask.h).
 
 There is NO fallback: if the library is missing or a symbol does not resolve the
 import raises, and every call that returns a non-zero code raises RecmanHipError
@@ -223,6 +224,17 @@ SIGNATURES_TOPK = {
 }
 
 
+# name -> (restype, argtypes): the entry points of include/recman_hip_multitask.h, in its order
+SIGNATURES_MULTITASK = {
+    "rm_cgc_mix_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "rm_cgc_mix_tile": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rm_cgc_mix_fwd": (c_int, [P, I64, P, I64, I64, c_int, c_int, c_int, c_int, c_int, P, I64, P, I64, P]),
+    "rm_cgc_mix_bwd": (c_int, [P, I64, P, I64, P, I64, I64, c_int, c_int, c_int, c_int, c_int, P, I64, P, I64, P]),
+    "rm_multitask_loss_es_workspace": (c_int64, [I64, c_int]),
+    "rm_multitask_loss_es": (c_int, [P, P, P, P, c_float, I64, c_int, c_int, c_int, P, P, P, P, P, P, P]),
+}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RecmanHipError(
@@ -243,10 +255,11 @@ def _load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = c_int
-    for name, (restype, argtypes) in SIGNATURES_TOPK.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
+    for table in (SIGNATURES_TOPK, SIGNATURES_MULTITASK):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = restype
     return lib
 
 

@@ -2843,6 +2843,31 @@ class MaskNetEngine(Engine):
              lambda: ops.masknet_row_fwd(self.Z[0], g1, b1, h), 4.0 * (2 * B * H + 2 * H), "hbm"))
 
 
+def entire_space_pair(hp, names, types):
+    """hp["entire_space"] = (ctr task, cvr task) -> their indices (c, v) for rm_multitask_loss_es; (-1, -1) without
+    it.  A ValueError unless it names two distinct classification tasks (ESMM, Ma et al., SIGIR 2018)."""
+    es = hp.get("entire_space")
+    if es is None:
+        return (-1, -1)
+    es = tuple(es) if isinstance(es, (list, tuple)) else (es,)
+    if (len(es) != 2 or es[0] == es[1] or any(n not in names for n in es)
+            or any(types[names.index(n)] != "classification" for n in es)):
+        raise ValueError(f"MMoE: entire_space={hp.get('entire_space')!r} must name two distinct classification tasks "
+                         f"of task_names {names!r}: (the click task, the conversion task)")
+    return names.index(es[0]), names.index(es[1])
+
+
+def _multitask_loss_step(e, y):
+    """The loss head of a training step of a multi-task engine `e` on labels y [B, T]: rm_multitask_loss, or - with
+    hp["entire_space"] - rm_multitask_loss_es."""
+    kw = dict(Y=y, task_weights=e.task_weights, grad_scale=e.grad_scale, dlogit=e.dlogit, n_t=e.n_t, loss_t=e.loss_t,
+              loss=e.loss, workspace=e.loss_ws)
+    if e.es == (-1, -1):
+        ops.multitask_loss(e.logit, e.task_types, e.pred, **kw)
+    else:
+        ops.multitask_loss_es(e.logit, e.task_types, e.pred, es=e.es, **kw)
+
+
 def mmoe_limits(hp):
     """MMoE's limits in one place (th.MMoE checks them at construction, MMoEEngine when it is built): a ValueError
     naming the limit, or (task_names, task_types, task_weights, num_experts, expert_hidden_units, tower_hidden_units)."""
@@ -2883,6 +2908,7 @@ class MMoEEngine(Engine):
         mixture:        M_t = sum_e p_te Z_e                                              (csrc/mmoe.hip)
         towers:         logit_t = DNN_t(M_t), tower_hidden_units + the output projection
         loss = sum_t w_t * mean over the examples whose label t is observed (not NaN) of l_t  + the l2 terms
+               (hp["entire_space"] = (ctr task, cvr task): the cvr task through pred_ctr pred_cvr, rm_multitask_loss_es)
     num_experts = 1 is the shared-bottom model.  Layout: the experts are STACKED - layer l of all experts is one
     [B, E H_l] buffer, expert e at columns e H_l ..; layer 0 is one GEMM over x, deeper layers run per expert on the
     column ranges; all gates are one GEMM x -> [B, T E]; M is one [B, T H] buffer whose column range t the tower of
@@ -2903,6 +2929,7 @@ class MMoEEngine(Engine):
         self.use_linear = False
         (self.task_names, self.task_types, self.task_weights, self.NE, self.expert_units,
          self.tower_units) = mmoe_limits(hp)
+        self.es = entire_space_pair(hp, self.task_names, self.task_types)
         if hp.get("strict_reference"):
             raise NotImplementedError("MMoE: strict_reference reproduces quirks of the reference, which has no "
                                       "multi-task model")
@@ -3018,9 +3045,7 @@ class MMoEEngine(Engine):
             raise ValueError(f"MMoE: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
                              f"{tuple(y.shape)}")
         self._model_fwd(idx, dense)
-        ops.multitask_loss(self.logit, self.task_types, self.pred, Y=y, task_weights=self.task_weights,
-                           grad_scale=self.grad_scale, dlogit=self.dlogit, n_t=self.n_t, loss_t=self.loss_t,
-                           loss=self.loss, workspace=self.loss_ws)
+        _multitask_loss_step(self, y)
         p, g, NE, T, H = self.params, self.grads, self.NE, self.T, self.H
         ident = self.act == "identity"
         for t, tw in enumerate(self.towers):
@@ -3059,6 +3084,292 @@ class MMoEEngine(Engine):
         """The gate weights p [B, T, E] of a batch (an inference forward with rm_mmoe_mix_fwd's optional output)."""
         self.forward(idx, dense, mv=mv, gate_weights=True)
         return self.P.reshape(idx.shape[0], self.T, self.NE)
+
+
+def ple_limits(hp):
+    """PLE's limits in one place (th.MMoE checks them at construction, PLEEngine when it is built): a ValueError naming
+    the limit, or (task_names, task_types, task_weights, task_experts S, shared experts C, num_levels L,
+    expert_hidden_units, tower_hidden_units).  The tasks and the units are under mmoe_limits."""
+    names, types, weights, _, experts, towers = mmoe_limits({**hp, "num_experts": 1})
+    S, C, L = hp.get("task_experts", 0), hp.get("num_experts", 2), hp.get("num_levels", 1)
+    limits = ("PLE: task_experts 1..4 per task, num_experts (the shared experts of a level) 1..8, "
+              "tasks x task_experts + num_experts <= 32, num_levels 1..4; task_experts=0 with num_levels=1 is MMoE")
+    if not isinstance(L, int) or isinstance(L, bool) or not 1 <= L <= 4:
+        raise ValueError(f"MMoE: num_levels={L!r} ({limits})")
+    if not isinstance(S, int) or isinstance(S, bool) or not 1 <= S <= 4:
+        raise ValueError(f"MMoE: task_experts={S!r} with num_levels={L!r} ({limits})")
+    if not isinstance(C, int) or isinstance(C, bool) or not 1 <= C <= 8:
+        raise ValueError(f"MMoE: num_experts={C!r} with task_experts={S!r} ({limits})")
+    if len(names) * S + C > 32:
+        raise ValueError(f"MMoE: {len(names)} tasks x task_experts={S} + num_experts={C} = {len(names) * S + C} "
+                         f"experts per level ({limits})")
+    return names, types, weights, S, C, L, experts, towers
+
+
+class PLEEngine(Engine):
+    """Progressive Layered Extraction (PLE, Tang et al., RecSys 2020; one level is CGC, Customized Gate Control): T
+    tasks over one set of embedding tables, with task-specific experts beside the shared ones and L = num_levels
+    extraction levels.  Nothing in the reference implements it.  Streams s = 0..T-1 are the tasks', s = T the shared
+    one; X_s^0 = x = [E | dense] [B, K0], never concatenated.  Per level l, N = T S + C experts (S per task, then C
+    shared), group s = the experts of stream s:
+        experts of group s:  a DNN of expert_hidden_units over X_s^l (bias, deep_activation)  ->  Z^l [B, N H]
+        gates g:             A_g = X_g^l G_g^l (no bias); task gate t over its own S experts and the C shared ones,
+                             and - on every level but the last - the shared gate g = T over all N
+        mixture:             X_g^{l+1} = M_g = sum_e p_ge Z_e, p_g = softmax(A_g)                  (csrc/ple.hip)
+        towers:              logit_t = DNN_t(X_t^L), tower_hidden_units + the output projection
+        loss: MMoEEngine's; with hp["entire_space"] = (ctr task, cvr task) the cvr task is trained through
+              pred_ctr pred_cvr over all impressions (rm_multitask_loss_es)
+    Layout: the experts of a level are STACKED as in MMoEEngine - layer k of all experts is one [B, N H_k] buffer,
+    expert e at columns e H_k ..  Level 0: layer 0 is one GEMM over x, all gates are one GEMM.  Levels >= 1: the
+    experts and the gate of stream s read column range s of the previous level's M in place - one GEMM per group for
+    layer 0, one per gate.  Deeper layers run per expert on the column ranges.  In the backward dX_s^l is the sum of
+    the input gradients of group s's experts and of gate s: the second GEMM adds the first one's result in its
+    epilogue.  The gate weights p never reach HBM in training.
+    Variables (names chosen here), per level l with K = K0 at level 0 and H above:
+        level_{l}_expert_layer_0_weights [K, N H_1] / _bias [N H_1] (expert e at columns e H_1 ..);
+        level_{l}_expert_layer_{k}_weights [N, H_k, H_{k+1}] / _bias [N, H_{k+1}] for k >= 1;
+        level_{l}_gate_weights [K, T (S + C) + shared_gate N] (rm_cgc_mix_fwd's layout of A);
+        per task the tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".
+    Every matrix is glorot with the fans of ONE expert or gate (a gate's fan-out is S + C) and under deep_l2_reg;
+    biases start at zero.  No bias tables, no linear term, no dropout, one GPU.  logit / pred / dlogit are [T, B]."""
+
+    model = "ple"
+    use_bias_tables = False
+    shardable = False
+
+    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
+        super().__init__(spec, embedding_size, hp, task, device)
+        self.use_linear = False
+        (self.task_names, self.task_types, self.task_weights, self.S, self.C, self.L, self.expert_units,
+         self.tower_units) = ple_limits(hp)
+        self.es = entire_space_pair(hp, self.task_names, self.task_types)
+        if hp.get("strict_reference"):
+            raise NotImplementedError("PLE: strict_reference reproduces quirks of the reference, which has no "
+                                      "multi-task model")
+        for key in ("deep_dropout", "expert_dropout", "tower_dropout"):
+            keep = hp.get(key)
+            if keep is not None and any(float(k) != 1.0 for k in keep):
+                raise NotImplementedError(f"PLE: {key}={keep!r}: the experts and towers run without dropout")
+        T, S, C, L = len(self.task_names), self.S, self.C, self.L
+        self.T, self.H, self.N, self.W = T, self.expert_units[-1], T * S + C, S + C
+        if not ops.cgc_mix_supported(T, S, C, self.H, 1):
+            raise ValueError(f"PLE: {T} tasks, {S} task experts, {C} shared experts, expert width {self.H} are not "
+                             f"supported by rm_cgc_mix_fwd ({ops.CGC_LIMITS})")
+        self.act = act_name(hp.get("deep_activation", "relu"))
+        self.dense_gemm = hp.get("dense_gemm", "bf16x6")
+        K0, N, H, units = self.FD + self.Dn, self.N, self.H, self.expert_units
+        self.K0 = K0
+        self._gemms = []
+        for l in range(L):
+            K, AW = (K0 if l == 0 else H), self._aw(l)
+            self._var(f"level_{l}_expert_layer_0_weights", (K, N * units[0]), ("glorot", K, units[0]), "deep_l2_reg")
+            self._var(f"level_{l}_expert_layer_0_bias", (N * units[0],))
+            for k in range(1, len(units)):
+                self._var(f"level_{l}_expert_layer_{k}_weights", (N, units[k - 1], units[k]),
+                          ("glorot", units[k - 1], units[k]), "deep_l2_reg")
+                self._var(f"level_{l}_expert_layer_{k}_bias", (N, units[k]))
+            self._var(f"level_{l}_gate_weights", (K, AW), ("glorot", K, self.W), "deep_l2_reg")
+            # the GEMM shapes (K, N) of this level: the workspaces are sized for the largest
+            self._gemms += [(K, N * units[0]), (K, AW)] + [(units[k - 1], units[k]) for k in range(1, len(units))]
+        self.towers = [self._dnn(H, 0, self.tower_units, "relu", prefix=f"{n}_", stream_d_rows=False)
+                       for n in self.task_names]
+
+    # ------------------------------------------------------------------ the layout of a level
+    def _sg(self, l):
+        """shared_gate of level l: every level but the last."""
+        return int(l < self.L - 1)
+
+    def _aw(self, l):
+        return ops.cgc_widths(self.T, self.S, self.C, self._sg(l))[1]
+
+    def _group(self, s, h):
+        """The columns of group s (a task's experts, s = T: the shared ones) in a stacked buffer of expert width h."""
+        first = s * self.S
+        return first * h, (first + (self.S if s < self.T else self.C)) * h
+
+    def _gate(self, g):
+        """The columns of gate g (g = T: the shared gate) in A."""
+        return (g * self.W, (g + 1) * self.W) if g < self.T else (self.T * self.W, self.T * self.W + self.N)
+
+    def _stream(self, buf, s):
+        return buf[:, s * self.H: (s + 1) * self.H]
+
+    @staticmethod
+    def _ws6(ws6, *operands):
+        """The split-operand GEMMs load and store whole float4s of their activation, gradient and output rows: they
+        take only 16-byte aligned column ranges (with S + C no multiple of 4 a gate starts unaligned in A; it runs on
+        the plain kernels).  The weights are read, and their gradients written, element by element on both paths."""
+        ok = all(t is None or (t.data_ptr() % 16 == 0 and (t.dim() < 2 or t.stride(0) % 4 == 0 or t.shape[0] == 1))
+                 for t in operands)
+        return ws6 if ok else None
+
+    def _alloc_model(self, B):
+        dev, N, T, H, L = self.device, self.N, self.T, self.H, self.L
+        buf = lambda *shape: torch.empty(*shape, dtype=F32, device=dev)  # noqa: E731
+        pad4 = lambda n: (n + 3) // 4 * 4  # noqa: E731  (the mixture kernels take rows of whole float4s)
+        # per level: the stacked expert activations (Z = ha[l][-1]) and dLoss/d(pre-activation) of the same
+        self.ha = [[buf(B, N * h) for h in self.expert_units] for _ in range(L)]
+        self.dha = [[buf(B, N * h) for h in self.expert_units] for _ in range(L)]
+        self.A = [buf(B, pad4(self._aw(l)))[:, : self._aw(l)] for l in range(L)]
+        self.dA = [buf(B, pad4(self._aw(l)))[:, : self._aw(l)] for l in range(L)]
+        self.M = [buf(B, (T + self._sg(l)) * H) for l in range(L)]
+        self.dM = [buf(B, (T + self._sg(l)) * H) for l in range(L)]
+        self.P = None                                            # gate weights of one level: made by gate_weights()
+        self.dx = buf(B, self.FD)
+        self.dxg = buf(B, H)                                     # a gate's input gradient, before its experts' is added
+        self.logit, self.pred, self.dlogit = buf(T, B), buf(T, B), buf(T, B)
+        self.n_t = torch.zeros(T, dtype=I64, device=dev)
+        self.loss_t = torch.zeros(T, dtype=F32, device=dev)
+        self.loss_ws = buf(ops.multitask_loss_es_workspace(B, T))
+        # a tower on the fused skinny-MLP kernels reads and writes contiguous rows: its own copy of M_t / dM_t
+        copies = T > 1
+        self.Mc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
+        self.dMc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
+        for t, tw in enumerate(self.towers):
+            tw._alloc(B, dev)
+            tw.out = self.logit[t].view(B, 1)  # the tower's logit lands in its row of the [T, B] buffer
+        side = max(d for kn in self._gemms for d in kn)
+        self._fws = buf(max(ops.dense_filter_workspace(max(k, n), max(k, n)) for k, n in self._gemms))
+        self._wws = buf(max(1, max(ops.dense_wgrad_workspace(k, n, B) for k, n in self._gemms)))
+        self._fws6 = self._wws6 = None
+        if self.dense_gemm == "bf16x6":
+            self._fws6 = buf(ops.dense6_workspace(side, side, B))
+            self._wws6 = buf(max(ops.dense_wgrad6_workspace(k, n, B) for k, n in self._gemms))
+
+    def _fwd(self, a1, a2, W, out, **kw):
+        ops.dense_fwd(a1, a2, W, out, self._fws, ws6=self._ws6(self._fws6, a1, out, kw.get("aux1")), **kw)
+
+    def _wgrad(self, a1, a2, G, dW, db=None):
+        ops.dense_wgrad(a1, a2, G, dW, self._wws, db=db, ws6=self._ws6(self._wws6, a1, G))
+
+    def _tower_in(self, t):
+        M_t = self._stream(self.M[-1], t)
+        if self.Mc[t] is None:
+            return M_t
+        self.Mc[t].copy_(M_t)
+        return self.Mc[t]
+
+    def _model_fwd(self, idx, dense, p_level=None):
+        """Embedding lookup, the extraction levels and the towers: self.logit [T, B].  p_level: the level whose gate
+        weights go to self.P."""
+        if self.spec.Dn and dense is None:
+            raise ValueError("PLE: the dense features are missing")
+        self._embed(idx, dense, False, {}, None)
+        p, T, S, C, units = self.params, self.T, self.S, self.C, self.expert_units
+        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
+        for l in range(self.L):
+            sg, ha = self._sg(l), self.ha[l]
+            W0, b0, Gw = (p[f"level_{l}_expert_layer_0_weights"], p[f"level_{l}_expert_layer_0_bias"],
+                          p[f"level_{l}_gate_weights"])
+            if l == 0:
+                self._fwd(xe, xd, W0, ha[0], bias=b0, act=self.act)
+                self._fwd(xe, xd, Gw, self.A[0], act="identity")
+            else:
+                X = self.M[l - 1]
+                for s in range(T + 1):
+                    c0, c1 = self._group(s, units[0])
+                    self._fwd(self._stream(X, s), None, W0[:, c0:c1], ha[0][:, c0:c1], bias=b0[c0:c1], act=self.act)
+                for g in range(T + sg):
+                    a0, a1 = self._gate(g)
+                    self._fwd(self._stream(X, g), None, Gw[:, a0:a1], self.A[l][:, a0:a1], act="identity")
+            for k in range(1, len(units)):
+                W, b = p[f"level_{l}_expert_layer_{k}_weights"], p[f"level_{l}_expert_layer_{k}_bias"]
+                for e in range(self.N):
+                    self._fwd(ha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]], None, W[e],
+                              ha[k][:, e * units[k]: (e + 1) * units[k]], bias=b[e], act=self.act)
+            P = None
+            if p_level == l:
+                aw = self._aw(l)
+                self.P = P = torch.empty(idx.shape[0], (aw + 3) // 4 * 4, dtype=F32, device=self.device)[:, :aw]
+            ops.cgc_mix_fwd(ha[-1], self.A[l], T, S, C, sg, self.M[l], P=P)
+        for t, tw in enumerate(self.towers):
+            tw.forward(self._tower_in(t), None)
+
+    def forward(self, idx, dense=None, training=False, masks=None, manual_weights=None, mv=None, gate_level=None):
+        """-> (logit [T, B], pred [T, B]); pred_t = sigmoid(logit_t) for a classification task, logit_t for a
+        regression task.  gate_level = l also leaves the gate weights of level l in self.P (A's layout)."""
+        if manual_weights is not None:
+            raise NotImplementedError("PLE has no linear term: manual feature weights do not apply")
+        self._alloc(idx.shape[0])
+        self._mv = mv
+        self._seq_save = bool(training)
+        self._model_fwd(idx, dense, p_level=gate_level)
+        ops.multitask_loss(self.logit, self.task_types, self.pred)
+        return self.logit, self.pred
+
+    def fwd_bwd(self, idx, dense, y, masks=None, mv=None):
+        """One training step's forward + backward on labels y [B, T] (float32, NaN = unobserved).  Returns the loss
+        tensor [1] (the weighted task losses + the l2 terms); self.loss_t [T] and self.n_t [T] hold the tasks' mean
+        losses and observed counts.  Gradients: self.grads, self.d_rows [B,F,D] + idx."""
+        B = idx.shape[0]
+        self._alloc(B)
+        self._mv = mv
+        self._seq_save = True
+        if y.dtype != F32 or tuple(y.shape) != (B, self.T):
+            raise ValueError(f"PLE: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
+                             f"{tuple(y.shape)}")
+        self._model_fwd(idx, dense)
+        _multitask_loss_step(self, y)
+        p, g, T, S, C, units = self.params, self.grads, self.T, self.S, self.C, self.expert_units
+        ident = self.act == "identity"
+        for t, tw in enumerate(self.towers):
+            dM_t = self._stream(self.dM[-1], t)
+            if self.dMc[t] is None:
+                tw.backward(self.dlogit[t], dM_t)
+            else:
+                tw.backward(self.dlogit[t], self.dMc[t])
+                dM_t.copy_(self.dMc[t])
+        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
+        for l in range(self.L - 1, -1, -1):
+            sg, ha, dha, dA = self._sg(l), self.ha[l], self.dha[l], self.dA[l]
+            ops.cgc_mix_bwd(ha[-1], self.A[l], T, S, C, sg, self.dM[l], dha[-1], dA)
+            if not ident:
+                ops.act_bwd_(dha[-1], ha[-1], self.act)
+            for k in range(len(units) - 1, 0, -1):
+                W = p[f"level_{l}_expert_layer_{k}_weights"]
+                gW, gb = g[f"level_{l}_expert_layer_{k}_weights"], g[f"level_{l}_expert_layer_{k}_bias"]
+                for e in range(self.N):
+                    prev = ha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]]
+                    da = dha[k][:, e * units[k]: (e + 1) * units[k]]
+                    self._wgrad(prev, None, da, gW[e], db=gb[e])
+                    self._fwd(da, None, W[e], dha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]],
+                              transposed=True, epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD,
+                              act=self.act, aux1=None if ident else prev)
+            W0, Gw = p[f"level_{l}_expert_layer_0_weights"], p[f"level_{l}_gate_weights"]
+            gW0, gb0, gG = (g[f"level_{l}_expert_layer_0_weights"], g[f"level_{l}_expert_layer_0_bias"],
+                            g[f"level_{l}_gate_weights"])
+            if l == 0:
+                self._wgrad(xe, xd, dha[0], gW0, db=gb0)
+                self._wgrad(xe, xd, dA, gG)
+                # dLoss/dx of the gates and of the experts, summed into d_rows (the dense inputs need no gradient)
+                self._fwd(dA, None, Gw[: self.FD], self.dx, transposed=True, epilogue=ops.DENSE_ADD)
+                self._fwd(dha[0], None, W0[: self.FD], self.d_rows.view(-1, self.FD), transposed=True,
+                          epilogue=ops.DENSE_ADD, aux1=self.dx)
+                continue
+            X, dX = self.M[l - 1], self.dM[l - 1]
+            for s in range(T + 1):
+                xs, dxs = self._stream(X, s), self._stream(dX, s)
+                c0, c1 = self._group(s, units[0])
+                das = dha[0][:, c0:c1]
+                self._wgrad(xs, None, das, gW0[:, c0:c1], db=gb0[c0:c1])
+                gated = s < T + sg  # (on the last level the shared stream has experts and no gate)
+                if gated:
+                    a0, a1 = self._gate(s)
+                    self._wgrad(xs, None, dA[:, a0:a1], gG[:, a0:a1])
+                    self._fwd(dA[:, a0:a1], None, Gw[:, a0:a1], self.dxg, transposed=True, epilogue=ops.DENSE_ADD)
+                # dX_s = the experts' input gradient (+ the gate's, added in the epilogue)
+                self._fwd(das, None, W0[:, c0:c1], dxs, transposed=True, epilogue=ops.DENSE_ADD,
+                          aux1=self.dxg if gated else None)
+        self._add_l2_grads()
+        self._seq_bwd()
+        return self._add_l2(self.loss)
+
+    def gate_weights(self, idx, dense=None, mv=None, level=-1):
+        """The task gates' weights p [B, T, S + C] of a level of a batch (an inference forward with rm_cgc_mix_fwd's
+        optional output): per task its own S experts first, then the C shared ones."""
+        l = range(self.L)[level]
+        self.forward(idx, dense, mv=mv, gate_level=l)
+        return self.P[:, : self.T * self.W].reshape(idx.shape[0], self.T, self.W)
 
 
 def _one_run(positions, what, side):
@@ -3315,5 +3626,5 @@ class TwoTowerEngine(Engine):
 
 ENGINES = {"deepfm": DeepFMEngine, "dcn": DCNEngine, "xdeepfm": XDeepFMEngine, "afm": AFMEngine, "din": DINEngine,
            "autoint": AutoIntEngine, "dlrm": DLRMEngine, "fibinet": FiBiNETEngine, "fmfm": FmFMEngine, "pnn": PNNEngine,
-           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine, "mmoe": MMoEEngine,
+           "masknet": MaskNetEngine, "bst": BSTEngine, "dien": DIENEngine, "mmoe": MMoEEngine, "ple": PLEEngine,
            "twotower": TwoTowerEngine}

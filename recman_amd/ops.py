@@ -1914,6 +1914,113 @@ def multitask_loss(logit, task_types, pred, *, Y=None, task_weights=None, grad_s
               _chk(workspace, "workspace", F32, allow_none=True), _stream())
 
 
+# ---- multi-task learning, continued: PLE / CGC's grouped gate mixture and ESMM's entire-space loss (csrc/ple.hip) ---
+CGC_TILE = {"tile": 0, "cap": 1}  # RM_CGC_TILE / RM_CGC_CAP
+CGC_LIMITS = ("1 <= T <= 8 tasks, 1 <= S <= 4 task experts, 1 <= C <= 8 shared experts, N = T S + C <= 32, H a "
+              "multiple of 4 in 4..512, shared_gate 0 or 1, row strides multiples of 4 floats")
+CGC_H_MIN, CGC_H_MAX = 4, 512
+
+
+def cgc_mix_supported(T, S, C, H, shared_gate):
+    """rm_cgc_mix_supported: 1 <= T <= 8, 1 <= S <= 4, 1 <= C <= 8, T S + C <= 32, H a multiple of 4 in 4..512."""
+    return bool(_lib.lib().rm_cgc_mix_supported(int(T), int(S), int(C), int(H), int(shared_gate)))
+
+
+def cgc_mix_tile(T, S, C, H, shared_gate, which="tile", backward=False):
+    """rm_cgc_mix_tile: "tile" = the examples a block of the mixture kernels owns per tile, "cap" = the cap of their
+    grids (a block walks the batch again from B > cap * tile on)."""
+    n = int(_lib.lib().rm_cgc_mix_tile(int(T), int(S), int(C), int(H), int(shared_gate), int(bool(backward)),
+                                       CGC_TILE[which]))
+    if n < 0:
+        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, H={H}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
+    return n
+
+
+def cgc_widths(T, S, C, shared_gate):
+    """(N experts, gate-logit columns T (S + C) + shared_gate N, gates T + shared_gate) of one extraction level."""
+    T, S, C, sg = int(T), int(S), int(C), int(bool(shared_gate))
+    N = T * S + C
+    return N, T * (S + C) + sg * N, T + sg
+
+
+def _cgc_dims(Z, A, T, S, C, shared_gate):
+    T, S, C, sg = int(T), int(S), int(C), int(shared_gate)
+    if sg not in (0, 1) or min(T, S, C) < 1:
+        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
+    N, AW, G = cgc_widths(T, S, C, sg)
+    if Z.dim() != 2 or A.dim() != 2 or Z.shape[1] % N or A.shape[1] != AW:
+        raise ValueError(f"cgc_mix: Z {tuple(Z.shape)} must be [B, N H] and A {tuple(A.shape)} [B, T (S + C) + "
+                         f"shared_gate N] (T={T}, S={S}, C={C}, shared_gate={sg}: N={N}, {AW} gate logits)")
+    return int(Z.shape[0]), T, S, C, sg, N, AW, G, int(Z.shape[1]) // N
+
+
+def cgc_mix_fwd(Z, A, T, S, C, shared_gate, M, P=None):
+    """rm_cgc_mix_fwd: Z [B, N H] the expert outputs of a level (S own experts per task, then C shared ones), A the
+    gate logits [B, T (S + C) + shared_gate N] -> M [B, (T + shared_gate) H], M_g = softmax(A_g) over the experts gate
+    g sees, and - when given - P (A's layout), the gate weights.  Every operand may be a column range of a wider buffer
+    (16-byte aligned, row stride a multiple of 4 floats); only the own columns are written.  The limits are checked by
+    the library."""
+    B, T, S, C, sg, N, AW, G, H = _cgc_dims(Z, A, T, S, C, shared_gate)
+    pz, ldz = _strided_rows(Z, "Z", B, N * H, True)
+    pa, lda = _strided_rows(A, "A", B, AW, True)
+    pm, ldm = _strided_rows(M, "M", B, G * H, True)
+    pp, ldp = (None, 0) if P is None else _strided_rows(P, "P", B, AW, True)
+    _lib.call("rm_cgc_mix_fwd", pz, ldz, pa, lda, B, T, S, C, H, sg, pm, ldm, pp, ldp, _stream())
+
+
+def cgc_mix_bwd(Z, A, T, S, C, shared_gate, dM, dZ, dA):
+    """rm_cgc_mix_bwd: dM [B, (T + shared_gate) H] = dLoss/dM -> dZ [B, N H] and dA (A's layout), both written once
+    (column ranges as in cgc_mix_fwd).  The gate weights are recomputed.  No workspace; deterministic."""
+    B, T, S, C, sg, N, AW, G, H = _cgc_dims(Z, A, T, S, C, shared_gate)
+    pz, ldz = _strided_rows(Z, "Z", B, N * H, True)
+    pa, lda = _strided_rows(A, "A", B, AW, True)
+    pdm, lddm = _strided_rows(dM, "dM", B, G * H, True)
+    pdz, lddz = _strided_rows(dZ, "dZ", B, N * H, True)
+    pda, ldda = _strided_rows(dA, "dA", B, AW, True)
+    _lib.call("rm_cgc_mix_bwd", pz, ldz, pa, lda, pdm, lddm, B, T, S, C, H, sg, pdz, lddz, pda, ldda, _stream())
+
+
+def multitask_loss_es_workspace(B, T):
+    """Floats of workspace for multitask_loss_es (rm_multitask_loss_es_workspace)."""
+    n = int(_lib.lib().rm_multitask_loss_es_workspace(int(B), int(T)))
+    if n < 0:
+        raise ValueError(f"multitask_loss_es: B={B}, T={T} unsupported (B >= 1, 1 <= T <= 8 tasks)")
+    return n
+
+
+def multitask_loss_es(logit, task_types, pred, *, es=(-1, -1), Y=None, task_weights=None, grad_scale=1.0, dlogit=None,
+                      n_t=None, loss_t=None, loss=None, workspace=None):
+    """rm_multitask_loss_es: multitask_loss with the entire-space pair es = (c, v), two distinct classification tasks:
+    task v is trained through pred_c pred_v against z (0 where Y[:, c] == 0, Y[:, v] where Y[:, c] == 1, unobserved
+    otherwise) over all those rows, and its gradient reaches both logits.  es = (-1, -1): multitask_loss's bits."""
+    if logit.dim() != 2:
+        raise ValueError(f"logit: expected [T, B], got {tuple(logit.shape)}")
+    T, B = int(logit.shape[0]), int(logit.shape[1])
+    if len(task_types) != T:
+        raise ValueError(f"multitask_loss_es: {len(task_types)} task types for {T} rows of logits")
+    c, v = (int(i) for i in es)
+    if (c, v) != (-1, -1) and not (0 <= c < T and 0 <= v < T and c != v and task_types[c] == task_types[v]
+                                   == "classification"):
+        raise ValueError(f"multitask_loss_es: es={tuple(es)!r} must be two distinct classification tasks below T={T}, "
+                         "or (-1, -1)")
+    types = _int_array([TASK_TYPES[t] for t in task_types])
+    train = any(t is not None for t in (dlogit, n_t, loss_t, loss))
+    weights = None
+    if train:
+        if Y is None or workspace is None:
+            raise ValueError("multitask_loss_es: the loss and its gradient need labels Y and a workspace")
+        w = [1.0] * T if task_weights is None else [float(x) for x in task_weights]
+        if len(w) != T:
+            raise ValueError(f"multitask_loss_es: {len(w)} task weights for {T} tasks")
+        weights = (ctypes.c_float * T)(*w)
+        _need_workspace("multitask_loss_es", workspace, multitask_loss_es_workspace(B, T))
+    _lib.call("rm_multitask_loss_es", _chk(logit, "logit", F32), _chk(Y, "Y", F32, (B, T), allow_none=not train),
+              types, weights, float(grad_scale), B, T, c, v, _chk(pred, "pred", F32, (T, B)),
+              _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
+              _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
+              _chk(workspace, "workspace", F32, allow_none=True), _stream())
+
+
 # ---- two-tower retrieval: the in-batch softmax loss and the row normalisation (csrc/inbatch.hip) -------------------
 IBS_TILE = {"rows": 0, "cols": 1, "max_splits": 2}  # RM_IBS_ROWS / RM_IBS_COLS / RM_IBS_MAX_SPLITS
 IBS_LIMITS = "H a multiple of 4 in 4..256, row strides multiples of 4 floats, col_splits 0..8"

@@ -37,7 +37,7 @@ log = logging.getLogger(__name__)
 
 
 class DeepModel(BaseEstimator, TransformerMixin):
-    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din" | "autoint" | "dlrm" | "fibinet" | "fmfm" | "pnn" | "masknet" | "mmoe" | "twotower"
+    model = None  # "deepfm" | "dcn" | "xdeepfm" | "afm" | "din" | "autoint" | "dlrm" | "fibinet" | "fmfm" | "pnn" | "masknet" | "mmoe" | "ple" | "twotower"
 
     def __init__(self, feat_dict: FeatureDictionary, hparams: dict, metrics, epoch, batch_size=64,
                  random_seed=2019, task="classification", strict_reference=False, device="cuda"):

@@ -11,7 +11,7 @@ from .DeepFM import DeepFM
 from .FiBiNET import FiBiNET
 from .FmFM import FmFM, FwFM
 from .MaskNet import MaskNet
-from .MMoE import MMoE
+from .MMoE import MMoE, PLE
 from .PNN import PNN
 from .TwoTower import TwoTower
 from .BST import BST
@@ -24,6 +24,6 @@ from .xDeepFM import xDeepFM
 from . import hparams
 from . import layers
 
-__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "MMoE", "PNN", "TwoTower", "xDeepFM", "DataInputs",
+__all__ = ["AFM", "AutoInt", "BST", "BestModelFinder", "DCN", "DIEN", "DIN", "DLRM", "DeepFM", "DeepModel", "FiBiNET", "FmFM", "FwFM", "MaskNet", "MMoE", "PLE", "PNN", "TwoTower", "xDeepFM", "DataInputs",
            "DenseFeat", "FeatureDictionary", "MultiValCsvFeat", "ResilientLabelEncoder", "SequenceFeat", "SparseFeat", "SparseValueFeat",
            "hparams", "layers"]
