@@ -1,5 +1,5 @@
-"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h, include/recman_hip_topk.h and
-include/recman_hip_multitask.h).
+"""ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h, include/recman_hip_topk.h,
+include/recman_hip_multitask.h and include/recman_hip_rank.h).
 
 There is NO fallback: if the library is missing or a symbol does not resolve the
 import raises, and every call that returns a non-zero code raises RecmanHipError
@@ -235,6 +235,13 @@ SIGNATURES_MULTITASK = {
 }
 
 
+# name -> (restype, argtypes): the entry points of include/recman_hip_rank.h, in its order
+SIGNATURES_RANK = {
+    "rm_rank_loss_workspace": (c_int64, [I64]),
+    "rm_rank_loss": (c_int, [P, P, P, I64, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P]),
+}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RecmanHipError(
@@ -255,7 +262,7 @@ def _load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud
         fn.argtypes = argtypes
         fn.restype = c_int
-    for table in (SIGNATURES_TOPK, SIGNATURES_MULTITASK):
+    for table in (SIGNATURES_TOPK, SIGNATURES_MULTITASK, SIGNATURES_RANK):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes

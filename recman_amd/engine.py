@@ -576,6 +576,7 @@ class Engine:
         self.grad_scale = 1.0   # this batch's share of a step's gradient (micro-batches, recman_amd/dist.py)
         self._head_req = None   # fwd_bwd's offer of the fused head to the model's last DNN (_mlp_last)
         self.d_bias = None      # per-occurrence bias-table gradients [B,F] (FM bias dropout only)
+        self.rank = self._rank_objective()  # the ranking term next to the log loss (None: not configured)
         self._probe_ready = None
         self._alloc_tables()
         self._var("linear_w0", (1,))
@@ -583,6 +584,41 @@ class Engine:
         self._B = None
         self.use_linear = True
         self._init_seq()
+
+    def _rank_objective(self):
+        """hp["rank_loss"] ("pairwise" | "listwise"; None: no ranking term) with rank_norm, rank_loss_weight and the
+        group ids - hp["rank_group_col"], a column of idx, or hp["rank_group_by"], the name of a plain id feature; None:
+        the whole batch is one list - as dict(kind, norm, alpha, col).  th.DeepModel._rank_config is the checked public
+        surface; this is what an engine built directly accepts."""
+        hp = self.hp
+        kind = hp.get("rank_loss")
+        if kind is None:
+            return None
+        if self.model in ("mmoe", "ple", "twotower"):
+            raise NotImplementedError(f"rank_loss={kind!r}: {self.model} has no single logit with a 0/1 label to rank")
+        if getattr(self, "sharded", False):
+            raise NotImplementedError(f"rank_loss={kind!r} runs on one GPU: pairs across ranks or micro-batches are not "
+                                      "built; use table_sharding='none'")
+        if self.task != "classification":
+            raise ValueError(f"rank_loss={kind!r} needs 0/1 labels: the task is {self.task!r}")
+        norm, alpha = hp.get("rank_norm", "group"), float(hp.get("rank_loss_weight", 0.5))
+        if kind not in ops.RANK_KINDS or norm not in ops.RANK_NORMS or not 0 < alpha <= 1:
+            raise ValueError(f"rank_loss={kind!r}, rank_norm={norm!r}, rank_loss_weight={alpha!r}: expected "
+                             f"{sorted(ops.RANK_KINDS)}, {sorted(ops.RANK_NORMS)} and 0 < rank_loss_weight <= 1")
+        col, by = hp.get("rank_group_col"), hp.get("rank_group_by")
+        if col is None and by is not None:
+            if by not in self.spec.sparse_names or by in self.spec.scratch_names:
+                raise ValueError(f"rank_group_by={by!r} must name a plain id feature")
+            col = self.spec.sparse_names.index(by)
+        return dict(kind=kind, norm=norm, alpha=alpha, col=None if col is None else int(col))
+
+    def _rank_step(self, idx, y, scale):
+        """After rm_logit_loss: loss <- (1 - alpha) loss + alpha L, dlogit <- scale ((1 - alpha) dlogit + alpha
+        dL/dlogit) over the groups of THIS batch (rm_rank_loss).  The device record is not asked for: no sync."""
+        r = self.rank
+        groups = None if r["col"] is None else idx[:, r["col"]].contiguous()
+        ops.rank_loss(self.logit, y, groups, r["kind"], r["norm"], r["alpha"], self.dlogit, grad_scale=scale,
+                      dlogit_in=self.dlogit, loss_in=self.loss, loss_out=self.loss, workspace=self._rank_ws)
 
     def _var(self, name, shape, init="zeros", l2=None):
         """Declares a dense variable of this engine (_declare): params / grads pair, init rule, l2 key."""
@@ -805,6 +841,8 @@ class Engine:
         self.loss = torch.zeros(1, dtype=F32, device=dev)
         self.loss_part = torch.empty((B + 31) // 32, dtype=F32, device=dev)  # fused head: per-tile loss sums
         self.ws = torch.empty(256 * 1024, dtype=F32, device=dev)
+        if self.rank is not None:
+            self._rank_ws = torch.empty(ops.rank_loss_workspace(B), dtype=torch.uint8, device=dev)
         self.mv_fields = [f for f, n in enumerate(self.spec.sparse_names) if n in self.spec.scratch_names]
         self._alloc_mv(B)
         self._alloc_model(B)
@@ -926,9 +964,11 @@ class Engine:
         yk = dict(y=y) if y.dtype == I64 else dict(y_f=y)
         scale = self.grad_scale
         # models whose DNN is the last branch of the forward offer it the fused head (rm_mlp_tail):
-        # final logit, prediction, loss and dLoss/dlogit in the MLP kernel's epilogue
-        self._head_req = dict(task=self.task, grad_scale=scale, logit=self.logit, pred=self.pred,
-                              dlogit=self.dlogit, loss_partial=self.loss_part, loss=self.loss, **yk)
+        # final logit, prediction, loss and dLoss/dlogit in the MLP kernel's epilogue.  Not with a ranking term: it
+        # needs every logit of the batch before any dlogit exists, so the head is rm_logit_loss + rm_rank_loss
+        self._head_req = None if self.rank is not None else dict(
+            task=self.task, grad_scale=scale, logit=self.logit, pred=self.pred, dlogit=self.dlogit,
+            loss_partial=self.loss_part, loss=self.loss, **yk)
         self._head_done = False
         try:
             branches = self._branches_fwd(idx, dense, True, masks, None)
@@ -937,7 +977,9 @@ class Engine:
         if not self._head_done:
             ops.logit_loss(branches, task=self.task, logit=self.logit, pred=self.pred,
                            dlogit=self.dlogit, loss=self.loss, workspace=self.ws, **yk)
-            if scale != 1.0:
+            if self.rank is not None:
+                self._rank_step(idx, y, scale)
+            elif scale != 1.0:
                 # this batch is one of several micro-batches of a step: its gradients are its share
                 # of the full-batch mean (recman_amd/dist.py)
                 self.dlogit.mul_(scale)
@@ -1338,6 +1380,8 @@ class DeepFMEngine(Engine):
         """rm_deepfm_step covers this call: everything _front_fused asks for, plus FM + bias tables on, two
         hidden layers, no dropout masks.  hp["step_fusion"] overrides STEP_FUSION_DEFAULT."""
         if not (self.step_fusable and self.hp.get("step_fusion", STEP_FUSION_DEFAULT)) or masks or mv is not None:
+            return False
+        if self.rank is not None:  # (the step kernel's head is the pointwise loss alone)
             return False
         if not (self.use_fm and self.use_bias_tables and self._front_fused({}, None)):
             return False

@@ -2183,3 +2183,54 @@ def topk_ip(Q, C, k, scale, out_rows, out_scores, workspace, *, exclude=None, it
     _lib.call("rm_topk_ip", pq, ldq, pc, ldc, Nq, N, H, float(scale), int(k),
               None if eo is None else eo.data_ptr(), None if er is None else er.data_ptr(), int(item_splits),
               out_rows.data_ptr(), out_scores.data_ptr(), int(ldo), _chk(workspace, "workspace", F32), _stream())
+
+
+# ---- grouped ranking objectives next to the pointwise loss (csrc/rank.hip, include/recman_hip_rank.h) -------------
+RANK_KINDS = {"pairwise": 0, "listwise": 1}  # RM_RANK_PAIRWISE / RM_RANK_LISTWISE
+RANK_NORMS = {"pairs": 0, "group": 1}        # RM_RANK_NORM_PAIRS / RM_RANK_NORM_GROUP
+RANK_MAX_B = 1 << 24
+
+
+def rank_loss_workspace(B):
+    """Bytes of the workspace rm_rank_loss needs for B examples (1 <= B <= 2^24)."""
+    n = int(_lib.lib().rm_rank_loss_workspace(int(B)))
+    if n <= 0:
+        raise ValueError(f"rank_loss: B={B} outside [1, 2^24]")
+    return n
+
+
+def rank_loss(logit, y, groups, kind, norm, alpha, dlogit_out, *, grad_scale=1.0, dlogit_in=None, loss_in=None,
+              loss_out=None, out=None, workspace=None):
+    """rm_rank_loss: the pairwise (RankNet / BPR) or listwise (ListNet softmax) term L over the examples of the batch
+    that share a group id (groups int64 [B], or None: one group), combined with the pointwise head's results:
+        dlogit_out = grad_scale ((1 - alpha) dlogit_in + alpha dL/dlogit),   loss_out = (1 - alpha) loss_in + alpha L
+    (dlogit_in / loss_in None: the ranking term alone; dlogit_out may be dlogit_in, loss_out may be loss_in).  logit
+    float32 [B], y int64 [B] in {0, 1}.  out: int64 [7], the device record (read_rank_loss); workspace: uint8 of
+    rank_loss_workspace(B) bytes (allocated when None).  Returns `out` (None when none was given)."""
+    B = logit.shape[0] if logit.dim() == 1 else -1
+    if kind not in RANK_KINDS:
+        raise ValueError(f"rank_loss: kind must be one of {sorted(RANK_KINDS)}, got {kind!r}")
+    if norm not in RANK_NORMS:
+        raise ValueError(f"rank_loss: norm must be one of {sorted(RANK_NORMS)}, got {norm!r}")
+    lp = _chk(logit, "logit", F32, (B,))
+    need = rank_loss_workspace(B)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=logit.device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"rank_loss: workspace too small: {need} bytes needed")
+    wp = _chk(workspace, "workspace", workspace.dtype)
+    op = _chk(out, "out", I64, (7,), allow_none=True)
+    if wp % 16 or (op or 0) % 16:
+        raise ValueError("rank_loss: workspace / out must be 16-byte aligned")
+    _lib.call("rm_rank_loss", lp, _chk(y, "y", I64, (B,)), _chk(groups, "groups", I64, (B,), allow_none=True), B,
+              RANK_KINDS[kind], RANK_NORMS[norm], float(alpha), float(grad_scale),
+              _chk(dlogit_in, "dlogit_in", F32, (B,), allow_none=True), _chk(dlogit_out, "dlogit_out", F32, (B,)),
+              _chk(loss_in, "loss_in", F32, (1,), allow_none=True),
+              _chk(loss_out, "loss_out", F32, (1,), allow_none=True), op, wp, _stream())
+    return out
+
+
+def read_rank_loss(out):
+    """(value, groups, scored_groups, pairs, pos, weight, flags) of a ranking-loss record: one device-to-host copy."""
+    r = out.cpu().numpy()
+    return (float(r[:1].view("float64")[0]),) + tuple(int(v) for v in r[1:7])

@@ -104,6 +104,9 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                seq_max_len={f.name: f.max_len for f in fd.sequence_feats})
         hp = dict(self.hparams)
         hp["strict_reference"] = self.strict_reference
+        rank = self._rank_config()  # (raises on a bad ranking objective before any device work)
+        if rank is not None:
+            hp["rank_group_col"] = rank["col"]
         self._shard = self._dist_info()
         if self._shard is not None:
             if fd.sequence_feats:
@@ -360,6 +363,7 @@ class DeepModel(BaseEstimator, TransformerMixin):
         dense = torch.from_numpy(np.ascontiguousarray(inp.dense)).to(dev)
         yt = None
         if y is not None:
+            self._check_rank_labels(y)
             ya = np.asarray(y)
             yt = torch.from_numpy(ya.astype(np.int64 if self.task == "classification" else np.float32)).to(dev)
         self._mv_host = inp.mv  # name -> CSR (host) of the multi-valued features of the LAST encoded frame
@@ -489,6 +493,56 @@ class DeepModel(BaseEstimator, TransformerMixin):
                                  "(dense, multi-valued, value and sequence features have no id column)")
             cols[by] = names.index(by)
         return cols
+
+    def _rank_config(self):
+        """The ranking objective of hparams (rank_loss, rank_group_by, rank_loss_weight, rank_norm; th/hparams.py) as
+        dict(kind, norm, alpha, col) - col the column of idx that holds the ids of rank_group_by, None for the whole
+        batch as one list - or None when rank_loss is not set.  Raises ValueError / NotImplementedError on anything
+        the engines cannot train; needs no GPU.  The pairs and lists form inside ONE batch of fit(): examples of a
+        group that land in different batches never meet (there is no group-aware batching)."""
+        from .inputs import SparseFeat
+
+        hp = self.hparams or {}
+        kind = hp.get("rank_loss")
+        if kind is None:
+            return None
+        if kind not in ("pairwise", "listwise"):
+            raise ValueError(f"rank_loss={kind!r}: expected None, 'pairwise' or 'listwise'")
+        norm = hp.get("rank_norm", "group")
+        if norm not in ("pairs", "group"):
+            raise ValueError(f"rank_norm={norm!r}: expected 'pairs' or 'group'")
+        alpha = hp.get("rank_loss_weight", 0.5)
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 < alpha <= 1:
+            raise ValueError(f"rank_loss_weight={alpha!r}: expected a number with 0 < rank_loss_weight <= 1")
+        if self.model in ("mmoe", "ple"):
+            raise NotImplementedError(
+                f"rank_loss={kind!r}: {self.model} has one logit per task, and the ranking objectives order the examples "
+                "of a group by ONE logit; train a single-logit model, or leave rank_loss unset")
+        if self.model == "twotower":
+            raise NotImplementedError(
+                f"rank_loss={kind!r}: twotower trains by the in-batch softmax over user-item scores and has no "
+                "per-example logit with a 0/1 label to rank; leave rank_loss unset")
+        if self.task != "classification":
+            raise ValueError(f"rank_loss={kind!r} needs 0/1 labels: the task is {self.task!r} (loss_type='mse')")
+        by, col = hp.get("rank_group_by"), None
+        if by is not None:
+            if by not in self.feat_dict or not isinstance(self.feat_dict[by], SparseFeat):
+                raise ValueError(f"rank_group_by={by!r} must name a SparseFeat of the feature dictionary (dense, "
+                                 "multi-valued, value and sequence features have no id column)")
+            col = [f.name for f in self.feat_dict.embedding_feats].index(by)
+        if self._dist_info() is not None:
+            raise NotImplementedError(
+                f"rank_loss={kind!r} runs on one GPU: pairs across ranks or micro-batches are not built "
+                "(table_sharding='row' or a multi-rank torch.distributed job); use table_sharding='none'")
+        return dict(kind=kind, norm=norm, alpha=float(alpha), col=col)
+
+    def _check_rank_labels(self, y):
+        """Once per fit() / fit_on_batch(), on the host: a ranking objective needs labels in {0, 1}."""
+        if y is not None and (self.hparams or {}).get("rank_loss") is not None:
+            ya = np.asarray(y)
+            if not bool(np.isin(ya, (0, 1)).all()):
+                raise ValueError(f"rank_loss={self.hparams['rank_loss']!r} needs labels in {{0, 1}}; got "
+                                 f"{np.unique(ya)[:5].tolist()}..")
 
     def _groups_of(self, idx, on_device):
         """The id columns the grouped metrics take, from the encoded idx: device tensors when the metrics run

@@ -28,6 +28,15 @@ class BaseHyperParameters(dict):
     FtrlL2 = "ftrl_l2"
     FtrlBeta = "ftrl_beta"
 
+    # a ranking objective next to the log loss (not in the reference; include/recman_hip_rank.h): the single-logit
+    # models minimise (1 - rank_loss_weight) log loss + rank_loss_weight L, L over the examples of ONE batch that share
+    # an id of the feature rank_group_by.  Gen-2 classes read the keys from their hparams dict, gen-1 classes from
+    # model.hparams
+    RankLoss = "rank_loss"              # None | "pairwise" (RankNet / BPR pairs) | "listwise" (ListNet softmax)
+    RankGroupBy = "rank_group_by"       # the name of a SparseFeat, or None: the whole batch is one list
+    RankLossWeight = "rank_loss_weight"  # alpha, 0 < alpha <= 1
+    RankNorm = "rank_norm"              # "group": every scored group weighs its impressions | "pairs": every pair 1/Q
+
     def __init__(self):
         dict.__init__(self)
         self.add_param(self.LearningRate, 0.001)
@@ -37,6 +46,10 @@ class BaseHyperParameters(dict):
         self.add_param(self.FtrlL1, 0.0)
         self.add_param(self.FtrlL2, 0.0)
         self.add_param(self.FtrlBeta, 0.0)
+        self.add_param(self.RankLoss, None)
+        self.add_param(self.RankGroupBy, None)
+        self.add_param(self.RankLossWeight, 0.5)
+        self.add_param(self.RankNorm, "group")
 
     def add_param(self, name, default_val):
         self[name] = HParam(name, default_val)()
