@@ -4,7 +4,15 @@ No autograd and no tracing compiler: each engine owns its parameters (laid out
 for the kernels: ONE concatenated embedding table in HBM, per-feature variables
 are views of it), a workspace sized once per batch size, and enqueues a fixed
 sequence of HIP kernels (recman_amd/ops.py -> librecman_hip.so) on the current
-stream - which makes a whole step capturable in a hipGraph (`capture=True`).
+stream - which is meant to make a whole step capturable in a hipGraph, as bench.py's
+time_steps captures it.  A capture requires:
+  * fwd_bwd and forward to enqueue on the current stream only, with no host read of
+    device data, and the engine warmed at that batch size first (the first call at a
+    batch size allocates the workspaces);
+  * the optimizers' step (recman_amd/optim.py) outside the graph - it takes the step
+    count t by value - and the optimizers built before the capture;
+  * no call at another batch size between capture and replay (_alloc releases the
+    buffers the graph points to).
 
 The MLP ("DNN", layers.py:576-609) runs on hand-written f32-MFMA kernels as well:
 csrc/mlp.hip (all layers fused, hidden widths <= 32) or csrc/gemm.hip (one launch per

@@ -108,8 +108,8 @@ EXEMPT = {  # entry point -> (file, its kernels: none of them declares __shared_
 }
 
 
-def _stream_entry_points():
-    text = open(os.path.join(ROOT, "include", "recman_hip.h")).read()
+def _stream_entry_points(header="recman_hip.h"):
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return {m.group(1) for m in re.finditer(r"\b(rm_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
             if re.search(r"\brm_stream_t\s+stream\b", m.group(2))}
