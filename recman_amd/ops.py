@@ -1825,6 +1825,94 @@ def read_group_auc(out):
     return (float(r[:1].view("float64")[0]),) + tuple(int(v) for v in r[1:6])
 
 
+# ------------------------------------------------- grouped top-k ranking metrics (csrc/rankmetrics.hip)
+GAIN_MAX_K, GAIN_MAX_CUTOFFS = 1024, 8  # RM_GAIN_MAX_K / RM_GAIN_MAX_CUTOFFS
+GAIN_NORMS = {"ideal": 0, "positives": 1, "k": 2}
+GAIN_SCORED = {"both_classes": 0, "has_positive": 1}
+GAIN_WEIGHTS = {"groups": 0, "impressions": 1, "clicks": 2}
+_GAIN_RECORD = GAIN_MAX_CUTOFFS + 5
+_discounts = {}
+
+
+def gain_discounts(device, kind, kmax):
+    """The float64 device table of per-rank discounts: kind "log2" is 1 / log2(r + 2) (DCG), "none" is 1 (counts);
+    kmax entries.  Built once per (device, kind, kmax)."""
+    import numpy as np
+
+    device = torch.device(device)
+    key = (device, kind, int(kmax))
+    if key not in _discounts:
+        if kind == "log2":
+            table = 1 / np.log2(np.arange(2, kmax + 2, dtype=np.float64))
+        elif kind == "none":
+            table = np.ones(kmax, dtype=np.float64)
+        else:
+            raise ValueError(f"discount kind must be 'log2' or 'none', got {kind!r}")
+        _discounts[key] = torch.from_numpy(table).to(device)
+    return _discounts[key]
+
+
+def group_gain_workspace(n):
+    """Bytes of the workspace rm_group_gain needs for n elements (0 outside 1 <= n < 2^31)."""
+    return int(_lib.lib().rm_group_gain_workspace(int(n)))
+
+
+def group_gain(scores, labels, groups, disc, cutoffs, norm=0, scored_rule=0, weight_kind=0, workspace=None, out=None,
+               per_group=None):
+    """Grouped top-k gain (rm_group_gain): scores fp32 [n], labels int64 [n], groups int64 [n] or None (one group)
+    on the GPU; disc float64 [>= cutoffs[-1]] on the GPU; cutoffs: 1..8 strictly ascending ints in 1..1024; norm /
+    scored_rule / weight_kind: values of GAIN_NORMS / GAIN_SCORED / GAIN_WEIGHTS.  per_group: None, or (ids, n, pos)
+    int64 [n] and values float64 [n, len(cutoffs)], whose first `groups` rows are written in ascending id order.
+    Returns the device record `out` (int64 [13]: eight values as float64 bits, groups, scored groups, weight sum, P,
+    flags); read it with read_group_gain."""
+    n = scores.shape[0] if scores.dim() == 1 else -1
+    xp = _chk(scores, "scores", F32, (n,))
+    yp = _chk(labels, "labels", I64, (n,))
+    gp = _chk(groups, "groups", I64, (n,), allow_none=True)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"scores: need 1 <= n < 2^31 elements, got {n}")
+    ks = [int(k) for k in cutoffs]
+    if not 1 <= len(ks) <= GAIN_MAX_CUTOFFS:
+        raise ValueError(f"cutoffs: 1 to {GAIN_MAX_CUTOFFS} values, got {len(ks)}")
+    if any(not 1 <= k <= GAIN_MAX_K for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"cutoffs must be strictly ascending in [1, {GAIN_MAX_K}], got {ks}")
+    for name, v, table in (("norm", norm, GAIN_NORMS), ("scored_rule", scored_rule, GAIN_SCORED),
+                           ("weight_kind", weight_kind, GAIN_WEIGHTS)):
+        if v not in table.values():
+            raise ValueError(f"{name} must be one of {table}, got {v!r}")
+    dp = _chk(disc, "disc", torch.float64)
+    if disc.dim() != 1 or disc.shape[0] < ks[-1]:
+        raise ValueError(f"disc: need a 1-D table of at least {ks[-1]} entries, got shape {tuple(disc.shape)}")
+    need = group_gain_workspace(n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=scores.device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"group_gain workspace too small: {need} bytes needed")
+    wp = _chk(workspace, "workspace", workspace.dtype)
+    if out is None:
+        out = torch.empty(_GAIN_RECORD, dtype=I64, device=scores.device)
+    op = _chk(out, "out", I64, (_GAIN_RECORD,))
+    if wp % 16 or op % 16:
+        raise ValueError("group_gain workspace / out must be 16-byte aligned")
+    pg = [None] * 4
+    if per_group is not None:
+        if len(per_group) != 4:
+            raise ValueError("per_group: int64 [n] tensors (ids, n, pos) and float64 [n, len(cutoffs)] values")
+        pg = [_chk(t, name, I64, (n,)) for t, name in zip(per_group[:3], ("group_ids", "group_n", "group_pos"))]
+        pg.append(_chk(per_group[3], "group_value", torch.float64, (n, len(ks))))
+    _lib.call("rm_group_gain", xp, yp, gp, n, dp, (ctypes.c_int * len(ks))(*ks), len(ks), int(norm),
+              int(scored_rule), int(weight_kind), wp, *pg, op, _stream())
+    return out
+
+
+def read_group_gain(out, n_cutoffs=GAIN_MAX_CUTOFFS):
+    """(values, groups, scored_groups, weight, P, flags) of a grouped-gain record, values a tuple of the first
+    n_cutoffs floats: one device-to-host copy."""
+    r = out.cpu().numpy()
+    values = tuple(float(v) for v in r[:GAIN_MAX_CUTOFFS].view("float64")[:n_cutoffs])
+    return (values,) + tuple(int(v) for v in r[GAIN_MAX_CUTOFFS:_GAIN_RECORD])
+
+
 # ---- multi-task learning: MMoE's gate mixture and the loss head for several labels (csrc/mmoe.hip) ---------------
 MMOE_TILE = {"tile": 0, "cap": 1}  # RM_MMOE_TILE / RM_MMOE_CAP
 MMOE_LIMITS = "1 <= E <= 16 experts, 1 <= T <= 8 tasks, H a multiple of 4 in 4..512, row strides multiples of 4 floats"

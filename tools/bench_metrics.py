@@ -139,18 +139,23 @@ def host_loop(y, s, g):
     return num / den
 
 
+def gauc_inputs(n, G):
+    """(labels, scores, group ids) on the GPU, seeded by n: a click rate of 0.2, sigmoid scores, ids drawn Zipf-like
+    over the ranks 1 .. G and hashed into 24 bits."""
+    gen = torch.Generator(device="cuda").manual_seed(n)
+    y = (torch.rand(n, device="cuda", generator=gen) < 0.2).to(torch.int64)
+    s = torch.sigmoid(torch.randn(n, device="cuda", generator=gen) * 2 + y.float())
+    rank = torch.pow(float(G), torch.rand(n, device="cuda", generator=gen, dtype=torch.float64)).to(torch.int64)
+    return y, s, (rank * 2654435761) % (1 << 24)
+
+
 def gauc_run(sizes, calls, groups, loop_rows):
     from recman_amd import metrics as M
 
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
     import gauc_ref
 
-    def draw(n, G):
-        gen = torch.Generator(device="cuda").manual_seed(n)
-        y = (torch.rand(n, device="cuda", generator=gen) < 0.2).to(torch.int64)
-        s = torch.sigmoid(torch.randn(n, device="cuda", generator=gen) * 2 + y.float())
-        rank = torch.pow(float(G), torch.rand(n, device="cuda", generator=gen, dtype=torch.float64)).to(torch.int64)
-        return y, s, (rank * 2654435761) % (1 << 24)  # Zipf-like ranks 1 .. G, hashed into 24 bits
+    draw = gauc_inputs
 
     out = {"groups_drawn_from": groups, "sizes": []}
     for i, n in enumerate(sizes):
