@@ -38,10 +38,16 @@
 //  * one workgroup barrier per tile.  Segment s (between barriers s-1 and s): workers run backward(s-2) + the DMAs
 //    of tile s+1, then forward(s); the head runs epilogue(s-1) meanwhile.  forward(s) -> [barrier] -> epilogue(s) ->
 //    [barrier] -> backward(s): the head's serial chain (32 dependent MFMAs + the loss) always overlaps the workers'
-//    matrix work of the neighbouring tiles.
+//    matrix work of the neighbouring tiles.  A block of T tiles runs the segments s = -1 .. T + 1 (T + 3 of them) behind
+//    one prologue barrier: the fill starts in the PROLOGUE - the head requests tile 0's ids first of all, stages its
+//    parameters under that latency (every load issued before the first wait), writes tile 0's row numbers and issues
+//    the first prefetch loads; the workers load W0 meanwhile (the dX operand as 16-byte pieces where W0's rows keep
+//    them aligned) and meet the head at the prologue barrier.  Segment -1 requests tile 0's rows at once.  (The loops
+//    used to start at s = -2, a segment spent waiting for the head: r06.)
 //  * per-block partial sums (dW0 slab, small gradients, loss) go to the same finishing launch as rm_mlp_bwd's
 //    (mlp_finish_kernel): fixed order, deterministic.
-// Measured history and the per-wave phase times: profiles/r03_deepfm_step.md, r04_deepfm_step.md, r05_deepfm_step.md.
+// Measured history and the per-wave phase times: profiles/r03_deepfm_step.md, r04_deepfm_step.md, r05_deepfm_step.md;
+// the time per segment class (prologue, fill, steady, drain, epilogue) and the prologue's share: r06_deepfm_step.md.
 #include "mlp_internal.h"
 #include "rm_common.h"
 
@@ -86,16 +92,42 @@ static_assert(kLdsBytes <= 160 * 1024, "LDS map exceeds a CU");
 #define RM_STEP_ABL 0  // ablation builds (wrong results): 1 no bias / linear entry loads, 2 no d_rows stores, 4 every row = row 0, 8 no DMAs, 16 no worker MFMAs
 #endif
 // diagnostic build (-DRM_STEP_STAMP, never in the product library): every wave adds up the shader-clock ticks it spends
-// in its phases; rm_debug_step_stamps reads them (tools/probe/step_stamps.py).
+// in its phases; rm_debug_step_stamps reads them (tools/probe/step_stamps.py).  Per wave kStampW counters: [0, 8) the
+// phases (7 = the wave's whole life), then per SEGMENT CLASS the time of its segments and, of that, the time in the
+// tile barrier.  Classes: 0 prologue (entry .. loop), 1..4 the fill segments s = -2, -1, 0, 1 (a loop that starts at
+// -1 leaves class 1 empty), 5 steady (2 .. T - 1), 6 and 7 the drain segments T and T + 1, 8 epilogue (loop .. exit).
 #ifdef RM_STEP_STAMP
-__device__ unsigned long long rm_step_stamp_buf[256 * 8 * 8];
+constexpr int kStampC = 9, kStampW = 8 + 2 * kStampC;
+__device__ unsigned long long rm_step_stamp_buf[256 * 8 * kStampW];
 #define ST_NOW() __builtin_amdgcn_s_memtime()
-#define ST_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = ST_NOW(), st_t0 = st_t
-#define ST_ADD(i) { const unsigned long long st_n = ST_NOW(); st_acc[i] += st_n - st_t; st_t = st_n; }
-#define ST_FLUSH(wv) if (lane == 0 && blockIdx.x < 256) { st_acc[7] = ST_NOW() - st_t0; for (int i_ = 0; i_ < 8; ++i_) rm_step_stamp_buf[(blockIdx.x * 8 + (wv)) * 8 + i_] = st_acc[i_]; }
+#define ST_DECL                                                                                                   \
+  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_cls[kStampC] = {0, 0, 0, 0, 0, 0, 0, 0, 0},            \
+                     st_clb[kStampC] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st_t = ST_NOW(), st_t0 = st_t, st_seg = st_t, st_d = 0
+#define ST_ADD(i) { const unsigned long long st_n = ST_NOW(); st_d = st_n - st_t; st_acc[i] += st_d; st_t = st_n; }
+// the time since the last ST_CLS goes to class c (constant, or wave-uniform: a select per class, no indexed array);
+// bar: the stamp just taken was the tile barrier's
+#define ST_CLS(c, bar)                                                                                            \
+  {                                                                                                               \
+    const int st_c = (c);                                                                                         \
+    const unsigned long long st_e = st_t - st_seg;                                                                \
+    st_seg = st_t;                                                                                                \
+    _Pragma("unroll") for (int i_ = 0; i_ < kStampC; ++i_) {                                                      \
+      st_cls[i_] += i_ == st_c ? st_e : 0ull;                                                                     \
+      st_clb[i_] += ((bar) && i_ == st_c) ? st_d : 0ull;                                                          \
+    }                                                                                                             \
+  }
+#define ST_SEG_CLASS(s, T) ((s) < 2 ? (s) + 3 : ((s) < (T) ? 5 : (s) - (T) + 6))
+#define ST_FLUSH(wv)                                                                                              \
+  if (lane == 0 && blockIdx.x < 256) {                                                                            \
+    st_acc[7] = ST_NOW() - st_t0;                                                                                 \
+    unsigned long long *st_o = rm_step_stamp_buf + (blockIdx.x * 8 + (wv)) * kStampW;                             \
+    for (int i_ = 0; i_ < 8; ++i_) st_o[i_] = st_acc[i_];                                                         \
+    for (int i_ = 0; i_ < kStampC; ++i_) { st_o[8 + i_] = st_cls[i_]; st_o[8 + kStampC + i_] = st_clb[i_]; }      \
+  }
 #else
 #define ST_DECL
 #define ST_ADD(i)
+#define ST_CLS(c, bar)
 #define ST_FLUSH(wv)
 #endif
 
@@ -292,6 +324,8 @@ template <bool NT, bool NT_OUT, bool PACKED>
 __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const int w, const int lane, const int T) {
   const int n = lane & 15, q = lane >> 4;
   const int F = a.F, H0 = a.H0, K = 16 * F + a.Dn;
+  ST_DECL;
+  const bool w0_x4 = (((uintptr_t)a.W0 & 15) | (unsigned)(H0 & 3)) == 0;
   int fld[kSlots];
   bool sv[kSlots], sx[kSlots];  // slot in use; slot is an embedding field (has rows to fetch and a dX)
   float w0f[kSlots][2][4];      // forward A operand: W0[kb + 4 q + ks][16 uh + n]
@@ -312,13 +346,46 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
         const bool okf = sv[j] && kf < K && uf < H0;
         const float vf = a.W0[okf ? (int64_t)kf * H0 + uf : 0];
         w0f[j][uh][e] = okf ? vf : 0.f;
-        const int kx = kb + n, ux = 16 * uh + 4 * q + e;
-        const bool okx = sx[j] && kx < K && ux < H0;
-        const float vx = a.W0[okx ? (int64_t)kx * H0 + ux : 0];
-        w0x[j][uh][e] = okx ? vx : 0.f;
       }
       dw[j][uh] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+  }
+  // the dX operand's four values lie side by side in row kb + n: ONE 16-byte load where the rows of W0 keep it aligned
+  // (w0_x4: H0 a multiple of 4, W0 16-byte aligned; then all four units 4 q .. 4 q + 3 are inside H0 or none is).  As
+  // dword loads every instruction touches 16 rows for 4 bytes of each: the 7 workers' 7 x 32 of them were most of the
+  // prologue.  The 8 loads are issued behind every other load of the prologue and awaited ONCE (the empty asm names
+  // them: hipcc puts its one wait there, not a counted wait per select).
+  if (w0_x4) {
+    f32x4 vx[kSlots][2];
+    bool okx[kSlots][2];
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+#pragma unroll
+      for (int uh = 0; uh < 2; ++uh) {
+        const int kx = 16 * fld[j] + n, ux = 16 * uh + 4 * q;
+        okx[j][uh] = sx[j] && kx < K && ux < H0;
+        vx[j][uh] = *reinterpret_cast<const f32x4 *>(a.W0 + (okx[j][uh] ? (int64_t)kx * H0 + ux : 0));
+      }
+    asm volatile("" : "+v"(vx[0][0]), "+v"(vx[0][1]), "+v"(vx[1][0]), "+v"(vx[1][1]), "+v"(vx[2][0]), "+v"(vx[2][1]),
+                      "+v"(vx[3][0]), "+v"(vx[3][1])::"memory");
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+#pragma unroll
+      for (int uh = 0; uh < 2; ++uh)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w0x[j][uh][e] = okx[j][uh] ? vx[j][uh][e] : 0.f;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+#pragma unroll
+      for (int uh = 0; uh < 2; ++uh)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int kx = 16 * fld[j] + n, ux = 16 * uh + 4 * q + e;
+          const bool okx = sx[j] && kx < K && ux < H0;
+          const float vx = a.W0[okx ? (int64_t)kx * H0 + ux : 0];
+          w0x[j][uh][e] = okx ? vx : 0.f;
+        }
   }
   const int64_t tstride = gridDim.x;
   // per-lane offsets inside a slot's 1 KiB image, computed once: slice q of example n; element n of examples
@@ -361,7 +428,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
   // when PACKED (row + tail); asm volatile / sched_barrier(0) pin the order):
   //     E_0 D_0 | E_1 D_1 S_0 | E_2 D_2 S_1 | E_3 D_3 S_2 | S_3            = 8 + 4 SP operations per segment
   // Segments without a tile s + 1 fetch row 0 (DMA into the sink), segments without a backward store into a buffer
-  // resource of zero records, empty slots do both: the sequence never changes - fill (s = -2 ..), steady state and
+  // resource of zero records, empty slots do both: the sequence never changes - fill (s = -1 ..), steady state and
   // drain alike - and both counts are constants.  vmcnt retires in issue order: "at most N outstanding" = everything
   // but the youngest N has landed.
   //  * kYoungerE, in front of the use of sdv[j] at the top of slot j (before E_j of this segment is issued).  Behind
@@ -378,10 +445,20 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
   // (a kernel argument first used inside the loop is waited for THERE, by an s_waitcnt lgkmcnt(0) per use: a drain of
   // the LDS reads in flight - the row size is used here once, and the scalar load's wait stands in front of the loop)
   asm volatile("" ::"s"(a.row_bytes) : "memory");
-  ST_DECL;
   ST_ADD(0);  // prologue
+  // ---- the fill starts in the prologue: the head has turned tile 0's ids into row numbers (oRow buffer 0) while the W0
+  // loads above were in flight, and this barrier publishes them - segment -1 requests tile 0's rows at once.  (The
+  // loop used to start at s = -2, a segment in which the workers did nothing but issue their dummy operations and wait
+  // at the barrier for the head's id latency.)  The counts below do not care: a worker issues nothing ahead of the
+  // loop that they would have to count (the W0 / lin_mask loads are hipcc's own, awaited by hipcc), the first segment's
+  // entry_wait finds fewer than kYoungerE operations outstanding and sums sdv = 0 into a side_sum nobody reads (no
+  // forward at s = -1), and forward(0)'s kYounger counts back to D_3 of segment -1 as in every later segment.  The LDS
+  // counter is empty behind the barrier's lgkmcnt(0), as at every loop top.
+  tile_barrier();
+  ST_ADD(5);
+  ST_CLS(0, true);
 
-  for (int s = -2; s <= T + 1; ++s) {
+  for (int s = -1; s <= T + 1; ++s) {
     const bool hasB = s - 2 >= 0 && s - 2 < T;  // backward of tile s - 2 (4 d_rows stores)
     const bool hasD = s + 1 >= 0 && s + 1 < T;  // rows of tile s + 1 (4 DMAs + 4 entry loads)
     // ---- the bias / linear entries of tile s (loaded a segment ago) are summed slot by slot in the D phase below,
@@ -568,6 +645,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
     ST_ADD(4);  // forward
     tile_barrier();
     ST_ADD(5);  // barrier
+    ST_CLS(ST_SEG_CLASS(s, T), true);
   }
   // the last segment's entry loads are still in flight: their registers must not be reused before they land
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -582,6 +660,7 @@ __device__ __forceinline__ void step_worker(const StepArgs &a, char *smem, const
           a.dW0_part[((int64_t)blockIdx.x * a.Kp + 16 * fld[j] + 4 * q + i) * 32 + 16 * uh + n] = dw[j][uh][i];
     }
   ST_ADD(0);
+  ST_CLS(8, false);
   ST_FLUSH(w);
 }
 
@@ -591,32 +670,76 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
   const int F = a.F, Dn = a.Dn, H0 = a.H0, H1 = a.H1;
   const float act = act_slope(a.act);
   const int64_t B = a.B, tstride = gridDim.x;
+  ST_DECL;
+  auto ex_of = [&](int t) {  // this lane's example of tile t, clamped into the batch
+    const int64_t b = ((int64_t)blockIdx.x + t * tstride) * 16 + n;
+    return b < B ? b : B - 1;
+  };
+  // prefetch registers, loaded a segment before their use by loads that hipcc does not count (entry_load): with
+  // counted loads and the output stores pending together, hipcc's wait in front of every use is s_waitcnt vmcnt(0),
+  // i.e. for the stores just issued too.  The head issues the SAME vector-memory operations in EVERY segment, in this
+  // program order - the three output stores (logit, pred, dlogit; into buffer resources of zero records without an
+  // epilogue), then 4 dense columns, the label, 7 ids:
+  //     St St St | [wait A: dense + label] [wait B: ids] | Dn Dn Dn Dn Y | Id x 7        = 15 operations per segment
+  // Everything about this lane's fields q + 4 j is UNCONDITIONAL: fields past F read field F - 1 again and land in
+  // row-number slots nobody reads, tiles past the block's last read example B - 1 (ex_of clamps), without dense
+  // inputs the four columns read w_out[0].  Behind the label Y of the previous segment: its 7 ids and this segment's
+  // 3 stores = 10 (wait A); behind the last id: the 3 stores (wait B).  The prologue stands in for the segment in
+  // front of the first one (below): tile 0's ids drained there, then the same 12 loads.
+  unsigned idr[7];  // ids (low words: row numbers < 2^32) of tile s + 2, loaded one segment earlier
+  float dnr[4];     // dense columns 4 q .. 4 q + 3 of tile s + 1
+  unsigned yr = 0;  // ... and its label (low word of the int64 / the float's bits)
+#pragma unroll
+  for (int j = 0; j < 7; ++j) idr[j] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dnr[i] = 0.f;
+  auto load_ids = [&](int t) {
+    const unsigned *p = reinterpret_cast<const unsigned *>(a.idx + ex_of(t) * F);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) entry_load(idr[j], p + 2 * (q + 4 * j < F ? q + 4 * j : F - 1));
+  };
   // ---- parameters: in LDS, read per tile (as registers they pushed this wave past 256 VGPRs: W1 in both operand
   // layouts alone is 32).  W1[u][v] row-major with the 16-byte blocks of a row XOR-swizzled by the row, so that the
   // forward's column reads (ds_read_b32, lanes along v) and the chain's row reads (ds_read_b128) both spread over the banks.
+  // Every load of the prologue is issued BEFORE the first wait, tile 0's ids first: one memory latency in all.  (The
+  // loads used to stand inside the lane conditions that guard the LDS writes, each block behind a wait of its own:
+  // six latencies one behind the other, and the ids behind the last.)  The ids are uncounted loads (entry_load):
+  // OLDER than every load hipcc counts here, they cannot make one of its counts too small.
+  load_ids(0);
+  float w0o, lw0;
   {
+    float w1v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int e = lane + 64 * i, u = e >> 5, v = e & 31;
+      w1v[i] = a.W1[(u < H0 && v < H1) ? u * H1 + v : 0];
+    }
+    const int l32 = lane & 31;  // (every lane loads from a valid address; lanes >= 32 write nothing)
+    const float f0 = a.b0[l32 < H0 ? l32 : 0], f1 = a.b1[l32 < H1 ? l32 : 0], f2 = a.w_out[l32 < H1 ? l32 : 0];
+    const float f3 = a.lin_wd[l32 < Dn ? l32 : 0];
+    const unsigned fo = (unsigned)a.field_off[l32 < F ? l32 : F - 1];
+    w0o = a.w0_out[0];
+    lw0 = a.lin_w0[0];
+    // (hipcc sinks a load into the lane condition of its only use otherwise - a latency of its own behind the others';
+    // the two scalars are waited for here too: a counted load first used inside the loop is a vmcnt(0) per tile)
+    asm volatile("" ::"v"(f3), "v"(fo), "v"(w0o), "v"(lw0) : "memory");
     float *w1s = reinterpret_cast<float *>(smem + oW1);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int e = lane + 64 * i, u = e >> 5, v = e & 31;
-      const bool ok = u < H0 && v < H1;
-      const float f = a.W1[ok ? u * H1 + v : 0];
-      w1s[u * 32 + 4 * ((v >> 2) ^ (u & 7)) + (v & 3)] = ok ? f : 0.f;
+      w1s[u * 32 + 4 * ((v >> 2) ^ (u & 7)) + (v & 3)] = (u < H0 && v < H1) ? w1v[i] : 0.f;
     }
     float *par = reinterpret_cast<float *>(smem + oPar);
     if (lane < 32) {
-      const float f0 = a.b0[lane < H0 ? lane : 0], f1 = a.b1[lane < H1 ? lane : 0], f2 = a.w_out[lane < H1 ? lane : 0];
       par[kParB0 / 4 + lane] = lane < H0 ? f0 : 0.f;
       par[kParB1 / 4 + lane] = lane < H1 ? f1 : 0.f;
       par[kParWo / 4 + lane] = lane < H1 ? f2 : 0.f;
-      const float f3 = a.lin_wd[lane < Dn ? lane : 0];
       if (lane < 16) par[kParWd / 4 + lane] = lane < Dn ? f3 : 0.f;
-      if (lane < 28) reinterpret_cast<unsigned *>(par)[kParFo / 4 + lane] = (unsigned)a.field_off[lane < F ? lane : F - 1];
+      if (lane < 28) reinterpret_cast<unsigned *>(par)[kParFo / 4 + lane] = fo;
     }
   }
   const float *w1s = reinterpret_cast<const float *>(smem + oW1);
   const char *par = smem + oPar;
-  const float w0o = a.w0_out[0], lw0 = a.lin_w0[0];
 
   // ---- accumulators of the small gradients
   f32x4 dW1[2][2];
@@ -631,40 +754,36 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
 #pragma unroll
   for (int i = 0; i < 4; ++i) dxd[i] = 0.f;
 
-  auto ex_of = [&](int t) {  // this lane's example of tile t, clamped into the batch
-    const int64_t b = ((int64_t)blockIdx.x + t * tstride) * 16 + n;
-    return b < B ? b : B - 1;
-  };
-  // prefetch registers, loaded a segment before their use by loads that hipcc does not count (entry_load): with
-  // counted loads and the output stores pending together, hipcc's wait in front of every use is s_waitcnt vmcnt(0),
-  // i.e. for the stores just issued too.  The head issues the SAME vector-memory operations in EVERY segment, in this
-  // program order - the three output stores (logit, pred, dlogit; into buffer resources of zero records without an
-  // epilogue), then 4 dense columns, the label, 7 ids:
-  //     St St St | [wait A: dense + label] [wait B: ids] | Dn Dn Dn Dn Y | Id x 7        = 15 operations per segment
-  // Everything about this lane's fields q + 4 j is UNCONDITIONAL: fields past F read field F - 1 again and land in
-  // row-number slots nobody reads, tiles past the block's last read example B - 1 (ex_of clamps), without dense
-  // inputs the four columns read w_out[0].  Behind the label Y of the previous segment: its 7 ids and this segment's
-  // 3 stores = 10 (wait A); behind the last id: the 3 stores (wait B).  The prologue's ids (tile 0) are waited for in
-  // the first segment by the same count B.
-  unsigned idr[7];  // ids (low words: row numbers < 2^32) of tile s + 2, loaded one segment earlier
-  float dnr[4];     // dense columns 4 q .. 4 q + 3 of tile s + 1
-  unsigned yr = 0;  // ... and its label (low word of the int64 / the float's bits)
+  // ---- the fill starts HERE, not in a segment of its own: wait for tile 0's ids (a drain is fine outside the tile
+  // loop; the workers' W0 loads run meanwhile), write its row numbers into oRow buffer 0, then issue what the loop's
+  // prefetch chain issues per segment - dense columns and label of tile 0, ids of tile 1.  The first loop segment
+  // (s = -1) then finds the counters as every later one does: behind the label Y stand the 7 ids and, by its wait A,
+  // its own 3 stores = 10; behind the last id the 3 stores (wait B).  Segment -1's workers read buffer 0 while this
+  // wave writes tile 1's row numbers into buffer 1: two buffers suffice, as before.
+  asm volatile("s_waitcnt vmcnt(0)"
+               : "+v"(idr[0]), "+v"(idr[1]), "+v"(idr[2]), "+v"(idr[3]), "+v"(idr[4]), "+v"(idr[5]), "+v"(idr[6])::"memory");
+  {  // (every block has a tile 0)
+    unsigned *rowid = reinterpret_cast<unsigned *>(smem + oRow);
 #pragma unroll
-  for (int j = 0; j < 7; ++j) idr[j] = 0;
+    for (int j = 0; j < 7; ++j)
+      rowid[(q + 4 * j) * 16 + n] = idr[j] + *reinterpret_cast<const unsigned *>(par + kParFo + (q + 4 * j) * 4);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    const int64_t b = ex_of(0);
+    const float *dp = Dn > 0 ? a.dense + b * Dn : a.w_out;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) dnr[i] = 0.f;
-  auto load_ids = [&](int t) {
-    const unsigned *p = reinterpret_cast<const unsigned *>(a.idx + ex_of(t) * F);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) entry_load(idr[j], p + 2 * (q + 4 * j < F ? q + 4 * j : F - 1));
-  };
-  // (the two scalars above are waited for HERE: a counted load first used inside the loop is a vmcnt(0) per tile)
-  asm volatile("" ::"v"(w0o), "v"(lw0) : "memory");
-  load_ids(0);
-  ST_DECL;
+    for (int i = 0; i < 4; ++i) entry_load(dnr[i], dp + (4 * q + i < Dn ? 4 * q + i : 0));
+    const unsigned *yp = a.y ? reinterpret_cast<const unsigned *>(a.y + b) : reinterpret_cast<const unsigned *>(a.y_f + b);
+    entry_load(yr, yp);
+  }
+  load_ids(1);
   ST_ADD(0);
+  tile_barrier();
+  ST_ADD(5);
+  ST_CLS(0, true);
 
-  for (int s = -2; s <= T + 1; ++s) {
+  for (int s = -1; s <= T + 1; ++s) {
     const bool epi = s - 1 >= 0 && s - 1 < T;
     float o_z = 0.f, o_p = 0.f, o_g = 0.f;  // logit, pred, dlogit of this lane's example
     // ------------------------------------------------------------ epilogue of tile s - 1
@@ -857,41 +976,50 @@ __device__ __forceinline__ void step_head(const StepArgs &a, char *smem, const i
     ST_ADD(6);  // prefetch chain
     tile_barrier();
     ST_ADD(5);  // barrier
+    ST_CLS(ST_SEG_CLASS(s, T), true);
   }
 
   // the last segment's prefetch loads are still in flight: their registers must not be reused before they land
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // ---- this block's partial of the small gradients and the loss
-  float *sgp = a.sg_part + (int64_t)blockIdx.x * kRmSgStride;
+  // ---- this block's partial of the small gradients and the loss.  (Lane coordinates taken anew behind the loop: the
+  // store offsets below, computed off the function's n and q, were hoisted in front of the loop and one of them
+  // spilled - this wave has no register to spare across its loop)
+  int el = lane;
+  asm volatile("" : "+v"(el));
+  {
+    const int n = el & 15, q = el >> 4;
+    float *sgp = a.sg_part + (int64_t)blockIdx.x * kRmSgStride;
 #pragma unroll
-  for (int uh = 0; uh < 2; ++uh)
+    for (int uh = 0; uh < 2; ++uh)
 #pragma unroll
-    for (int vh = 0; vh < 2; ++vh)
+      for (int vh = 0; vh < 2; ++vh)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sgp[(16 * uh + 4 * q + i) * 32 + 16 * vh + n] = dW1[uh][vh][i];
+        for (int i = 0; i < 4; ++i) sgp[(16 * uh + 4 * q + i) * 32 + 16 * vh + n] = dW1[uh][vh][i];
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float s0 = sum_n(db0[h][i]), s1 = sum_n(db1[h][i]), s2 = sum_n(dwo[h][i]);
+        if (n == 0) {
+          const int u = 16 * h + 4 * q + i;
+          sgp[2 * 1024 + u] = s0;
+          sgp[2 * 1024 + 32 + u] = s1;
+          sgp[2 * 1024 + 64 + u] = s2;  // NL = 2: d w_out behind the two db_l
+        }
+      }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float s0 = sum_n(db0[h][i]), s1 = sum_n(db1[h][i]), s2 = sum_n(dwo[h][i]);
-      if (n == 0) {
-        const int u = 16 * h + 4 * q + i;
-        sgp[2 * 1024 + u] = s0;
-        sgp[2 * 1024 + 32 + u] = s1;
-        sgp[2 * 1024 + 64 + u] = s2;  // NL = 2: d w_out behind the two db_l
-      }
+      const float sx = sum_n(dxd[i]);
+      if (n == 0) sgp[kRmSgDense + 4 * q + i] = sx;
     }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float sx = sum_n(dxd[i]);
-    if (n == 0) sgp[kRmSgDense + 4 * q + i] = sx;
-  }
-  const float sgt = rm_wave_sum(sg), lst = rm_wave_sum(loss_acc);
-  if (lane == 0) {
-    sgp[2 * 1024 + 64 + 32] = sgt;
-    a.loss_part[blockIdx.x] = lst;
+    const float sgt = rm_wave_sum(sg), lst = rm_wave_sum(loss_acc);
+    if (lane == 0) {
+      sgp[2 * 1024 + 64 + 32] = sgt;
+      a.loss_part[blockIdx.x] = lst;
+    }
   }
   ST_ADD(0);
+  ST_CLS(8, false);
   ST_FLUSH(7);
 }
 

@@ -28,10 +28,11 @@ ev[1].record()
 torch.cuda.synchronize()
 print(f"eager step {ev[0].elapsed_time(ev[1]) / 50 * 1e3:.1f} us")
 lib = ctypes.CDLL(_lib.LIB_PATH)
+NW = 8 + 2 * 9  # kStampW of csrc/step.hip: 8 phases, 9 segment classes (time, and of it the time in the tile barrier)
 n = 256 * 8
-buf = (ctypes.c_ulonglong * (8 * n))()
-assert lib.rm_debug_step_stamps(buf, 8 * n) == 0
-s = np.frombuffer(buf, dtype=np.uint64).reshape(256, 8, 8).astype(np.float64)
+buf = (ctypes.c_ulonglong * (NW * n))()
+assert lib.rm_debug_step_stamps(buf, NW * n) == 0
+s = np.frombuffer(buf, dtype=np.uint64).reshape(256, 8, NW).astype(np.float64)
 names_w = ["pro+epilogue", "bwd reads", "dma issue", "row wait", "forward", "barrier", "bwd mfma+store", "total"]
 names_h = ["pro+epilogue", "partial+FM", "L1+loss", "chain+publish", "small grads", "barrier", "prefetch", "total"]
 print("ticks are shader-clock cycles (s_memtime); mean over the 256 blocks")
@@ -39,3 +40,17 @@ for wv in range(8):
     q = s[:, wv, :].mean(0)
     nm = names_h if wv == 7 else names_w
     print(f"wave {wv}: " + "  ".join(f"{nm[i]} {q[i]:8.0f}" for i in range(8) if nm[i] != "-"))
+# per segment class: a block runs T tiles in the segments s = -2 (or -1) .. T + 1; "steady" is the sum over its
+# T - 2 segments, every other class is one segment (or the stretch in front of / behind the loop)
+classes = ["prologue", "s=-2", "s=-1", "s=0", "s=1", "steady", "s=T", "s=T+1", "epilogue"]
+T = -(-(-(-w["B"] // 16)) // 256)
+print(f"segment classes, cycles (of which in the tile barrier); steady = {T - 2} segments; mean over the 256 blocks")
+print("| wave | " + " | ".join(classes) + " | sum |")
+print("|---|" + "---:|" * (len(classes) + 1))
+for wv in (7, 0, 3, 4):
+    q = s[:, wv, :].mean(0)
+    c, b = q[8:17], q[17:26]
+    print(f"| {'head' if wv == 7 else wv} | " + " | ".join(f"{c[i]:,.0f} ({b[i]:,.0f})" for i in range(9)) + f" | {c.sum():,.0f} |")
+q = s[:, 0, :].mean(0)
+print(f"worker 0: steady per segment {q[13] / max(T - 2, 1):,.0f}; outside the steady segments {q[8:17].sum() - q[13]:,.0f} "
+      f"of {q[8:17].sum():,.0f} cycles")
