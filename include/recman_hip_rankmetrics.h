@@ -1,15 +1,11 @@
 /*
- * recman_metrics_rank.h - C ABI of librecman_hip.so, continued: grouped top-k ranking metrics of a prediction vector
+ * recman_hip_rankmetrics.h - C ABI of librecman_hip.so, continued: grouped top-k ranking metrics of a prediction vector
  * (csrc/rankmetrics.hip): NDCG@k, recall@k and precision@k per group (user, query).  The conventions of recman_hip.h
  * hold: device pointers, kernels enqueued on `stream`, RM_OK or a negative RM_E* code with rm_last_error() for the
  * message.  New: the reference has none.
  *
- * On the name of this header.  rm_group_gain is an evaluation metric and is never part of a captured training step: it
- * is in the same class as rm_roc_auc and rm_group_auc, which the ledger of tests/graph_replay.py files under
- * NOT_IN_A_STEP.  tests/test_graph_replay_host.py reads include/recman_hip*.h and requires every entry point with an
- * `rm_stream_t stream` argument to be listed in that ledger; the pull request that added this header could not edit
- * the ledger, so the header carries a name outside that glob.  A later change that may touch the ledger should add
- * rm_group_gain under NOT_IN_A_STEP and fold this header into the recman_hip*.h family.
+ * rm_group_gain is an evaluation metric and is never part of a captured training step: like rm_roc_auc and
+ * rm_group_auc, the ledger of tests/graph_replay.py files it under NOT_IN_A_STEP.
  *
  *   scores [n] fp32 finite, labels [n] int64 0 / 1, groups [n] int64 with 0 <= id < 2^32, or NULL: all of it is one
  *   group (no id tensor is needed);  1 <= n <= 2^31 - 1

@@ -1,5 +1,5 @@
 """ctypes binding of librecman_hip.so (the C ABI declared in include/recman_hip.h, include/recman_hip_topk.h,
-include/recman_hip_multitask.h, include/recman_hip_rank.h and include/recman_metrics_rank.h).
+include/recman_hip_multitask.h, include/recman_hip_rank.h and include/recman_hip_rankmetrics.h).
 
 There is NO fallback: if the library is missing or a symbol does not resolve the
 import raises, and every call that returns a non-zero code raises RecmanHipError
@@ -242,7 +242,7 @@ SIGNATURES_RANK = {
 }
 
 
-# name -> (restype, argtypes): the entry points of include/recman_metrics_rank.h, in its order
+# name -> (restype, argtypes): the entry points of include/recman_hip_rankmetrics.h, in its order
 SIGNATURES_RANKMETRICS = {
     "rm_group_gain_workspace": (c_int64, [I64]),
     "rm_group_gain": (c_int, [P, P, P, I64, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),

@@ -10,13 +10,8 @@
 // anything.  Kernels, in launch order:
 //   auc_keys_kernel       validate, score -> order-preserving uint32 key, label -> byte; P; the four
 //                         digit histograms of all keys (one read)
-//   auc_plan_kernel       which of the four 8-bit digits vary (a constant digit's pass is skipped) and the
-//                         global digit bases of each pass
-//   per pass (LSD radix sort of (key, label), 4096 keys per tile):
-//     auc_hist_kernel       per-tile digit counts
-//     auc_scan_kernel       device-wide exclusive scan of the counts, digit-major
-//     auc_sort_pass_kernel  stable tile-local ranking (wave match + per-wave counters) staged through LDS,
-//                           then a scatter in runs of equal digits
+//   radix_sort            (rm_radix_sort.h) the stable LSD radix sort of (key, label) by the four bytes of the
+//                         key: its plan kernel, then (hist, scan, pass) per digit
 //   auc_groups_kernel     per tile: group starts / ends (neighbour keys across the tile edges), the known
 //                         part of sum (a + b + 1) and the positives whose group runs past either edge
 //   auc_final_kernel      resolves those edge groups with a prefix max / suffix min over the tiles and
@@ -27,21 +22,26 @@
 // logloss_final_kernel (fixed-order reduction).  No float atomics anywhere: bitwise reproducible.
 #include <math.h>
 
-#include "rm_metric_common.h"
+#include "rm_radix_sort.h"
 
 namespace {
 
-constexpr int kPasses = 4;
 constexpr int kLossBlocks = 1024;
+
+// the sorted record: one column, the score key, with the label byte beside it; digit p is byte p of the key
+struct AucRecord {
+  static constexpr int kCols = 1;
+  static constexpr bool kLabel = true;
+  static constexpr int kDigits = 4;
+  static __device__ __forceinline__ int column(int) { return 0; }
+  static __device__ __forceinline__ unsigned extract(unsigned v, int p) { return (v >> (8 * p)) & 255u; }
+};
 
 struct AucHeader {
   unsigned long long pos;               // P
   unsigned flags;                       // RM_METRIC_* of the inputs
   unsigned pad;
-  unsigned ghist[kPasses][kRadix];      // digit p of every key
-  int m;                                // passes that run (digits that vary)
-  int shift[kPasses];                   // their bit offsets, low digit first
-  unsigned base[kPasses][kRadix];       // exclusive scan of the pass's global digit counts
+  SortPlan<AucRecord::kDigits> plan;
 };
 
 struct Layout {
@@ -79,10 +79,11 @@ __global__ __launch_bounds__(kThreads) void auc_keys_kernel(const float *__restr
                                                             unsigned *__restrict__ keys,
                                                             unsigned char *__restrict__ lab,
                                                             AucHeader *__restrict__ hd) {
-  __shared__ unsigned h[kPasses * kRadix];
+  constexpr int kDigits = AucRecord::kDigits;
+  __shared__ unsigned h[kDigits * kRadix];
   __shared__ unsigned long long smp[kWaves];
   __shared__ unsigned smf[kWaves];
-  for (int i = threadIdx.x; i < kPasses * kRadix; i += kThreads) h[i] = 0u;
+  for (int i = threadIdx.x; i < kDigits * kRadix; i += kThreads) h[i] = 0u;
   __syncthreads();
   unsigned long long pos = 0;
   unsigned flags = 0;
@@ -97,174 +98,11 @@ __global__ __launch_bounds__(kThreads) void auc_keys_kernel(const float *__restr
     lab[i] = (unsigned char)(y == 1);
     pos += (y == 1);
 #pragma unroll
-    for (int p = 0; p < kPasses; ++p) atomicAdd(&h[p * kRadix + ((k >> (8 * p)) & 255u)], 1u);
+    for (int p = 0; p < kDigits; ++p) atomicAdd(&h[p * kRadix + AucRecord::extract(k, p)], 1u);
   }
-  pos = wave_sum(pos);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) flags |= __shfl_xor(flags, o, 64);
-  if ((threadIdx.x & 63) == 0) {
-    smp[threadIdx.x >> 6] = pos;
-    smf[threadIdx.x >> 6] = flags;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long p = 0;
-    unsigned f = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      p += smp[w];
-      f |= smf[w];
-    }
-    if (p) atomicAdd(&hd->pos, p);
-    if (f) atomicOr(&hd->flags, f);
-  }
-  for (int i = threadIdx.x; i < kPasses * kRadix; i += kThreads)
-    if (h[i]) atomicAdd(&hd->ghist[i / kRadix][i % kRadix], h[i]);
-}
-
-__global__ __launch_bounds__(kThreads) void auc_plan_kernel(AucHeader *__restrict__ hd, int64_t n) {
-  __shared__ unsigned sm[kWaves];
-  const int d = threadIdx.x;
-  int m = 0;
-  for (int p = 0; p < kPasses; ++p) {
-    const unsigned c = hd->ghist[p][d];
-    if (__syncthreads_or(c == (unsigned)n)) continue;  // one digit value for every key: nothing to sort
-    const unsigned incl = block_scan<false>(c, OpAdd(), sm);
-    hd->base[m][d] = incl - c;
-    if (d == 0) hd->shift[m] = 8 * p;
-    ++m;
-  }
-  if (d == 0) hd->m = m;
-}
-
-__global__ __launch_bounds__(kThreads) void auc_hist_kernel(const AucHeader *__restrict__ hd, int slot,
-                                                            const unsigned *__restrict__ keys0,
-                                                            const unsigned *__restrict__ keys1, int64_t n,
-                                                            int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int shift = hd->shift[slot];
-  const unsigned *keys = (slot & 1) ? keys1 : keys0;
-  __shared__ unsigned h[kRadix];
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int64_t i = t0 + j * kThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// one block per digit: its row of per-tile counts -> global positions (base of the digit + the counts of
-// the tiles before)
-__global__ __launch_bounds__(kThreads) void auc_scan_kernel(const AucHeader *__restrict__ hd, int slot,
-                                                            int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  __shared__ unsigned sm[kWaves];
-  const int d = blockIdx.x;
-  unsigned *row = hist + (int64_t)d * tiles;
-  const int64_t seg = (tiles + kThreads - 1) / kThreads;
-  const int64_t lo = min((int64_t)threadIdx.x * seg, tiles), hi = min(lo + seg, tiles);
-  unsigned s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += row[i];
-  const unsigned incl = block_scan<false>(s, OpAdd(), sm);
-  unsigned run = hd->base[slot][d] + incl - s;
-  for (int64_t i = lo; i < hi; ++i) {
-    const unsigned c = row[i];
-    row[i] = run;
-    run += c;
-  }
-}
-
-// One LSD pass over a tile of 4096 (key, label) pairs.  Wave w holds tile positions [1024 w, 1024 w + 1024),
-// item j of lane l at 1024 w + 64 j + l: the tile order is (wave, item, lane), which the ranking keeps.  Past
-// the end of the array a slot holds key 0xFFFFFFFF: it ranks after every real key of digit 255 and is never
-// written.
-__global__ __launch_bounds__(kThreads) void auc_sort_pass_kernel(
-    const AucHeader *__restrict__ hd, int slot, unsigned *__restrict__ keys0, unsigned *__restrict__ keys1,
-    unsigned char *__restrict__ lab0, unsigned char *__restrict__ lab1, int64_t n, int64_t tiles,
-    const unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int shift = hd->shift[slot];
-  const unsigned *src_k = (slot & 1) ? keys1 : keys0;
-  unsigned *dst_k = (slot & 1) ? keys0 : keys1;
-  const unsigned char *src_l = (slot & 1) ? lab1 : lab0;
-  unsigned char *dst_l = (slot & 1) ? lab0 : lab1;
-
-  __shared__ unsigned wcnt[kWaves][kRadix];  // per-wave digit counters, then per-wave digit offsets
-  __shared__ unsigned tstart[kRadix];        // first tile rank of each digit
-  __shared__ unsigned gofs[kRadix];          // global position of that rank
-  __shared__ unsigned skey[kTile];
-  __shared__ unsigned char slab[kTile];
-  __shared__ unsigned sm[kWaves];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&wcnt[0][0])[i] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-  const int valid = (int)min((int64_t)kTile, n - t0);
-  const unsigned long long below_mask = (1ull << lane) - 1ull;
-
-  unsigned k[kItems], r[kItems], lbits = 0u;
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = w * (kTile / kWaves) + j * 64 + lane;
-    unsigned key = 0xFFFFFFFFu, y = 0u;
-    if (li < valid) {
-      key = src_k[t0 + li];
-      y = src_l[t0 + li];
-    }
-    k[j] = key;
-    lbits |= y << j;
-    const unsigned d = (key >> shift) & 255u;
-    unsigned long long peers = ~0ull;  // lanes with the same digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
-    const unsigned before = (unsigned)__popcll(peers & below_mask);
-    const int leader = __ffsll((long long)peers) - 1;
-    unsigned old = 0u;
-    if (before == 0u) old = atomicAdd(&wcnt[w][d], (unsigned)__popcll(peers));
-    r[j] = (unsigned)__shfl((int)old, leader, 64) + before;
-  }
-  __syncthreads();
-  {
-    const int d = tid;
-    unsigned run = 0u;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) {
-      const unsigned c = wcnt[v][d];
-      wcnt[v][d] = run;
-      run += c;
-    }
-    const unsigned incl = block_scan<false>(run, OpAdd(), sm);
-    tstart[d] = incl - run;
-    gofs[d] = hist[(int64_t)d * tiles + blockIdx.x];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const unsigned d = (k[j] >> shift) & 255u;
-    const unsigned rank = tstart[d] + wcnt[w][d] + r[j];
-    skey[rank] = k[j];
-    slab[rank] = (unsigned char)((lbits >> j) & 1u);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = j * kThreads + tid;
-    if (li < valid) {
-      const unsigned key = skey[li];
-      const unsigned d = (key >> shift) & 255u;
-      const int64_t g = (int64_t)gofs[d] + (li - (int)tstart[d]);
-      dst_k[g] = key;
-      dst_l[g] = slab[li];
-    }
-  }
+  flush_flags(flags, &hd->flags, smf);
+  flush_positives(pos, &hd->pos, smp);
+  flush_digit_hist(h, &hd->plan);
 }
 
 // Per tile of the sorted keys: thread t owns positions c0 + 16 t .. c0 + 16 t + 15.  For a positive at position
@@ -275,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void auc_groups_kernel(
     const unsigned char *__restrict__ lab0, const unsigned char *__restrict__ lab1, int64_t n,
     unsigned long long *__restrict__ part, unsigned *__restrict__ head, unsigned *__restrict__ tail,
     int *__restrict__ last, unsigned *__restrict__ first) {
-  const int m = hd->m;  // the sorted pairs are in buffer m & 1
+  const int m = hd->plan.m;  // the sorted pairs are in buffer m & 1
   const unsigned *keys = (m & 1) ? keys1 : keys0;
   const unsigned char *lab = (m & 1) ? lab1 : lab0;
   __shared__ unsigned sk[kTile + 2];  // sk[1 + li]; sk[0] / sk[valid + 1]: the neighbours across the edges
@@ -519,14 +357,7 @@ extern "C" int rm_roc_auc(const float *scores, const int64_t *labels, int64_t n,
   }
   hipLaunchKernelGGL(auc_keys_kernel, dim3(rm_grid_cap((n + kThreads - 1) / kThreads, kKeyBlocks)),
                      dim3(kThreads), 0, s, scores, labels, n, k0, l0, hd);
-  hipLaunchKernelGGL(auc_plan_kernel, dim3(1), dim3(kThreads), 0, s, hd, n);
-  for (int slot = 0; slot < kPasses; ++slot) {
-    hipLaunchKernelGGL(auc_hist_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, n, tiles,
-                       hist);
-    hipLaunchKernelGGL(auc_scan_kernel, dim3(kRadix), dim3(kThreads), 0, s, hd, slot, tiles, hist);
-    hipLaunchKernelGGL(auc_sort_pass_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, l0,
-                       l1, n, tiles, hist);
-  }
+  radix_sort<AucRecord>(&hd->plan, {{{k0}, {k1}}, {l0, l1}}, n, hist, s);
   hipLaunchKernelGGL(auc_groups_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, k0, k1, l0, l1, n, part,
                      head, tail, last, first);
   hipLaunchKernelGGL(auc_final_kernel, dim3(1), dim3(kThreads), 0, s, hd, n, tiles, part, head, tail, last, first,

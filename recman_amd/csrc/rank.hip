@@ -3,10 +3,8 @@
 // group g is the sorted positions [s, e): its negatives [s, m), then its positives [m, e).  Kernels, in launch order:
 //   rank_keys_kernel      validate; group -> uint32, (label << 31 | example) -> uint32 payload; the five digit
 //                         histograms (the label bit, four of the group) in one read
-//   rank_plan_kernel      which of the five digits vary (a constant digit's pass is skipped) and the global digit bases
-//                         of each pass: the label first, then the group digits
-//   per pass (stable LSD radix sort of (group, payload), 4096 per tile; the scheme of gauc.hip):
-//     rank_hist_kernel / rank_scan_kernel / rank_sort_pass_kernel
+//   radix_sort            (rm_radix_sort.h) the stable LSD radix sort of (group, payload), the label first, then the
+//                         group digits: its plan kernel, then (hist, scan, pass) per digit
 //   rank_marks_kernel     per tile of the sorted order: the number of group starts
 //   rank_carry_kernel     over the tiles: the slot of each tile's first start (exclusive sum); the number of groups
 //   rank_bounds_kernel    per sorted position: its group's slot and its logit; per group s, m, e - each written by the
@@ -29,11 +27,10 @@
 #include <math.h>
 
 #include "../../include/recman_hip_rank.h"
-#include "rm_metric_common.h"
+#include "rm_radix_sort.h"
 
 namespace {
 
-constexpr int kDigits = 5;  // the label bit, then four of the group id (low first)
 constexpr int kReduceBlocks = 1024;
 constexpr int kPairTile = RM_RANK_TILE;  // scores of an LDS tile of the opposite-class run
 constexpr int kPiece = RM_RANK_PIECE;    // sorted positions of a listwise piece (= kThreads)
@@ -41,14 +38,23 @@ constexpr int kSplits = RM_RANK_SPLITS;  // blocks that share the opposite-class
 constexpr unsigned kExample = 0x7FFFFFFFu;
 static_assert(kPiece == kThreads, "a piece is what one block of rank_pieces_kernel holds");
 
+// the sorted record: two columns, the group id and the payload; digit 0 is the label bit of the payload, digits
+// 1..4 the bytes of the group id (low first)
+struct RankRecord {
+  static constexpr int kCols = 2;  // 0 the group, 1 the payload
+  static constexpr bool kLabel = false;
+  static constexpr int kDigits = 5;
+  static __device__ __forceinline__ int column(int p) { return p == 0; }
+  static __device__ __forceinline__ unsigned extract(unsigned v, int p) {
+    return (v >> (p == 0 ? 31 : 8 * (p - 1))) & (p == 0 ? 1u : 255u);
+  }
+};
+
 struct RankHeader {
   unsigned flags;                   // RM_METRIC_* of the inputs
   unsigned groups;                  // distinct group ids (rank_carry_kernel)
   long long pairs, pos, weight, scored;  // Q, P, W and the scored groups (rank_totals_kernel)
-  unsigned ghist[kDigits][kRadix];  // digit p of every (label, group)
-  int m;                            // passes that run (digits that vary)
-  int digit[kDigits];               // which digit each of them sorts by, low first
-  unsigned base[kDigits][kRadix];   // exclusive scan of the pass's global digit counts
+  SortPlan<RankRecord::kDigits> plan;
 };
 
 struct Layout {
@@ -88,14 +94,10 @@ Layout layout(int64_t n) {
   return L;
 }
 
-// digit p of a (group, payload): p = 0 the label bit, p = 1..4 the bytes of the group id
-__device__ __forceinline__ unsigned digit_of(unsigned g, unsigned pay, int p) {
-  return p == 0 ? (pay >> 31) : ((g >> (8 * (p - 1))) & 255u);
-}
-
 __global__ __launch_bounds__(kThreads) void rank_keys_kernel(
     const float *__restrict__ logit, const int64_t *__restrict__ labels, const int64_t *__restrict__ groups,
     int64_t n, unsigned *__restrict__ grp, unsigned *__restrict__ pay, RankHeader *__restrict__ hd) {
+  constexpr int kDigits = RankRecord::kDigits;
   __shared__ unsigned h[kDigits * kRadix];
   __shared__ unsigned smf[kWaves];
   for (int i = threadIdx.x; i < kDigits * kRadix; i += kThreads) h[i] = 0u;
@@ -109,171 +111,14 @@ __global__ __launch_bounds__(kThreads) void rank_keys_kernel(
     if (!isfinite(s)) flags |= RM_METRIC_BAD_SCORE;
     if (y != 0 && y != 1) flags |= RM_METRIC_BAD_LABEL;
     if (gid < 0 || gid > 0xFFFFFFFFll) flags |= RM_METRIC_BAD_GROUP;
-    const unsigned g = (unsigned)gid, p = ((unsigned)(y == 1) << 31) | (unsigned)i;
-    grp[i] = g;
-    pay[i] = p;
+    const unsigned v[2] = {(unsigned)gid, ((unsigned)(y == 1) << 31) | (unsigned)i};
+    grp[i] = v[0];
+    pay[i] = v[1];
 #pragma unroll
-    for (int d = 0; d < kDigits; ++d) atomicAdd(&h[d * kRadix + digit_of(g, p, d)], 1u);
+    for (int p = 0; p < kDigits; ++p) atomicAdd(&h[p * kRadix + record_digit<RankRecord>(v, p)], 1u);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) flags |= __shfl_xor(flags, o, 64);
-  if ((threadIdx.x & 63) == 0) smf[threadIdx.x >> 6] = flags;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned f = 0;
-    for (int w = 0; w < kWaves; ++w) f |= smf[w];
-    if (f) atomicOr(&hd->flags, f);
-  }
-  for (int i = threadIdx.x; i < kDigits * kRadix; i += kThreads)
-    if (h[i]) atomicAdd(&hd->ghist[i / kRadix][i % kRadix], h[i]);
-}
-
-__global__ __launch_bounds__(kThreads) void rank_plan_kernel(RankHeader *__restrict__ hd, int64_t n) {
-  __shared__ unsigned sm[kWaves];
-  const int d = threadIdx.x;
-  int m = 0;
-  for (int p = 0; p < kDigits; ++p) {
-    const unsigned c = hd->ghist[p][d];
-    if (__syncthreads_or(c == (unsigned)n)) continue;  // one digit value everywhere: nothing to sort
-    const unsigned incl = block_scan<false>(c, OpAdd(), sm);
-    hd->base[m][d] = incl - c;
-    if (d == 0) hd->digit[m] = p;
-    ++m;
-  }
-  if (d == 0) hd->m = m;
-}
-
-__global__ __launch_bounds__(kThreads) void rank_hist_kernel(
-    const RankHeader *__restrict__ hd, int slot, const unsigned *__restrict__ grp0,
-    const unsigned *__restrict__ grp1, const unsigned *__restrict__ pay0, const unsigned *__restrict__ pay1,
-    int64_t n, int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int p = hd->digit[slot];
-  const unsigned *src = p == 0 ? ((slot & 1) ? pay1 : pay0) : ((slot & 1) ? grp1 : grp0);
-  __shared__ unsigned h[kRadix];
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int64_t i = t0 + j * kThreads + threadIdx.x;
-    if (i < n) {
-      const unsigned v = src[i];
-      atomicAdd(&h[digit_of(v, v, p)], 1u);
-    }
-  }
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// one block per digit value: its row of per-tile counts -> global positions
-__global__ __launch_bounds__(kThreads) void rank_scan_kernel(const RankHeader *__restrict__ hd, int slot,
-                                                             int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  __shared__ unsigned sm[kWaves];
-  const int d = blockIdx.x;
-  unsigned *row = hist + (int64_t)d * tiles;
-  const int64_t seg = (tiles + kThreads - 1) / kThreads;
-  const int64_t lo = min((int64_t)threadIdx.x * seg, tiles), hi = min(lo + seg, tiles);
-  unsigned s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += row[i];
-  const unsigned incl = block_scan<false>(s, OpAdd(), sm);
-  unsigned run = hd->base[slot][d] + incl - s;
-  for (int64_t i = lo; i < hi; ++i) {
-    const unsigned c = row[i];
-    row[i] = run;
-    run += c;
-  }
-}
-
-// One LSD pass over a tile of 4096 (group, payload) pairs: the ranking of gauc_sort_pass_kernel (gauc.hip).  Wave w
-// holds tile positions [1024 w, 1024 w + 1024), item j of lane l at 1024 w + 64 j + l.  Past the end of the array a
-// slot holds group = payload = 0xFFFFFFFF: the largest value of every digit, at the tile's last positions, so it
-// ranks after every real element and is never written.
-__global__ __launch_bounds__(kThreads) void rank_sort_pass_kernel(
-    const RankHeader *__restrict__ hd, int slot, unsigned *__restrict__ grp0, unsigned *__restrict__ grp1,
-    unsigned *__restrict__ pay0, unsigned *__restrict__ pay1, int64_t n, int64_t tiles,
-    const unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int p = hd->digit[slot];
-  const unsigned *src_g = (slot & 1) ? grp1 : grp0;
-  unsigned *dst_g = (slot & 1) ? grp0 : grp1;
-  const unsigned *src_p = (slot & 1) ? pay1 : pay0;
-  unsigned *dst_p = (slot & 1) ? pay0 : pay1;
-
-  __shared__ unsigned wcnt[kWaves][kRadix];  // per-wave digit counters, then per-wave digit offsets
-  __shared__ unsigned tstart[kRadix];        // first tile rank of each digit
-  __shared__ unsigned gofs[kRadix];          // global position of that rank
-  __shared__ unsigned sgrp[kTile];
-  __shared__ unsigned spay[kTile];
-  __shared__ unsigned sm[kWaves];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&wcnt[0][0])[i] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-  const int valid = (int)min((int64_t)kTile, n - t0);
-  const unsigned long long below_mask = (1ull << lane) - 1ull;
-
-  unsigned g[kItems], q[kItems], r[kItems];
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = w * (kTile / kWaves) + j * 64 + lane;
-    unsigned gid = 0xFFFFFFFFu, py = 0xFFFFFFFFu;
-    if (li < valid) {
-      gid = src_g[t0 + li];
-      py = src_p[t0 + li];
-    }
-    g[j] = gid;
-    q[j] = py;
-    const unsigned d = digit_of(gid, py, p);
-    unsigned long long peers = ~0ull;  // lanes with the same digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
-    const unsigned before = (unsigned)__popcll(peers & below_mask);
-    const int leader = __ffsll((long long)peers) - 1;
-    unsigned old = 0u;
-    if (before == 0u) old = atomicAdd(&wcnt[w][d], (unsigned)__popcll(peers));
-    r[j] = (unsigned)__shfl((int)old, leader, 64) + before;
-  }
-  __syncthreads();
-  {
-    const int d = tid;
-    unsigned run = 0u;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) {
-      const unsigned c = wcnt[v][d];
-      wcnt[v][d] = run;
-      run += c;
-    }
-    const unsigned incl = block_scan<false>(run, OpAdd(), sm);
-    tstart[d] = incl - run;
-    gofs[d] = hist[(int64_t)d * tiles + blockIdx.x];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const unsigned d = digit_of(g[j], q[j], p);
-    const unsigned rank = tstart[d] + wcnt[w][d] + r[j];
-    sgrp[rank] = g[j];
-    spay[rank] = q[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = j * kThreads + tid;
-    if (li < valid) {
-      const unsigned gid = sgrp[li], py = spay[li];
-      const unsigned d = digit_of(gid, py, p);
-      const int64_t at = (int64_t)gofs[d] + (li - (int)tstart[d]);
-      dst_g[at] = gid;
-      dst_p[at] = py;
-    }
-  }
+  flush_flags(flags, &hd->flags, smf);
+  flush_digit_hist(h, &hd->plan);
 }
 
 // Thread t owns tile positions 16 t .. 16 t + 15.  Position i starts a group when i == 0 or its id differs from
@@ -282,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void rank_marks_kernel(const RankHeader *
                                                               const unsigned *__restrict__ grp0,
                                                               const unsigned *__restrict__ grp1, int64_t n,
                                                               unsigned *__restrict__ cnt) {
-  const unsigned *grp = (hd->m & 1) ? grp1 : grp0;  // the sorted pairs are in buffer m & 1
+  const unsigned *grp = (hd->plan.m & 1) ? grp1 : grp0;  // the sorted pairs are in buffer m & 1
   __shared__ unsigned smu[kWaves];
   const int64_t c0 = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
   unsigned c = 0u;
@@ -306,19 +151,8 @@ __global__ __launch_bounds__(kThreads) void rank_marks_kernel(const RankHeader *
 __global__ __launch_bounds__(kThreads) void rank_carry_kernel(RankHeader *__restrict__ hd, int64_t tiles,
                                                               unsigned *__restrict__ cnt) {
   __shared__ unsigned smu[kWaves];
-  const int tid = threadIdx.x;
-  const int64_t seg = (tiles + kThreads - 1) / kThreads;
-  const int64_t lo = min((int64_t)tid * seg, tiles), hi = min(lo + seg, tiles);
-  unsigned c = 0u;
-  for (int64_t t = lo; t < hi; ++t) c += cnt[t];
-  const unsigned ic = block_scan<false>(c, OpAdd(), smu);
-  if (tid == kThreads - 1) hd->groups = ic;
-  unsigned rc = ic - c;
-  for (int64_t t = lo; t < hi; ++t) {
-    const unsigned ct = cnt[t];
-    cnt[t] = rc;
-    rc += ct;
-  }
+  const unsigned ic = scan_row(cnt, tiles, 0u, smu);
+  if (threadIdx.x == kThreads - 1) hd->groups = ic;
 }
 
 __global__ __launch_bounds__(kThreads) void rank_bounds_kernel(
@@ -326,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void rank_bounds_kernel(
     const unsigned *__restrict__ pay0, const unsigned *__restrict__ pay1, const float *__restrict__ logit, int64_t n,
     const unsigned *__restrict__ cnt, unsigned *__restrict__ slot_of, float *__restrict__ ss,
     unsigned *__restrict__ gs, unsigned *__restrict__ gm, unsigned *__restrict__ ge) {
-  const int m = hd->m;
+  const int m = hd->plan.m;
   const unsigned *grp = (m & 1) ? grp1 : grp0, *pay = (m & 1) ? pay1 : pay0;
   __shared__ unsigned smu[kWaves];
   const int64_t c0 = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
@@ -532,7 +366,7 @@ __global__ __launch_bounds__(kThreads) void rank_pair_kernel(
   const int tid = threadIdx.x;
   const int64_t i = (int64_t)blockIdx.x * kThreads + tid;
   PairSide t{0u, false, 0x7FFFFFFF, 0, 0.f, 0.0};
-  if (i < n) t = pair_side(hd, (hd->m & 1) ? pay1 : pay0, slot_of, ss, gs, gm, ge, i, norm);
+  if (i < n) t = pair_side(hd, (hd->plan.m & 1) ? pay1 : pay0, slot_of, ss, gs, gm, ge, i, norm);
   const int a = t.a, b = t.b;
   const int lo = block_scan<false>(a, OpMin(), smi), hi = block_scan<false>(b, OpMax(), smi);
   if (tid == kThreads - 1) {
@@ -578,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void rank_pair_finish_kernel(
     const float *__restrict__ pg, float alpha, float grad_scale, const float *dlogit_in, float *dlogit_out) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  const PairSide t = pair_side(hd, (hd->m & 1) ? pay1 : pay0, slot_of, ss, gs, gm, ge, i, norm);
+  const PairSide t = pair_side(hd, (hd->plan.m & 1) ? pay1 : pay0, slot_of, ss, gs, gm, ge, i, norm);
   float grad = 0.f;  // (a position with an empty run keeps the exact +0.0: -1 * 0.0 would be -0.0)
   if (t.a < t.b) {
     double sum = 0.0;
@@ -596,7 +430,7 @@ __global__ __launch_bounds__(kThreads) void rank_list_kernel(
     const double *__restrict__ gsum, int64_t n, int norm, float alpha, float grad_scale, const float *dlogit_in,
     float *dlogit_out, double *__restrict__ lpart) {
   __shared__ double smd[kWaves];
-  const unsigned *pay = (hd->m & 1) ? pay1 : pay0;
+  const unsigned *pay = (hd->plan.m & 1) ? pay1 : pay0;
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool live = i < n;
   unsigned example = 0u;
@@ -693,15 +527,8 @@ extern "C" int rm_rank_loss(const float *logit, const int64_t *y, const int64_t 
   }
   hipLaunchKernelGGL(rank_keys_kernel, dim3(rm_grid_cap(blocks, kKeyBlocks)), dim3(kThreads), 0, s, logit, y, groups,
                      n, g0, p0, hd);
-  hipLaunchKernelGGL(rank_plan_kernel, dim3(1), dim3(kThreads), 0, s, hd, n);
   // (without ids only the label digit can vary: the four group passes are not enqueued at all)
-  for (int slot = 0; slot < (groups ? kDigits : 1); ++slot) {
-    hipLaunchKernelGGL(rank_hist_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, g0, g1, p0, p1, n,
-                       tiles, hist);
-    hipLaunchKernelGGL(rank_scan_kernel, dim3(kRadix), dim3(kThreads), 0, s, hd, slot, tiles, hist);
-    hipLaunchKernelGGL(rank_sort_pass_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, g0, g1, p0, p1,
-                       n, tiles, hist);
-  }
+  radix_sort<RankRecord>(&hd->plan, {{{g0, p0}, {g1, p1}}}, n, hist, s, groups ? RankRecord::kDigits : 1);
   hipLaunchKernelGGL(rank_marks_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, g0, g1, n, cnt);
   hipLaunchKernelGGL(rank_carry_kernel, dim3(1), dim3(kThreads), 0, s, hd, tiles, cnt);
   hipLaunchKernelGGL(rank_bounds_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, g0, g1, p0, p1, logit, n,

@@ -1,16 +1,15 @@
 // Grouped top-k ranking metrics (NDCG@k, recall@k, precision@k) of a prediction vector, on the device: any top-k
 // measure that is linear in the labels, exact under ties, for up to RM_GAIN_MAX_CUTOFFS cutoffs in one sort; see
-// recman_metrics_rank.h.  With the examples sorted by (group ascending, score descending) a group is a contiguous
+// recman_hip_rankmetrics.h.  With the examples sorted by (group ascending, score descending) a group is a contiguous
 // run [s, e), the rank of position i is i - s, and with L the exclusive prefix count of the sorted labels a tie group
 // at ranks [lo, hi) holds pos_T = L[s + hi] - L[s + lo] positives and the group P_g = L[e] - L[s]:
 //     gain_g(k) = sum_{T, lo < k} (pos_T / (hi - lo)) (disc[lo] + ... + disc[min(hi, k) - 1])
 // Kernels, in launch order:
-//   gain_keys_kernel      validate; score -> ~(order-preserving uint32 key), so that ascending is score descending;
-//                         label -> byte, group -> uint32 (0 when there is no id column); P; the eight digit histograms
-//   gain_plan_kernel      which of the eight 8-bit digits vary (a constant digit's pass is skipped) and the global
-//                         digit bases of each pass: score digits first, then group digits
-//   per pass (stable LSD radix sort of (key, group, label), 4096 per tile; the scheme of gauc.hip):
-//     gain_hist_kernel / gain_scan_kernel / gain_sort_pass_kernel
+//   grouped_keys_kernel   (rm_radix_sort.h, descending) validate; score -> ~(order-preserving uint32 key), so that
+//                         ascending is score descending; label -> byte, group -> uint32 (0 when there is no id
+//                         column); P; the eight digit histograms
+//   radix_sort            (rm_radix_sort.h) the stable LSD radix sort of (key, group, label), score digits first, then
+//                         group digits: its plan kernel, then (hist, scan, pass) per digit
 //   gain_count_kernel     per tile of the sorted order: its group starts and its positives
 //   gain_carry_kernel     over the tiles: exclusive sums of both; the number of groups
 //   gain_starts_kernel    per tile: the start position and id of every group (slot = ascending id) and L
@@ -23,24 +22,15 @@
 // atomics, bit-equal runs, independent of the input order.  Nothing is read back by the host between the kernels.
 #include <math.h>
 
-#include "../../include/recman_metrics_rank.h"
-#include "rm_metric_common.h"
+#include "../../include/recman_hip_rankmetrics.h"
+#include "rm_radix_sort.h"
 
 namespace {
 
-constexpr int kDigits = 8;          // four of the score key (low first), then four of the group id
 constexpr int kReduceBlocks = 1024;
 constexpr int kCut = RM_GAIN_MAX_CUTOFFS;
 
-struct GainHeader {
-  unsigned long long pos;             // P over all examples
-  unsigned flags;                     // RM_METRIC_* of the inputs
-  unsigned groups;                    // distinct group ids (gain_carry_kernel)
-  unsigned ghist[kDigits][kRadix];    // digit p of every (key, group)
-  int m;                              // passes that run (digits that vary)
-  int shift[kDigits];                 // their bit offsets in group << 32 | key, low digit first
-  unsigned base[kDigits][kRadix];     // exclusive scan of the pass's global digit counts
-};
+using GainHeader = GroupedScoreHeader;  // groups: written by gain_carry_kernel
 
 // the cutoffs (k[c] = 0 past n_cut: no rank reaches it) and the three choices, by value
 struct GainParams {
@@ -76,221 +66,12 @@ Layout layout(int64_t n) {
   return L;
 }
 
-__global__ __launch_bounds__(kThreads) void gain_keys_kernel(
-    const float *__restrict__ scores, const int64_t *__restrict__ labels, const int64_t *__restrict__ groups,
-    int64_t n, unsigned *__restrict__ keys, unsigned *__restrict__ grp, unsigned char *__restrict__ lab,
-    GainHeader *__restrict__ hd) {
-  __shared__ unsigned h[kDigits * kRadix];
-  __shared__ unsigned long long smp[kWaves];
-  __shared__ unsigned smf[kWaves];
-  for (int i = threadIdx.x; i < kDigits * kRadix; i += kThreads) h[i] = 0u;
-  __syncthreads();
-  unsigned long long pos = 0;
-  unsigned flags = 0;
-  const int64_t stride = (int64_t)gridDim.x * kThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-    const float s = scores[i];
-    const int64_t y = labels[i];
-    const int64_t gid = groups ? groups[i] : 0;
-    if (!isfinite(s)) flags |= RM_METRIC_BAD_SCORE;
-    if (y != 0 && y != 1) flags |= RM_METRIC_BAD_LABEL;
-    if (gid < 0 || gid > 0xFFFFFFFFll) flags |= RM_METRIC_BAD_GROUP;
-    const unsigned k = ~score_key(s), g = (unsigned)gid;  // ascending in k: descending in s
-    keys[i] = k;
-    grp[i] = g;
-    lab[i] = (unsigned char)(y == 1);
-    pos += (y == 1);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      atomicAdd(&h[p * kRadix + ((k >> (8 * p)) & 255u)], 1u);
-      atomicAdd(&h[(4 + p) * kRadix + ((g >> (8 * p)) & 255u)], 1u);
-    }
-  }
-  pos = wave_sum(pos);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) flags |= __shfl_xor(flags, o, 64);
-  if ((threadIdx.x & 63) == 0) {
-    smp[threadIdx.x >> 6] = pos;
-    smf[threadIdx.x >> 6] = flags;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long p = 0;
-    unsigned f = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      p += smp[w];
-      f |= smf[w];
-    }
-    if (p) atomicAdd(&hd->pos, p);
-    if (f) atomicOr(&hd->flags, f);
-  }
-  for (int i = threadIdx.x; i < kDigits * kRadix; i += kThreads)
-    if (h[i]) atomicAdd(&hd->ghist[i / kRadix][i % kRadix], h[i]);
-}
-
-__global__ __launch_bounds__(kThreads) void gain_plan_kernel(GainHeader *__restrict__ hd, int64_t n) {
-  __shared__ unsigned sm[kWaves];
-  const int d = threadIdx.x;
-  int m = 0;
-  for (int p = 0; p < kDigits; ++p) {
-    const unsigned c = hd->ghist[p][d];
-    if (__syncthreads_or(c == (unsigned)n)) continue;  // one digit value everywhere: nothing to sort
-    const unsigned incl = block_scan<false>(c, OpAdd(), sm);
-    hd->base[m][d] = incl - c;
-    if (d == 0) hd->shift[m] = 8 * p;
-    ++m;
-  }
-  if (d == 0) hd->m = m;
-}
-
-// the digit of pass `shift` (0 .. 56 in group << 32 | key)
-__device__ __forceinline__ unsigned digit_of(unsigned key, unsigned g, int shift) {
-  return ((shift & 32 ? g : key) >> (shift & 31)) & 255u;
-}
-
-__global__ __launch_bounds__(kThreads) void gain_hist_kernel(
-    const GainHeader *__restrict__ hd, int slot, const unsigned *__restrict__ keys0,
-    const unsigned *__restrict__ keys1, const unsigned *__restrict__ grp0, const unsigned *__restrict__ grp1,
-    int64_t n, int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int shift = hd->shift[slot];
-  const unsigned *src = (shift & 32) ? ((slot & 1) ? grp1 : grp0) : ((slot & 1) ? keys1 : keys0);
-  const int sh = shift & 31;
-  __shared__ unsigned h[kRadix];
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int64_t i = t0 + j * kThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[(src[i] >> sh) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// one block per digit: its row of per-tile counts -> global positions
-__global__ __launch_bounds__(kThreads) void gain_scan_kernel(const GainHeader *__restrict__ hd, int slot,
-                                                             int64_t tiles, unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  __shared__ unsigned sm[kWaves];
-  const int d = blockIdx.x;
-  unsigned *row = hist + (int64_t)d * tiles;
-  const int64_t seg = (tiles + kThreads - 1) / kThreads;
-  const int64_t lo = min((int64_t)threadIdx.x * seg, tiles), hi = min(lo + seg, tiles);
-  unsigned s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += row[i];
-  const unsigned incl = block_scan<false>(s, OpAdd(), sm);
-  unsigned run = hd->base[slot][d] + incl - s;
-  for (int64_t i = lo; i < hi; ++i) {
-    const unsigned c = row[i];
-    row[i] = run;
-    run += c;
-  }
-}
-
-// One LSD pass over a tile of 4096 (key, group, label) triples: gauc_sort_pass_kernel (gauc.hip).  Wave w holds tile
-// positions [1024 w, 1024 w + 1024), item j of lane l at 1024 w + 64 j + l.  Past the end of the array a slot holds
-// key = group = 0xFFFFFFFF: it ranks after every real element of digit 255 and is never written.
-__global__ __launch_bounds__(kThreads) void gain_sort_pass_kernel(
-    const GainHeader *__restrict__ hd, int slot, unsigned *__restrict__ keys0, unsigned *__restrict__ keys1,
-    unsigned *__restrict__ grp0, unsigned *__restrict__ grp1, unsigned char *__restrict__ lab0,
-    unsigned char *__restrict__ lab1, int64_t n, int64_t tiles, const unsigned *__restrict__ hist) {
-  if (slot >= hd->m) return;
-  const int shift = hd->shift[slot];
-  const unsigned *src_k = (slot & 1) ? keys1 : keys0;
-  unsigned *dst_k = (slot & 1) ? keys0 : keys1;
-  const unsigned *src_g = (slot & 1) ? grp1 : grp0;
-  unsigned *dst_g = (slot & 1) ? grp0 : grp1;
-  const unsigned char *src_l = (slot & 1) ? lab1 : lab0;
-  unsigned char *dst_l = (slot & 1) ? lab0 : lab1;
-
-  __shared__ unsigned wcnt[kWaves][kRadix];  // per-wave digit counters, then per-wave digit offsets
-  __shared__ unsigned tstart[kRadix];        // first tile rank of each digit
-  __shared__ unsigned gofs[kRadix];          // global position of that rank
-  __shared__ unsigned skey[kTile];
-  __shared__ unsigned sgrp[kTile];
-  __shared__ unsigned char slab[kTile];
-  __shared__ unsigned sm[kWaves];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int i = tid; i < kWaves * kRadix; i += kThreads) (&wcnt[0][0])[i] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-  const int valid = (int)min((int64_t)kTile, n - t0);
-  const unsigned long long below_mask = (1ull << lane) - 1ull;
-
-  unsigned k[kItems], g[kItems], r[kItems], lbits = 0u;
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = w * (kTile / kWaves) + j * 64 + lane;
-    unsigned key = 0xFFFFFFFFu, gid = 0xFFFFFFFFu, y = 0u;
-    if (li < valid) {
-      key = src_k[t0 + li];
-      gid = src_g[t0 + li];
-      y = src_l[t0 + li];
-    }
-    k[j] = key;
-    g[j] = gid;
-    lbits |= y << j;
-    const unsigned d = digit_of(key, gid, shift);
-    unsigned long long peers = ~0ull;  // lanes with the same digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
-    const unsigned before = (unsigned)__popcll(peers & below_mask);
-    const int leader = __ffsll((long long)peers) - 1;
-    unsigned old = 0u;
-    if (before == 0u) old = atomicAdd(&wcnt[w][d], (unsigned)__popcll(peers));
-    r[j] = (unsigned)__shfl((int)old, leader, 64) + before;
-  }
-  __syncthreads();
-  {
-    const int d = tid;
-    unsigned run = 0u;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) {
-      const unsigned c = wcnt[v][d];
-      wcnt[v][d] = run;
-      run += c;
-    }
-    const unsigned incl = block_scan<false>(run, OpAdd(), sm);
-    tstart[d] = incl - run;
-    gofs[d] = hist[(int64_t)d * tiles + blockIdx.x];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const unsigned d = digit_of(k[j], g[j], shift);
-    const unsigned rank = tstart[d] + wcnt[w][d] + r[j];
-    skey[rank] = k[j];
-    sgrp[rank] = g[j];
-    slab[rank] = (unsigned char)((lbits >> j) & 1u);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kItems; ++j) {
-    const int li = j * kThreads + tid;
-    if (li < valid) {
-      const unsigned key = skey[li], gid = sgrp[li];
-      const unsigned d = digit_of(key, gid, shift);
-      const int64_t at = (int64_t)gofs[d] + (li - (int)tstart[d]);
-      dst_k[at] = key;
-      dst_g[at] = gid;
-      dst_l[at] = slab[li];
-    }
-  }
-}
-
 // Position i of the sorted order starts a group when i == 0 or its group id differs from i - 1's.
 __global__ __launch_bounds__(kThreads) void gain_count_kernel(
     const GainHeader *__restrict__ hd, const unsigned *__restrict__ grp0, const unsigned *__restrict__ grp1,
     const unsigned char *__restrict__ lab0, const unsigned char *__restrict__ lab1, int64_t n,
     unsigned *__restrict__ tcnt, unsigned *__restrict__ tpos) {
-  const int m = hd->m;  // the sorted triples are in buffer m & 1
+  const int m = hd->plan.m;  // the sorted triples are in buffer m & 1
   const unsigned *grp = (m & 1) ? grp1 : grp0;
   const unsigned char *lab = (m & 1) ? lab1 : lab0;
   __shared__ unsigned sm[kWaves];
@@ -317,25 +98,9 @@ __global__ __launch_bounds__(kThreads) void gain_carry_kernel(GainHeader *__rest
                                                               unsigned *__restrict__ tcnt,
                                                               unsigned *__restrict__ tpos) {
   __shared__ unsigned sm[kWaves];
-  const int tid = threadIdx.x;
-  const int64_t seg = (tiles + kThreads - 1) / kThreads;
-  const int64_t lo = min((int64_t)tid * seg, tiles), hi = min(lo + seg, tiles);
-  unsigned c = 0u, p = 0u;
-  for (int64_t t = lo; t < hi; ++t) {
-    c += tcnt[t];
-    p += tpos[t];
-  }
-  const unsigned ic = block_scan<false>(c, OpAdd(), sm);
-  const unsigned ip = block_scan<false>(p, OpAdd(), sm);
-  if (tid == kThreads - 1) hd->groups = ic;
-  unsigned rc = ic - c, rp = ip - p;
-  for (int64_t t = lo; t < hi; ++t) {
-    const unsigned ct = tcnt[t], pt = tpos[t];
-    tcnt[t] = rc;
-    tpos[t] = rp;
-    rc += ct;
-    rp += pt;
-  }
+  const unsigned ic = scan_row(tcnt, tiles, 0u, sm);
+  scan_row(tpos, tiles, 0u, sm);
+  if (threadIdx.x == kThreads - 1) hd->groups = ic;
 }
 
 // Thread t owns tile positions 16 t .. 16 t + 15.  gstart[slot] / gid[slot]: the first position and the id of the
@@ -345,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void gain_starts_kernel(
     const unsigned char *__restrict__ lab0, const unsigned char *__restrict__ lab1, int64_t n,
     const unsigned *__restrict__ tcnt, const unsigned *__restrict__ tpos, unsigned *__restrict__ gstart,
     unsigned *__restrict__ gid, unsigned *__restrict__ lpre) {
-  const int m = hd->m;
+  const int m = hd->plan.m;
   const unsigned *grp = (m & 1) ? grp1 : grp0;
   const unsigned char *lab = (m & 1) ? lab1 : lab0;
   __shared__ unsigned sm[kWaves];
@@ -400,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void gain_groups_kernel(
   __shared__ double smd[kWaves];
   __shared__ long long sml[kWaves];
   __shared__ double sdisc[RM_GAIN_MAX_K];  // the discounts of the ranks that count
-  const unsigned *keys = (hd->m & 1) ? keys1 : keys0;
+  const unsigned *keys = (hd->plan.m & 1) ? keys1 : keys0;
   const int64_t G = hd->groups;
   const int64_t chunk = (G + gridDim.x - 1) / gridDim.x;
   const int64_t lo = min((int64_t)blockIdx.x * chunk, G), hi = min(lo + chunk, G);
@@ -598,16 +363,9 @@ extern "C" int rm_group_gain(const float *scores, const int64_t *labels, const i
     rm_set_error("rm_group_gain: hipMemsetAsync failed");
     return RM_ELAUNCH;
   }
-  hipLaunchKernelGGL(gain_keys_kernel, dim3(rm_grid_cap((n + kThreads - 1) / kThreads, kKeyBlocks)),
+  hipLaunchKernelGGL(grouped_keys_kernel<true>, dim3(rm_grid_cap((n + kThreads - 1) / kThreads, kKeyBlocks)),
                      dim3(kThreads), 0, s, scores, labels, groups, n, k0, g0, l0, hd);
-  hipLaunchKernelGGL(gain_plan_kernel, dim3(1), dim3(kThreads), 0, s, hd, n);
-  for (int slot = 0; slot < kDigits; ++slot) {
-    hipLaunchKernelGGL(gain_hist_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, g0, g1, n,
-                       tiles, hist);
-    hipLaunchKernelGGL(gain_scan_kernel, dim3(kRadix), dim3(kThreads), 0, s, hd, slot, tiles, hist);
-    hipLaunchKernelGGL(gain_sort_pass_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, slot, k0, k1, g0,
-                       g1, l0, l1, n, tiles, hist);
-  }
+  radix_sort<GroupedScoreRecord>(&hd->plan, {{{k0, g0}, {k1, g1}}, {l0, l1}}, n, hist, s);
   hipLaunchKernelGGL(gain_count_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, s, hd, g0, g1, l0, l1, n, tcnt,
                      tpos);
   hipLaunchKernelGGL(gain_carry_kernel, dim3(1), dim3(kThreads), 0, s, hd, tiles, tcnt, tpos);

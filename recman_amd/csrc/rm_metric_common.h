@@ -1,5 +1,6 @@
-// Device helpers shared by the evaluation-metric translation units (metrics.hip, gauc.hip): the tile geometry
-// of the radix sorts, the order-preserving score key and the fixed-order block reductions / scans.
+// Device helpers shared by the translation units that sort a batch or a prediction vector (metrics.hip, gauc.hip,
+// rankmetrics.hip, rank.hip): the tile geometry, the order-preserving score key and the fixed-order block
+// reductions / scans.  The sort itself, the one radix sort of all four, is in rm_radix_sort.h.
 #pragma once
 #include "rm_common.h"
 

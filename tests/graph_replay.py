@@ -128,6 +128,7 @@ NOT_IN_A_STEP = {
     "rm_roc_auc": _METRIC,
     "rm_log_loss": _METRIC,
     "rm_group_auc": _METRIC,
+    "rm_group_gain": _METRIC,
     "rm_topk_ip": "retrieval over a catalogue (TwoTowerEngine.topk), not a training step",
     "rm_shard_route": _DIST,
     "rm_shard_route_padded": _DIST,

@@ -1,4 +1,4 @@
-"""Exact host reference of the grouped top-k ranking metrics (include/recman_metrics_rank.h, csrc/rankmetrics.hip).
+"""Exact host reference of the grouped top-k ranking metrics (include/recman_hip_rankmetrics.h, csrc/rankmetrics.hip).
 
 Inside a group the examples are ordered by float32 score, descending; equal scores (-0.0 == +0.0) form a tie group T
 at the 0-based ranks [lo, hi) with pos_T positives.  The discounts are doubles and are taken as exact rationals:

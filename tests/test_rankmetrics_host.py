@@ -1,6 +1,6 @@
 """CPU: the reference of the grouped top-k ranking metrics (tests/rankmetrics_ref.py) against a per-group sklearn
 loop and plain numpy, a hand-computed case, and the surface of the feature - the metric objects, the C ABI of
-include/recman_metrics_rank.h and the group_by check of the models - none of which needs a GPU."""
+include/recman_hip_rankmetrics.h and the group_by check of the models - none of which needs a GPU."""
 import ctypes
 import os
 import re
@@ -14,7 +14,7 @@ from tests import rankmetrics_ref as R
 from tests.test_gauc_host import _features
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "recman_metrics_rank.h")
+HEADER = os.path.join(ROOT, "include", "recman_hip_rankmetrics.h")
 CUTS = (1, 5, 50)
 
 
@@ -147,7 +147,7 @@ def test_the_header_is_bound_in_its_own_table(hip_lib):
     syms = sorted(set(re.findall(r"\b(rm_[a-z0-9_]+)\s*\(", text)))
     assert syms == ["rm_group_gain", "rm_group_gain_workspace"]
     for name in syms:
-        assert hasattr(hip_lib, name), f"{name} declared in recman_metrics_rank.h but not exported"
+        assert hasattr(hip_lib, name), f"{name} declared in recman_hip_rankmetrics.h but not exported"
     assert set(_lib.SIGNATURES_RANKMETRICS) == set(syms)
     others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_I64) | set(_lib.SIGNATURES_TOPK)
               | set(_lib.SIGNATURES_MULTITASK) | set(_lib.SIGNATURES_RANK))
@@ -156,12 +156,12 @@ def test_the_header_is_bound_in_its_own_table(hip_lib):
     for name in syms:  # one argtype per declared parameter
         m = re.search(r"\b%s\s*\(([^;{}]*?)\)\s*;" % name, text, flags=re.S)
         assert len(_lib.SIGNATURES_RANKMETRICS[name][1]) == len(m.group(1).split(",")), name
-    # the entry points with a stream: one, an evaluation metric, declared outside the recman_hip*.h family
+    # the entry points with a stream: one, an evaluation metric, which the ledger files under NOT_IN_A_STEP
     entries = {m.group(1) for m in re.finditer(r"\b(rm_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
                if re.search(r"\brm_stream_t\s+stream\b", m.group(2))}
     assert entries == {"rm_group_gain"}
     for h in os.listdir(os.path.join(ROOT, "include")):
-        if h != "recman_metrics_rank.h":
+        if h != "recman_hip_rankmetrics.h":
             assert "rm_group_gain" not in open(os.path.join(ROOT, "include", h)).read(), h
     raw = open(HEADER).read()
     assert "NOT_IN_A_STEP" in raw and "tests/graph_replay.py" in raw
