@@ -1211,7 +1211,7 @@ int rm_group_auc(const float *scores, const int64_t *labels, const int64_t *grou
 
 /* ------------------------------------------------------------------------
  * Multi-task learning: the gate-softmax + expert mixture of MMoE (Multi-gate Mixture-of-Experts, Ma et al., KDD
- * 2018) for all tasks in one pass, and the loss head for several labels (csrc/mmoe.hip).  Nothing in the reference
+ * 2018) for all tasks in one pass, and the loss head for several labels (csrc/multitask.hip).  Nothing in the reference
  * implements them: it knows one label per example (DeepModel.py:31-34).  Per example, E experts of width H, T tasks:
  *     p_t = softmax_e(A_t), max-subtracted;   M_t = sum_e p_te Z_e
  *   Z [B, ldz] (E H columns used, expert e at columns e H ..), A [B, lda] (T E columns, task t at t E ..),

@@ -1,7 +1,8 @@
 /*
- * recman_hip_multitask.h - C ABI of librecman_hip.so, continued: multi-task learning beyond MMoE (csrc/ple.hip).  The
- * conventions of recman_hip.h hold: device pointers, kernels enqueued on `stream`, RM_OK or a negative RM_E* code with
- * rm_last_error() for the message.  Nothing in the reference implements any of it: it knows one label per example.
+ * recman_hip_multitask.h - C ABI of librecman_hip.so, continued: multi-task learning beyond MMoE (csrc/multitask.hip).
+ * The conventions of recman_hip.h hold: device pointers, kernels enqueued on `stream`, RM_OK or a negative RM_E* code
+ * with rm_last_error() for the message.  Nothing in the reference implements any of it: it knows one label per
+ * example.
  *
  * ------------------------------------------------------------------------
  * The grouped gate mixture of one extraction level of PLE / CGC (Progressive Layered Extraction and its one-level

@@ -2952,192 +2952,6 @@ def mmoe_limits(hp):
     return names, types, weights, E, experts, towers
 
 
-class MMoEEngine(Engine):
-    """Multi-gate Mixture-of-Experts (MMoE, Ma et al., KDD 2018): T tasks over one set of embedding tables.  Nothing in
-    the reference implements it (it knows one label per example).  x = [E | dense] [B, K0], never concatenated:
-        experts e < E:  h_e^0 = x;  h_e^{l+1} = act(h_e^l W_e^l + b_e^l) over expert_hidden_units;  Z_e = h_e^L [B, H]
-        gates t < T:    A_t = x G_t [B, E] (no bias, no hidden layer);  p_t = softmax(A_t)
-        mixture:        M_t = sum_e p_te Z_e                                              (csrc/mmoe.hip)
-        towers:         logit_t = DNN_t(M_t), tower_hidden_units + the output projection
-        loss = sum_t w_t * mean over the examples whose label t is observed (not NaN) of l_t  + the l2 terms
-               (hp["entire_space"] = (ctr task, cvr task): the cvr task through pred_ctr pred_cvr, rm_multitask_loss_es)
-    num_experts = 1 is the shared-bottom model.  Layout: the experts are STACKED - layer l of all experts is one
-    [B, E H_l] buffer, expert e at columns e H_l ..; layer 0 is one GEMM over x, deeper layers run per expert on the
-    column ranges; all gates are one GEMM x -> [B, T E]; M is one [B, T H] buffer whose column range t the tower of
-    task t reads in place (a tower narrow enough for the fused skinny-MLP kernels, which take contiguous rows, gets a
-    copy).  The gate weights p never reach HBM in training.
-    Variables (names chosen here): expert_layer_0_weights [K0, E H_1] / _bias [E H_1]; expert_layer_{l}_weights
-    [E, H_l, H_{l+1}] / _bias [E, H_{l+1}] for l >= 1; gate_weights [K0, T E] (task t at columns t E ..); per task the
-    tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".  Every matrix is glorot with the
-    fans of ONE expert or gate and under deep_l2_reg; biases start at zero.  No bias tables, no linear term, no
-    dropout, one GPU.  logit / pred / dlogit are [T, B]."""
-
-    model = "mmoe"
-    use_bias_tables = False
-    shardable = False
-
-    def __init__(self, spec, embedding_size, hp, task="classification", device="cuda"):
-        super().__init__(spec, embedding_size, hp, task, device)
-        self.use_linear = False
-        (self.task_names, self.task_types, self.task_weights, self.NE, self.expert_units,
-         self.tower_units) = mmoe_limits(hp)
-        self.es = entire_space_pair(hp, self.task_names, self.task_types)
-        if hp.get("strict_reference"):
-            raise NotImplementedError("MMoE: strict_reference reproduces quirks of the reference, which has no "
-                                      "multi-task model")
-        for key in ("deep_dropout", "expert_dropout", "tower_dropout"):
-            keep = hp.get(key)
-            if keep is not None and any(float(k) != 1.0 for k in keep):
-                raise NotImplementedError(f"MMoE: {key}={keep!r}: the experts and towers run without dropout")
-        self.T, self.H = len(self.task_names), self.expert_units[-1]
-        if not ops.mmoe_mix_supported(self.NE, self.T, self.H):
-            raise ValueError(f"MMoE: {self.NE} experts, {self.T} tasks, expert width {self.H} are not supported by "
-                             f"rm_mmoe_mix_fwd ({ops.MMOE_LIMITS})")
-        self.act = act_name(hp.get("deep_activation", "relu"))
-        self.dense_gemm = hp.get("dense_gemm", "bf16x6")
-        K0, NE, T = self.FD + self.Dn, self.NE, self.T
-        self.K0 = K0
-        units = self.expert_units
-        self._var("expert_layer_0_weights", (K0, NE * units[0]), ("glorot", K0, units[0]), "deep_l2_reg")
-        self._var("expert_layer_0_bias", (NE * units[0],))
-        for l in range(1, len(units)):
-            self._var(f"expert_layer_{l}_weights", (NE, units[l - 1], units[l]), ("glorot", units[l - 1], units[l]),
-                      "deep_l2_reg")
-            self._var(f"expert_layer_{l}_bias", (NE, units[l]))
-        self._var("gate_weights", (K0, T * NE), ("glorot", K0, NE), "deep_l2_reg")
-        self.towers = [self._dnn(self.H, 0, self.tower_units, "relu", prefix=f"{n}_", stream_d_rows=False)
-                       for n in self.task_names]
-        # the GEMM shapes (K, N) of the experts and gates: their workspaces are sized for the largest
-        self._gemms = ([(K0, NE * units[0]), (K0, T * NE)]
-                       + [(units[l - 1], units[l]) for l in range(1, len(units))])
-
-    def _alloc_model(self, B):
-        dev, NE, T, H = self.device, self.NE, self.T, self.H
-        buf = lambda *shape: torch.empty(*shape, dtype=F32, device=dev)  # noqa: E731
-        self.ha = [buf(B, NE * h) for h in self.expert_units]    # the stacked expert activations, Z = ha[-1]
-        self.dha = [buf(B, NE * h) for h in self.expert_units]   # dLoss/d(pre-activation) of the same
-        lda = (T * NE + 3) // 4 * 4                              # (the mixture kernels take rows of whole float4s)
-        self.A, self.dA = buf(B, lda)[:, : T * NE], buf(B, lda)[:, : T * NE]
-        self.M, self.dM = buf(B, T * H), buf(B, T * H)
-        self.P = None                                            # gate weights [B, T E]: made by gate_weights()
-        self.dx = buf(B, self.FD)
-        self.logit, self.pred, self.dlogit = buf(T, B), buf(T, B), buf(T, B)
-        self.n_t = torch.zeros(T, dtype=I64, device=dev)
-        self.loss_t = torch.zeros(T, dtype=F32, device=dev)
-        self.loss_ws = buf(ops.multitask_loss_workspace(B, T))
-        # a tower on the fused skinny-MLP kernels reads and writes contiguous rows: its own copy of M_t / dM_t
-        copies = T > 1
-        self.Mc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
-        self.dMc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
-        for t, tw in enumerate(self.towers):
-            tw._alloc(B, dev)
-            tw.out = self.logit[t].view(B, 1)  # the tower's logit lands in its row of the [T, B] buffer
-        dims = [d for kn in self._gemms for d in kn]
-        side = max(dims)
-        self._fws = buf(max(ops.dense_filter_workspace(max(k, n), max(k, n)) for k, n in self._gemms))
-        self._wws = buf(max(1, max(ops.dense_wgrad_workspace(k, n, B) for k, n in self._gemms)))
-        self._fws6 = self._wws6 = None
-        if self.dense_gemm == "bf16x6":
-            self._fws6 = buf(ops.dense6_workspace(side, side, B))
-            self._wws6 = buf(max(ops.dense_wgrad6_workspace(k, n, B) for k, n in self._gemms))
-
-    def _cols(self, buf, l, e):
-        h = self.expert_units[l]
-        return buf[:, e * h: (e + 1) * h]
-
-    def _tower_in(self, t):
-        M_t = self.M[:, t * self.H: (t + 1) * self.H]
-        if self.Mc[t] is None:
-            return M_t
-        self.Mc[t].copy_(M_t)
-        return self.Mc[t]
-
-    def _model_fwd(self, idx, dense, want_p=False):
-        """Embedding lookup, experts, gates, mixture and towers: self.logit [T, B]."""
-        if self.spec.Dn and dense is None:
-            raise ValueError("MMoE: the dense features are missing")
-        self._embed(idx, dense, False, {}, None)
-        p, NE, T = self.params, self.NE, self.T
-        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
-        ops.dense_fwd(xe, xd, p["expert_layer_0_weights"], self.ha[0], self._fws, bias=p["expert_layer_0_bias"],
-                      act=self.act, ws6=self._fws6)
-        for l in range(1, len(self.expert_units)):
-            W, b = p[f"expert_layer_{l}_weights"], p[f"expert_layer_{l}_bias"]
-            for e in range(NE):
-                ops.dense_fwd(self._cols(self.ha[l - 1], l - 1, e), None, W[e], self._cols(self.ha[l], l, e),
-                              self._fws, bias=b[e], act=self.act, ws6=self._fws6)
-        ops.dense_fwd(xe, xd, p["gate_weights"], self.A, self._fws, act="identity", ws6=self._fws6)
-        if want_p and self.P is None:
-            self.P = torch.empty(idx.shape[0], (T * NE + 3) // 4 * 4, dtype=F32, device=self.device)[:, : T * NE]
-        ops.mmoe_mix_fwd(self.ha[-1], self.A, NE, T, self.M, P=self.P if want_p else None)
-        for t, tw in enumerate(self.towers):
-            tw.forward(self._tower_in(t), None)
-
-    def forward(self, idx, dense=None, training=False, masks=None, manual_weights=None, mv=None, gate_weights=False):
-        """-> (logit [T, B], pred [T, B]); pred_t = sigmoid(logit_t) for a classification task, logit_t for a
-        regression task.  gate_weights=True also leaves the gate weights in self.P [B, T E]."""
-        if manual_weights is not None:
-            raise NotImplementedError("MMoE has no linear term: manual feature weights do not apply")
-        self._alloc(idx.shape[0])
-        self._mv = mv
-        self._seq_save = bool(training)
-        self._model_fwd(idx, dense, want_p=gate_weights)
-        ops.multitask_loss(self.logit, self.task_types, self.pred)
-        return self.logit, self.pred
-
-    def fwd_bwd(self, idx, dense, y, masks=None, mv=None):
-        """One training step's forward + backward on labels y [B, T] (float32, NaN = unobserved).  Returns the loss
-        tensor [1] (the weighted task losses + the l2 terms); self.loss_t [T] and self.n_t [T] hold the tasks' mean
-        losses and observed counts.  Gradients: self.grads, self.d_rows [B,F,D] + idx."""
-        B = idx.shape[0]
-        self._alloc(B)
-        self._mv = mv
-        self._seq_save = True
-        if y.dtype != F32 or tuple(y.shape) != (B, self.T):
-            raise ValueError(f"MMoE: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
-                             f"{tuple(y.shape)}")
-        self._model_fwd(idx, dense)
-        _multitask_loss_step(self, y)
-        p, g, NE, T, H = self.params, self.grads, self.NE, self.T, self.H
-        ident = self.act == "identity"
-        for t, tw in enumerate(self.towers):
-            dM_t = self.dM[:, t * H: (t + 1) * H]
-            if self.dMc[t] is None:
-                tw.backward(self.dlogit[t], dM_t)
-            else:
-                tw.backward(self.dlogit[t], self.dMc[t])
-                dM_t.copy_(self.dMc[t])
-        ops.mmoe_mix_bwd(self.ha[-1], self.A, NE, T, self.dM, self.dha[-1], self.dA)
-        if not ident:
-            ops.act_bwd_(self.dha[-1], self.ha[-1], self.act)
-        for l in range(len(self.expert_units) - 1, 0, -1):
-            W = p[f"expert_layer_{l}_weights"]
-            gW, gb = g[f"expert_layer_{l}_weights"], g[f"expert_layer_{l}_bias"]
-            for e in range(NE):
-                prev, da = self._cols(self.ha[l - 1], l - 1, e), self._cols(self.dha[l], l, e)
-                ops.dense_wgrad(prev, None, da, gW[e], self._wws, db=gb[e], ws6=self._wws6)
-                ops.dense_fwd(da, None, W[e], self._cols(self.dha[l - 1], l - 1, e), self._fws, transposed=True,
-                              epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD, act=self.act,
-                              aux1=None if ident else prev, ws6=self._fws6)
-        xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
-        ops.dense_wgrad(xe, xd, self.dha[0], g["expert_layer_0_weights"], self._wws, db=g["expert_layer_0_bias"],
-                        ws6=self._wws6)
-        ops.dense_wgrad(xe, xd, self.dA, g["gate_weights"], self._wws, ws6=self._wws6)
-        # dLoss/dx of the gates and of the experts, summed into d_rows (the dense inputs need no gradient)
-        ops.dense_fwd(self.dA, None, p["gate_weights"][: self.FD], self.dx, self._fws, transposed=True,
-                      epilogue=ops.DENSE_ADD, ws6=self._fws6)
-        ops.dense_fwd(self.dha[0], None, p["expert_layer_0_weights"][: self.FD], self.d_rows.view(-1, self.FD),
-                      self._fws, transposed=True, epilogue=ops.DENSE_ADD, aux1=self.dx, ws6=self._fws6)
-        self._add_l2_grads()
-        self._seq_bwd()
-        return self._add_l2(self.loss)
-
-    def gate_weights(self, idx, dense=None, mv=None):
-        """The gate weights p [B, T, E] of a batch (an inference forward with rm_mmoe_mix_fwd's optional output)."""
-        self.forward(idx, dense, mv=mv, gate_weights=True)
-        return self.P.reshape(idx.shape[0], self.T, self.NE)
-
-
 def ple_limits(hp):
     """PLE's limits in one place (th.MMoE checks them at construction, PLEEngine when it is built): a ValueError naming
     the limit, or (task_names, task_types, task_weights, task_experts S, shared experts C, num_levels L,
@@ -3158,34 +2972,14 @@ def ple_limits(hp):
     return names, types, weights, S, C, L, experts, towers
 
 
-class PLEEngine(Engine):
-    """Progressive Layered Extraction (PLE, Tang et al., RecSys 2020; one level is CGC, Customized Gate Control): T
-    tasks over one set of embedding tables, with task-specific experts beside the shared ones and L = num_levels
-    extraction levels.  Nothing in the reference implements it.  Streams s = 0..T-1 are the tasks', s = T the shared
-    one; X_s^0 = x = [E | dense] [B, K0], never concatenated.  Per level l, N = T S + C experts (S per task, then C
-    shared), group s = the experts of stream s:
-        experts of group s:  a DNN of expert_hidden_units over X_s^l (bias, deep_activation)  ->  Z^l [B, N H]
-        gates g:             A_g = X_g^l G_g^l (no bias); task gate t over its own S experts and the C shared ones,
-                             and - on every level but the last - the shared gate g = T over all N
-        mixture:             X_g^{l+1} = M_g = sum_e p_ge Z_e, p_g = softmax(A_g)                  (csrc/ple.hip)
-        towers:              logit_t = DNN_t(X_t^L), tower_hidden_units + the output projection
-        loss: MMoEEngine's; with hp["entire_space"] = (ctr task, cvr task) the cvr task is trained through
-              pred_ctr pred_cvr over all impressions (rm_multitask_loss_es)
-    Layout: the experts of a level are STACKED as in MMoEEngine - layer k of all experts is one [B, N H_k] buffer,
-    expert e at columns e H_k ..  Level 0: layer 0 is one GEMM over x, all gates are one GEMM.  Levels >= 1: the
-    experts and the gate of stream s read column range s of the previous level's M in place - one GEMM per group for
-    layer 0, one per gate.  Deeper layers run per expert on the column ranges.  In the backward dX_s^l is the sum of
-    the input gradients of group s's experts and of gate s: the second GEMM adds the first one's result in its
-    epilogue.  The gate weights p never reach HBM in training.
-    Variables (names chosen here), per level l with K = K0 at level 0 and H above:
-        level_{l}_expert_layer_0_weights [K, N H_1] / _bias [N H_1] (expert e at columns e H_1 ..);
-        level_{l}_expert_layer_{k}_weights [N, H_k, H_{k+1}] / _bias [N, H_{k+1}] for k >= 1;
-        level_{l}_gate_weights [K, T (S + C) + shared_gate N] (rm_cgc_mix_fwd's layout of A);
-        per task the tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".
-    Every matrix is glorot with the fans of ONE expert or gate (a gate's fan-out is S + C) and under deep_l2_reg;
-    biases start at zero.  No bias tables, no linear term, no dropout, one GPU.  logit / pred / dlogit are [T, B]."""
+class _MultiTaskEngine(Engine):
+    """The body of MMoEEngine and PLEEngine: T tasks over one set of embedding tables, L levels of N = T S + C stacked
+    experts (S per task, then C shared) mixed by T task gates and - on every level but the last - one shared gate,
+    then one tower per task and the loss head for several labels.  MMoE is S = 0, L = 1.  A subclass gives `model`,
+    `who` (the prefix of its messages), its limits as (names, types, weights, S, C, L, expert units, tower units),
+    the prefix of a level's variable names, and its pair of mixture ops; its docstring has the arithmetic and the
+    variable names."""
 
-    model = "ple"
     use_bias_tables = False
     shardable = False
 
@@ -3193,34 +2987,32 @@ class PLEEngine(Engine):
         super().__init__(spec, embedding_size, hp, task, device)
         self.use_linear = False
         (self.task_names, self.task_types, self.task_weights, self.S, self.C, self.L, self.expert_units,
-         self.tower_units) = ple_limits(hp)
+         self.tower_units) = self._limits(hp)
         self.es = entire_space_pair(hp, self.task_names, self.task_types)
         if hp.get("strict_reference"):
-            raise NotImplementedError("PLE: strict_reference reproduces quirks of the reference, which has no "
+            raise NotImplementedError(f"{self.who}: strict_reference reproduces quirks of the reference, which has no "
                                       "multi-task model")
         for key in ("deep_dropout", "expert_dropout", "tower_dropout"):
             keep = hp.get(key)
             if keep is not None and any(float(k) != 1.0 for k in keep):
-                raise NotImplementedError(f"PLE: {key}={keep!r}: the experts and towers run without dropout")
-        T, S, C, L = len(self.task_names), self.S, self.C, self.L
-        self.T, self.H, self.N, self.W = T, self.expert_units[-1], T * S + C, S + C
-        if not ops.cgc_mix_supported(T, S, C, self.H, 1):
-            raise ValueError(f"PLE: {T} tasks, {S} task experts, {C} shared experts, expert width {self.H} are not "
-                             f"supported by rm_cgc_mix_fwd ({ops.CGC_LIMITS})")
+                raise NotImplementedError(f"{self.who}: {key}={keep!r}: the experts and towers run without dropout")
+        T, S, C, units = len(self.task_names), self.S, self.C, self.expert_units
+        self.T, self.H, self.N, self.W, self.NE = T, units[-1], T * S + C, S + C, C  # (NE: hp["num_experts"])
+        self._check_mix()
         self.act = act_name(hp.get("deep_activation", "relu"))
         self.dense_gemm = hp.get("dense_gemm", "bf16x6")
-        K0, N, H, units = self.FD + self.Dn, self.N, self.H, self.expert_units
+        K0, N, H = self.FD + self.Dn, self.N, self.H
         self.K0 = K0
         self._gemms = []
-        for l in range(L):
-            K, AW = (K0 if l == 0 else H), self._aw(l)
-            self._var(f"level_{l}_expert_layer_0_weights", (K, N * units[0]), ("glorot", K, units[0]), "deep_l2_reg")
-            self._var(f"level_{l}_expert_layer_0_bias", (N * units[0],))
+        for l in range(self.L):
+            K, AW, pre = (K0 if l == 0 else H), self._aw(l), self._prefix(l)
+            self._var(f"{pre}expert_layer_0_weights", (K, N * units[0]), ("glorot", K, units[0]), "deep_l2_reg")
+            self._var(f"{pre}expert_layer_0_bias", (N * units[0],))
             for k in range(1, len(units)):
-                self._var(f"level_{l}_expert_layer_{k}_weights", (N, units[k - 1], units[k]),
+                self._var(f"{pre}expert_layer_{k}_weights", (N, units[k - 1], units[k]),
                           ("glorot", units[k - 1], units[k]), "deep_l2_reg")
-                self._var(f"level_{l}_expert_layer_{k}_bias", (N, units[k]))
-            self._var(f"level_{l}_gate_weights", (K, AW), ("glorot", K, self.W), "deep_l2_reg")
+                self._var(f"{pre}expert_layer_{k}_bias", (N, units[k]))
+            self._var(f"{pre}gate_weights", (K, AW), ("glorot", K, self.W), "deep_l2_reg")
             # the GEMM shapes (K, N) of this level: the workspaces are sized for the largest
             self._gemms += [(K, N * units[0]), (K, AW)] + [(units[k - 1], units[k]) for k in range(1, len(units))]
         self.towers = [self._dnn(H, 0, self.tower_units, "relu", prefix=f"{n}_", stream_d_rows=False)
@@ -3268,11 +3060,11 @@ class PLEEngine(Engine):
         self.dM = [buf(B, (T + self._sg(l)) * H) for l in range(L)]
         self.P = None                                            # gate weights of one level: made by gate_weights()
         self.dx = buf(B, self.FD)
-        self.dxg = buf(B, H)                                     # a gate's input gradient, before its experts' is added
+        self.dxg = buf(B, H) if L > 1 else None                  # a gate's input gradient, before its experts' is added
         self.logit, self.pred, self.dlogit = buf(T, B), buf(T, B), buf(T, B)
         self.n_t = torch.zeros(T, dtype=I64, device=dev)
         self.loss_t = torch.zeros(T, dtype=F32, device=dev)
-        self.loss_ws = buf(ops.multitask_loss_es_workspace(B, T))
+        self.loss_ws = buf(ops.multitask_loss_workspace(B, T))
         # a tower on the fused skinny-MLP kernels reads and writes contiguous rows: its own copy of M_t / dM_t
         copies = T > 1
         self.Mc = [buf(B, H) if (copies and tw.fused_ok) else None for tw in self.towers]
@@ -3305,14 +3097,13 @@ class PLEEngine(Engine):
         """Embedding lookup, the extraction levels and the towers: self.logit [T, B].  p_level: the level whose gate
         weights go to self.P."""
         if self.spec.Dn and dense is None:
-            raise ValueError("PLE: the dense features are missing")
+            raise ValueError(f"{self.who}: the dense features are missing")
         self._embed(idx, dense, False, {}, None)
-        p, T, S, C, units = self.params, self.T, self.S, self.C, self.expert_units
+        p, T, units = self.params, self.T, self.expert_units
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
         for l in range(self.L):
-            sg, ha = self._sg(l), self.ha[l]
-            W0, b0, Gw = (p[f"level_{l}_expert_layer_0_weights"], p[f"level_{l}_expert_layer_0_bias"],
-                          p[f"level_{l}_gate_weights"])
+            sg, ha, pre = self._sg(l), self.ha[l], self._prefix(l)
+            W0, b0, Gw = p[f"{pre}expert_layer_0_weights"], p[f"{pre}expert_layer_0_bias"], p[f"{pre}gate_weights"]
             if l == 0:
                 self._fwd(xe, xd, W0, ha[0], bias=b0, act=self.act)
                 self._fwd(xe, xd, Gw, self.A[0], act="identity")
@@ -3325,7 +3116,7 @@ class PLEEngine(Engine):
                     a0, a1 = self._gate(g)
                     self._fwd(self._stream(X, g), None, Gw[:, a0:a1], self.A[l][:, a0:a1], act="identity")
             for k in range(1, len(units)):
-                W, b = p[f"level_{l}_expert_layer_{k}_weights"], p[f"level_{l}_expert_layer_{k}_bias"]
+                W, b = p[f"{pre}expert_layer_{k}_weights"], p[f"{pre}expert_layer_{k}_bias"]
                 for e in range(self.N):
                     self._fwd(ha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]], None, W[e],
                               ha[k][:, e * units[k]: (e + 1) * units[k]], bias=b[e], act=self.act)
@@ -3333,7 +3124,7 @@ class PLEEngine(Engine):
             if p_level == l:
                 aw = self._aw(l)
                 self.P = P = torch.empty(idx.shape[0], (aw + 3) // 4 * 4, dtype=F32, device=self.device)[:, :aw]
-            ops.cgc_mix_fwd(ha[-1], self.A[l], T, S, C, sg, self.M[l], P=P)
+            self._mix_fwd(l, P)
         for t, tw in enumerate(self.towers):
             tw.forward(self._tower_in(t), None)
 
@@ -3341,7 +3132,7 @@ class PLEEngine(Engine):
         """-> (logit [T, B], pred [T, B]); pred_t = sigmoid(logit_t) for a classification task, logit_t for a
         regression task.  gate_level = l also leaves the gate weights of level l in self.P (A's layout)."""
         if manual_weights is not None:
-            raise NotImplementedError("PLE has no linear term: manual feature weights do not apply")
+            raise NotImplementedError(f"{self.who} has no linear term: manual feature weights do not apply")
         self._alloc(idx.shape[0])
         self._mv = mv
         self._seq_save = bool(training)
@@ -3358,11 +3149,11 @@ class PLEEngine(Engine):
         self._mv = mv
         self._seq_save = True
         if y.dtype != F32 or tuple(y.shape) != (B, self.T):
-            raise ValueError(f"PLE: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
+            raise ValueError(f"{self.who}: labels must be float32 [B, {self.T}] (NaN = unobserved), got {y.dtype} "
                              f"{tuple(y.shape)}")
         self._model_fwd(idx, dense)
         _multitask_loss_step(self, y)
-        p, g, T, S, C, units = self.params, self.grads, self.T, self.S, self.C, self.expert_units
+        p, g, T, units = self.params, self.grads, self.T, self.expert_units
         ident = self.act == "identity"
         for t, tw in enumerate(self.towers):
             dM_t = self._stream(self.dM[-1], t)
@@ -3373,13 +3164,13 @@ class PLEEngine(Engine):
                 dM_t.copy_(self.dMc[t])
         xe, xd = self.E.view(-1, self.FD), (dense if self.Dn else None)
         for l in range(self.L - 1, -1, -1):
-            sg, ha, dha, dA = self._sg(l), self.ha[l], self.dha[l], self.dA[l]
-            ops.cgc_mix_bwd(ha[-1], self.A[l], T, S, C, sg, self.dM[l], dha[-1], dA)
+            sg, ha, dha, dA, pre = self._sg(l), self.ha[l], self.dha[l], self.dA[l], self._prefix(l)
+            self._mix_bwd(l)
             if not ident:
                 ops.act_bwd_(dha[-1], ha[-1], self.act)
             for k in range(len(units) - 1, 0, -1):
-                W = p[f"level_{l}_expert_layer_{k}_weights"]
-                gW, gb = g[f"level_{l}_expert_layer_{k}_weights"], g[f"level_{l}_expert_layer_{k}_bias"]
+                W = p[f"{pre}expert_layer_{k}_weights"]
+                gW, gb = g[f"{pre}expert_layer_{k}_weights"], g[f"{pre}expert_layer_{k}_bias"]
                 for e in range(self.N):
                     prev = ha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]]
                     da = dha[k][:, e * units[k]: (e + 1) * units[k]]
@@ -3387,9 +3178,8 @@ class PLEEngine(Engine):
                     self._fwd(da, None, W[e], dha[k - 1][:, e * units[k - 1]: (e + 1) * units[k - 1]],
                               transposed=True, epilogue=ops.DENSE_ADD if ident else ops.DENSE_MUL_ACTGRAD,
                               act=self.act, aux1=None if ident else prev)
-            W0, Gw = p[f"level_{l}_expert_layer_0_weights"], p[f"level_{l}_gate_weights"]
-            gW0, gb0, gG = (g[f"level_{l}_expert_layer_0_weights"], g[f"level_{l}_expert_layer_0_bias"],
-                            g[f"level_{l}_gate_weights"])
+            W0, Gw = p[f"{pre}expert_layer_0_weights"], p[f"{pre}gate_weights"]
+            gW0, gb0, gG = g[f"{pre}expert_layer_0_weights"], g[f"{pre}expert_layer_0_bias"], g[f"{pre}gate_weights"]
             if l == 0:
                 self._wgrad(xe, xd, dha[0], gW0, db=gb0)
                 self._wgrad(xe, xd, dA, gG)
@@ -3417,11 +3207,103 @@ class PLEEngine(Engine):
         return self._add_l2(self.loss)
 
     def gate_weights(self, idx, dense=None, mv=None, level=-1):
-        """The task gates' weights p [B, T, S + C] of a level of a batch (an inference forward with rm_cgc_mix_fwd's
+        """The task gates' weights p [B, T, S + C] of a level of a batch (an inference forward with the mixture's
         optional output): per task its own S experts first, then the C shared ones."""
         l = range(self.L)[level]
         self.forward(idx, dense, mv=mv, gate_level=l)
         return self.P[:, : self.T * self.W].reshape(idx.shape[0], self.T, self.W)
+
+
+class MMoEEngine(_MultiTaskEngine):
+    """Multi-gate Mixture-of-Experts (MMoE, Ma et al., KDD 2018): T tasks over one set of embedding tables.  Nothing in
+    the reference implements it (it knows one label per example).  x = [E | dense] [B, K0], never concatenated:
+        experts e < E:  h_e^0 = x;  h_e^{l+1} = act(h_e^l W_e^l + b_e^l) over expert_hidden_units;  Z_e = h_e^L [B, H]
+        gates t < T:    A_t = x G_t [B, E] (no bias, no hidden layer);  p_t = softmax(A_t)
+        mixture:        M_t = sum_e p_te Z_e                                         (csrc/multitask.hip)
+        towers:         logit_t = DNN_t(M_t), tower_hidden_units + the output projection
+        loss = sum_t w_t * mean over the examples whose label t is observed (not NaN) of l_t  + the l2 terms
+               (hp["entire_space"] = (ctr task, cvr task): the cvr task through pred_ctr pred_cvr, rm_multitask_loss_es)
+    num_experts = 1 is the shared-bottom model.  Layout: the experts are STACKED - layer l of all experts is one
+    [B, E H_l] buffer, expert e at columns e H_l ..; layer 0 is one GEMM over x, deeper layers run per expert on the
+    column ranges; all gates are one GEMM x -> [B, T E]; M is one [B, T H] buffer whose column range t the tower of
+    task t reads in place (a tower narrow enough for the fused skinny-MLP kernels, which take contiguous rows, gets a
+    copy).  The gate weights p never reach HBM in training.
+    Variables (names chosen here): expert_layer_0_weights [K0, E H_1] / _bias [E H_1]; expert_layer_{l}_weights
+    [E, H_l, H_{l+1}] / _bias [E, H_{l+1}] for l >= 1; gate_weights [K0, T E] (task t at columns t E ..); per task the
+    tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".  Every matrix is glorot with the
+    fans of ONE expert or gate and under deep_l2_reg; biases start at zero.  No bias tables, no linear term, no
+    dropout, one GPU.  logit / pred / dlogit are [T, B]."""
+
+    model = "mmoe"
+    who = "MMoE"
+
+    @staticmethod
+    def _limits(hp):
+        names, types, weights, E, experts, towers = mmoe_limits(hp)
+        return names, types, weights, 0, E, 1, experts, towers
+
+    @staticmethod
+    def _prefix(l):
+        return ""
+
+    def _check_mix(self):
+        if not ops.mmoe_mix_supported(self.NE, self.T, self.H):
+            raise ValueError(f"MMoE: {self.NE} experts, {self.T} tasks, expert width {self.H} are not supported by "
+                             f"rm_mmoe_mix_fwd ({ops.MMOE_LIMITS})")
+
+    def _mix_fwd(self, l, P):
+        ops.mmoe_mix_fwd(self.ha[l][-1], self.A[l], self.NE, self.T, self.M[l], P=P)
+
+    def _mix_bwd(self, l):
+        ops.mmoe_mix_bwd(self.ha[l][-1], self.A[l], self.NE, self.T, self.dM[l], self.dha[l][-1], self.dA[l])
+
+
+class PLEEngine(_MultiTaskEngine):
+    """Progressive Layered Extraction (PLE, Tang et al., RecSys 2020; one level is CGC, Customized Gate Control): T
+    tasks over one set of embedding tables, with task-specific experts beside the shared ones and L = num_levels
+    extraction levels.  Nothing in the reference implements it.  Streams s = 0..T-1 are the tasks', s = T the shared
+    one; X_s^0 = x = [E | dense] [B, K0], never concatenated.  Per level l, N = T S + C experts (S per task, then C
+    shared), group s = the experts of stream s:
+        experts of group s:  a DNN of expert_hidden_units over X_s^l (bias, deep_activation)  ->  Z^l [B, N H]
+        gates g:             A_g = X_g^l G_g^l (no bias); task gate t over its own S experts and the C shared ones,
+                             and - on every level but the last - the shared gate g = T over all N
+        mixture:             X_g^{l+1} = M_g = sum_e p_ge Z_e, p_g = softmax(A_g)            (csrc/multitask.hip)
+        towers:              logit_t = DNN_t(X_t^L), tower_hidden_units + the output projection
+        loss: MMoEEngine's; with hp["entire_space"] = (ctr task, cvr task) the cvr task is trained through
+              pred_ctr pred_cvr over all impressions (rm_multitask_loss_es)
+    Layout: the experts of a level are STACKED as in MMoEEngine - layer k of all experts is one [B, N H_k] buffer,
+    expert e at columns e H_k ..  Level 0: layer 0 is one GEMM over x, all gates are one GEMM.  Levels >= 1: the
+    experts and the gate of stream s read column range s of the previous level's M in place - one GEMM per group for
+    layer 0, one per gate.  Deeper layers run per expert on the column ranges.  In the backward dX_s^l is the sum of
+    the input gradients of group s's experts and of gate s: the second GEMM adds the first one's result in its
+    epilogue.  The gate weights p never reach HBM in training.
+    Variables (names chosen here), per level l with K = K0 at level 0 and H above:
+        level_{l}_expert_layer_0_weights [K, N H_1] / _bias [N H_1] (expert e at columns e H_1 ..);
+        level_{l}_expert_layer_{k}_weights [N, H_k, H_{k+1}] / _bias [N, H_{k+1}] for k >= 1;
+        level_{l}_gate_weights [K, T (S + C) + shared_gate N] (rm_cgc_mix_fwd's layout of A);
+        per task the tower's "{task}_dnn_layer_{i}_weights" / _bias, "{task}_dnn_w", "{task}_dnn_w0".
+    Every matrix is glorot with the fans of ONE expert or gate (a gate's fan-out is S + C) and under deep_l2_reg;
+    biases start at zero.  No bias tables, no linear term, no dropout, one GPU.  logit / pred / dlogit are [T, B]."""
+
+    model = "ple"
+    who = "PLE"
+    _limits = staticmethod(ple_limits)
+
+    @staticmethod
+    def _prefix(l):
+        return f"level_{l}_"
+
+    def _check_mix(self):
+        if not ops.cgc_mix_supported(self.T, self.S, self.C, self.H, 1):
+            raise ValueError(f"PLE: {self.T} tasks, {self.S} task experts, {self.C} shared experts, expert width "
+                             f"{self.H} are not supported by rm_cgc_mix_fwd ({ops.CGC_LIMITS})")
+
+    def _mix_fwd(self, l, P):
+        ops.cgc_mix_fwd(self.ha[l][-1], self.A[l], self.T, self.S, self.C, self._sg(l), self.M[l], P=P)
+
+    def _mix_bwd(self, l):
+        ops.cgc_mix_bwd(self.ha[l][-1], self.A[l], self.T, self.S, self.C, self._sg(l), self.dM[l], self.dha[l][-1],
+                        self.dA[l])
 
 
 def _one_run(positions, what, side):

@@ -1913,16 +1913,26 @@ def read_group_gain(out, n_cutoffs=GAIN_MAX_CUTOFFS):
     return (values,) + tuple(int(v) for v in r[GAIN_MAX_CUTOFFS:_GAIN_RECORD])
 
 
-# ---- multi-task learning: MMoE's gate mixture and the loss head for several labels (csrc/mmoe.hip) ---------------
+# ---- multi-task learning: the gate mixtures of MMoE and of PLE / CGC, the loss head for several labels, plain and
+# ---- with ESMM's entire-space pair (csrc/multitask.hip) ---------------------------------------------------------
 MMOE_TILE = {"tile": 0, "cap": 1}  # RM_MMOE_TILE / RM_MMOE_CAP
 MMOE_LIMITS = "1 <= E <= 16 experts, 1 <= T <= 8 tasks, H a multiple of 4 in 4..512, row strides multiples of 4 floats"
 MMOE_H_MIN, MMOE_H_MAX = 4, 512
+CGC_TILE = {"tile": 0, "cap": 1}  # RM_CGC_TILE / RM_CGC_CAP
+CGC_LIMITS = ("1 <= T <= 8 tasks, 1 <= S <= 4 task experts, 1 <= C <= 8 shared experts, N = T S + C <= 32, H a "
+              "multiple of 4 in 4..512, shared_gate 0 or 1, row strides multiples of 4 floats")
+CGC_H_MIN, CGC_H_MAX = 4, 512
 TASK_TYPES = {"classification": 0, "regression": 1}
 
 
 def mmoe_mix_supported(E, T, H):
     """rm_mmoe_mix_supported: 1 <= E <= 16, 1 <= T <= 8, H a multiple of 4 in 4..512."""
     return bool(_lib.lib().rm_mmoe_mix_supported(int(E), int(T), int(H)))
+
+
+def cgc_mix_supported(T, S, C, H, shared_gate):
+    """rm_cgc_mix_supported: 1 <= T <= 8, 1 <= S <= 4, 1 <= C <= 8, T S + C <= 32, H a multiple of 4 in 4..512."""
+    return bool(_lib.lib().rm_cgc_mix_supported(int(T), int(S), int(C), int(H), int(shared_gate)))
 
 
 def mmoe_mix_tile(E, T, H, which="tile", backward=False):
@@ -1934,12 +1944,40 @@ def mmoe_mix_tile(E, T, H, which="tile", backward=False):
     return n
 
 
+def cgc_mix_tile(T, S, C, H, shared_gate, which="tile", backward=False):
+    """rm_cgc_mix_tile: "tile" = the examples a block of the mixture kernels owns per tile, "cap" = the cap of their
+    grids (a block walks the batch again from B > cap * tile on)."""
+    n = int(_lib.lib().rm_cgc_mix_tile(int(T), int(S), int(C), int(H), int(shared_gate), int(bool(backward)),
+                                       CGC_TILE[which]))
+    if n < 0:
+        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, H={H}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
+    return n
+
+
+def cgc_widths(T, S, C, shared_gate):
+    """(N experts, gate-logit columns T (S + C) + shared_gate N, gates T + shared_gate) of one extraction level."""
+    T, S, C, sg = int(T), int(S), int(C), int(bool(shared_gate))
+    N = T * S + C
+    return N, T * (S + C) + sg * N, T + sg
+
+
 def _mmoe_dims(Z, A, E, T):
     E, T = int(E), int(T)
     if Z.dim() != 2 or A.dim() != 2 or E < 1 or T < 1 or Z.shape[1] % E or A.shape[1] != T * E:
         raise ValueError(f"mmoe_mix: Z {tuple(Z.shape)} must be [B, E H] and A {tuple(A.shape)} [B, T E] "
                          f"(E={E}, T={T})")
     return int(Z.shape[0]), E, T, int(Z.shape[1]) // E
+
+
+def _cgc_dims(Z, A, T, S, C, shared_gate):
+    T, S, C, sg = int(T), int(S), int(C), int(shared_gate)
+    if sg not in (0, 1) or min(T, S, C) < 1:
+        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
+    N, AW, G = cgc_widths(T, S, C, sg)
+    if Z.dim() != 2 or A.dim() != 2 or Z.shape[1] % N or A.shape[1] != AW:
+        raise ValueError(f"cgc_mix: Z {tuple(Z.shape)} must be [B, N H] and A {tuple(A.shape)} [B, T (S + C) + "
+                         f"shared_gate N] (T={T}, S={S}, C={C}, shared_gate={sg}: N={N}, {AW} gate logits)")
+    return int(Z.shape[0]), T, S, C, sg, N, AW, G, int(Z.shape[1]) // N
 
 
 def mmoe_mix_fwd(Z, A, E, T, M, P=None):
@@ -1964,82 +2002,6 @@ def mmoe_mix_bwd(Z, A, E, T, dM, dZ, dA):
     pdz, lddz = _strided_rows(dZ, "dZ", B, E * H, True)
     pda, ldda = _strided_rows(dA, "dA", B, T * E, True)
     _lib.call("rm_mmoe_mix_bwd", pz, ldz, pa, lda, pdm, lddm, B, E, T, H, pdz, lddz, pda, ldda, _stream())
-
-
-def multitask_loss_workspace(B, T):
-    """Floats of workspace for multitask_loss (rm_multitask_loss_workspace)."""
-    n = int(_lib.lib().rm_multitask_loss_workspace(int(B), int(T)))
-    if n < 0:
-        raise ValueError(f"multitask_loss: B={B}, T={T} unsupported (B >= 1, 1 <= T <= 8 tasks)")
-    return n
-
-
-def multitask_loss(logit, task_types, pred, *, Y=None, task_weights=None, grad_scale=1.0, dlogit=None, n_t=None,
-                   loss_t=None, loss=None, workspace=None):
-    """rm_multitask_loss: logit [T, B], task_types T names ("classification" / "regression") -> pred [T, B]; with
-    labels Y [B, T] (float32, NaN = unobserved) and task_weights (T floats) also dlogit [T, B] = w_t dl/dlogit / n_t *
-    grad_scale (0 where unobserved), n_t [T] int64, loss_t [T] and loss [1] = sum_t w_t loss_t."""
-    if logit.dim() != 2:
-        raise ValueError(f"logit: expected [T, B], got {tuple(logit.shape)}")
-    T, B = int(logit.shape[0]), int(logit.shape[1])
-    if len(task_types) != T:
-        raise ValueError(f"multitask_loss: {len(task_types)} task types for {T} rows of logits")
-    types = _int_array([TASK_TYPES[t] for t in task_types])
-    train = any(t is not None for t in (dlogit, n_t, loss_t, loss))
-    weights = None
-    if train:
-        if Y is None or workspace is None:
-            raise ValueError("multitask_loss: the loss and its gradient need labels Y and a workspace")
-        w = [1.0] * T if task_weights is None else [float(v) for v in task_weights]
-        if len(w) != T:
-            raise ValueError(f"multitask_loss: {len(w)} task weights for {T} tasks")
-        weights = (ctypes.c_float * T)(*w)
-        _need_workspace("multitask_loss", workspace, multitask_loss_workspace(B, T))
-    _lib.call("rm_multitask_loss", _chk(logit, "logit", F32), _chk(Y, "Y", F32, (B, T), allow_none=not train),
-              types, weights, float(grad_scale), B, T, _chk(pred, "pred", F32, (T, B)),
-              _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
-              _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
-              _chk(workspace, "workspace", F32, allow_none=True), _stream())
-
-
-# ---- multi-task learning, continued: PLE / CGC's grouped gate mixture and ESMM's entire-space loss (csrc/ple.hip) ---
-CGC_TILE = {"tile": 0, "cap": 1}  # RM_CGC_TILE / RM_CGC_CAP
-CGC_LIMITS = ("1 <= T <= 8 tasks, 1 <= S <= 4 task experts, 1 <= C <= 8 shared experts, N = T S + C <= 32, H a "
-              "multiple of 4 in 4..512, shared_gate 0 or 1, row strides multiples of 4 floats")
-CGC_H_MIN, CGC_H_MAX = 4, 512
-
-
-def cgc_mix_supported(T, S, C, H, shared_gate):
-    """rm_cgc_mix_supported: 1 <= T <= 8, 1 <= S <= 4, 1 <= C <= 8, T S + C <= 32, H a multiple of 4 in 4..512."""
-    return bool(_lib.lib().rm_cgc_mix_supported(int(T), int(S), int(C), int(H), int(shared_gate)))
-
-
-def cgc_mix_tile(T, S, C, H, shared_gate, which="tile", backward=False):
-    """rm_cgc_mix_tile: "tile" = the examples a block of the mixture kernels owns per tile, "cap" = the cap of their
-    grids (a block walks the batch again from B > cap * tile on)."""
-    n = int(_lib.lib().rm_cgc_mix_tile(int(T), int(S), int(C), int(H), int(shared_gate), int(bool(backward)),
-                                       CGC_TILE[which]))
-    if n < 0:
-        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, H={H}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
-    return n
-
-
-def cgc_widths(T, S, C, shared_gate):
-    """(N experts, gate-logit columns T (S + C) + shared_gate N, gates T + shared_gate) of one extraction level."""
-    T, S, C, sg = int(T), int(S), int(C), int(bool(shared_gate))
-    N = T * S + C
-    return N, T * (S + C) + sg * N, T + sg
-
-
-def _cgc_dims(Z, A, T, S, C, shared_gate):
-    T, S, C, sg = int(T), int(S), int(C), int(shared_gate)
-    if sg not in (0, 1) or min(T, S, C) < 1:
-        raise ValueError(f"cgc_mix: T={T}, S={S}, C={C}, shared_gate={shared_gate} unsupported ({CGC_LIMITS})")
-    N, AW, G = cgc_widths(T, S, C, sg)
-    if Z.dim() != 2 or A.dim() != 2 or Z.shape[1] % N or A.shape[1] != AW:
-        raise ValueError(f"cgc_mix: Z {tuple(Z.shape)} must be [B, N H] and A {tuple(A.shape)} [B, T (S + C) + "
-                         f"shared_gate N] (T={T}, S={S}, C={C}, shared_gate={sg}: N={N}, {AW} gate logits)")
-    return int(Z.shape[0]), T, S, C, sg, N, AW, G, int(Z.shape[1]) // N
 
 
 def cgc_mix_fwd(Z, A, T, S, C, shared_gate, M, P=None):
@@ -2068,12 +2030,62 @@ def cgc_mix_bwd(Z, A, T, S, C, shared_gate, dM, dZ, dA):
     _lib.call("rm_cgc_mix_bwd", pz, ldz, pa, lda, pdm, lddm, B, T, S, C, H, sg, pdz, lddz, pda, ldda, _stream())
 
 
+def _loss_workspace(op, B, T):
+    n = int(getattr(_lib.lib(), f"rm_{op}_workspace")(int(B), int(T)))
+    if n < 0:
+        raise ValueError(f"{op}: B={B}, T={T} unsupported (B >= 1, 1 <= T <= 8 tasks)")
+    return n
+
+
+def multitask_loss_workspace(B, T):
+    """Floats of workspace for multitask_loss (rm_multitask_loss_workspace)."""
+    return _loss_workspace("multitask_loss", B, T)
+
+
 def multitask_loss_es_workspace(B, T):
     """Floats of workspace for multitask_loss_es (rm_multitask_loss_es_workspace)."""
-    n = int(_lib.lib().rm_multitask_loss_es_workspace(int(B), int(T)))
-    if n < 0:
-        raise ValueError(f"multitask_loss_es: B={B}, T={T} unsupported (B >= 1, 1 <= T <= 8 tasks)")
-    return n
+    return _loss_workspace("multitask_loss_es", B, T)
+
+
+def _multitask_loss(op, logit, task_types, pred, es, Y, task_weights, grad_scale, dlogit, n_t, loss_t, loss,
+                    workspace):
+    """The loss head through entry point rm_{op}; es: () for rm_multitask_loss, the pair (c, v) for the other."""
+    if logit.dim() != 2:
+        raise ValueError(f"logit: expected [T, B], got {tuple(logit.shape)}")
+    T, B = int(logit.shape[0]), int(logit.shape[1])
+    if len(task_types) != T:
+        raise ValueError(f"{op}: {len(task_types)} task types for {T} rows of logits")
+    pair = tuple(int(i) for i in es)
+    if pair and pair != (-1, -1):
+        c, v = pair
+        if not (0 <= c < T and 0 <= v < T and c != v and task_types[c] == task_types[v] == "classification"):
+            raise ValueError(f"{op}: es={tuple(es)!r} must be two distinct classification tasks below T={T}, "
+                             "or (-1, -1)")
+    types = _int_array([TASK_TYPES[t] for t in task_types])
+    train = any(t is not None for t in (dlogit, n_t, loss_t, loss))
+    weights = None
+    if train:
+        if Y is None or workspace is None:
+            raise ValueError(f"{op}: the loss and its gradient need labels Y and a workspace")
+        w = [1.0] * T if task_weights is None else [float(x) for x in task_weights]
+        if len(w) != T:
+            raise ValueError(f"{op}: {len(w)} task weights for {T} tasks")
+        weights = (ctypes.c_float * T)(*w)
+        _need_workspace(op, workspace, _loss_workspace(op, B, T))
+    _lib.call(f"rm_{op}", _chk(logit, "logit", F32), _chk(Y, "Y", F32, (B, T), allow_none=not train), types, weights,
+              float(grad_scale), B, T, *pair, _chk(pred, "pred", F32, (T, B)),
+              _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
+              _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
+              _chk(workspace, "workspace", F32, allow_none=True), _stream())
+
+
+def multitask_loss(logit, task_types, pred, *, Y=None, task_weights=None, grad_scale=1.0, dlogit=None, n_t=None,
+                   loss_t=None, loss=None, workspace=None):
+    """rm_multitask_loss: logit [T, B], task_types T names ("classification" / "regression") -> pred [T, B]; with
+    labels Y [B, T] (float32, NaN = unobserved) and task_weights (T floats) also dlogit [T, B] = w_t dl/dlogit / n_t *
+    grad_scale (0 where unobserved), n_t [T] int64, loss_t [T] and loss [1] = sum_t w_t loss_t."""
+    _multitask_loss("multitask_loss", logit, task_types, pred, (), Y, task_weights, grad_scale, dlogit, n_t, loss_t,
+                    loss, workspace)
 
 
 def multitask_loss_es(logit, task_types, pred, *, es=(-1, -1), Y=None, task_weights=None, grad_scale=1.0, dlogit=None,
@@ -2081,32 +2093,8 @@ def multitask_loss_es(logit, task_types, pred, *, es=(-1, -1), Y=None, task_weig
     """rm_multitask_loss_es: multitask_loss with the entire-space pair es = (c, v), two distinct classification tasks:
     task v is trained through pred_c pred_v against z (0 where Y[:, c] == 0, Y[:, v] where Y[:, c] == 1, unobserved
     otherwise) over all those rows, and its gradient reaches both logits.  es = (-1, -1): multitask_loss's bits."""
-    if logit.dim() != 2:
-        raise ValueError(f"logit: expected [T, B], got {tuple(logit.shape)}")
-    T, B = int(logit.shape[0]), int(logit.shape[1])
-    if len(task_types) != T:
-        raise ValueError(f"multitask_loss_es: {len(task_types)} task types for {T} rows of logits")
-    c, v = (int(i) for i in es)
-    if (c, v) != (-1, -1) and not (0 <= c < T and 0 <= v < T and c != v and task_types[c] == task_types[v]
-                                   == "classification"):
-        raise ValueError(f"multitask_loss_es: es={tuple(es)!r} must be two distinct classification tasks below T={T}, "
-                         "or (-1, -1)")
-    types = _int_array([TASK_TYPES[t] for t in task_types])
-    train = any(t is not None for t in (dlogit, n_t, loss_t, loss))
-    weights = None
-    if train:
-        if Y is None or workspace is None:
-            raise ValueError("multitask_loss_es: the loss and its gradient need labels Y and a workspace")
-        w = [1.0] * T if task_weights is None else [float(x) for x in task_weights]
-        if len(w) != T:
-            raise ValueError(f"multitask_loss_es: {len(w)} task weights for {T} tasks")
-        weights = (ctypes.c_float * T)(*w)
-        _need_workspace("multitask_loss_es", workspace, multitask_loss_es_workspace(B, T))
-    _lib.call("rm_multitask_loss_es", _chk(logit, "logit", F32), _chk(Y, "Y", F32, (B, T), allow_none=not train),
-              types, weights, float(grad_scale), B, T, c, v, _chk(pred, "pred", F32, (T, B)),
-              _chk(dlogit, "dlogit", F32, (T, B), allow_none=True), _chk(n_t, "n_t", I64, (T,), allow_none=True),
-              _chk(loss_t, "loss_t", F32, (T,), allow_none=True), _chk(loss, "loss", F32, (1,), allow_none=True),
-              _chk(workspace, "workspace", F32, allow_none=True), _stream())
+    _multitask_loss("multitask_loss_es", logit, task_types, pred, es, Y, task_weights, grad_scale, dlogit, n_t, loss_t,
+                    loss, workspace)
 
 
 # ---- two-tower retrieval: the in-batch softmax loss and the row normalisation (csrc/inbatch.hip) -------------------

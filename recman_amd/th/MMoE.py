@@ -1,9 +1,9 @@
 """MMoE: the Multi-gate Mixture-of-Experts multi-task model (Ma et al., KDD 2018) - several labels per example over one
 set of embedding tables.  Nothing in the reference implements it (its DeepModel knows one label); the constructor
 follows the pattern of the reference's other classes (recman/tf/core/AFM.py:27-48), the gate softmax + expert mixture
-and the loss head for several labels are fused HIP kernels (csrc/mmoe.hip).  The same class is PLE / CGC (Progressive
-Layered Extraction, Tang et al., RecSys 2020: task_experts, num_levels; th.PLE) and carries ESMM's entire-space loss
-(Ma et al., SIGIR 2018: entire_space), both on the kernels of csrc/ple.hip."""
+and the loss head for several labels are fused HIP kernels (csrc/multitask.hip).  The same class is PLE / CGC
+(Progressive Layered Extraction, Tang et al., RecSys 2020: task_experts, num_levels; th.PLE) and carries ESMM's
+entire-space loss (Ma et al., SIGIR 2018: entire_space), on the same kernels."""
 import numpy as np
 import torch
 from sklearn.metrics import log_loss, roc_auc_score
@@ -214,17 +214,16 @@ class MMoE(DeepModel):
         """The gate weights softmax(x G_t) of every example: [N, T, num_experts] float32, rows summing to 1.  PLE: the
         task gates of extraction level `level`, [N, T, task_experts + num_experts] (a task's own experts first)."""
         e = self._build()
-        ple = self.model == "ple"
-        if not ple and level not in (-1, 0):
+        if self.model != "ple" and level not in (-1, 0):
             raise ValueError(f"MMoE: level={level!r}: the model has one level of gates")
         idx, dense, _ = self._encode(X)
         mv_host = self._mv_host
         n = idx.shape[0]
-        out = np.empty((n, e.T, e.W if ple else e.NE), dtype=np.float32)
+        out = np.empty((n, e.T, e.W), dtype=np.float32)
         for s in range(0, n, self.batch_size):
             t = min(s + self.batch_size, n)
-            kw = dict(level=level) if ple else {}
-            p = e.gate_weights(idx[s:t].contiguous(), dense[s:t].contiguous(), mv=self._mv_batch(mv_host, s, t), **kw)
+            p = e.gate_weights(idx[s:t].contiguous(), dense[s:t].contiguous(), mv=self._mv_batch(mv_host, s, t),
+                               level=level)
             out[s:t] = p.cpu().numpy()
         return out
 

@@ -222,6 +222,22 @@ def test_loss_head_matches_float64(hip_lib, T, B):
         assert torch.equal(out[n], again[n]), f"{n} differs between two runs"
 
 
+def test_loss_head_inference_without_labels_through_both_entry_points(hip_lib):
+    """Y = None and no training output: pred alone, the same bits from rm_multitask_loss and from
+    rm_multitask_loss_es without a pair."""
+    from recman_amd import ops
+
+    T, B = 3, 257
+    c = R.loss_case(T, B)
+    logit = c["logit"].to(F32).cuda()
+    pred, pred_es = torch.full((T, B), NAN, device="cuda"), torch.full((T, B), NAN, device="cuda")
+    ops.multitask_loss(logit, c["types"], pred)
+    ops.multitask_loss_es(logit, c["types"], pred_es, es=(-1, -1))
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(pred).all()) and torch.equal(pred, pred_es)
+    _check(f"inference T={T} B={B} pred", pred, c["pred"], c["f32"]["pred"])
+
+
 @pytest.mark.parametrize("B", [1, 77, 4099])
 @pytest.mark.parametrize("kind", ["classification", "regression"])
 def test_one_task_without_missing_labels_is_logit_loss(hip_lib, kind, B):

@@ -151,6 +151,22 @@ def test_two_runs_are_bit_equal_and_p_changes_nothing(hip_lib, shape):
     assert torch.equal(b["P"], again["P"])
 
 
+@pytest.mark.parametrize("B,S,C,H,pad", [(33, 1, 1, 8, 0), (37, 2, 3, 36, 4), (5, 4, 8, 260, 0)])
+def test_one_task_without_the_shared_gate_is_the_mmoe_mixture(hip_lib, B, S, C, H, pad):
+    """T = 1, shared_gate = 0: the one gate sees its S own experts, then the C shared ones - all E = S + C experts in
+    Z's order, as rm_mmoe_mix_fwd/bwd(E, T = 1) do.  The same bits from both entry points.  (A ragged tile; a lane
+    group that H / 4 does not fill, on column ranges; two column vectors per lane.)"""
+    from tests.test_gpu_mmoe import _run as mmoe_run
+
+    c = R.mix_case(B, 1, S, C, H, 0)
+    assert (c["N"], c["AW"], c["G"]) == (S + C, S + C, 1)
+    cgc, _ = _run(c, pad=pad, want_p=True)
+    mmoe, _ = mmoe_run(dict(B=B, E=S + C, T=1, H=H, Z=c["Z"], A=c["A"], dM=c["dM"]), pad=pad, want_p=True)
+    for n in ("M", "P", "dZ", "dA"):
+        assert bool(torch.isfinite(cgc[n]).all()), n
+        assert torch.equal(cgc[n], mmoe[n]), f"{n}: rm_cgc_mix and rm_mmoe_mix differ"
+
+
 def test_refusals_name_the_limits(hip_lib):
     from recman_amd import ops
     from recman_amd._lib import RecmanHipError
